@@ -37,11 +37,6 @@ import os
 import sys
 import time
 
-# The step pipeline keeps several HIP streams busy at once (search, and per call thread: POA x2, realignment, ratio).
-# The ROCm runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a
-# queue execute in order; give it enough queues before the runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -228,7 +223,7 @@ class CallWorkload:
                      "poa_cells": lib.svdss_poa_batch_cells(self._poa), "poa_hbm": lib.svdss_poa_batch_hbm(self._poa),
                      "realign_kernel_ms": lib.svdss_aln_batch_kernel_ms(self._aln),
                      "realign_cells": lib.svdss_aln_batch_cells(self._aln),
-                     "cons_len": cons_len, "n_cig": n_cig, "cig": cig, "scores": scores, "ratio": ratio}
+                     "cons_len": cons_len, "cons": cons, "n_cig": n_cig, "cig": cig, "scores": scores, "ratio": ratio}
 
     def svs_recovered(self, min_len=50):
         """sub-clusters of the alt allele whose CIGAR carries the implanted I/D (length within 2 %)."""
@@ -244,6 +239,60 @@ class CallWorkload:
             if any((int(x) & 0xf) == want and abs((int(x) >> 4) - ln) <= max(2, ln // 50) for x in ops):
                 ok += 1
         return ok, n_alt
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, spp, call_batch, sample_reads=8192, sample_subclusters=1024, max_reads=1 << 21):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as <name>.npy (float32 where every
+    value is exact in it, float64 otherwise).  Per read: SFS count and extension count (a seeded sample of the reads
+    beyond max_reads); the SFS themselves (start, length) of a seeded sample of the reads; the call side's consensus
+    lengths, alignment scores, CIGARs and ratios, and the consensus sequences of a seeded sample of its sub-clusters.
+    The samples depend on the sizes alone, so runs with the same arguments dump the same elements."""
+    got = spp._fetch()
+    n = len(got.counts)
+    arrays = {}
+    if n > max_reads:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=max_reads, replace=False))
+        arrays["search_reads"] = idx.astype(np.float64)
+    else:
+        idx = np.arange(n)
+    arrays["search_counts"] = got.counts[idx].astype(np.float64)
+    arrays["search_n_ext"] = got.n_ext[idx].astype(np.float64)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum(got.counts)
+    pick = np.sort(np.random.default_rng(1).choice(n, size=min(n, sample_reads), replace=False))
+    sel = np.concatenate([np.arange(off[r], off[r + 1]) for r in pick]) if len(pick) else np.zeros(0, dtype=np.int64)
+    arrays["sfs_sample_reads"] = pick.astype(np.float64)
+    arrays["sfs_sample_counts"] = got.counts[pick].astype(np.float64)
+    arrays["sfs_sample_start"] = got.qs[sel].astype(np.float64)
+    arrays["sfs_sample_len"] = got.len[sel].astype(np.float64)
+    if call_batch is not None:
+        r = call_batch.last
+        arrays["call_cons_len"] = r["cons_len"].astype(np.float64)
+        arrays["call_scores"] = r["scores"].astype(np.float64)
+        arrays["call_n_cigar"] = r["n_cig"].astype(np.float64)
+        arrays["call_cigar"] = r["cig"].astype(np.float64)
+        arrays["call_ratio"] = r["ratio"].astype(np.float64)
+        n_sub = len(r["cons_len"])
+        c_off = np.zeros(n_sub + 1, dtype=np.int64)
+        c_off[1:] = np.cumsum(r["cons_len"])
+        sub = np.sort(np.random.default_rng(2).choice(n_sub, size=min(n_sub, sample_subclusters), replace=False))
+        arrays["call_cons_sample_subclusters"] = sub.astype(np.float64)
+        arrays["call_cons_sample"] = (np.concatenate([r["cons"][c_off[k]:c_off[k + 1]] for k in sub]).astype(np.float32)
+                                      if len(sub) else np.zeros(0, dtype=np.float32))
+    # small integer arrays go out as float32 where every value is exact there
+    for k, a in arrays.items():
+        if a.dtype == np.float64 and (a.size == 0 or (np.abs(a).max() < (1 << 24) and k != "call_ratio")):
+            arrays[k] = a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes is over the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "bytes": int(total), "arrays": {k: int(a.size) for k, a in arrays.items()}}
 
 
 def main():
@@ -285,7 +334,13 @@ def main():
                          "longest chains); every step's sub-clusters are processed inside the timed region either way; "
                          "steps that do not fill a group go one by one; 1 (default) = a batch per step.  Measured: the step does not "
                          "move with it (profiles/r05x_call_group.txt) -- in the pipeline the search fills the tails already")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (search results per read, a "
+                         "seeded sample of the SFS and of the consensus sequences, the call side's scores / CIGARs / "
+                         "ratios) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.call_group = max(1, args.call_group)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -445,16 +500,17 @@ def main():
                 if record:
                     stats["kernel_ms"].append(pp.last_search_kernel_ms)
                     stats["pipeline_ms"].append(pp.last_kernel_ms)
+                    last_step["search"] = pp
                 if cw is not None:
                     if i < n_grouped:
                         if (i + 1) % G == 0:
                             workers[0][1].run(lib, check, local_rank)
                             if record:
-                                note_call(workers[0][1], G)
+                                note_call(workers[0][1], G, i)
                     else:
                         cw.run(lib, check, local_rank)
                         if record:
-                            note_call(cw, 1)
+                            note_call(cw, 1, i)
             return
         todo = queue.Queue()
         errors = []
@@ -463,13 +519,14 @@ def main():
             torch.cuda.set_device(local_rank)
             try:
                 while True:
-                    n = todo.get()
-                    if n is None:
+                    item = todo.get()
+                    if item is None:
                         return
+                    n, last = item                   # (steps in the batch, index of its last step)
                     b = w[1] if n > 1 else w[0]      # the batch of G steps' sub-clusters / of one step's
                     b.run(lib, check, local_rank)
                     if record:
-                        note_call(b, n)
+                        note_call(b, n, last)
             except BaseException as e:   # noqa: BLE001  (re-raised in the main thread)
                 errors.append(e)
 
@@ -494,13 +551,15 @@ def main():
                         with lock:
                             stats["kernel_ms"].append(spp.last_search_kernel_ms)   # HIP events on the search stream
                             stats["pipeline_ms"].append(spp.last_kernel_ms)
+                            if i == n_steps - 1:
+                                last_step["search"] = spp
                     with lock:       # the call side is handed the steps whose search is done, G at a time
                         searched[0] += 1
                         k = searched[0]
                     if k > n_grouped:
-                        todo.put(1)
+                        todo.put((1, k - 1))
                     elif k % G == 0:
-                        todo.put(G)
+                        todo.put((G, k - 1))
             except BaseException as e:   # noqa: BLE001
                 errors.append(e)
 
@@ -520,9 +579,12 @@ def main():
             raise errors[0]
 
     lock = __import__("threading").Lock()
+    last_step = {"search": None, "call": None, "call_step": -1}   # the objects holding the last timed step's results
 
-    def note_call(w, n):
+    def note_call(w, n, last):
         with lock:
+            if last > last_step["call_step"]:
+                last_step["call"], last_step["call_step"] = w, last
             stats["poa_ms"].append(w.last["poa_kernel_ms"])
             stats["aln_ms"].append(w.last["realign_kernel_ms"])
             stats["call_wall_ms"].append(w.last["poa_wall_ms"] + w.last["realign_wall_ms"] + w.last["ratio_wall_ms"])
@@ -582,6 +644,9 @@ def main():
         elapsed = float(t.item())
     kernel_ms, pipeline_ms = stats["kernel_ms"], stats["pipeline_ms"]
     poa_ms, aln_ms, call_wall_ms = stats["poa_ms"], stats["aln_ms"], stats["call_wall_ms"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last_step["search"], last_step["call"])
     search(assemble=True)     # leave the assembled results of one more search in the batch object for the verification
     finish_gathers()
 
@@ -674,6 +739,8 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["verified_reads"], out["verified_subclusters"], oracle_fm = cpu_baseline_and_verify(
                 ix, pp, d_reads, L, n_reads, args.cpu_seconds, cw)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if e2e_error:
             out["e2e_error"] = e2e_error
         if world == 1 and not args.no_e2e and e2e_dir:

@@ -59,3 +59,48 @@ def test_call_workload_and_the_batch_oracle():
 
 def test_cpu_quota_is_positive():
     assert 1 <= bench.cpu_quota() <= (os.cpu_count() or 1)
+
+
+def test_dump_outputs_writes_the_step_results_within_budget(tmp_path):
+    """--dump-outputs: the per-read arrays whole, the samples seeded (the same elements on every run), float32 / float64
+    only, every value exact, under 64 MB."""
+    from svdss_amd.pingpong import SFSBatch
+
+    rng = np.random.default_rng(5)
+    n = 20000
+    counts = rng.integers(0, 6, size=n).astype(np.int64)
+    tot = int(counts.sum())
+    res = SFSBatch(counts, rng.integers(0, 15000, size=tot).astype(np.int32), rng.integers(1, 200, size=tot).astype(np.int32),
+                   rng.integers(0, 1 << 26, size=n).astype(np.int64))
+
+    class Search:
+        def _fetch(self):
+            return res
+
+    n_sub = 300
+    cons_len = rng.integers(50, 2000, size=n_sub).astype(np.int64)
+    n_cig = rng.integers(1, 8, size=n_sub).astype(np.int64)
+
+    class Call:
+        last = {"cons_len": cons_len, "cons": rng.integers(0, 4, size=int(cons_len.sum())).astype(np.uint8),
+                "n_cig": n_cig, "cig": rng.integers(0, 1 << 32, size=int(n_cig.sum()), dtype=np.uint64).astype(np.uint32),
+                "scores": rng.integers(-3000, 3000, size=n_sub).astype(np.int32), "ratio": rng.random(n_sub - 1)}
+
+    info = bench.dump_outputs(str(tmp_path / "a"), Search(), Call(), sample_reads=512, sample_subclusters=40)
+    bench.dump_outputs(str(tmp_path / "b"), Search(), Call(), sample_reads=512, sample_subclusters=40)
+    assert info["bytes"] <= 64 << 20
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in info["arrays"]}
+    for k, a in got.items():
+        assert a.dtype in (np.float32, np.float64), k
+        assert np.array_equal(a, np.load(tmp_path / "b" / (k + ".npy"))), k
+    assert np.array_equal(got["search_counts"], counts) and np.array_equal(got["search_n_ext"], res.n_ext)
+    off = np.concatenate([[0], np.cumsum(counts)])
+    pick = got["sfs_sample_reads"].astype(np.int64)
+    assert len(pick) == 512 and np.array_equal(got["sfs_sample_counts"], counts[pick])
+    sel = np.concatenate([np.arange(off[r], off[r + 1]) for r in pick])
+    assert np.array_equal(got["sfs_sample_start"], res.qs[sel]) and np.array_equal(got["sfs_sample_len"], res.len[sel])
+    assert np.array_equal(got["call_cigar"], Call.last["cig"]) and np.array_equal(got["call_scores"], Call.last["scores"])
+    assert np.array_equal(got["call_ratio"], Call.last["ratio"]) and np.array_equal(got["call_cons_len"], cons_len)
+    c_off = np.concatenate([[0], np.cumsum(cons_len)])
+    sub = got["call_cons_sample_subclusters"].astype(np.int64)
+    assert np.array_equal(got["call_cons_sample"], np.concatenate([Call.last["cons"][c_off[k]:c_off[k + 1]] for k in sub]))
