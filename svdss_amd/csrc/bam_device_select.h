@@ -1,7 +1,7 @@
-// bam_device_select.h -- host side of the device path for callers that need whole records of a few reads (`SVDSS call`,
-// csrc/bam_device.hip svdss_bam_select_run): the BAM header probe, and a reader that hands out, in file order, the records
-// a svdss_bam_filter_t keeps.  Scanner (loader threads) -> batcher -> feeding threads (one batch object each) -> ordered
-// output; the caller sees plain record bytes.
+// bam_device_select.h -- host side of the device path (csrc/bam_device.hip) for `SVDSS search`, `call` and `smooth`: the BAM
+// header probe, and a reader that runs the batches of a file -- or of its regions, one per GPU -- through a device entry
+// point of the caller's and hands out what each batch left, in file order.  Scanner (loader threads) -> batcher -> feeding
+// threads (one batch object each) -> ordered hand-over with back-pressure.
 #pragma once
 #include <sys/stat.h>
 
@@ -147,45 +147,63 @@ inline bool view_of_record(const uint8_t* rec, size_t avail, BamReader::RawView&
   return true;
 }
 
-struct BamSelectRegion { size_t begin = 0, end = 0; bool open_start = false, open_end = false; std::vector<uint8_t> carry; int loaders = 8; size_t pending = 64; };
+// What a feeding thread does with a batch: one of the device path's entry points (svdss_bam_select_store_run,
+// svdss_bam_smooth_run, svdss_bam_batch_run, ...) for device slot `dev` of the reader
+typedef std::function<int(svdss_bam_stream_t*, int64_t seq, int32_t is_last, int64_t skip, size_t dev, int32_t n_chunks, const uint8_t* const* comp,
+                          const int64_t* comp_bytes, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                          svdss_bam_batch_t** batch)> BamRunFn;
 
+// why a run failed: the entry point's return code, the batch's or the stream's message (may be empty) and the HIP error
+// the failing thread saw
+struct BamRunError {
+  int rc = SVDSS_OK;
+  std::string msg, hip;
+  bool failed() const { return rc != SVDSS_OK; }
+  std::string text() const { return !failed() ? std::string() : !msg.empty() ? msg : std::string(svdss_strerror(rc)) + " " + hip; }
+};
+
+// A region of the file (ShardedBamSelect below): [begin, end) at member starts (end = 0: the file's end); open_start: the
+// region begins inside a record nobody has located (svdss_bam_stream_region: the chain starts at a guess, to be proved at
+// the seam); open_end: it may end inside one; carry: the incomplete record in front of it when the region runs from a known
+// start; pending: batches that may wait for the caller while it reads this region (current: from the start; a later region
+// is not bounded until it becomes current -- its results wait until the regions in front are handed out)
+struct BamSelectRegion { size_t begin = 0, end = 0; bool open_start = false, open_end = false; std::vector<uint8_t> carry; int loaders = 8; size_t pending = 64; bool current = true; };
+
+// One region of a BAM through the device path, batch results handed out in file order as `Out`: scanner (loader threads)
+// -> batcher -> feeding threads (n_devices x feeders, one batch object each; `run` is told the device slot) -> ordered
+// hand-over with back-pressure.  `collect` turns a batch's result into an Out; it may return nullptr: that batch's result
+// is delivered later, by deliver(seq, result) -- it does not count against the pending bound, and the run is not over
+// until it has come.
+template <class Out>
 class DeviceBamSelect {
  public:
-  // what a feeding thread does with a batch (default: svdss_bam_select_run with the device's filter) and how its result
-  // becomes a SelectedBatch -- `SVDSS smooth` runs svdss_bam_smooth_run / _measure through the same scanner, batcher,
-  // feeders and ordered hand-over
-  typedef std::function<int(svdss_bam_stream_t*, int64_t seq, int32_t is_last, int64_t skip, size_t dev, int32_t n_chunks, const uint8_t* const* comp,
-                            const int64_t* comp_bytes, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
-                            svdss_bam_batch_t** batch)> RunFn;
-  typedef std::function<void(const svdss_bam_batch_t*, SelectedBatch&)> CollectFn;
-  // filters[d]: the filter on device d (one per GPU used); feeders: feeding threads per GPU
-  // A region of the file (ShardedBamSelect below): [begin, end) at member starts (end = 0: the file's end); open_start: the
-  // region begins inside a record nobody has located (svdss_bam_stream_region: the chain starts at a guess, to be proved at
-  // the seam); open_end: it may end inside one; carry: the incomplete record in front of it when the region runs from a known
-  // start; pending: batches that may wait for the caller (a later region's wait until the regions in front are done)
+  typedef std::function<std::unique_ptr<Out>(const svdss_bam_batch_t*, uint64_t seq)> CollectFn;
   typedef BamSelectRegion Region;
-  DeviceBamSelect(const std::string& path, const std::vector<svdss_bam_filter_t*>& filters, const std::vector<int>& devices, int32_t n_ref,
-                  int64_t skip, int feeders, int64_t batch_bytes, RunFn run = RunFn(), CollectFn collect = CollectFn(),
-                  svdss_bam_stream_t* prepared_stream = nullptr, const Region& region = Region())
-      : filters_(filters), devices_(devices), skip_(skip), target_(batch_bytes), run_(run), collect_(collect), stream_(prepared_stream),
-        max_pending_(region.pending) {
-    BgzfScanner::Hooks hooks;
-    hooks.host_alloc = svdss_host_alloc;
-    hooks.host_free = svdss_host_free;
-    const size_t slab = (getenv("SVDSS_BAM_SLAB_KB") && atoll(getenv("SVDSS_BAM_SLAB_KB")) >= 64 ? (size_t)atoll(getenv("SVDSS_BAM_SLAB_KB")) << 10 : (size_t)16 << 20);
-    const size_t per_batch = (size_t)target_ / slab + 2;
+  // scanner: one the caller opened for the region and keeps open past this object (nullptr: one is opened here)
+  DeviceBamSelect(const std::string& path, size_t n_devices, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes, BamRunFn run,
+                  CollectFn collect, svdss_bam_stream_t* prepared_stream = nullptr, const Region& region = Region(), BgzfScanner* scanner = nullptr)
+      : skip_(skip), target_(batch_bytes), run_(run), collect_(collect), sc_(scanner), stream_(prepared_stream), max_pending_(region.pending),
+        current_(region.current) {
     feeders = std::max(1, feeders);
-    sc_.reset(new BgzfScanner(path, hooks, slab, region.loaders, (size_t)region.loaders + ((size_t)filters.size() * (size_t)feeders + 3) * per_batch, region.begin,
-                              region.end));
-    if (!sc_->ok()) { err_ = "cannot open file"; finished_ = true; return; }
-    if (!stream_ && svdss_bam_stream_create(n_ref, &stream_) != SVDSS_OK) { err_ = "out of memory"; finished_ = true; return; }
+    if (!sc_) {
+      BgzfScanner::Hooks hooks;
+      hooks.host_alloc = svdss_host_alloc;
+      hooks.host_free = svdss_host_free;
+      const size_t slab = (getenv("SVDSS_BAM_SLAB_KB") && atoll(getenv("SVDSS_BAM_SLAB_KB")) >= 64 ? (size_t)atoll(getenv("SVDSS_BAM_SLAB_KB")) << 10 : (size_t)16 << 20);
+      const size_t per_batch = (size_t)target_ / slab + 2;
+      own_sc_.reset(new BgzfScanner(path, hooks, slab, region.loaders, (size_t)region.loaders + (n_devices * (size_t)feeders + 3) * per_batch, region.begin,
+                                    region.end));
+      sc_ = own_sc_.get();
+    }
+    if (!sc_->ok()) { err_ = BamRunError{SVDSS_EIO, "cannot open file", ""}; return; }
+    if (!stream_ && svdss_bam_stream_create(n_ref, &stream_) != SVDSS_OK) { err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return; }
     if (region.open_start || region.open_end || !region.carry.empty())
       if (svdss_bam_stream_region(stream_, region.open_start ? 1 : 0, region.open_end ? 1 : 0, region.carry.data(), (int64_t)region.carry.size()) != SVDSS_OK) {
-        err_ = "out of memory"; finished_ = true; return;
+        err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return;
       }
-    n_feeders_ = filters_.size() * (size_t)feeders;
+    n_feeders_ = n_devices * (size_t)feeders;
     batcher_ = std::thread([this] { batch_loop(); });
-    for (size_t d = 0; d < filters_.size(); ++d)
+    for (size_t d = 0; d < n_devices; ++d)
       for (int k = 0; k < feeders; ++k) feeders_.emplace_back([this, d] { feed_loop(d); });
   }
   ~DeviceBamSelect() {
@@ -199,40 +217,52 @@ class DeviceBamSelect {
   DeviceBamSelect& operator=(const DeviceBamSelect&) = delete;
 
   // the next batch in file order; nullptr at the end of the file or on an error (error() says which)
-  std::unique_ptr<SelectedBatch> next() {
+  std::unique_ptr<Out> next() {
     std::unique_lock<std::mutex> lk(m_);
-    cv_.wait(lk, [&] { return done_.count(want_) || !err_.empty() || (finished_ && done_.empty()); });
-    if (!err_.empty()) return nullptr;
+    cv_.wait(lk, [&] { return done_.count(want_) || err_.failed() || (fed() && deferred_ == 0 && done_.empty()); });
+    if (err_.failed()) return nullptr;
     auto it = done_.find(want_);
     if (it == done_.end()) return nullptr;
-    std::unique_ptr<SelectedBatch> b = std::move(it->second);
+    std::unique_ptr<Out> b = std::move(it->second);
     done_.erase(it);
     ++want_;
     lk.unlock();
     cv_.notify_all();
     return b;
   }
-  const std::string& error() const { return err_; }
+  // the result of batch `seq`, whose collect returned nullptr
+  void deliver(uint64_t seq, std::unique_ptr<Out> out) {
+    { std::lock_guard<std::mutex> lk(m_); done_[seq] = std::move(out); --deferred_; }
+    cv_.notify_all();
+  }
+  std::string error() const { return failure().text(); }
+  BamRunError failure() const { std::lock_guard<std::mutex> lk(m_); return err_; }
+  // the caller reads this region now: its feeders are held to the pending bound from here on
+  void make_current() {
+    { std::lock_guard<std::mutex> lk(m_); current_ = true; }
+    cv_.notify_all();
+  }
   // blocks until batch 0 has had its turn (svdss_bam_stream_head is final), the file has ended or the run has failed
   void wait_first() {
     std::unique_lock<std::mutex> lk(m_);
-    cv_.wait(lk, [&] { return want_ > 0 || done_.count(0) || !err_.empty() || finished_; });
+    cv_.wait(lk, [&] { return want_ > 0 || done_.count(0) || err_.failed() || fed(); });
   }
-  // blocks until every feeding thread has ended (the stream's tail is final)
+  // blocks until every feeding thread has ended (the stream's tail is final; results still to be delivered may follow)
   void wait_finished() {
     std::unique_lock<std::mutex> lk(m_);
-    cv_.wait(lk, [&] { return finished_; });
+    cv_.wait(lk, [&] { return fed(); });
   }
   svdss_bam_stream_t* stream() const { return stream_; }
-  // seconds the batcher waited for the file's loaders / for a feeding thread to take a batch (valid once the file has ended)
-  double waited_for_file() const { return wait_file_s_; }
-  double waited_for_feeders() const { return wait_feed_s_; }
+  // seconds the batcher waited for the file's loaders / for a feeding thread to take a batch
+  double waited_for_file() const { std::lock_guard<std::mutex> lk(m_); return wait_file_s_; }
+  double waited_for_feeders() const { std::lock_guard<std::mutex> lk(m_); return wait_feed_s_; }
   int64_t segments_walked_again(int64_t* n_segments) const { return stream_ ? svdss_bam_stream_rewalked(stream_, n_segments) : 0; }
 
  private:
   struct Job { uint64_t seq = 0; bool last = false; std::vector<std::unique_ptr<CompChunk>> chunks; };
-  void fail(const std::string& e) {
-    { std::lock_guard<std::mutex> lk(m_); if (err_.empty()) err_ = e; }
+  bool fed() const { return feeders_done_ == n_feeders_; }
+  void fail(const BamRunError& e) {
+    { std::lock_guard<std::mutex> lk(m_); if (!err_.failed()) err_ = e; }
     cv_.notify_all();
   }
   void batch_loop() {
@@ -240,10 +270,15 @@ class DeviceBamSelect {
     int64_t acc = 0;
     uint64_t seq = 0;
     bool any_last = false;
+    double w_file = 0;
     auto push = [&](std::unique_ptr<Job> j) {
+      const auto w0 = std::chrono::steady_clock::now();
       std::unique_lock<std::mutex> lk(m_);
-      cv_.wait(lk, [&] { return jobs_.size() < 2 || stop_ || !err_.empty(); });
-      if (stop_ || !err_.empty()) return false;
+      cv_.wait(lk, [&] { return jobs_.size() < 2 || stop_ || err_.failed(); });
+      wait_feed_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+      wait_file_s_ += w_file;
+      w_file = 0;
+      if (stop_ || err_.failed()) return false;
       jobs_.push_back(std::move(j));
       lk.unlock();
       cv_.notify_all();
@@ -252,7 +287,7 @@ class DeviceBamSelect {
     for (;;) {
       const auto w0 = std::chrono::steady_clock::now();
       std::unique_ptr<CompChunk> c = sc_->next();
-      wait_file_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+      w_file += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
       if (!c) break;
       acc += c->inflated;
       const bool last = c->last;
@@ -261,16 +296,14 @@ class DeviceBamSelect {
         cur->seq = seq++;
         cur->last = last;
         any_last = any_last || last;
-        const auto w1 = std::chrono::steady_clock::now();
         if (!push(std::move(cur))) return;
-        wait_feed_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - w1).count();
         cur.reset(new Job);
         acc = 0;
       }
     }
-    if (!sc_->error().empty()) { fail(sc_->error()); return; }
-    if (!any_last) { cur->seq = seq++; cur->last = true; if (!push(std::move(cur))) return; }
-    { std::lock_guard<std::mutex> lk(m_); jobs_closed_ = true; }
+    if (!sc_->error().empty()) { fail(BamRunError{SVDSS_EIO, sc_->error(), ""}); return; }
+    if (!any_last) { cur->seq = seq++; cur->last = true; if (!push(std::move(cur))) return; }   // (an empty region)
+    { std::lock_guard<std::mutex> lk(m_); jobs_closed_ = true; wait_file_s_ += w_file; }
     cv_.notify_all();
   }
   void feed_loop(size_t d) {
@@ -283,8 +316,8 @@ class DeviceBamSelect {
       std::unique_ptr<Job> job;
       {
         std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&] { return !jobs_.empty() || jobs_closed_ || stop_ || !err_.empty(); });
-        if (stop_ || !err_.empty() || jobs_.empty()) break;
+        cv_.wait(lk, [&] { return !jobs_.empty() || jobs_closed_ || stop_ || err_.failed(); });
+        if (stop_ || err_.failed() || jobs_.empty()) break;
         job = std::move(jobs_.front());
         jobs_.erase(jobs_.begin());
       }
@@ -294,65 +327,52 @@ class DeviceBamSelect {
         comp.push_back(c->data); comp_bytes.push_back((int64_t)c->n_bytes); n_blocks.push_back((int64_t)c->blocks.size());
         blocks.push_back(c->blocks.data()); crcs.push_back(c->crc.data());
       }
-      const int rc = run_ ? run_(stream_, (int64_t)job->seq, job->last ? 1 : 0, job->seq == 0 ? skip_ : 0, d, (int32_t)comp.size(), comp.data(),
-                                 comp_bytes.data(), blocks.data(), crcs.data(), n_blocks.data(), &batch)
-                          : svdss_bam_select_run(stream_, (int64_t)job->seq, job->last ? 1 : 0, job->seq == 0 ? skip_ : 0, filters_[d], (int32_t)comp.size(),
-                                                 comp.data(), comp_bytes.data(), blocks.data(), crcs.data(), n_blocks.data(), &batch);
+      const int rc = run_(stream_, (int64_t)job->seq, job->last ? 1 : 0, job->seq == 0 ? skip_ : 0, d, (int32_t)comp.size(), comp.data(), comp_bytes.data(),
+                          blocks.data(), crcs.data(), n_blocks.data(), &batch);
       for (std::unique_ptr<CompChunk>& c : job->chunks) sc_->recycle(std::move(c));
       if (rc != SVDSS_OK) {
         std::string msg = batch ? svdss_bam_batch_error(batch) : "";
         if (msg.empty()) msg = svdss_bam_stream_error(stream_);
-        if (msg.empty()) msg = std::string(svdss_strerror(rc)) + " " + svdss_last_hip_error();
-        fail(msg);
+        fail(BamRunError{rc, msg, svdss_last_hip_error()});
         break;
       }
-      std::unique_ptr<SelectedBatch> out(new SelectedBatch);
-      if (collect_) collect_(batch, *out);
-      else {
-        svdss_bam_selection_t r;
-        (void)svdss_bam_batch_selection(batch, &r);
-        out->n_records = (uint64_t)r.n_records;
-        out->slim = r.slim != 0;
-        out->off.assign(r.rec_off, r.rec_off + r.n_selected + 1);
-        out->bytes.assign(r.bytes, r.bytes + r.n_bytes);
-        for (int k = 0; k < 8; ++k) out->stage_s[k] = r.stage_ms[k] * 1e-3;
-        out->inflate_kernel_s = r.inflate_kernel_ms * 1e-3;
-      }
+      std::unique_ptr<Out> out = collect_(batch, job->seq);
       {
         std::unique_lock<std::mutex> lk(m_);
         const uint64_t sq = job->seq;
-        cv_.wait(lk, [&] { return stop_ || done_.size() < max_pending_ || done_.begin()->first > sq; });   // (kept records are few: let the GPU run ahead)
-        done_[sq] = std::move(out);
+        if (!out) ++deferred_;
+        else {
+          cv_.wait(lk, [&] { return stop_ || !current_ || done_.size() < max_pending_ || done_.begin()->first > sq; });
+          done_[sq] = std::move(out);
+        }
       }
       cv_.notify_all();
     }
     if (batch) svdss_bam_batch_free(batch);
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      if (++feeders_done_ == n_feeders_) finished_ = true;
-    }
+    { std::lock_guard<std::mutex> lk(m_); ++feeders_done_; }
     cv_.notify_all();
   }
 
-  std::vector<svdss_bam_filter_t*> filters_;
-  std::vector<int> devices_;
   int64_t skip_ = 0, target_ = 0;
   double wait_file_s_ = 0, wait_feed_s_ = 0;
-  RunFn run_;
+  BamRunFn run_;
   CollectFn collect_;
-  std::unique_ptr<BgzfScanner> sc_;
+  std::unique_ptr<BgzfScanner> own_sc_;
+  BgzfScanner* sc_ = nullptr;
   svdss_bam_stream_t* stream_ = nullptr;
   size_t max_pending_ = 64;
+  bool current_ = true;
   std::thread batcher_;
   std::vector<std::thread> feeders_;
-  std::mutex m_;
+  mutable std::mutex m_;
   std::condition_variable cv_;
   std::vector<std::unique_ptr<Job>> jobs_;
-  bool jobs_closed_ = false, stop_ = false, finished_ = false;
+  bool jobs_closed_ = false, stop_ = false;
   size_t feeders_done_ = 0, n_feeders_ = 0;
-  std::map<uint64_t, std::unique_ptr<SelectedBatch>> done_;
+  int64_t deferred_ = 0;        // results collect left for deliver() (below 0 for a moment when one comes first)
+  std::map<uint64_t, std::unique_ptr<Out>> done_;
   uint64_t want_ = 0;
-  std::string err_;
+  BamRunError err_;
 };
 
 
@@ -379,29 +399,31 @@ inline std::vector<size_t> plan_bam_regions(const std::string& path, int n, int6
   return cuts;
 }
 
-// `SVDSS call --gpus N` (round 6; SURVEY 8(e): the BAM's regions partition across the GPUs): the file is cut at BGZF members
-// into one region per GPU, and every region has its own scanner (loader threads), batcher, feeding threads, record stream,
-// filter and -- when the caller keeps one -- record store: nothing is shared on the way in, as in `SVDSS search --gpus N`
-// (svdss_main.cpp).  A region that does not begin the file begins inside a record: its chain starts at a guess
-// (svdss_bam_stream_region) that is PROVED when the region in front has been handed out -- its leftover + the bytes this
-// region set aside must be a chain of whole records (the seam: a batch of its own through the same entry point); if they
-// are not, or the region failed in any way, it runs again from the known carry.  The caller sees the batches of the file in
-// file order, as from one DeviceBamSelect.
+// `SVDSS search / call / smooth --gpus N` (the BAM's regions partition across the GPUs): the file is cut at
+// BGZF members into one region per GPU, and every region has its own DeviceBamSelect -- scanner (loader threads), batcher,
+// feeding threads, record stream -- and whatever its caller's hooks give it (a filter and a record store, an index
+// replica): nothing is shared on the way in.  A region that does not begin the file begins inside a record: its chain
+// starts at a guess (svdss_bam_stream_region) that is PROVED when the region in front has been handed out -- its leftover +
+// the bytes this region set aside must be a chain of whole records (the seam: a batch of its own through the same entry
+// point); if they are not, or the region failed in any way, it runs again from the known carry.  The caller sees the
+// batches of the file in file order, as from one DeviceBamSelect; the region it reads holds `pending` results at most.
+template <class Out>
 class ShardedBamSelect {
  public:
-  struct Shard { svdss_bam_filter_t* filter = nullptr; int device = 0; svdss_bam_store_t* store = nullptr; svdss_bam_store_t* seam_store = nullptr; };
-  // What a region's batches go through (the select / store entry point below; `SVDSS smooth --gpus N`: svdss_bam_smooth_run).
+  typedef typename DeviceBamSelect<Out>::CollectFn CollectFn;
+  struct Shard { svdss_bam_filter_t* filter = nullptr; svdss_bam_store_t* store = nullptr; svdss_bam_store_t* seam_store = nullptr; };
+  // What a region's batches go through (`SVDSS call`: the select / store entry point of the constructor below).
   // run(g, seam) / collect(g, seam): for the feeding threads of region g, or (seam = true) for the one batch of the seam in
-  // front of it, run on the caller's thread with is_last = 1; stream(g): a prepared record stream for region g's run (nullptr
-  // or no hook: a plain one) -- asked again if the region runs again; again(g): the region runs again (forget what its first
-  // run left); seam_kept(g): the seam's batch stays somewhere the caller looks for it (region_has_seam)
+  // front of it, run on the caller's thread with is_last = 1 (its collect may not leave the result for later); stream(g): a
+  // prepared record stream for region g's run (nullptr or no hook: a plain one) -- asked again if the region runs again;
+  // again(g, why): the region runs again (forget what its first run left; why: its failure, empty when the seam did not
+  // fit); seam_kept(g): the seam's batch stays somewhere the caller looks for it (region_has_seam)
   struct Hooks {
-    std::function<DeviceBamSelect::RunFn(size_t g, bool seam)> run;
-    std::function<DeviceBamSelect::CollectFn(size_t g, bool seam)> collect;
+    std::function<BamRunFn(size_t g, bool seam)> run;
+    std::function<CollectFn(size_t g, bool seam)> collect;
     std::function<svdss_bam_stream_t*(size_t g)> stream;
-    std::function<void(size_t g)> again;
+    std::function<void(size_t g, const std::string& why)> again;
     std::function<bool(size_t g)> seam_kept;
-    std::function<int(size_t g)> device;
   };
   ShardedBamSelect(const std::string& path, const std::vector<Shard>& shards, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes,
                    const std::vector<size_t>& cuts)
@@ -409,21 +431,37 @@ class ShardedBamSelect {
     hooks_.run = [shards](size_t g, bool seam) {
       const Shard S = shards[g % shards.size()];
       svdss_bam_store_t* store = seam ? S.seam_store : S.store;
-      return DeviceBamSelect::RunFn([S, store, seam](svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, size_t, int32_t n_chunks,
-                                                     const uint8_t* const* comp, const int64_t* comp_bytes, const svdss_bgzf_block_t* const* blocks,
-                                                     const uint32_t* const* crc, const int64_t* n_blocks, svdss_bam_batch_t** batch) {
+      return BamRunFn([S, store, seam](svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, size_t, int32_t n_chunks, const uint8_t* const* comp,
+                                       const int64_t* comp_bytes, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                                       svdss_bam_batch_t** batch) {
         if (seam && store) svdss_bam_store_reset(store);
         return svdss_bam_select_store_run(s, seq, is_last, skip, S.filter, store, n_chunks, comp, comp_bytes, blocks, crc, n_blocks, batch);
       });
     };
-    hooks_.again = [shards](size_t g) { if (shards[g % shards.size()].store) svdss_bam_store_reset(shards[g % shards.size()].store); };
+    hooks_.collect = [](size_t, bool) {
+      return CollectFn([](const svdss_bam_batch_t* batch, uint64_t) {
+        std::unique_ptr<Out> out(new Out);
+        svdss_bam_selection_t r;
+        (void)svdss_bam_batch_selection(batch, &r);
+        out->n_records = (uint64_t)r.n_records;
+        out->slim = r.slim != 0;
+        out->off.assign(r.rec_off, r.rec_off + r.n_selected + 1);
+        out->bytes.assign(r.bytes, r.bytes + r.n_bytes);
+        for (int k = 0; k < 8; ++k) out->stage_s[k] = r.stage_ms[k] * 1e-3;
+        out->inflate_kernel_s = r.inflate_kernel_ms * 1e-3;
+        return out;
+      });
+    };
+    hooks_.again = [shards](size_t g, const std::string&) { if (shards[g % shards.size()].store) svdss_bam_store_reset(shards[g % shards.size()].store); };
     hooks_.seam_kept = [shards](size_t g) { return shards[g % shards.size()].seam_store != nullptr; };
-    hooks_.device = [shards](size_t g) { return shards[g % shards.size()].device; };
-    start(cuts);
+    start(cuts, std::vector<BgzfScanner*>());
   }
-  ShardedBamSelect(const std::string& path, const Hooks& hooks, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes, const std::vector<size_t>& cuts)
-      : path_(path), hooks_(hooks), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes) {
-    start(cuts);
+  // scanners: those of the regions' first runs, opened by the caller and kept open past this object (none given: each
+  // region opens its own)
+  ShardedBamSelect(const std::string& path, const Hooks& hooks, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes, const std::vector<size_t>& cuts,
+                   size_t pending = 64, const std::vector<BgzfScanner*>& scanners = std::vector<BgzfScanner*>())
+      : path_(path), hooks_(hooks), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes), pending_(pending) {
+    start(cuts, scanners);
   }
   size_t n_regions() const { return regions_.size(); }
   int64_t seams_run() const { return n_seams_; }
@@ -432,53 +470,70 @@ class ShardedBamSelect {
   bool region_has_seam(size_t g) const { return regions_[g].seam_stored; }
   int64_t region_batches(size_t g) const { return regions_[g].n_batches; }
 
-  std::unique_ptr<SelectedBatch> next() {
+  std::unique_ptr<Out> next() {
     for (;;) {
       if (cur_ >= regions_.size()) return nullptr;
       Reg& R = regions_[cur_];
       if (!R.entered) {
         R.entered = true;
         if (cur_ > 0 && !enter(cur_)) return nullptr;
-        if (R.seam) { std::unique_ptr<SelectedBatch> b = std::move(R.seam); return b; }
+        R.sel->make_current();
+        if (R.seam) return std::move(R.seam);
       }
-      std::unique_ptr<SelectedBatch> b = R.sel->next();
+      std::unique_ptr<Out> b = R.sel->next();
       if (b) { ++R.n_batches; return b; }
-      if (!R.sel->error().empty()) { err_ = R.sel->error(); return nullptr; }
+      if (R.sel->failure().failed()) { err_ = R.sel->failure(); return nullptr; }
       ++cur_;
     }
   }
-  const std::string& error() const { return err_; }
-  double waited_for_file() const { double s = 0; for (const Reg& R : regions_) if (R.sel) s += R.sel->waited_for_file(); return s; }
-  double waited_for_feeders() const { double s = 0; for (const Reg& R : regions_) if (R.sel) s += R.sel->waited_for_feeders(); return s; }
+  std::string error() const { return err_.text(); }
+  const BamRunError& failure() const { return err_; }
+  // summed over every run of every region (valid once the regions have been read)
+  double waited_for_file() const { double s = wait_file_s_; for (const Reg& R : regions_) if (R.sel) s += R.sel->waited_for_file(); return s; }
+  double waited_for_feeders() const { double s = wait_feed_s_; for (const Reg& R : regions_) if (R.sel) s += R.sel->waited_for_feeders(); return s; }
+  int64_t segments_walked_again(int64_t* n_segments) const {
+    int64_t seg = n_seg_, rew = n_rewalk_;
+    for (const Reg& R : regions_)
+      if (R.sel) { int64_t n = 0; rew += R.sel->segments_walked_again(&n); seg += n; }
+    if (n_segments) *n_segments = seg;
+    return rew;
+  }
 
  private:
   struct Reg {
     size_t begin = 0, end = 0;
-    std::unique_ptr<DeviceBamSelect> sel;
-    std::unique_ptr<SelectedBatch> seam;
+    std::unique_ptr<DeviceBamSelect<Out>> sel;
+    std::unique_ptr<Out> seam;
     bool entered = false, seam_stored = false;
     int64_t n_batches = 0;
   };
-  void start(const std::vector<size_t>& cuts) {
+  void start(const std::vector<size_t>& cuts, const std::vector<BgzfScanner*>& scanners) {
     const size_t n = cuts.size() - 1;
     regions_.resize(n);
     for (size_t g = 0; g < n; ++g) {
       regions_[g].begin = cuts[g]; regions_[g].end = g + 1 < n ? cuts[g + 1] : 0;
-      launch(g, g > 0, std::vector<uint8_t>());
+      launch(g, g > 0, std::vector<uint8_t>(), g < scanners.size() ? scanners[g] : nullptr);
     }
   }
-  void launch(size_t g, bool open_start, const std::vector<uint8_t>& carry) {
-    DeviceBamSelect::Region rg;
+  void launch(size_t g, bool open_start, const std::vector<uint8_t>& carry, BgzfScanner* scanner = nullptr) {
+    typename DeviceBamSelect<Out>::Region rg;
     rg.begin = regions_[g].begin; rg.end = regions_[g].end;
     rg.open_start = open_start; rg.open_end = g + 1 < regions_.size();
     rg.carry = carry;
     rg.loaders = regions_.size() > 1 ? std::max(2, 8 / (int)std::min<size_t>(regions_.size(), 4)) : 8;
-    rg.pending = g == 0 ? 64 : (size_t)1 << 30;       // (a later region's results wait in memory until the regions in front are handed out)
-    const std::vector<svdss_bam_filter_t*> one(1, nullptr);
-    const std::vector<int> dev(1, hooks_.device ? hooks_.device(g) : 0);
-    regions_[g].sel.reset(new DeviceBamSelect(path_, one, dev, n_ref_, g == 0 ? skip_ : 0, feeders_, batch_bytes_, hooks_.run(g, false),
-                                              hooks_.collect ? hooks_.collect(g, false) : DeviceBamSelect::CollectFn(),
-                                              hooks_.stream ? hooks_.stream(g) : nullptr, rg));
+    rg.pending = pending_;
+    rg.current = g == cur_;
+    regions_[g].sel.reset(new DeviceBamSelect<Out>(path_, 1, n_ref_, g == 0 ? skip_ : 0, feeders_, batch_bytes_, hooks_.run(g, false), hooks_.collect(g, false),
+                                                   hooks_.stream ? hooks_.stream(g) : nullptr, rg, scanner));
+  }
+  // a region's run is over (its feeding threads have ended): what it counted goes into the sums
+  void drop(Reg& R) {
+    int64_t n = 0;
+    n_rewalk_ += R.sel->segments_walked_again(&n);
+    n_seg_ += n;
+    wait_file_s_ += R.sel->waited_for_file();
+    wait_feed_s_ += R.sel->waited_for_feeders();
+    R.sel.reset();
   }
   // the seam in front of region g, proved; false = the run has failed (err_)
   bool enter(size_t g) {
@@ -489,24 +544,27 @@ class ShardedBamSelect {
     const int64_t n_tail = svdss_bam_stream_tail(P.sel->stream(), &tail);
     const std::vector<uint8_t> carry(tail, tail + (n_tail > 0 ? n_tail : 0));
     R.sel->wait_first();
-    bool good = R.sel->error().empty();
+    const BamRunError why = R.sel->failure();
+    bool good = !why.failed();
     if (good) {
       const int64_t n_head = svdss_bam_stream_head(R.sel->stream(), &head);
       if ((int64_t)carry.size() + n_head > 0) { good = run_seam(g, carry, head, n_head); ++n_seams_; }
     }
     if (!good) {
-      if (!err_.empty()) return false;
+      if (err_.failed()) return false;
       // not proved (or the region failed): once more, from the record the region in front ended in
       R.sel->wait_finished();
-      R.sel.reset();
+      drop(R);
       R.seam.reset();
-      if (hooks_.again) hooks_.again(g);
+      if (hooks_.again) hooks_.again(g, why.text());
       ++n_reruns_;
       launch(g, false, carry);
     }
-    P.sel.reset();       // (its stream's tail has been copied)
+    drop(P);       // (its stream's tail has been copied)
     return true;
   }
+  // the seam's bytes as a stream of their own: stored deflate blocks through the region's entry point.  false: not a
+  // chain of whole records (the guess was wrong), or the run has failed (err_)
   bool run_seam(size_t g, const std::vector<uint8_t>& tail, const uint8_t* head, int64_t n_head) {
     std::vector<uint8_t> bytes(tail);
     if (n_head > 0) bytes.insert(bytes.end(), head, head + n_head);
@@ -523,43 +581,28 @@ class ShardedBamSelect {
       comp.push_back((uint8_t)(~len & 0xff)); comp.push_back((uint8_t)((~len >> 8) & 0xff));
       comp.insert(comp.end(), bytes.begin() + (long)off, bytes.begin() + (long)(off + len));
       blk.push_back(b);
-      crc.push_back(bgzf_crc32(bytes.data() + off, len));
+      crc.push_back((uint32_t)crc32(crc32(0L, Z_NULL, 0), bytes.data() + off, (uInt)len));
     }
     comp.resize(comp.size() + 64);
     svdss_bam_stream_t* st = nullptr;
-    if (svdss_bam_stream_create(n_ref_, &st) != SVDSS_OK) { err_ = "out of memory"; return false; }
+    if (svdss_bam_stream_create(n_ref_, &st) != SVDSS_OK) { err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return false; }
     svdss_bam_batch_t* batch = nullptr;
     const uint8_t* cp = comp.data();
     const int64_t cb = (int64_t)comp.size(), nb = (int64_t)blk.size();
     const svdss_bgzf_block_t* bp = blk.data();
     const uint32_t* rp = crc.data();
     const int rc = hooks_.run(g, true)(st, 0, 1, 0, 0, 1, &cp, &cb, &bp, &rp, &nb, &batch);
-    bool ok = rc == SVDSS_OK;
+    const bool ok = rc == SVDSS_OK;
     if (ok) {
-      std::unique_ptr<SelectedBatch> out(new SelectedBatch);
-      if (hooks_.collect && hooks_.collect(g, true)) hooks_.collect(g, true)(batch, *out);
-      else {
-        svdss_bam_selection_t r;
-        (void)svdss_bam_batch_selection(batch, &r);
-        out->n_records = (uint64_t)r.n_records;
-        out->slim = r.slim != 0;
-        out->off.assign(r.rec_off, r.rec_off + r.n_selected + 1);
-        out->bytes.assign(r.bytes, r.bytes + r.n_bytes);
-      }
-      regions_[g].seam = std::move(out);
+      regions_[g].seam = hooks_.collect(g, true)(batch, 0);
       regions_[g].seam_stored = hooks_.seam_kept && hooks_.seam_kept(g);
     } else if (rc != SVDSS_EIO) {
-      err_ = std::string("seam: ") + svdss_strerror(rc) + " " + (batch ? svdss_bam_batch_error(batch) : "") + " " + svdss_last_hip_error();
+      err_ = BamRunError{rc, std::string("seam: ") + svdss_strerror(rc) + " " + (batch ? svdss_bam_batch_error(batch) : "") + " " + svdss_last_hip_error(),
+                         svdss_last_hip_error()};
     }
     if (batch) svdss_bam_batch_free(batch);
     svdss_bam_stream_free(st);
     return ok;
-  }
-  static uint32_t bgzf_crc32(const uint8_t* p, size_t n) {
-    static const std::vector<uint32_t> tab = [] { std::vector<uint32_t> t(256); for (uint32_t i = 0; i < 256; ++i) { uint32_t c = i; for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u))); t[i] = c; } return t; }();
-    uint32_t c = 0xffffffffu;
-    for (size_t i = 0; i < n; ++i) c = tab[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-    return c ^ 0xffffffffu;
   }
 
   std::string path_;
@@ -568,8 +611,10 @@ class ShardedBamSelect {
   int64_t skip_ = 0;
   int feeders_ = 3;
   int64_t batch_bytes_ = 0;
+  size_t pending_ = 64;
   std::vector<Reg> regions_;
   size_t cur_ = 0;
-  int64_t n_seams_ = 0, n_reruns_ = 0;
-  std::string err_;
+  int64_t n_seams_ = 0, n_reruns_ = 0, n_seg_ = 0, n_rewalk_ = 0;
+  double wait_file_s_ = 0, wait_feed_s_ = 0;
+  BamRunError err_;
 };

@@ -611,7 +611,7 @@ struct CallRun {
       // SVDSS_BAM_DEVICE=0: the host reader (chunks inflated on the GPU or the host, records sliced here).
       const bool dev_bam = svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0);
       std::unique_ptr<BamReader> bam_p;
-      std::unique_ptr<ShardedBamSelect> sel;
+      std::unique_ptr<ShardedBamSelect<SelectedBatch>> sel;
       std::vector<svdss_bam_filter_t*> filters;
       if (dev_bam) {
         if (bam_cuts.empty()) {      // (load_inputs probes the header; a caller that skipped it)
@@ -637,19 +637,19 @@ struct CallRun {
           for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
           stores.clear(); seam_stores.clear();
         }
-        std::vector<ShardedBamSelect::Shard> shards;
+        std::vector<ShardedBamSelect<SelectedBatch>::Shard> shards;
         for (size_t g = 0; g < n_reg; ++g) {
           svdss_bam_filter_t* f = nullptr;
           check(svdss_bam_filter_create((int32_t)(g % (size_t)n_phys), (int32_t)std::min<unsigned>(o.min_mapq, 256u), n_ref_hdr, names.data(), name_off.data(),
                                         (int64_t)name_off.size() - 1, nullptr, nullptr, nullptr, 0, &f), "svdss_bam_filter_create");
           filters.push_back(f);
-          ShardedBamSelect::Shard sh;
-          sh.filter = f; sh.device = (int)(g % (size_t)n_phys);
+          ShardedBamSelect<SelectedBatch>::Shard sh;
+          sh.filter = f;
           sh.store = stores.empty() ? nullptr : stores[g];
           sh.seam_store = seam_stores.empty() ? nullptr : seam_stores[g];
           shards.push_back(sh);
         }
-        sel.reset(new ShardedBamSelect(o.bam, shards, n_ref_hdr, bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts));
+        sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref_hdr, bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts));
         cache_ok = false;
         dev_pass = true;
       } else {
@@ -1226,18 +1226,18 @@ struct CallRun {
             const int n_phys = std::max(1, svdss_device_count());
             if (bam_cuts.empty()) bam_cuts = plan_bam_regions(o.bam, 1, bam_skip);
             std::vector<svdss_bam_filter_t*> filters;
-            std::vector<ShardedBamSelect::Shard> shards;
+            std::vector<ShardedBamSelect<SelectedBatch>::Shard> shards;
             for (size_t g = 0; g + 1 < bam_cuts.size(); ++g) {
               svdss_bam_filter_t* f = nullptr;
               check(svdss_bam_filter_create((int32_t)(g % (size_t)n_phys), (int32_t)std::min<unsigned>(o.min_mapq, 256u), (int32_t)ref_names.size(), nullptr, nullptr, 0,
                                             rt.data(), rb.data(), re.data(), (int64_t)rt.size(), &f), "svdss_bam_filter_create");
               filters.push_back(f);
-              ShardedBamSelect::Shard sh;
-              sh.filter = f; sh.device = (int)(g % (size_t)n_phys);
+              ShardedBamSelect<SelectedBatch>::Shard sh;
+              sh.filter = f;
               shards.push_back(sh);
             }
             {
-              ShardedBamSelect sel(o.bam, shards, (int32_t)ref_names.size(), bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts);
+              ShardedBamSelect<SelectedBatch> sel(o.bam, shards, (int32_t)ref_names.size(), bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts);
               BamReader::RawView rr;
               while (std::unique_ptr<SelectedBatch> sb = sel.next())
                 for (size_t k = 0; k + 1 < sb->off.size(); ++k) {

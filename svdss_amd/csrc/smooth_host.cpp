@@ -238,8 +238,6 @@ int main_smooth(const CallOptions& o) {
     const int64_t skip = hp.skip;
     const int64_t target = (getenv("SVDSS_BAM_BATCH_MB") && atoll(getenv("SVDSS_BAM_BATCH_MB")) > 0 ? atoll(getenv("SVDSS_BAM_BATCH_MB")) : 64) << 20;
     const int per_gpu = getenv("SVDSS_SEARCH_FEEDERS") ? std::max(1, atoi(getenv("SVDSS_SEARCH_FEEDERS"))) : 6;
-    const std::vector<svdss_bam_filter_t*> one(1, nullptr);
-    const std::vector<int> dev0(1, 0);
     // --gpus N (round 6): the file's regions, one per GPU (ShardedBamSelect, bam_device_select.h: the machinery of `SVDSS call
     // --gpus N`) -- every region has its own loaders, feeding threads and record stream, and every GPU its copy of the
     // chromosomes; SVDSS_GPUS_OVERSUBSCRIBE puts the N regions on the GPUs there are.  The records and their order are those
@@ -313,9 +311,9 @@ int main_smooth(const CallOptions& o) {
     // (the pool is the first region's: a later region's members wait in plain memory until the regions in front are written,
     // and would hold every buffer of the pool while the first region's feeders wait for one)
     auto run_for = [&](size_t g, bool use_pool) {
-      return DeviceBamSelect::RunFn([&, g, use_pool](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t, int32_t nc, const uint8_t* const* comp,
-                                                     const int64_t* cb, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb,
-                                                     svdss_bam_batch_t** batch) {
+      return BamRunFn([&, g, use_pool](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t, int32_t nc, const uint8_t* const* comp,
+                                       const int64_t* cb, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb,
+                                       svdss_bam_batch_t** batch) {
         { std::unique_lock<std::mutex> lk(gate.m); gate.cv.wait(lk, [&] { return gate.open; }); }
         tl_slot = use_pool ? pool.take() : -1;
         const int rc = svdss_bam_smooth_run(st, seq, last, sk, sms[g % sms.size()], al_accuracy, tl_slot >= 0 ? pool.buf[(size_t)tl_slot] : nullptr,
@@ -324,32 +322,33 @@ int main_smooth(const CallOptions& o) {
         return rc;
       });
     };
-    DeviceBamSelect::CollectFn collect = [&](const svdss_bam_batch_t* b, SelectedBatch& out) {
+    DeviceBamSelect<SelectedBatch>::CollectFn collect = [&](const svdss_bam_batch_t* b, uint64_t) {
+      std::unique_ptr<SelectedBatch> out(new SelectedBatch);
       svdss_bam_smoothed_t r;
       (void)svdss_bam_batch_smoothed(b, &r);
-      out.n_records = (uint64_t)r.n_records; out.n_kept = (uint64_t)r.n_kept;
-      for (int k = 0; k < 4; ++k) out.n_xf[k] = (uint64_t)r.n_xf[k];
-      if (tl_slot >= 0 && r.bgzf == pool.buf[(size_t)tl_slot]) { out.ext = r.bgzf; out.ext_n = (size_t)r.bgzf_bytes; out.ext_slot = tl_slot; }
+      out->n_records = (uint64_t)r.n_records; out->n_kept = (uint64_t)r.n_kept;
+      for (int k = 0; k < 4; ++k) out->n_xf[k] = (uint64_t)r.n_xf[k];
+      if (tl_slot >= 0 && r.bgzf == pool.buf[(size_t)tl_slot]) { out->ext = r.bgzf; out->ext_n = (size_t)r.bgzf_bytes; out->ext_slot = tl_slot; }
       else {
-        out.bytes.assign(r.bgzf, r.bgzf + r.bgzf_bytes);
+        out->bytes.assign(r.bgzf, r.bgzf + r.bgzf_bytes);
         if (tl_slot >= 0) pool.give(tl_slot);
       }
       tl_slot = -1;
-      for (int k = 0; k < 8; ++k) out.stage_s[k] = r.stage_ms[k] * 1e-3;
-      out.inflate_kernel_s = r.inflate_kernel_ms * 1e-3;
+      for (int k = 0; k < 8; ++k) out->stage_s[k] = r.stage_ms[k] * 1e-3;
+      out->inflate_kernel_s = r.inflate_kernel_ms * 1e-3;
+      return out;
     };
     if (dbg) fprintf(stderr, "[smooth] BAM header read, output prefix set at +%.3f s\n", since());
-    std::unique_ptr<DeviceBamSelect> rd;
-    std::unique_ptr<ShardedBamSelect> rds;
-    if (n_regions == 1) rd.reset(new DeviceBamSelect(o.bam, one, dev0, n_ref, skip, per_gpu, target, run_for(0, true), collect, stream));
+    std::unique_ptr<DeviceBamSelect<SelectedBatch>> rd;
+    std::unique_ptr<ShardedBamSelect<SelectedBatch>> rds;
+    if (n_regions == 1) rd.reset(new DeviceBamSelect<SelectedBatch>(o.bam, 1, n_ref, skip, per_gpu, target, run_for(0, true), collect, stream));
     else {
-      ShardedBamSelect::Hooks hk;
+      ShardedBamSelect<SelectedBatch>::Hooks hk;
       hk.run = [&](size_t g, bool seam) { return run_for(g, g == 0 && !seam); };
       hk.collect = [&](size_t, bool) { return collect; };
       // (the output's header is in front of the first region's stream; the first region never runs again)
       hk.stream = [&](size_t g) { svdss_bam_stream_t* st = g == 0 ? stream : nullptr; if (g == 0) stream = nullptr; return st; };
-      hk.device = [&](size_t g) { return (int)(g % (size_t)n_phys); };
-      rds.reset(new ShardedBamSelect(o.bam, hk, n_ref, skip, per_gpu, target, cuts));
+      rds.reset(new ShardedBamSelect<SelectedBatch>(o.bam, hk, n_ref, skip, per_gpu, target, cuts));
     }
     if (dbg) fprintf(stderr, "[smooth] reader of the smoothing pass started at +%.3f s\n", since());
     // the chromosomes the BAM names, in its order, one device buffer (svdss_ref_upload_parts: no concatenation on the host)
@@ -381,20 +380,22 @@ int main_smooth(const CallOptions& o) {
     // compute_maxaccuracy (smoother.cpp:259-346): the mismatch rates of the first 10,000 records that fit, their percentile
     {
       std::vector<double> acc;
-      DeviceBamSelect::RunFn mrun = [&](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t, int32_t nc, const uint8_t* const* comp,
-                                       const int64_t* cb, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb,
-                                       svdss_bam_batch_t** batch) {
+      BamRunFn mrun = [&](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t, int32_t nc, const uint8_t* const* comp,
+                          const int64_t* cb, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb,
+                          svdss_bam_batch_t** batch) {
         return svdss_bam_smooth_measure(st, seq, last, sk, sms[0], nc, comp, cb, blocks, crc, nb, batch);
       };
-      DeviceBamSelect::CollectFn mcollect = [](const svdss_bam_batch_t* b, SelectedBatch& out) {
+      DeviceBamSelect<SelectedBatch>::CollectFn mcollect = [](const svdss_bam_batch_t* b, uint64_t) {
+        std::unique_ptr<SelectedBatch> out(new SelectedBatch);
         svdss_bam_smoothed_t r;
         (void)svdss_bam_batch_smoothed(b, &r);
-        out.n_records = (uint64_t)r.n_records; out.n_kept = (uint64_t)r.n_kept;
-        out.match_mismatch.assign(r.match_mismatch, r.match_mismatch + 2 * r.n_kept);
-        out.fits.assign(r.fits, r.fits + r.n_kept);
+        out->n_records = (uint64_t)r.n_records; out->n_kept = (uint64_t)r.n_kept;
+        out->match_mismatch.assign(r.match_mismatch, r.match_mismatch + 2 * r.n_kept);
+        out->fits.assign(r.fits, r.fits + r.n_kept);
+        return out;
       };
       // (10,000 records are a few tens of megabytes: small batches, two feeders, and the reader is dropped as soon as it has them)
-      DeviceBamSelect pre(o.bam, one, dev0, n_ref, skip, 2, std::min<int64_t>(target, (int64_t)48 << 20), mrun, mcollect);
+      DeviceBamSelect<SelectedBatch> pre(o.bam, 1, n_ref, skip, 2, std::min<int64_t>(target, (int64_t)48 << 20), mrun, mcollect);
       while (acc.size() < 10000) {
         std::unique_ptr<SelectedBatch> b = pre.next();
         if (!b) { if (!pre.error().empty()) die("error reading " + o.bam + ": " + pre.error()); break; }

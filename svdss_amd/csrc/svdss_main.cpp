@@ -349,24 +349,18 @@ static void format_batch(const Options& o, SearchBatch& b) {
 }
 
 // ---- `search --bam` with the records handled where they are inflated (csrc/bam_device.hip): the host reads the file,
-// finds the BGZF members, hands runs of them to the GPUs and gets names, tags and SFS back.  Stages, PER REGION of the
-// file: scanner (loader threads) -> batcher -> feeding threads (svdss_bam_batch_run, one batch object each); then, once
-// for the file: assembler (device batches end where a BGZF member ends; the text is defined on batches of --bsize reads,
-// ping_pong.cpp:213-236: the reads are dealt again into units of whole reference batches) -> formatting threads ->
-// writer.  The same bytes as the host path.
+// finds the BGZF members, hands runs of them to the GPUs and gets names, tags and SFS back -- through the front end that
+// `call` and `smooth` read the file with as well (bam_device_select.h: scanner -> batcher -> feeding threads ->
+// ordered hand-over, per region of the file).  Then, once for the file: assembler (device batches end where a BGZF member
+// ends; the text is defined on batches of --bsize reads, ping_pong.cpp:213-236: the reads are dealt again into units of
+// whole reference batches) -> formatting threads -> writer.  The same bytes as the host path.
 //
 // --gpus N (north_star: "BAM regions partition across the GPUs"; the per-shard loop of ping_pong.cpp:53-128): the file is
 // cut at BGZF members into N regions of about equal size, every GPU reads, inflates, walks and searches its own region
-// with its own scanner, batcher and feeders -- nothing is shared on the way in.  A region that does not begin the file
-// begins inside a record: its first batch starts the record chain at the first record its segments guess
-// (svdss_bam_stream_region) and sets the bytes in front aside; when the region before it has ended, what that one left
-// over and those bytes go through the device as a batch of their own (the SEAM: normally one record): if they are a
-// chain of whole records the guess is proved, if not -- or if the region failed in any way -- the region runs again from
-// the known carry.  The reads of a region are dealt into units when everything before it has been (the unit a read
-// belongs to depends on the reads in front of it), so the later regions' results wait in memory (~0.6 KB per read).
-struct DevJob { uint64_t seq = 0; bool last = false; std::vector<std::unique_ptr<CompChunk>> chunks; };
+// (ShardedBamSelect: a region's first record is guessed, and proved at the seam or the region runs again).  The reads of a
+// region are dealt into units when everything before it has been (the unit a read belongs to depends on the reads in front
+// of it), so the later regions' results wait in memory (~0.6 KB per read).
 struct DevOut { std::vector<Read> reads; std::vector<int32_t> qs, ln; int64_t n_short = 0; std::vector<int32_t> sidx; };
-struct BamRegion;
 // `SVDSS search` with the BAM front end started BEFORE the index is resident (include/svdss_hip.h, svdss_bam_park_*): while
 // `ix` is null the feeders run the front half of their batches and park the unpacked reads in HBM; when the index is there the
 // parked groups are searched one large launch each, and the feeders go on with whole batches.
@@ -378,7 +372,7 @@ struct EarlySearch {
   bool ready = false;
   bool ix_avail = false;            // the index is resident but held back from the feeders (the rank blocks alone): the drain
                                     // thread may search the groups that have closed while the later ones still fill
-  struct Pending { BamRegion* R; uint64_t seq; std::unique_ptr<DevOut> out; int64_t first, n; };
+  struct Pending { uint64_t seq; std::unique_ptr<DevOut> out; int64_t first, n; };
   std::map<int64_t, std::vector<Pending>> by_group;     // under m
   // what the front end has seen so far (the order of the k-mer table is chosen from it: svdss_index_kmer_limit)
   std::atomic<int64_t> records{0}, searched{0}, comp_bytes{0}, index_n{0};
@@ -388,26 +382,11 @@ struct EarlySearch {
   int64_t file_bytes = 0;
   int kmer_limit = 0;               // the last limit given (under m)
 };
-struct BamRegion {
-  size_t begin = 0, end = 0;                 // file range (member starts)
-  std::unique_ptr<BgzfScanner> sc;
-  std::vector<svdss_index_t*> gpus;          // the replicas whose feeders take this region's batches
-  svdss_bam_stream_t* stream = nullptr;
-  int64_t skip = 0;                          // inflated bytes of BAM header in front (the file's first region)
-  bool open_start = false, open_end = false;
-  std::unique_ptr<BoundedQueue<DevJob>> jobs;
-  std::vector<std::thread> threads;          // batcher + feeders
-  // under dev_m:
-  std::map<uint64_t, std::unique_ptr<DevOut>> done;
-  bool finished = false;                     // its threads have ended
-  bool head_known = false;                   // batch 0 had its turn (svdss_bam_stream_head is final)
-  std::string error;                         // open_start only: why the run failed (the region runs again)
-};
 
-// (plan_bam_regions: bam_device_select.h -- where the regions of a file begin, shared with `SVDSS call --gpus N`)
-
-static void search_bam_device(const Options& o, const std::vector<svdss_index_t*>& replicas, std::vector<BamRegion>& regions,
-                              const BgzfScanner::Hooks& hooks, size_t slab, int loaders, size_t pool_chunks, int32_t n_ref,
+// cuts: the file's regions (plan_bam_regions); scanners: one per region, opened by the caller and kept open past the call
+// (the process ends with _exit: their page-locked slabs are never handed back one by one)
+static void search_bam_device(const Options& o, const std::vector<svdss_index_t*>& replicas, const std::vector<size_t>& cuts,
+                              const std::vector<BgzfScanner*>& scanners, int32_t n_ref, int64_t skip,
                               const std::function<std::string()>& since, EarlySearch* early = nullptr) {
   const int64_t super = std::max<int64_t>(o.bsize, 32768 / o.bsize * (int64_t)o.bsize);
   const int64_t target = (getenv("SVDSS_BAM_BATCH_MB") && atoll(getenv("SVDSS_BAM_BATCH_MB")) > 0 ? atoll(getenv("SVDSS_BAM_BATCH_MB")) : 192) << 20;
@@ -417,133 +396,37 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
   std::mutex t_m;
   double t_gpu = 0, t_inflate_ms = 0, t_build = 0, t_format = 0, t_write = 0, t_assemble = 0;
   double t_stage[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double t_wait_file = 0, t_wait_gpu = 0;       // (the batchers')
   uint64_t n_seen = 0, n_batches = 0, total_sfs = 0;
-  int64_t n_seg_all = 0, n_rewalk_all = 0, n_seams = 0, n_reruns = 0;
   const int32_t flags = (o.assemble ? SVDSS_SFS_ASSEMBLE : 0) | (o.putative ? SVDSS_BAM_PUTATIVE : 0);
 
-  // device batches in file order, region after region
-  std::mutex dev_m;
-  std::condition_variable dev_cv;
-  size_t cursor = 0;            // the region the assembler is taking batches from (under dev_m)
-
-  // what a batch object holds after its run -> reads with their SFS
-  auto collect = [&](svdss_bam_batch_t* batch, double gpu_s, std::chrono::steady_clock::time_point t1, bool searched = true) {
-    svdss_bam_result_t r;
-    check(svdss_bam_batch_result(batch, &r), "svdss_bam_batch_result");
-    std::unique_ptr<DevOut> out(new DevOut);
-    out->n_short = r.n_short;
-    out->reads.resize((size_t)r.n_slots);
-    if (!searched) {
-      // the front half only: names and tags; counts and SFS follow when the batch's group has been searched (fill_parked)
-      out->sidx.assign(r.sidx, r.sidx + r.n_slots);
-      for (int64_t i = 0; i < r.n_slots; ++i) {
-        Read& rd = out->reads[(size_t)i];
-        rd.name.assign(r.names + r.name_off[i], (size_t)(r.name_off[i + 1] - r.name_off[i]));
-        rd.hp = r.hp[i];
-        rd.count = r.sidx[i] < 0 ? -1 : 0; rd.first = 0;
-      }
-    } else {
-    out->qs.assign(r.qs, r.qs + r.total_sfs);
-    out->ln.assign(r.len, r.len + r.total_sfs);
-    {
-      // (searched reads are numbered in slot order, so their SFS follow each other in slot order too)
-      int64_t acc = 0;
-      for (int64_t i = 0; i < r.n_slots; ++i) {
-        Read& rd = out->reads[(size_t)i];
-        rd.name.assign(r.names + r.name_off[i], (size_t)(r.name_off[i + 1] - r.name_off[i]));
-        rd.hp = r.hp[i];
-        if (r.sidx[i] < 0) { rd.count = -1; rd.first = acc; }
-        else { rd.first = acc; rd.count = r.counts[r.sidx[i]]; acc += rd.count; }
-      }
-    }
-    }
-    std::lock_guard<std::mutex> lk(t_m);
-    t_gpu += gpu_s; t_build += secs(t1, now()); t_inflate_ms += r.inflate_kernel_ms;
-    n_seen += (uint64_t)r.n_records; ++n_batches;
-    for (int k = 0; k < 8; ++k) t_stage[k] += r.stage_ms[k] * 1e-3;
-    return out;
-  };
-
-  auto batcher = [&](BamRegion& R) {
-    BgzfScanner& sc = *R.sc;
-    std::unique_ptr<DevJob> cur(new DevJob);
-    int64_t acc = 0;
-    uint64_t seq = 0;
-    bool any_last = false;
-    double w_file = 0, w_gpu = 0;
-    for (;;) {
-      const auto w0 = now();
-      std::unique_ptr<CompChunk> c = sc.next();
-      w_file += secs(w0, now());           // (the loaders behind: the file is what bounds the run)
-      if (!c) break;
-      acc += c->inflated;
-      const bool last = c->last;
-      cur->chunks.push_back(std::move(c));
-      if (acc >= target || last) {
-        cur->seq = seq++;
-        cur->last = last;
-        any_last = any_last || last;
-        const auto w1 = now();
-        R.jobs->push(std::move(cur));
-        w_gpu += secs(w1, now());          // (the feeding threads behind: the GPU side is)
-        cur.reset(new DevJob);
-        acc = 0;
-      }
-    }
-    if (!sc.error().empty()) {
-      if (!R.open_start) die("error reading " + o.bam + ": " + sc.error());
-      std::lock_guard<std::mutex> lk(dev_m);
-      if (R.error.empty()) R.error = sc.error();
-    } else if (!any_last) {            // (an empty region; cannot happen otherwise: the scanner marks the final slab)
-      cur->seq = seq++;
-      cur->last = true;
-      R.jobs->push(std::move(cur));
-    }
-    R.jobs->close();
-    std::lock_guard<std::mutex> lk(t_m);
-    t_wait_file += w_file; t_wait_gpu += w_gpu;
-  };
-
-  auto feeder = [&](BamRegion& R, size_t g, svdss_index_t* ix) {
-    svdss_bam_batch_t* batch = nullptr;
-    std::vector<const uint8_t*> comp;
-    std::vector<int64_t> comp_bytes, n_blocks;
-    std::vector<const svdss_bgzf_block_t*> blocks;
-    std::vector<const uint32_t*> crcs;
-    while (std::unique_ptr<DevJob> job = R.jobs->pop()) {
+  // a batch through the device on replica (r + dev): the whole of it -- or, early, while the index is not resident, its front
+  // half, the reads parked
+  auto run_on = [&](size_t r) {
+    return BamRunFn([&, r](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t dev, int32_t nc, const uint8_t* const* comp, const int64_t* cb,
+                           const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb, svdss_bam_batch_t** batch) {
       const auto t0 = now();
-      comp.clear(); comp_bytes.clear(); n_blocks.clear(); blocks.clear(); crcs.clear();
-      for (const std::unique_ptr<CompChunk>& c : job->chunks) {
-        comp.push_back(c->data); comp_bytes.push_back((int64_t)c->n_bytes); n_blocks.push_back((int64_t)c->blocks.size());
-        blocks.push_back(c->blocks.data()); crcs.push_back(c->crc.data());
-      }
-      // (early: while the index is being restored the front half of the batch runs and its reads are parked)
+      svdss_index_t* ix = replicas[(r + dev) % replicas.size()];
       bool front_only = false;
       if (early) {
         std::lock_guard<std::mutex> lk(early->m);
         if (early->ready) ix = early->ix; else front_only = true;
       }
-      int64_t job_comp = 0;
-      for (const std::unique_ptr<CompChunk>& c : job->chunks) job_comp += (int64_t)c->n_bytes;
-      int rc = front_only
-                   ? svdss_bam_batch_front(R.stream, (int64_t)job->seq, job->last ? 1 : 0, job->seq == 0 ? R.skip : 0, 0, early->park, (int32_t)comp.size(),
-                                           comp.data(), comp_bytes.data(), blocks.data(), crcs.data(), n_blocks.data(), flags, &batch)
-                   : svdss_bam_batch_run(R.stream, (int64_t)job->seq, job->last ? 1 : 0, job->seq == 0 ? R.skip : 0, ix, (int32_t)comp.size(),
-                                         comp.data(), comp_bytes.data(), blocks.data(), crcs.data(), n_blocks.data(), flags, &batch);
-      for (std::unique_ptr<CompChunk>& c : job->chunks) R.sc->recycle(std::move(c));
+      int rc = front_only ? svdss_bam_batch_front(st, seq, last, sk, 0, early->park, nc, comp, cb, blocks, crc, nb, flags, batch)
+                          : svdss_bam_batch_run(st, seq, last, sk, ix, nc, comp, cb, blocks, crc, nb, flags, batch);
       if (rc == SVDSS_OK && front_only) {
-        int64_t grp = -1, first = 0, n_srch = 0;
-        check(svdss_bam_batch_parked(batch, &grp, &first, &n_srch), "svdss_bam_batch_parked");
+        int64_t grp = -1;
+        check(svdss_bam_batch_parked(*batch, &grp, nullptr, nullptr), "svdss_bam_batch_parked");
         {
           // how much there will be to search, from what has been seen: the order of the k-mer table (its build begins when the
           // suffix array is sorted; the limit is read then)
           svdss_bam_result_t r0;
-          check(svdss_bam_batch_result(batch, &r0), "svdss_bam_batch_result");
-          const int64_t recs = (early->records += r0.n_records), srch = (early->searched += r0.n_searched), cb = (early->comp_bytes += job_comp);
+          check(svdss_bam_batch_result(*batch, &r0), "svdss_bam_batch_result");
+          int64_t job_comp = 0;
+          for (int32_t k = 0; k < nc; ++k) job_comp += cb[k];
+          const int64_t recs = (early->records += r0.n_records), srch = (early->searched += r0.n_searched), cbytes = (early->comp_bytes += job_comp);
           const int64_t n_ix = early->index_n.load();
-          if (n_ix >= ((int64_t)1 << 31) && recs >= 50000 && cb > 0 && !getenv("SVDSS_KMER") && !getenv("SVDSS_NO_KMER_LIMIT")) {
-            const double est = (double)srch / (double)recs * ((double)recs * (double)early->file_bytes / (double)cb);
+          if (n_ix >= ((int64_t)1 << 31) && recs >= 50000 && cbytes > 0 && !getenv("SVDSS_KMER") && !getenv("SVDSS_NO_KMER_LIMIT")) {
+            const double est = (double)srch / (double)recs * ((double)recs * (double)early->file_bytes / (double)cbytes);
             // build: 1.6 s at K = 16, a quarter of that per step down; kernel: 16 M reads/s at K = 16, half of that per step down
             // (profiles/r05i_restore_by_table_order.txt); its seconds count double, as in main_search
             auto cost = [&](int k) { return 1.6 * std::pow(4.0, k - 16) + 2 * est / 16e6 * std::pow(2.2, 16 - k); };
@@ -554,110 +437,81 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
             if (best != early->kmer_limit) { early->kmer_limit = best; svdss_index_kmer_limit(best == 16 ? 0 : best); }
           }
         }
-        if (grp >= 0) {
-          const auto t1 = now();
-          std::unique_ptr<DevOut> out = collect(batch, secs(t0, t1), t1, false);
-          { std::lock_guard<std::mutex> lk(early->m); early->by_group[grp].push_back(EarlySearch::Pending{&R, job->seq, std::move(out), first, n_srch}); }
-          early->cv.notify_all();
-          continue;
-        }
         if (grp == -1) {
           // no room in the park (or it has just been closed): this batch waits here for the index
           { std::unique_lock<std::mutex> lk(early->m); early->park_full = true; early->cv.notify_all(); early->cv.wait(lk, [&] { return early->ready; }); ix = early->ix; }
-          rc = svdss_bam_batch_search(batch, ix);
+          rc = svdss_bam_batch_search(*batch, ix);
         }   // (grp == -2: nothing to search in this batch, its results are complete)
       }
-      if (rc != SVDSS_OK) {
-        std::string msg = batch ? svdss_bam_batch_error(batch) : "";
-        if (msg.empty()) msg = svdss_bam_stream_error(R.stream);
-        if (R.open_start) {
-          // (a guess that was not a record can end in any of the messages below: the region runs again from the known
-          // carry and says then what a reader of the whole file would have said)
-          { std::lock_guard<std::mutex> lk(dev_m); if (R.error.empty()) R.error = msg.empty() ? svdss_strerror(rc) : msg; R.head_known = true; }
-          dev_cv.notify_all();
-          continue;   // (the stream has failed: the batches left return at once; the queue drains)
-        }
-        if (msg.find("core.tid") != std::string::npos) die(msg);                       // ping_pong.cpp:76-79
-        if (rc == SVDSS_EIO) die("error reading " + o.bam + ": " + msg);
-        die(std::string("svdss_bam_batch_run: ") + svdss_strerror(rc) + " " + msg + " " + svdss_last_hip_error());
-      }
-      const auto t1 = now();
-      std::unique_ptr<DevOut> out = collect(batch, secs(t0, t1), t1);
-      {
-        std::unique_lock<std::mutex> lk(dev_m);
-        const uint64_t sq = job->seq;
-        // (only the region the assembler is at holds its feeders back; the others' results wait for their turn)
-        dev_cv.wait(lk, [&] { return cursor != g || R.done.size() < 8 || R.done.begin()->first > sq; });
-        R.done[sq] = std::move(out);
-        R.head_known = true;
-      }
-      dev_cv.notify_all();
-    }
-    svdss_bam_batch_free(batch);
+      std::lock_guard<std::mutex> lk(t_m);
+      t_gpu += secs(t0, now());
+      return rc;
+    });
   };
 
-  auto launch = [&](BamRegion& R, size_t g, const uint8_t* carry, int64_t n_carry) {
-    if (!R.sc) R.sc.reset(new BgzfScanner(o.bam, hooks, slab, loaders, pool_chunks, R.begin, R.end));
-    if (!R.sc->ok()) die("cannot open " + o.bam);
-    check(svdss_bam_stream_create(n_ref, &R.stream), "svdss_bam_stream_create");
-    check(svdss_bam_stream_region(R.stream, R.open_start ? 1 : 0, R.open_end ? 1 : 0, carry, n_carry), "svdss_bam_stream_region");
-    R.jobs.reset(new BoundedQueue<DevJob>(2));
-    R.threads.emplace_back(batcher, std::ref(R));
-    for (svdss_index_t* ix : R.gpus)
-      for (int k = 0; k < per_gpu; ++k) R.threads.emplace_back(feeder, std::ref(R), g, ix);
-  };
-  auto join_region = [&](BamRegion& R) {
-    for (std::thread& th : R.threads) th.join();
-    R.threads.clear();
-    int64_t n_seg = 0;
-    const int64_t rew = svdss_bam_stream_rewalked(R.stream, &n_seg);
-    { std::lock_guard<std::mutex> lk(t_m); n_seg_all += n_seg; n_rewalk_all += rew; }
-    if (early) return;      // (its parked batches are still to come: finished when they have been searched and handed over)
-    { std::lock_guard<std::mutex> lk(dev_m); R.finished = true; }
-    dev_cv.notify_all();
+  // what a batch object holds after its run -> reads with their SFS.  A batch whose reads went into the park has names and
+  // tags only: it waits in early->by_group, and the drain thread below delivers it when its group has been searched.
+  auto collect = [&](const svdss_bam_batch_t* batch, uint64_t seq) -> std::unique_ptr<DevOut> {
+    const auto t1 = now();
+    int64_t grp = -1, first = 0, n_srch = 0;
+    const bool parked = early && svdss_bam_batch_parked(batch, &grp, &first, &n_srch) == SVDSS_OK && grp >= 0;
+    svdss_bam_result_t r;
+    check(svdss_bam_batch_result(batch, &r), "svdss_bam_batch_result");
+    std::unique_ptr<DevOut> out(new DevOut);
+    out->n_short = r.n_short;
+    out->reads.resize((size_t)r.n_slots);
+    if (parked) {
+      // the front half only: names and tags; counts and SFS follow when the batch's group has been searched
+      out->sidx.assign(r.sidx, r.sidx + r.n_slots);
+      for (int64_t i = 0; i < r.n_slots; ++i) {
+        Read& rd = out->reads[(size_t)i];
+        rd.name.assign(r.names + r.name_off[i], (size_t)(r.name_off[i + 1] - r.name_off[i]));
+        rd.hp = r.hp[i];
+        rd.count = r.sidx[i] < 0 ? -1 : 0; rd.first = 0;
+      }
+    } else {
+      out->qs.assign(r.qs, r.qs + r.total_sfs);
+      out->ln.assign(r.len, r.len + r.total_sfs);
+      // (searched reads are numbered in slot order, so their SFS follow each other in slot order too)
+      int64_t acc = 0;
+      for (int64_t i = 0; i < r.n_slots; ++i) {
+        Read& rd = out->reads[(size_t)i];
+        rd.name.assign(r.names + r.name_off[i], (size_t)(r.name_off[i + 1] - r.name_off[i]));
+        rd.hp = r.hp[i];
+        if (r.sidx[i] < 0) { rd.count = -1; rd.first = acc; }
+        else { rd.first = acc; rd.count = r.counts[r.sidx[i]]; acc += rd.count; }
+      }
+    }
+    {
+      std::lock_guard<std::mutex> lk(t_m);
+      t_build += secs(t1, now()); t_inflate_ms += r.inflate_kernel_ms;
+      n_seen += (uint64_t)r.n_records; ++n_batches;
+      for (int k = 0; k < 8; ++k) t_stage[k] += r.stage_ms[k] * 1e-3;
+    }
+    if (!parked) return out;
+    { std::lock_guard<std::mutex> lk(early->m); early->by_group[grp].push_back(EarlySearch::Pending{seq, std::move(out), first, n_srch}); }
+    early->cv.notify_all();
+    return nullptr;
   };
 
-  // the seam in front of region g: `tail` (what the region before left) + `head` (what region g set aside) as a stream of
-  // its own -- stored deflate blocks, the same entry point.  false: not a chain of whole records (the guess was wrong).
-  auto run_seam = [&](const uint8_t* tail, int64_t n_tail, const uint8_t* head, int64_t n_head, svdss_index_t* ix, std::unique_ptr<DevOut>& out) {
-    std::vector<uint8_t> bytes((size_t)(n_tail + n_head));
-    if (n_tail) memcpy(bytes.data(), tail, (size_t)n_tail);
-    if (n_head) memcpy(bytes.data() + n_tail, head, (size_t)n_head);
-    std::vector<uint8_t> comp;
-    std::vector<svdss_bgzf_block_t> blk;
-    std::vector<uint32_t> crc;
-    for (size_t off = 0; off < bytes.size(); off += 0xff00) {
-      const size_t len = std::min<size_t>(0xff00, bytes.size() - off);
-      while (comp.size() & 15) comp.push_back(0);
-      svdss_bgzf_block_t b;
-      b.coff = (int64_t)comp.size(); b.clen = (int32_t)(5 + len); b.isize = (int32_t)len; b.uoff = 0;
-      comp.push_back(1);   // BFINAL, stored
-      comp.push_back((uint8_t)(len & 0xff)); comp.push_back((uint8_t)(len >> 8));
-      comp.push_back((uint8_t)(~len & 0xff)); comp.push_back((uint8_t)((~len >> 8) & 0xff));
-      comp.insert(comp.end(), bytes.begin() + (long)off, bytes.begin() + (long)(off + len));
-      blk.push_back(b);
-      crc.push_back((uint32_t)crc32(crc32(0L, Z_NULL, 0), bytes.data() + off, (uInt)len));
-    }
-    comp.resize(comp.size() + 64);
-    svdss_bam_stream_t* st = nullptr;
-    check(svdss_bam_stream_create(n_ref, &st), "svdss_bam_stream_create");
-    svdss_bam_batch_t* batch = nullptr;
-    const uint8_t* cp = comp.data();
-    const int64_t cb = (int64_t)comp.size(), nb = (int64_t)blk.size();
-    const svdss_bgzf_block_t* bp = blk.data();
-    const uint32_t* rp = crc.data();
-    const auto t0 = now();
-    const int rc = svdss_bam_batch_run(st, 0, 1, 0, ix, 1, &cp, &cb, &bp, &rp, &nb, flags, &batch);
-    bool ok = rc == SVDSS_OK;
-    if (ok) { const auto t1 = now(); out = collect(batch, secs(t0, t1), t1); }
-    else {
-      const std::string msg = batch ? svdss_bam_batch_error(batch) : "";
-      if (rc != SVDSS_EIO) die(std::string("svdss_bam_batch_run (seam): ") + svdss_strerror(rc) + " " + msg + " " + svdss_last_hip_error());
-    }
-    svdss_bam_batch_free(batch);
-    svdss_bam_stream_free(st);
-    return ok;
-  };
+  // the file's batches in file order: one region (every replica's feeders take its batches) or one region per replica
+  std::unique_ptr<DeviceBamSelect<DevOut>> one;
+  std::unique_ptr<ShardedBamSelect<DevOut>> sharded;
+  const size_t pending = 8;       // (results of the region being dealt that may wait for the assembler)
+  if (cuts.size() == 2) {
+    DeviceBamSelect<DevOut>::Region rg;
+    rg.pending = pending;
+    one.reset(new DeviceBamSelect<DevOut>(o.bam, replicas.size(), n_ref, skip, per_gpu, target, run_on(0), collect, nullptr, rg, scanners[0]));
+  } else {
+    ShardedBamSelect<DevOut>::Hooks hk;
+    hk.run = [&](size_t g, bool) { return run_on(g); };
+    hk.collect = [&](size_t, bool) { return DeviceBamSelect<DevOut>::CollectFn(collect); };
+    hk.again = [&](size_t g, const std::string& why) {
+      if (o.verbose) logmsg("debug", "region " + std::to_string(g) + " runs again from the end of region " + std::to_string(g - 1) +
+                                         (why.empty() ? std::string(" (its first record was not where the chain arrives)") : " (" + why + ")"));
+    };
+    sharded.reset(new ShardedBamSelect<DevOut>(o.bam, hk, n_ref, skip, per_gpu, target, cuts, pending, scanners));
+  }
 
   // units of whole reference batches, formatted by a few threads, written in order
   BoundedQueue<SearchBatch> units(4);
@@ -700,61 +554,12 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
       }
       t_assemble += secs(ta, now());
     };
-    for (size_t g = 0; g < regions.size(); ++g) {
-      BamRegion& R = regions[g];
-      std::thread rerun_joiner;
-      if (g > 0) {
-        // the region in front has ended and is dealt: its tail is final.  This region's head: after its first batch.
-        BamRegion& P = regions[g - 1];
-        const uint8_t *tail = nullptr, *head = nullptr;
-        const int64_t n_tail = svdss_bam_stream_tail(P.stream, &tail);
-        bool good;
-        {
-          std::unique_lock<std::mutex> lk(dev_m);
-          dev_cv.wait(lk, [&] { return R.head_known || R.finished; });
-          good = R.error.empty();
-        }
-        std::unique_ptr<DevOut> seam;
-        if (good) {
-          const int64_t n_head = svdss_bam_stream_head(R.stream, &head);
-          if (n_tail + n_head > 0) { good = run_seam(tail, n_tail, head, n_head, R.gpus[0], seam); ++n_seams; }
-        }
-        if (!good) {
-          // not proved (or the region failed): once more, from the record the region before ended in
-          if (o.verbose) logmsg("debug", "region " + std::to_string(g) + " runs again from the end of region " + std::to_string(g - 1) +
-                                             (R.error.empty() ? std::string(" (its first record was not where the chain arrives)") : " (" + R.error + ")"));
-          {
-            std::unique_lock<std::mutex> lk(dev_m);
-            dev_cv.wait(lk, [&] { return R.finished; });   // (its first run: what is left of it ends at once, the stream has failed)
-            R.done.clear(); R.error.clear(); R.finished = false; R.head_known = false; R.open_start = false;
-          }
-          svdss_bam_stream_free(R.stream);
-          R.stream = nullptr;
-          R.sc.reset();
-          ++n_reruns;
-          launch(R, g, tail, n_tail);
-          rerun_joiner = std::thread([&join_region, &R] { join_region(R); });
-        } else if (seam) deal(*seam);
-        svdss_bam_stream_free(P.stream);
-        P.stream = nullptr;
-      }
-      { std::lock_guard<std::mutex> lk(dev_m); cursor = g; }
-      dev_cv.notify_all();
-      for (uint64_t want = 0;; ++want) {
-        std::unique_ptr<DevOut> d;
-        {
-          std::unique_lock<std::mutex> lk(dev_m);
-          dev_cv.wait(lk, [&] { return R.done.count(want) || !R.error.empty() || (R.finished && R.done.empty()); });
-          if (!R.error.empty()) die(R.error.find("core.tid") != std::string::npos ? R.error : "error reading " + o.bam + ": " + R.error);   // (after the proof: the file's own fault)
-          auto it = R.done.find(want);
-          if (it == R.done.end()) break;
-          d = std::move(it->second);
-          R.done.erase(it);
-        }
-        dev_cv.notify_all();
-        deal(*d);
-      }
-      if (rerun_joiner.joinable()) rerun_joiner.join();
+    while (std::unique_ptr<DevOut> d = one ? one->next() : sharded->next()) deal(*d);
+    const BamRunError e = one ? one->failure() : sharded->failure();
+    if (e.failed()) {
+      if (e.msg.find("core.tid") != std::string::npos) die(e.msg);                       // ping_pong.cpp:76-79
+      if (e.rc == SVDSS_EIO) die("error reading " + o.bam + ": " + e.msg);
+      die(std::string("svdss_bam_batch_run: ") + svdss_strerror(e.rc) + " " + e.msg + " " + e.hip);
     }
     if (!unit->reads.empty()) { unit->seq = unit_seq++; units.push(std::move(unit)); }
     units.close();
@@ -802,7 +607,6 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
                                                      : (int)std::max<size_t>(5, std::min<size_t>(5 * replicas.size(), effective_cpus()));
     std::vector<std::thread> fmt;
     for (int k = 0; k < n_fmt; ++k) fmt.emplace_back(formatter);
-    for (size_t g = 0; g < regions.size(); ++g) launch(regions[g], g, nullptr, 0);
     // early: once the index is resident, the parked groups -- ONE launch each, one lane per read -- and their batches' results
     std::thread drain;
     if (early) drain = std::thread([&] {
@@ -859,8 +663,7 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
             acc += rd.count;
           }
           d.sidx.clear();
-          { std::lock_guard<std::mutex> lk(dev_m); P.R->done[P.seq] = std::move(P.out); P.R->head_known = true; }
-          dev_cv.notify_all();
+          one->deliver(P.seq, std::move(P.out));
         }
         n_parked += nr; n_parked_batches += nb;
       }
@@ -872,15 +675,12 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
                             std::to_string(n_groups) + " launch(es), " + std::to_string(t_search) + " s" +
                             (n_early_groups ? " (" + std::to_string(n_early_groups) + " of them while the file was still being read)" : "") + ", done at +" + since() + " s");
     });
-    std::vector<std::thread> joiners;
-    for (BamRegion& R : regions) joiners.emplace_back([&join_region, &R] { join_region(R); });
-    for (std::thread& th : joiners) th.join();
-    if (early) { { std::lock_guard<std::mutex> lk(early->m); early->front_done = true; } early->cv.notify_all(); }
-    if (drain.joinable()) {
-      drain.join();
-      { std::lock_guard<std::mutex> lk(dev_m); for (BamRegion& R : regions) R.finished = true; }
-      dev_cv.notify_all();
+    if (early) {
+      one->wait_finished();
+      { std::lock_guard<std::mutex> lk(early->m); early->front_done = true; }
+      early->cv.notify_all();
     }
+    if (drain.joinable()) drain.join();
     assembler.join();
     for (std::thread& th : fmt) th.join();
     { std::lock_guard<std::mutex> lk(done_m); format_finished = true; }
@@ -888,21 +688,23 @@ static void search_bam_device(const Options& o, const std::vector<svdss_index_t*
     writer.join();
   }
   if (o.verbose) {
+    int64_t n_seg = 0;
+    const int64_t n_rewalk = one ? one->segments_walked_again(&n_seg) : sharded->segments_walked_again(&n_seg);
     logmsg("debug", std::to_string(n_seen) + " records read, " + std::to_string(total_sfs) + " SFS written at +" + since() + " s");
-    if (regions.size() > 1)
-      logmsg("debug", std::to_string(regions.size()) + " regions of the file, one per GPU: " + std::to_string(n_seams) + " seam(s) run, " +
-                          std::to_string(n_reruns) + " region(s) run again");
-    logmsg("debug", "device path: " + std::to_string(n_batches) + " batches, " + std::to_string(n_seg_all) + " segments (" + std::to_string(n_rewalk_all) +
+    if (sharded)
+      logmsg("debug", std::to_string(sharded->n_regions()) + " regions of the file, one per GPU: " + std::to_string(sharded->seams_run()) + " seam(s) run, " +
+                          std::to_string(sharded->regions_run_again()) + " region(s) run again");
+    logmsg("debug", "device path: " + std::to_string(n_batches) + " batches, " + std::to_string(n_seg) + " segments (" + std::to_string(n_rewalk) +
                         " walked again); busy seconds: GPU batches " + std::to_string(t_gpu) + " (inflate kernels " + std::to_string(t_inflate_ms * 1e-3) +
                         "), result unpacking " + std::to_string(t_build) + ", re-dealing " + std::to_string(t_assemble) + ", format " + std::to_string(t_format) +
                         ", write " + std::to_string(t_write));
     char buf[480];
     snprintf(buf, sizeof buf, "device batches, seconds summed: upload+inflate+crc+walk %.3f, waiting for the turn %.3f, turn (carry, link) %.3f, "
              "fields+scans %.3f, unpack %.3f, search %.3f, results down %.3f; the batchers waited %.3f s for the file's loaders and %.3f s for the feeding threads",
-             t_stage[0], t_stage[1], t_stage[2], t_stage[3], t_stage[4], t_stage[5], t_stage[6], t_wait_file, t_wait_gpu);
+             t_stage[0], t_stage[1], t_stage[2], t_stage[3], t_stage[4], t_stage[5], t_stage[6], one ? one->waited_for_file() : sharded->waited_for_file(),
+             one ? one->waited_for_feeders() : sharded->waited_for_feeders());
     logmsg("debug", buf);
   }
-  for (BamRegion& R : regions) if (R.stream) { svdss_bam_stream_free(R.stream); R.stream = nullptr; }
 }
 
 int main_search(const Options& o) {
@@ -917,10 +719,9 @@ int main_search(const Options& o) {
   // SVDSS_BAM_DEVICE=0: the host path below (BamReader: chunks inflated on the GPU or by the host pool, records sliced
   // on the host, packed bases uploaded) -- the tested fallback, and what a reader of stdin-like inputs needs.
   const bool dev_bam = bam_mode && svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0);
-  std::vector<BamRegion> bam_regions;
-  BgzfScanner::Hooks bam_hooks;
-  size_t bam_slab = 0, bam_pool_chunks = 0;
-  int bam_loaders = 0;
+  std::vector<size_t> bam_cuts;
+  std::vector<std::unique_ptr<BgzfScanner>> bam_scanners;
+  std::vector<BgzfScanner*> bam_scanner_ptrs;
   int32_t bam_n_ref = 0;
   int64_t bam_skip = 0;
   if (dev_bam) {
@@ -938,25 +739,20 @@ int main_search(const Options& o) {
     const size_t per_batch = target / slab + 2;
     const int loaders = getenv("SVDSS_BAM_LOADERS") ? std::max(1, atoi(getenv("SVDSS_BAM_LOADERS"))) : 8;
     // the file's regions, one per GPU (one region for a small file, or SVDSS_REGION_SHARDS=0: every GPU's feeders take its batches)
-    const std::vector<size_t> cuts = plan_bam_regions(o.bam, n_g, bam_skip);
-    bam_regions.resize(cuts.size() - 1);
-    bam_hooks = hooks; bam_slab = slab;
-    bam_loaders = bam_regions.size() > 1 ? std::max(2, std::min(loaders, (int)effective_cpus() / (int)bam_regions.size())) : loaders;
-    const size_t feeders_per_region = bam_regions.size() > 1 ? (size_t)per_gpu : (size_t)(n_g * per_gpu);
-    bam_pool_chunks = (size_t)bam_loaders + (feeders_per_region + 3) * per_batch;
-    for (size_t g = 0; g < bam_regions.size(); ++g) {
-      BamRegion& R = bam_regions[g];
-      R.begin = cuts[g]; R.end = cuts[g + 1];
-      R.skip = g == 0 ? bam_skip : 0;
-      R.open_start = g > 0;
-      R.open_end = g + 1 < bam_regions.size();
-      R.sc.reset(new BgzfScanner(o.bam, hooks, slab, bam_loaders, bam_pool_chunks, R.begin, R.end));
-      if (!R.sc->ok()) die("cannot open " + o.bam);
+    bam_cuts = plan_bam_regions(o.bam, n_g, bam_skip);
+    const size_t n_regions = bam_cuts.size() - 1;
+    const int bam_loaders = n_regions > 1 ? std::max(2, std::min(loaders, (int)effective_cpus() / (int)n_regions)) : loaders;
+    const size_t feeders_per_region = n_regions > 1 ? (size_t)per_gpu : (size_t)(n_g * per_gpu);
+    const size_t pool_chunks = (size_t)bam_loaders + (feeders_per_region + 3) * per_batch;
+    for (size_t g = 0; g < n_regions; ++g) {
+      bam_scanners.emplace_back(new BgzfScanner(o.bam, hooks, slab, bam_loaders, pool_chunks, bam_cuts[g], bam_cuts[g + 1]));
+      if (!bam_scanners.back()->ok()) die("cannot open " + o.bam);
+      bam_scanner_ptrs.push_back(bam_scanners.back().get());
     }
     if (!getenv("SVDSS_NO_PREWARM"))
-      bam_prewarm = std::thread([&bam_regions] {
+      bam_prewarm = std::thread([&bam_scanners] {
         std::vector<std::thread> th;
-        for (BamRegion& R : bam_regions) th.emplace_back([&R] { R.sc->prewarm(); });
+        for (std::unique_ptr<BgzfScanner>& sc : bam_scanners) th.emplace_back([&sc] { sc->prewarm(); });
         for (std::thread& t : th) t.join();
       });
   } else if (bam_mode) {
@@ -981,7 +777,7 @@ int main_search(const Options& o) {
     const int64_t min_mb = getenv("SVDSS_EARLY_MIN_MB") ? atoll(getenv("SVDSS_EARLY_MIN_MB")) : 800;   // (records + rank blocks: a byte per BWT symbol)
     if (stat((o.index + ".svdss").c_str(), &sti) == 0 || stat(o.index.c_str(), &sti) == 0) early_pays = (int64_t)sti.st_size >= (min_mb << 20);
   }
-  if (dev_bam && early_pays && bam_regions.size() == 1 && std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, std::max(1, svdss_device_count()))) == 1 &&
+  if (dev_bam && early_pays && bam_cuts.size() == 2 && std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, std::max(1, svdss_device_count()))) == 1 &&
       !(getenv("SVDSS_SEARCH_EARLY") && atoi(getenv("SVDSS_SEARCH_EARLY")) == 0)) {
     if (o.bsize <= 0) die("batch size smaller than the number of threads");
     early.reset(new EarlySearch);
@@ -990,13 +786,12 @@ int main_search(const Options& o) {
     // (SVDSS_PARK_GB: what may be parked at most, in arenas allocated as they are needed; SVDSS_PARK_MB: the same in MB, for tests)
     const int64_t park_b = getenv("SVDSS_PARK_MB") && atoll(getenv("SVDSS_PARK_MB")) > 0 ? atoll(getenv("SVDSS_PARK_MB")) << 20
                            : (getenv("SVDSS_PARK_GB") && atoll(getenv("SVDSS_PARK_GB")) > 0 ? atoll(getenv("SVDSS_PARK_GB")) : 32) << 30;
-    bam_regions[0].gpus = {nullptr};
     // (on a thread of its own from the first moment: this one goes straight to the index file)
     early_stream = std::thread([&, park_b] {
       check(svdss_bam_park_create(0, park_b, park_b / 512 + 4096, &early->park), "svdss_bam_park_create");
       if (bam_prewarm.joinable()) bam_prewarm.join();
       const std::vector<svdss_index_t*> none(1, nullptr);
-      search_bam_device(o, none, bam_regions, bam_hooks, bam_slab, bam_loaders, bam_pool_chunks, bam_n_ref, since, early.get());
+      search_bam_device(o, none, bam_cuts, bam_scanner_ptrs, bam_n_ref, bam_skip, since, early.get());
     });
   }
   // (Tried: the rank blocks of the sidecar read beside the records, on a thread of their own, so that they are in memory when
@@ -1090,7 +885,6 @@ int main_search(const Options& o) {
       _exit(0);
     }
     svdss_bam_park_free(early->park);
-    bam_regions.clear();
     svdss_index_free(ix);
     logmsg("info", "All done! Runtime: " + std::to_string((long)(time(nullptr) - g_t0)) + " seconds");
     return 0;
@@ -1117,23 +911,18 @@ int main_search(const Options& o) {
     if (o.bsize <= 0) die("batch size smaller than the number of threads");
     logmsg("info", "Extracting SFS strings on the GPU (output order as with " + std::to_string(o.threads) + " threads)..");
     // region g on GPU g (one region: every GPU's feeders take its batches)
-    for (size_t g = 0; g < bam_regions.size(); ++g) {
-      if (bam_regions.size() == 1) bam_regions[g].gpus = replicas;
-      else bam_regions[g].gpus = {replicas[g % replicas.size()]};
-    }
-    if (o.verbose && bam_regions.size() > 1) {
+    if (o.verbose && bam_cuts.size() > 2) {
       std::string m = "file regions (bytes):";
-      for (const BamRegion& R : bam_regions) m += " " + std::to_string(R.end - R.begin);
+      for (size_t g = 0; g + 1 < bam_cuts.size(); ++g) m += " " + std::to_string(bam_cuts[g + 1] - bam_cuts[g]);
       logmsg("debug", m);
     }
-    search_bam_device(o, replicas, bam_regions, bam_hooks, bam_slab, bam_loaders, bam_pool_chunks, bam_n_ref, since);
+    search_bam_device(o, replicas, bam_cuts, bam_scanner_ptrs, bam_n_ref, bam_skip, since);
     if (!getenv("SVDSS_CLEAN_EXIT")) {
       logmsg("info", "All done! Runtime: " + std::to_string((long)(time(nullptr) - g_t0)) + " seconds");
       fflush(stdout);
       fflush(stderr);
       _exit(0);
     }
-    bam_regions.clear();
     for (svdss_index_t* r : replicas) svdss_index_free(r);
     return 0;
   }
