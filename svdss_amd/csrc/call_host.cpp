@@ -17,8 +17,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <thread>
@@ -452,6 +454,207 @@ uint8_t enc26(char c) {   // caller.hpp:25-37
 
 namespace {
 
+// One pass over the BAM, record after record in file order: the records the device path keeps (sel; its filters, one per
+// region of the file, decide which) or every record of the host reader (bam).  next: 1 = record, 0 = end of the file,
+// -1 = error (err says which).
+struct RecordFeed {
+  std::unique_ptr<ShardedBamSelect<SelectedBatch>> sel;
+  std::vector<svdss_bam_filter_t*> filters;
+  std::unique_ptr<BamReader> bam;
+  // host reader: called with every chunk it inflates, before the first record of the chunk is handed out (the record
+  // views point into it)
+  std::function<void(const std::shared_ptr<BamReader::Bytes>&)> on_chunk;
+  uint64_t seen_chunk = ~0ull;
+  // device path: the batch being handed out; what pass 1's log sums over the batches
+  std::unique_ptr<SelectedBatch> cur;
+  size_t k = 0;
+  uint64_t n_batches = 0, n_records = 0;
+  double stage_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wait_s = 0;
+  std::string err;
+
+  ~RecordFeed() {
+    sel.reset();   // (its threads use the filters)
+    for (svdss_bam_filter_t* f : filters) svdss_bam_filter_free(f);
+  }
+
+  int next(BamReader::RawView& rr) {
+    if (bam) {
+      const int rc = bam->next_view(rr);
+      if (rc < 0) err = bam->error();
+      if (rc > 0 && on_chunk && bam->chunk_id() != seen_chunk) { seen_chunk = bam->chunk_id(); on_chunk(bam->chunk()); }
+      return rc;
+    }
+    while (!cur || k + 1 >= cur->off.size()) {
+      const auto tw0 = std::chrono::steady_clock::now();
+      cur = sel->next();
+      wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
+      k = 0;
+      if (!cur) { err = sel->error(); return err.empty() ? 0 : -1; }
+      n_records += cur->n_records;
+      for (int s = 0; s < 8; ++s) stage_s[s] += cur->stage_s[s];
+      stage_s[7] += cur->inflate_kernel_s; ++n_batches;
+    }
+    const size_t at = (size_t)cur->off[k], end = (size_t)cur->off[k + 1];
+    ++k;
+    if (!view_of_record(cur->bytes.data() + at, end - at, rr, cur->slim)) { err = "corrupt record"; return -1; }
+    return 1;
+  }
+};
+
+// what one alignment does to one cluster it overlaps (pass 2); applied in BAM order
+struct Ev { size_t ci; int hp; bool in_reads, unext; std::string name, sub; };
+
+// The clusters as pass 2 (Clusterer::fill_clusters, clusterer.cpp:477-610) looks them up, built once: per cluster the
+// names of its reads and its region; the clusters with enough reads per chromosome, sorted by region start, with the
+// running maximum of their ends; and their regions merged per chromosome -- what the record store's filter, the index
+// query and the device path's filter all take.
+struct ClusterRegions {
+  const size_t n_ref;
+  const unsigned min_mapq;
+  std::vector<std::set<std::string>> reads;
+  std::vector<int> min_s, max_e;
+  std::vector<char> live;
+  long n_small = 0;                                      // clusters with too few reads
+  std::map<std::string, std::vector<size_t>> by_chrom;   // cluster indices per chrom, sorted by region start
+  std::map<std::string, std::vector<int>> run_max_end;   // per chrom: running maximum of the region ends, same order
+  // per reference id: the clusters of that chromosome (sorted by start) and the running maximum of their ends
+  std::vector<const std::vector<size_t>*> tid_clusters;
+  std::vector<const std::vector<int>*> tid_run_max;
+  std::vector<int32_t> rt, rb, re;                       // the merged regions: reference id, [begin, end)
+
+  // (the clusters with enough reads get their region as coordinates)
+  ClusterRegions(std::vector<Cluster>& clusters, const std::vector<std::string>& ref_names, unsigned min_weight, unsigned mapq)
+      : n_ref(ref_names.size()), min_mapq(mapq), reads(clusters.size()), min_s(clusters.size()), max_e(clusters.size()),
+        live(clusters.size(), 0), tid_clusters(n_ref, nullptr), tid_run_max(n_ref, nullptr) {
+    for (size_t i = 0; i < clusters.size(); ++i) {
+      int mn = std::numeric_limits<int>::max(), mx = 0;
+      for (const ESFS& s : clusters[i].sfss) { mn = std::min(mn, s.rs); mx = std::max(mx, s.re); reads[i].insert(s.qname); }
+      min_s[i] = mn; max_e[i] = mx;
+      if (reads[i].size() < (size_t)min_weight) { ++n_small; continue; }
+      clusters[i].s = mn; clusters[i].e = mx;
+      live[i] = 1;
+      by_chrom[clusters[i].chrom].push_back(i);
+    }
+    for (auto& kv : by_chrom) {
+      std::sort(kv.second.begin(), kv.second.end(), [&](size_t a, size_t b) { return min_s[a] < min_s[b]; });
+      std::vector<int>& rm = run_max_end[kv.first];
+      int m = 0;
+      for (size_t ci : kv.second) { m = std::max(m, max_e[ci]); rm.push_back(m); }
+    }
+    for (size_t t = 0; t < n_ref; ++t) {
+      auto it = by_chrom.find(ref_names[t]);
+      if (it == by_chrom.end()) continue;
+      tid_clusters[t] = &it->second;
+      tid_run_max[t] = &run_max_end[it->first];
+      for (size_t ci : it->second) {   // (by start: a region overlaps the last one of the chromosome or starts a new one)
+        if (!rt.empty() && rt.back() == (int32_t)t && beg0(ci) <= re.back()) re.back() = std::max(re.back(), max_e[ci]);
+        else { rt.push_back((int32_t)t); rb.push_back(beg0(ci)); re.push_back(max_e[ci]); }
+      }
+    }
+  }
+
+  // region "chrom:min_s-max_e" = 0-based half-open [min_s-1, max_e)
+  int beg0(size_t ci) const { return std::max(min_s[ci] - 1, 0); }
+
+  // the merged regions as the device path's record filter, on GPU dev
+  svdss_bam_filter_t* filter(int32_t dev) const {
+    svdss_bam_filter_t* f = nullptr;
+    check(svdss_bam_filter_create(dev, (int32_t)std::min<unsigned>(min_mapq, 256u), (int32_t)n_ref, nullptr, nullptr, 0, rt.data(), rb.data(),
+                                  re.data(), (int64_t)rt.size(), &f), "svdss_bam_filter_create");
+    return f;
+  }
+
+  // What one alignment does to the clusters it overlaps, handed to sink as one Ev per cluster.  Records stay in their raw
+  // form: the end position and the two query positions the reference reads off the aligned-pairs vector (bam.cpp:92-134,
+  // clusterer.cpp:555-580) are functions of the CIGAR blocks alone, and only the bases of the extracted sub-read are decoded.
+  template <class Sink>
+  void process(const BamReader::RawView& rr, std::string& qname, Sink&& sink) const {
+    static const char NT16[] = "=ACMGRSVTWYHKDBN";
+    if (rr.tid < 0 || rr.tid >= (int)n_ref || !tid_clusters[(size_t)rr.tid]) return;
+    if (rr.flag & (4 | 2048 | 256)) return;        // clusterer.cpp:535-540: such a record touches no cluster
+    if ((unsigned)rr.mapq < min_mapq) return;
+    const uint8_t* cg = rr.name() + rr.l_name;
+    auto cig = [&](uint32_t i) { uint32_t c; memcpy(&c, cg + 4u * i, 4); return c; };
+    int32_t ref_len = 0;
+    for (uint32_t i = 0; i < rr.n_cigar; ++i) {
+      const uint32_t c = cig(i), op = c & 0xf;
+      if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += (int32_t)(c >> 4);
+    }
+    const int a_beg = rr.pos, a_end = rr.pos + (ref_len ? ref_len : 1);   // bam_endpos
+    const std::vector<size_t>& cl_ids = *tid_clusters[(size_t)rr.tid];
+    // clusters before `first` end at or before the alignment's start: none of them can overlap it
+    const std::vector<int>& rm = *tid_run_max[(size_t)rr.tid];
+    const size_t first = (size_t)(std::upper_bound(rm.begin(), rm.end(), a_beg) - rm.begin());
+    bool have_tags = false;
+    int64_t hp = 0;
+    for (size_t k = first; k < cl_ids.size(); ++k) {
+      const size_t ci = cl_ids[k];
+      const int b0 = beg0(ci), end0 = max_e[ci];
+      if (b0 >= a_end) break;   // clusters are sorted by start
+      if (!(a_beg < end0 && a_end > b0)) continue;
+      if (!have_tags) {
+        have_tags = true;
+        BamReader::aux_int(rr.aux(), rr.l_aux, "HP", hp);
+        qname.assign((const char*)rr.name(), rr.l_name ? rr.l_name - 1 : 0);
+      }
+      Ev ev{ci, (int)hp, false, false, std::string(), std::string()};
+      if (reads[ci].find(qname) == reads[ci].end()) { sink(ev); continue; }
+      ev.in_reads = true;
+      // qs: query position of the last aligned (M/=/X) pair with reference position <= min_s;
+      // qe: of the first one with reference position >= max_e
+      int qs = -1, qe = -1, ref_pos = rr.pos, read_pos = 0;
+      for (uint32_t i = 0; i < rr.n_cigar; ++i) {
+        const uint32_t c = cig(i), op = c & 0xf;
+        const int l = (int)(c >> 4);
+        if (op == 0 || op == 7 || op == 8) {
+          if (l > 0) {
+            if (ref_pos <= min_s[ci]) qs = read_pos + (std::min(min_s[ci], ref_pos + l - 1) - ref_pos);
+            if (qe == -1 && ref_pos + l - 1 >= max_e[ci]) qe = read_pos + (std::max(max_e[ci], ref_pos) - ref_pos);
+          }
+          read_pos += l; ref_pos += l;
+        } else if (op == 1 || op == 4) read_pos += l;
+        else if (op == 2 || op == 3) ref_pos += l;
+      }
+      if (qs == -1 || qe == -1) ev.unext = true;
+      else {
+        if (qs > rr.l_seq) die("corrupt alignment: sub-read start past the end of read " + qname);   // (std::string::substr throws in the reference)
+        const int n = std::max(0, std::min(qe - qs + 1, rr.l_seq - qs));
+        const uint8_t* sq = rr.seq4();
+        std::string sub((size_t)n, 'N');
+        for (int i = 0; i < n; ++i) { const int q = qs + i; sub[(size_t)i] = NT16[(sq[q >> 1] >> ((~q & 1) << 2)) & 0xf]; }
+        ev.name = qname;
+        ev.sub = std::move(sub);
+      }
+      sink(ev);
+    }
+  }
+};
+
+// Pass 2 over n_units units of consecutive records (in file order) on n_threads threads: unit(state, k, sink) hands what
+// the records of unit k do to the clusters to sink and returns "" or what went wrong (the run then ends with `fail` and
+// the first error in unit order); `state` belongs to the thread, and goes when the thread is done.  The events come back
+// per unit: applied unit after unit, they are in the order of the single scan.
+template <class State, class Unit>
+std::vector<std::vector<Ev>> scan_units(size_t n_units, size_t n_threads, const std::string& fail, Unit&& unit) {
+  std::vector<std::vector<Ev>> evs(n_units);
+  std::vector<std::string> errs(n_units);
+  std::atomic<size_t> next(0);
+  auto work = [&]() {
+    State state;
+    for (size_t k; (k = next.fetch_add(1)) < n_units;) {
+      auto sink = [&evs, k](Ev& e) { evs[k].push_back(std::move(e)); };
+      errs[k] = unit(state, k, sink);
+    }
+  };
+  std::vector<std::thread> pool;
+  for (size_t w = 1; w < n_threads; ++w) pool.emplace_back(work);
+  work();
+  for (std::thread& th : pool) th.join();
+  for (const std::string& e : errs)
+    if (!e.empty()) die(fail + e);
+  return evs;
+}
+
 // `SVDSS call`, stage by stage in the order of Caller::run / Clusterer::run (caller.cpp:12-57, clusterer.cpp:12-54); the
 // members are what one stage hands to the next.
 struct CallRun {
@@ -462,8 +665,6 @@ struct CallRun {
   std::vector<std::string> ref_names;    // BAM header order
   std::vector<ESFS> extended;            // pass 1: every placed SFS
   std::vector<Clip> clips;               // --clipped
-  // The inflated records of pass 1 are kept for pass 2 when they fit in memory (a second inflate of the whole file
-  // otherwise): SVDSS_CALL_CACHE_GB, default 40 % of MemAvailable, at most 64 GiB.
   std::thread fasta_loader;              // load_chromosomes, beside the SFS file and the start of pass 1
   // ONE pass over the BAM (round 6): what pass 2 needs of every record stays in HBM while pass 1 runs (svdss_bam_store_t)
   // (--gpus N: the file's regions, one per GPU, each with a store of its own in that GPU's HBM -- and a small one for the
@@ -478,7 +679,6 @@ struct CallRun {
   void reference_ready() { if (fasta_loader.joinable()) fasta_loader.join(); }
   bool dev_pass = false;                 // the BAM is read through the device path (csrc/bam_device.hip): no record cache
   int64_t bam_skip = 0;                  // the BAM header's length in the inflated stream
-  uint64_t n_records_seen = 0;
   static int64_t bam_batch_bytes() {
     const char* e = getenv("SVDSS_BAM_BATCH_MB");
     return (e && atoll(e) > 0 ? atoll(e) : 256) << 20;
@@ -493,13 +693,13 @@ struct CallRun {
     const char* e = getenv("SVDSS_CALL_FEEDERS");
     return e && atoi(e) > 0 ? atoi(e) : 3;
   }
-  std::vector<BamReader::RawView> cache_views;
+  std::vector<BamReader::RawView> cache_views;   // the record cache of the host reader (align_and_extend)
   std::vector<std::shared_ptr<BamReader::Bytes>> cache_chunks;
   size_t cache_bytes = 0, cache_limit = 0;
   bool cache_ok = true;
   std::thread cache_release;
   std::vector<Cluster> clusters;
-  int n_dev = 1, G = 1;                  // GPUs present / shards of the DP batches (--gpus)
+  int n_dev = 1, G = 1;                  // GPUs present / GPUs in use (--gpus): regions of the file, shards of the DP batches
   struct Sub { size_t parent; Cluster cl; };
   std::vector<Sub> subs;                 // sub-clusters after split_cluster, in the reference's order
   std::vector<std::string> consensus;    // one per sub-cluster
@@ -545,15 +745,21 @@ struct CallRun {
     // the record store(s) of the ONE pass over the BAM (round 6, align_and_extend / fill_clusters below): the memory is taken
     // NOW, on a thread of its own, beside the FASTA and the SFS file -- tens of GB that the driver clears before it hands them out
     {
-      const int n_phys = std::max(1, svdss_device_count());
-      const int n_dev = std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, n_phys));
-      const bool dev_bam = svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0);
-      if (dev_bam) {
+      // (SVDSS_GPUS_OVERSUBSCRIBE: more shards than GPUs, shard g on GPU g % count -- exercises the sharding on a one-GPU box)
+      n_dev = std::max(1, svdss_device_count());
+      G = std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, n_dev));
+      // Records handled on the GPU (csrc/bam_device.hip, svdss_bam_select_run; the default when there is a GPU and the
+      // input is a regular file): only the primary, mapq-ok alignments of reads that HAVE SFS come back to the host --
+      // the records clusterer.cpp:108-145 keeps -- instead of every inflated byte.  No record cache then: pass 2 takes the
+      // records kept in HBM, goes through the BAI index, or reads the file again through the same path with the cluster
+      // regions as the filter.  SVDSS_BAM_DEVICE=0: the host reader (chunks inflated on the GPU or the host, records sliced here).
+      dev_pass = svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0);
+      if (dev_pass) {
         std::string herr;
         if (!bam_header_probe(o.bam, n_ref_hdr, bam_skip, herr, &ref_names)) die("cannot read " + o.bam + ": " + herr);
-        bam_cuts = plan_bam_regions(o.bam, n_dev, bam_skip);
+        bam_cuts = plan_bam_regions(o.bam, G, bam_skip);
       }
-      if (dev_bam && !(getenv("SVDSS_CALL_STORE") && atoi(getenv("SVDSS_CALL_STORE")) == 0)) {
+      if (dev_pass && !(getenv("SVDSS_CALL_STORE") && atoi(getenv("SVDSS_CALL_STORE")) == 0)) {
         // (up to SVDSS_CALL_STORE_GB per GPU, default 160: a 30x human sample is ~50 GB; more than fits: the file is read again,
         // as before.  Expected size: the bases of the file, two per byte, + names and CIGARs -- at most ~2.5 x a well-compressed BAM)
         const int64_t gb = getenv("SVDSS_CALL_STORE_GB") && atoll(getenv("SVDSS_CALL_STORE_GB")) > 0 ? atoll(getenv("SVDSS_CALL_STORE_GB")) : 160;
@@ -561,13 +767,13 @@ struct CallRun {
         const size_t n_reg = bam_cuts.size() - 1;
         stores.assign(n_reg, nullptr);
         seam_stores.assign(n_reg, nullptr);
-        store_alloc = std::thread([this, cap, n_reg, n_phys] {
+        store_alloc = std::thread([this, cap, n_reg] {
           const auto t0 = std::chrono::steady_clock::now();
           for (size_t g = 0; g < n_reg; ++g) {
             const int64_t rsz = (int64_t)(bam_cuts[g + 1] - bam_cuts[g]);
             const int64_t initial = getenv("SVDSS_CALL_STORE_INITIAL_MB") ? atoll(getenv("SVDSS_CALL_STORE_INITIAL_MB")) << 20 : std::min(cap, rsz * 5 / 2 + ((int64_t)256 << 20));
-            if (svdss_bam_store_create((int32_t)(g % (size_t)n_phys), cap, initial, &stores[g]) != SVDSS_OK) stores[g] = nullptr;
-            if (g > 0 && svdss_bam_store_create((int32_t)(g % (size_t)n_phys), (int64_t)64 << 20, 0, &seam_stores[g]) != SVDSS_OK) seam_stores[g] = nullptr;
+            if (svdss_bam_store_create((int32_t)(g % (size_t)n_dev), cap, initial, &stores[g]) != SVDSS_OK) stores[g] = nullptr;
+            if (g > 0 && svdss_bam_store_create((int32_t)(g % (size_t)n_dev), (int64_t)64 << 20, 0, &seam_stores[g]) != SVDSS_OK) seam_stores[g] = nullptr;
           }
           store_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         });
@@ -580,12 +786,55 @@ struct CallRun {
     stage("reference + sfs file");
   }
 
+  // the device path over the file's regions (bam_cuts): one filter per region, filter(dev) on the region's GPU; with_stores:
+  // the slim form of every record that passes the flag / mapq filters also stays in the region's record store
+  void open_select(RecordFeed& f, int32_t n_ref, bool with_stores, const std::function<svdss_bam_filter_t*(int32_t)>& filter) {
+    std::vector<ShardedBamSelect<SelectedBatch>::Shard> shards(bam_cuts.size() - 1);
+    for (size_t g = 0; g < shards.size(); ++g) {
+      f.filters.push_back(shards[g].filter = filter((int32_t)(g % (size_t)n_dev)));
+      if (with_stores && !stores.empty()) { shards[g].store = stores[g]; shards[g].seam_store = seam_stores[g]; }
+    }
+    f.sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref, bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts));
+  }
+
+  // the host reader, its chunks inflated on n_gpus GPUs in turn (where there are)
+  void open_reader(RecordFeed& f, int n_gpus) {
+    f.bam.reset(new BamReader(o.bam));
+    svdss_enable_gpu_inflate(*f.bam, 0, n_gpus);
+    if (!f.bam->ok() || !f.bam->read_header()) die("cannot read " + o.bam + ": " + f.bam->error());
+  }
+
+  // Pass 1 through the device path: the records of reads that have SFS.  --gpus N: the file's regions, one per GPU
+  // (SVDSS_GPUS_OVERSUBSCRIBE puts the N shards on the GPUs there are -- the code path of N devices on a one-GPU box): every
+  // region has its own scanner, batcher, feeding threads, record stream and filter; the slim form of every record that
+  // passes the flag / mapq filters stays in that GPU's HBM for pass 2 (load_inputs took the memory; all of it or none is
+  // used).  SVDSS_CALL_STORE=0: two passes over the file.
+  void open_pass1_select(RecordFeed& f) {
+    std::string names;
+    std::vector<int64_t> name_off(1, 0);
+    for (const auto& kv : C.sfs) { names += kv.first; name_off.push_back((int64_t)names.size()); }
+    if (store_alloc.joinable()) store_alloc.join();
+    bool all_stores = !stores.empty();
+    for (svdss_bam_store_t* st : stores) all_stores = all_stores && st != nullptr;
+    for (size_t g = 1; g < seam_stores.size(); ++g) all_stores = all_stores && seam_stores[g] != nullptr;
+    if (!all_stores) {
+      for (svdss_bam_store_t* st : stores) svdss_bam_store_free(st);
+      for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
+      stores.clear(); seam_stores.clear();
+    }
+    open_select(f, n_ref_hdr, true, [&](int32_t dev) {
+      svdss_bam_filter_t* flt = nullptr;
+      check(svdss_bam_filter_create(dev, (int32_t)std::min<unsigned>(o.min_mapq, 256u), n_ref_hdr, names.data(), name_off.data(),
+                                    (int64_t)name_off.size() - 1, nullptr, nullptr, nullptr, 0, &flt), "svdss_bam_filter_create");
+      return flt;
+    });
+  }
+
   // Clusterer::align_and_extend (clusterer.cpp:56-156): pass 1 over the BAM, placement of every SFS
   void align_and_extend() {
     logmsg("info", "Placing SFSs on reference genome");
-    // ---- align_and_extend (clusterer.cpp:56-156): pass 1 over the BAM
     // The inflated records of pass 1 are kept for pass 2 when they fit in memory (a second inflate of the whole file
-    // otherwise): SVDSS_CALL_CACHE_GB, default 40 % of MemAvailable, at most 64 GiB.
+    // otherwise): SVDSS_CALL_CACHE_GB, default 40 % of MemAvailable, at most 64 GiB.  Not on the device path.
     {
       double gb = 0;
       if (const char* e = getenv("SVDSS_CALL_CACHE_GB")) gb = atof(e);
@@ -601,70 +850,28 @@ struct CallRun {
         if (gb > 64) gb = 64;
       }
       cache_limit = gb > 0 ? (size_t)(gb * 1024.0 * 1024.0 * 1024.0) : 0;
-      if (cache_limit == 0) cache_ok = false;
+      if (cache_limit == 0 || dev_pass) cache_ok = false;
     }
     {
-      // Records handled on the GPU (csrc/bam_device.hip, svdss_bam_select_run; the default when there is a GPU and the
-      // input is a regular file): only the primary, mapq-ok alignments of reads that HAVE SFS come back to the host --
-      // the records clusterer.cpp:108-145 keeps -- instead of every inflated byte.  No record cache then: pass 2 goes
-      // through the BAI index, or reads the file again through the same path with the cluster regions as the filter.
-      // SVDSS_BAM_DEVICE=0: the host reader (chunks inflated on the GPU or the host, records sliced here).
-      const bool dev_bam = svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0);
-      std::unique_ptr<BamReader> bam_p;
-      std::unique_ptr<ShardedBamSelect<SelectedBatch>> sel;
-      std::vector<svdss_bam_filter_t*> filters;
-      if (dev_bam) {
-        if (bam_cuts.empty()) {      // (load_inputs probes the header; a caller that skipped it)
-          std::string herr;
-          if (!bam_header_probe(o.bam, n_ref_hdr, bam_skip, herr, &ref_names)) die("cannot read " + o.bam + ": " + herr);
-          bam_cuts = plan_bam_regions(o.bam, 1, bam_skip);
-        }
-        std::string names;
-        std::vector<int64_t> name_off(1, 0);
-        for (const auto& kv : C.sfs) { names += kv.first; name_off.push_back((int64_t)names.size()); }
-        // --gpus N: the file's regions, one per GPU (SVDSS_GPUS_OVERSUBSCRIBE puts the N shards on the GPUs there are -- the code
-        // path of N devices on a one-GPU box): every region has its own scanner, batcher, feeding threads, record stream and
-        // filter; the slim form of every record that passes the flag / mapq filters stays in that GPU's HBM for pass 2
-        // (load_inputs took the memory).  SVDSS_CALL_STORE=0: two passes over the file.
-        const int n_phys = std::max(1, svdss_device_count());
-        const size_t n_reg = bam_cuts.size() - 1;
-        if (store_alloc.joinable()) store_alloc.join();
-        bool all_stores = !stores.empty();
-        for (svdss_bam_store_t* st : stores) all_stores = all_stores && st != nullptr;
-        for (size_t g = 1; g < seam_stores.size(); ++g) all_stores = all_stores && seam_stores[g] != nullptr;
-        if (!all_stores) {
-          for (svdss_bam_store_t* st : stores) svdss_bam_store_free(st);
-          for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
-          stores.clear(); seam_stores.clear();
-        }
-        std::vector<ShardedBamSelect<SelectedBatch>::Shard> shards;
-        for (size_t g = 0; g < n_reg; ++g) {
-          svdss_bam_filter_t* f = nullptr;
-          check(svdss_bam_filter_create((int32_t)(g % (size_t)n_phys), (int32_t)std::min<unsigned>(o.min_mapq, 256u), n_ref_hdr, names.data(), name_off.data(),
-                                        (int64_t)name_off.size() - 1, nullptr, nullptr, nullptr, 0, &f), "svdss_bam_filter_create");
-          filters.push_back(f);
-          ShardedBamSelect<SelectedBatch>::Shard sh;
-          sh.filter = f;
-          sh.store = stores.empty() ? nullptr : stores[g];
-          sh.seam_store = seam_stores.empty() ? nullptr : seam_stores[g];
-          shards.push_back(sh);
-        }
-        sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref_hdr, bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts));
-        cache_ok = false;
-        dev_pass = true;
-      } else {
-        bam_p.reset(new BamReader(o.bam));
-        // (--gpus N: the chunks of pass 1 are inflated on all N GPUs in turn, as `search` does)
-        svdss_enable_gpu_inflate(*bam_p, 0, std::max(1, std::min(o.gpus, svdss_device_count())));
-        if (!bam_p->ok() || !bam_p->read_header()) die("cannot read " + o.bam + ": " + bam_p->error());
-        ref_names = bam_p->ref_names();
+      RecordFeed feed;
+      if (dev_pass) open_pass1_select(feed);
+      else {
+        // (--gpus N: the chunks of pass 1 are inflated on all N GPUs in turn, as `search` does -- on GPUs that are there,
+        // whatever SVDSS_GPUS_OVERSUBSCRIBE says)
+        open_reader(feed, std::max(1, std::min(o.gpus, n_dev)));
+        ref_names = feed.bam->ref_names();
+        feed.on_chunk = [this](const std::shared_ptr<BamReader::Bytes>& chunk) {
+          if (!cache_ok) return;
+          cache_bytes += chunk->size();
+          if (cache_bytes > cache_limit) {   // too big to keep: pass 2 reads the file again
+            cache_ok = false;
+            cache_views.clear(); cache_views.shrink_to_fit();
+            cache_chunks.clear(); cache_chunks.shrink_to_fit();
+          } else cache_chunks.push_back(chunk);
+        };
       }
-      // the next record pass 1 looks at: 1 = record, 0 = end of file (errors end the run)
-      double pass1_stage[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pass1_wait_s = 0, pass1_join_s = 0;
-      uint64_t pass1_batches = 0;
+      double pass1_join_s = 0;
       const auto pass1_t0 = std::chrono::steady_clock::now();
-      std::unique_ptr<SelectedBatch> sel_cur;
-      size_t sel_k = 0;
       const int bsize = std::max(T, (10000 / T) * T);   // config.hpp:69, config.cpp:106
       std::vector<std::vector<ESFS>> per_thread((size_t)T);
       std::vector<std::vector<Clip>> per_thread_clips((size_t)T);
@@ -700,51 +907,15 @@ struct CallRun {
       int cur = 0;
       std::string qname;
       bool eof = false;
-      uint64_t seen_chunk = ~0ull;
-      std::shared_ptr<BamReader::Bytes> cur_chunk;
       while (!eof) {
         std::vector<BamRecord>& batch = batches[cur];
         batch.clear();
         while ((int)batch.size() < bsize) {
           // records are located in the inflated chunks and only decoded if the read has SFS at all
           BamReader::RawView rr;
-          if (sel) {
-            while (!sel_cur || sel_k + 1 >= sel_cur->off.size()) {
-              const auto tw0 = std::chrono::steady_clock::now();
-              sel_cur = sel->next();
-              pass1_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-              sel_k = 0;
-              if (!sel_cur) break;
-              n_records_seen += sel_cur->n_records;
-              for (int k = 0; k < 8; ++k) pass1_stage[k] += sel_cur->stage_s[k];
-              pass1_stage[7] += sel_cur->inflate_kernel_s; ++pass1_batches;
-            }
-            if (!sel_cur) {
-              if (!sel->error().empty()) { if (worker.joinable()) worker.join(); die("error reading " + o.bam + ": " + sel->error()); }
-              eof = true;
-              break;
-            }
-            const size_t at = (size_t)sel_cur->off[sel_k], end = (size_t)sel_cur->off[sel_k + 1];
-            ++sel_k;
-            if (!view_of_record(sel_cur->bytes.data() + at, end - at, rr, sel_cur->slim)) { if (worker.joinable()) worker.join(); die("error reading " + o.bam + ": corrupt record"); }
-          } else {
-          BamReader& bam = *bam_p;
-          const int rc = bam.next_view(rr);
+          const int rc = feed.next(rr);
           if (rc == 0) { eof = true; break; }
-          if (rc < 0) { if (worker.joinable()) worker.join(); die("error reading " + o.bam + ": " + bam.error()); }
-          if (bam.chunk_id() != seen_chunk) {
-            seen_chunk = bam.chunk_id();
-            cur_chunk = bam.chunk();
-            if (cache_ok) {
-              cache_bytes += cur_chunk->size();
-              if (cache_bytes > cache_limit) {   // too big to keep: pass 2 reads the file again
-                cache_ok = false;
-                cache_views.clear(); cache_views.shrink_to_fit();
-                cache_chunks.clear(); cache_chunks.shrink_to_fit();
-              } else cache_chunks.push_back(cur_chunk);
-            }
-          }
-          }
+          if (rc < 0) { if (worker.joinable()) worker.join(); die("error reading " + o.bam + ": " + feed.err); }
           if (rr.flag & (4 | 2048 | 256)) continue;   // clusterer.cpp:118-122
           if ((unsigned)rr.mapq < o.min_mapq) continue;
           if (cache_ok) cache_views.push_back(rr);    // every record pass 2 looks at (same filters, clusterer.cpp:535-540)
@@ -820,27 +991,26 @@ struct CallRun {
       }
       if (worker.joinable()) worker.join();
       set_up_reference();   // (an input without a single batch: the later stages still want the chromosomes)
-      if (sel) {
+      if (const ShardedBamSelect<SelectedBatch>* sel = feed.sel.get()) {
         region_batches.clear(); region_seam.clear();
         for (size_t g = 0; g < sel->n_regions(); ++g) { region_batches.push_back(sel->region_batches(g)); region_seam.push_back(sel->region_has_seam(g) ? 1 : 0); }
         if (sel->n_regions() > 1)
           logmsg("debug", std::to_string(sel->n_regions()) + " regions of the file, one per GPU: " + std::to_string(sel->seams_run()) + " seam(s) run, " +
                               std::to_string(sel->regions_run_again()) + " region(s) run again");
-      }
-      if (sel && pass1_batches) {
-        char buf[480];
-        snprintf(buf, sizeof buf, "pass 1 on the device: %llu batches, %llu records; feeder seconds summed: upload+inflate+crc+walk %.3f, turn wait %.3f, turn %.3f, "
-                 "select+scans%s %.3f, records down %.3f (inflate kernels %.3f)", (unsigned long long)pass1_batches, (unsigned long long)n_records_seen, pass1_stage[0],
-                 pass1_stage[1], pass1_stage[2], !stores.empty() ? "+store" : "", pass1_stage[3], pass1_stage[6], pass1_stage[7]);
-        logmsg("debug", buf);
-        snprintf(buf, sizeof buf, "pass 1, this thread: %.3f s in all, %.3f s waiting for the device's batches, %.3f s waiting for the placement of the batch before; "
-                 "the record store's memory took %.3f s; the batcher waited %.3f s for the file's loaders, %.3f s for the feeding threads",
-                 std::chrono::duration<double>(std::chrono::steady_clock::now() - pass1_t0).count(), pass1_wait_s, pass1_join_s, store_alloc_s, sel->waited_for_file(), sel->waited_for_feeders());
-        logmsg("debug", buf);
+        if (feed.n_batches) {
+          const double* st = feed.stage_s;
+          char buf[480];
+          snprintf(buf, sizeof buf, "pass 1 on the device: %llu batches, %llu records; feeder seconds summed: upload+inflate+crc+walk %.3f, turn wait %.3f, turn %.3f, "
+                   "select+scans%s %.3f, records down %.3f (inflate kernels %.3f)", (unsigned long long)feed.n_batches, (unsigned long long)feed.n_records, st[0],
+                   st[1], st[2], !stores.empty() ? "+store" : "", st[3], st[6], st[7]);
+          logmsg("debug", buf);
+          snprintf(buf, sizeof buf, "pass 1, this thread: %.3f s in all, %.3f s waiting for the device's batches, %.3f s waiting for the placement of the batch before; "
+                   "the record store's memory took %.3f s; the batcher waited %.3f s for the file's loaders, %.3f s for the feeding threads",
+                   std::chrono::duration<double>(std::chrono::steady_clock::now() - pass1_t0).count(), feed.wait_s, pass1_join_s, store_alloc_s, sel->waited_for_file(), sel->waited_for_feeders());
+          logmsg("debug", buf);
+        }
       }
       svdss_ref_free(dref);
-      sel.reset();
-      for (svdss_bam_filter_t* f : filters) svdss_bam_filter_free(f);
       for (int t = 0; t < T; ++t) extended.insert(extended.end(), per_thread[(size_t)t].begin(), per_thread[(size_t)t].end());
       for (int t = T; t-- > 0;)   // each thread's list goes in front of the others' (clusterer.cpp:24)
         clips.insert(clips.end(), per_thread_clips[(size_t)t].begin(), per_thread_clips[(size_t)t].end());
@@ -896,375 +1066,200 @@ struct CallRun {
     stage("cluster_by_proximity");
   }
 
+  // the compressed bytes of a file chunk, at most (it ends somewhere in the block its end names)
+  static uint64_t chunk_span(const std::pair<uint64_t, uint64_t>& ch) { return (ch.second >> 16) - (ch.first >> 16) + 65536; }
+
+  // Where pass 2 takes the records from, in the order the sources are tried: the records pass 1 left in HBM, the record
+  // cache of the host reader, the file chunks a BAI / CSI index names around the clusters, the whole file again (through
+  // the device path, or the host reader)
+  enum class Pass2 { store, cache, index, device, host };
+  struct StoreItem { svdss_bam_store_t* st; int64_t key; size_t dev; };
+  struct Pass2Plan {
+    Pass2 src = Pass2::host;
+    std::vector<StoreItem> items;                         // store: its batches, in file order
+    int64_t st_records = 0, st_bytes = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> chunks;   // index: the file chunks around the clusters, merged
+  };
+
+  Pass2Plan plan_pass2(const ClusterRegions& R) {
+    Pass2Plan p;
+    if (!stores.empty()) {
+      bool complete_all = true;
+      for (size_t g = 0; g < stores.size(); ++g) {
+        int32_t complete = 0;
+        int64_t nr = 0, nb = 0;
+        if (g > 0 && g < region_seam.size() && region_seam[g]) {
+          (void)svdss_bam_store_batches(seam_stores[g], &complete, &nr, &nb);
+          complete_all = complete_all && complete;
+          p.st_records += nr; p.st_bytes += nb;
+          p.items.push_back(StoreItem{seam_stores[g], 0, g % (size_t)n_dev});
+        }
+        const int64_t n_b = svdss_bam_store_batches(stores[g], &complete, &nr, &nb);
+        complete_all = complete_all && complete && n_b == (g < region_batches.size() ? region_batches[g] : -1);
+        p.st_records += nr; p.st_bytes += nb;
+        for (int64_t k = 0; k < n_b; ++k) p.items.push_back(StoreItem{stores[g], k, g % (size_t)n_dev});
+      }
+      if (complete_all) { p.src = Pass2::store; return p; }
+      logmsg("debug", "the record store is incomplete (" + std::to_string(p.st_bytes >> 20) + " MB kept): pass 2 reads the file again");
+    }
+    if (cache_ok) { p.src = Pass2::cache; return p; }
+    // The records of pass 1 are not at hand.  With a BAI index beside the file (what the reference requires:
+    // sam_index_load + one sam_itr_querys per cluster, clusterer.cpp:495-527) only the file chunks around the clusters are
+    // read -- all regions turned into one sorted, merged chunk list, read once in file order, which visits the same records
+    // in the same order as the full scan does among those that touch a cluster
+    BaiIndex bai;
+    bool have_bai = false;
+    if (!getenv("SVDSS_CALL_NO_BAI")) {
+      // (x.bam.bai, x.bai, x.bam.csi, x.csi: the names htslib's sam_index_load looks for)
+      const std::string stem = o.bam.size() > 4 && o.bam.compare(o.bam.size() - 4, 4, ".bam") == 0 ? o.bam.substr(0, o.bam.size() - 4) : std::string();
+      have_bai = bai.load(o.bam + ".bai") || (!stem.empty() && bai.load(stem + ".bai")) || bai.load(o.bam + ".csi") ||
+                 (!stem.empty() && bai.load(stem + ".csi"));
+      if (have_bai && bai.refs.size() != ref_names.size()) have_bai = false;
+    }
+    if (have_bai) {
+      for (size_t i = 0; i < R.rt.size(); ++i) bai.query(R.rt[i], R.rb[i], R.re[i], p.chunks);
+      BaiIndex::merge(p.chunks);
+      // The index names the file chunks around the clusters; host threads inflate them (~0.3 GB/s each; second session
+      // of round 5: all of them, until then one).  When the chunks are a large part of the file, reading ALL of it
+      // through the device path (tens of GB/s, only the overlapping records come back) is quicker: beyond 8 % of the
+      // file per thread that scans.  SVDSS_CALL_PASS2 = bai | device overrides the estimate.
+      if (dev_pass) {
+        uint64_t bytes = 0;
+        for (const auto& ch : p.chunks) bytes += chunk_span(ch);
+        struct stat st;
+        const uint64_t file_bytes = stat(o.bam.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
+        const char* p2 = getenv("SVDSS_CALL_PASS2");
+        const double share = std::min(0.6, 0.08 * (double)pass2_threads(p.chunks.size()));
+        if (p2 && !strcmp(p2, "device")) have_bai = false;
+        else if (!(p2 && !strcmp(p2, "bai")) && file_bytes && (double)bytes > share * (double)file_bytes) have_bai = false;
+      }
+    }
+    if (have_bai) {
+      logmsg("debug", std::string("pass 2 through the ") + (bai.csi ? "CSI" : "BAI") + " index: " + std::to_string(R.rt.size()) + " regions, " +
+                          std::to_string(p.chunks.size()) + " file chunks");
+      p.src = Pass2::index;
+    } else p.src = dev_pass ? Pass2::device : Pass2::host;
+    return p;
+  }
+
+  // Round 6: the records are in HBM since pass 1 (svdss_bam_store_t; --gpus N: the store of every region in its GPU's).
+  // Per stored batch a kernel keeps those that overlap a merged cluster region; they come down slim, in file order, and
+  // go through `process` on a few threads, a stored batch per unit.
+  std::vector<std::vector<Ev>> pass2_store(const ClusterRegions& R, const Pass2Plan& p) {
+    std::vector<std::vector<Ev>> evs;
+    uint64_t n_down = 0, bytes_down = 0;
+    if (!R.rt.empty() && !p.items.empty()) {
+      std::vector<svdss_bam_filter_t*> rf(std::min<size_t>((size_t)n_dev, stores.size()));   // the regions, on every GPU that holds a store
+      for (size_t d = 0; d < rf.size(); ++d) rf[d] = R.filter((int32_t)d);
+      const size_t Wt = std::max<size_t>(1, std::min<size_t>({(size_t)effective_cpus(), (size_t)8, p.items.size()}));
+      // a thread's batch objects, one per device (a batch object belongs to one device); freed by that thread, beside the
+      // others' frees (device and page-locked memory: milliseconds each)
+      struct Selections {
+        std::map<size_t, svdss_bam_batch_t*> on;
+        std::string nm;
+        ~Selections() { for (auto& kv : on) svdss_bam_batch_free(kv.second); }
+      };
+      std::atomic<uint64_t> a_down(0), a_bytes(0);
+      evs = scan_units<Selections>(p.items.size(), Wt, "pass 2 from the record store: ", [&](Selections& sl, size_t k, auto& sink) -> std::string {
+        const StoreItem& it = p.items[k];
+        svdss_bam_batch_t*& b = sl.on[it.dev];
+        const int rc = svdss_bam_store_select(it.st, it.key, rf[it.dev], &b);
+        if (rc != SVDSS_OK) return std::string(svdss_strerror(rc)) + " " + svdss_last_hip_error();
+        svdss_bam_selection_t r;
+        (void)svdss_bam_batch_selection(b, &r);
+        BamReader::RawView rr;
+        for (int64_t i = 0; i < r.n_selected; ++i) {
+          if (!view_of_record(r.bytes + r.rec_off[i], (size_t)(r.rec_off[i + 1] - r.rec_off[i]), rr, true)) return "corrupt record in the store";
+          R.process(rr, sl.nm, sink);
+        }
+        a_down += (uint64_t)r.n_selected; a_bytes += (uint64_t)r.n_bytes;
+        return std::string();
+      });
+      for (svdss_bam_filter_t* f : rf) svdss_bam_filter_free(f);
+      n_down = a_down.load(); bytes_down = a_bytes.load();
+    }
+    logmsg("debug", "pass 2 from the records kept in HBM: " + std::to_string(p.st_records) + " records (" + std::to_string(p.st_bytes >> 20) + " MB) in " +
+                        std::to_string(p.items.size()) + " batches" + (stores.size() > 1 ? " of " + std::to_string(stores.size()) + " stores" : "") + ", " +
+                        std::to_string(R.rt.size()) + " regions, " + std::to_string(n_down) + " records (" + std::to_string(bytes_down >> 20) + " MB) came down");
+    // (tens of GB of HBM stay allocated until the run ends: memory handed back is cleared by the driver beside whatever
+    // runs next -- here the POA batches -- and `call` has room to spare: it holds no index)
+    return evs;
+  }
+
+  // The chunks the index names, in runs of consecutive chunks of about the same size in the file, a few per thread:
+  // every run is scanned by one thread with a file handle and an inflater of its own (bam_scan_chunks).
+  std::vector<std::vector<Ev>> pass2_index(const ClusterRegions& R, const std::vector<std::pair<uint64_t, uint64_t>>& chunks) {
+    const size_t Wt = pass2_threads(chunks.size());
+    uint64_t total = 0, acc = 0;
+    for (const auto& ch : chunks) total += chunk_span(ch);
+    const uint64_t per = std::max<uint64_t>(1, total / (4 * Wt));
+    std::vector<std::vector<std::pair<uint64_t, uint64_t>>> runs;
+    for (const auto& ch : chunks) {
+      if (runs.empty() || acc >= per) { runs.emplace_back(); acc = 0; }
+      runs.back().push_back(ch);
+      acc += chunk_span(ch);
+    }
+    return scan_units<std::string>(runs.size(), Wt, "error reading " + o.bam + ": ", [&](std::string& nm, size_t g, auto& sink) {
+      return bam_scan_chunks(o.bam, runs[g], [&](const BamReader::RawView& rr) { R.process(rr, nm, sink); });
+    });
+  }
+
   // Clusterer::fill_clusters (clusterer.cpp:477-610): pass 2 over the BAM
   void fill_clusters() {
-    // ---- fill_clusters (clusterer.cpp:477-610): pass 2 over the BAM
-    {
-      std::vector<std::set<std::string>> reads(clusters.size());
-      std::vector<int> min_s(clusters.size()), max_e(clusters.size());
-      std::vector<char> live(clusters.size(), 0);
-      std::vector<std::vector<int>> cov(clusters.size(), std::vector<int>(3, 0));
-      std::map<std::string, std::vector<size_t>> by_chrom;   // cluster indices per chrom, sorted by region start
-      for (size_t i = 0; i < clusters.size(); ++i) {
-        int mn = std::numeric_limits<int>::max(), mx = 0;
-        for (const ESFS& s : clusters[i].sfss) { mn = std::min(mn, s.rs); mx = std::max(mx, s.re); reads[i].insert(s.qname); }
-        min_s[i] = mn; max_e[i] = mx;
-        if (reads[i].size() < (size_t)o.min_cluster_weight) { ++C.small; continue; }
-        clusters[i].s = mn; clusters[i].e = mx;
-        live[i] = 1;
-        by_chrom[clusters[i].chrom].push_back(i);
-      }
-      std::map<std::string, std::vector<int>> run_max_end;   // per chrom: running maximum of the region ends, same order
-      for (auto& kv : by_chrom) {
-        std::sort(kv.second.begin(), kv.second.end(), [&](size_t a, size_t b) { return min_s[a] < min_s[b]; });
-        std::vector<int>& rm = run_max_end[kv.first];
-        int m = 0;
-        for (size_t ci : kv.second) { m = std::max(m, max_e[ci]); rm.push_back(m); }
-      }
-      // per reference id: the clusters of that chromosome (sorted by start) and the running maximum of their ends
-      std::vector<const std::vector<size_t>*> tid_clusters(ref_names.size(), nullptr);
-      std::vector<const std::vector<int>*> tid_run_max(ref_names.size(), nullptr);
-      for (size_t t = 0; t < ref_names.size(); ++t) {
-        auto it = by_chrom.find(ref_names[t]);
-        if (it == by_chrom.end()) continue;
-        tid_clusters[t] = &it->second;
-        tid_run_max[t] = &run_max_end[it->first];
-      }
-      static const char NT16[] = "=ACMGRSVTWYHKDBN";
-      std::string qname;
-      // Records stay in their raw form: the end position and the two query positions the reference reads off the
-      // aligned-pairs vector (bam.cpp:92-134, clusterer.cpp:555-580) are functions of the CIGAR blocks alone, and only
-      // the bases of the extracted sub-read are decoded.
-      // what one alignment does to one cluster it overlaps; applied in BAM order (sequentially, or collected by worker
-      // threads over contiguous record ranges and applied range after range)
-      struct Ev { size_t ci; int hp; bool in_reads, unext; std::string name, sub; };
-      auto apply = [&](Ev& e) {
-        if (e.hp >= 0 && e.hp < 3) ++cov[e.ci][(size_t)e.hp];
-        clusters[e.ci].reads.emplace_back(e.in_reads ? 1 : 0, e.hp == 0 ? 3 : e.hp);
-        if (!e.in_reads) return;
-        if (e.unext) ++C.unextended;
-        else clusters[e.ci].subreads.push_back(SubRead{std::move(e.name), std::move(e.sub), e.hp});
-      };
-      auto process = [&](const BamReader::RawView& rr, std::string& qname, auto&& sink) {
-        if (rr.tid < 0 || rr.tid >= (int)ref_names.size() || !tid_clusters[(size_t)rr.tid]) return;
-        if (rr.flag & (4 | 2048 | 256)) return;        // clusterer.cpp:535-540: such a record touches no cluster
-        if ((unsigned)rr.mapq < o.min_mapq) return;
-        const uint8_t* cg = rr.name() + rr.l_name;
-        auto cig = [&](uint32_t i) { uint32_t c; memcpy(&c, cg + 4u * i, 4); return c; };
-        int32_t ref_len = 0;
-        for (uint32_t i = 0; i < rr.n_cigar; ++i) {
-          const uint32_t c = cig(i), op = c & 0xf;
-          if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += (int32_t)(c >> 4);
-        }
-        const int a_beg = rr.pos, a_end = rr.pos + (ref_len ? ref_len : 1);   // bam_endpos
-        const std::vector<size_t>& cl_ids = *tid_clusters[(size_t)rr.tid];
-        // clusters before `first` end at or before the alignment's start: none of them can overlap it
-        const std::vector<int>& rm = *tid_run_max[(size_t)rr.tid];
-        const size_t first = (size_t)(std::upper_bound(rm.begin(), rm.end(), a_beg) - rm.begin());
-        bool have_tags = false;
-        int64_t hp = 0;
-        for (size_t k = first; k < cl_ids.size(); ++k) {
-          const size_t ci = cl_ids[k];
-          // region "chrom:min_s-max_e" = 0-based half-open [min_s-1, max_e)
-          const int beg0 = std::max(min_s[ci] - 1, 0), end0 = max_e[ci];
-          if (beg0 >= a_end) break;   // clusters are sorted by start
-          if (!(a_beg < end0 && a_end > beg0)) continue;
-          if (!have_tags) {
-            have_tags = true;
-            BamReader::aux_int(rr.aux(), rr.l_aux, "HP", hp);
-            qname.assign((const char*)rr.name(), rr.l_name ? rr.l_name - 1 : 0);
-          }
-          Ev ev{ci, (int)hp, false, false, std::string(), std::string()};
-          if (reads[ci].find(qname) == reads[ci].end()) { sink(ev); continue; }
-          ev.in_reads = true;
-          // qs: query position of the last aligned (M/=/X) pair with reference position <= min_s;
-          // qe: of the first one with reference position >= max_e
-          int qs = -1, qe = -1, ref_pos = rr.pos, read_pos = 0;
-          for (uint32_t i = 0; i < rr.n_cigar; ++i) {
-            const uint32_t c = cig(i), op = c & 0xf;
-            const int l = (int)(c >> 4);
-            if (op == 0 || op == 7 || op == 8) {
-              if (l > 0) {
-                if (ref_pos <= min_s[ci]) qs = read_pos + (std::min(min_s[ci], ref_pos + l - 1) - ref_pos);
-                if (qe == -1 && ref_pos + l - 1 >= max_e[ci]) qe = read_pos + (std::max(max_e[ci], ref_pos) - ref_pos);
-              }
-              read_pos += l; ref_pos += l;
-            } else if (op == 1 || op == 4) read_pos += l;
-            else if (op == 2 || op == 3) ref_pos += l;
-          }
-          if (qs == -1 || qe == -1) ev.unext = true;
-          else {
-            if (qs > rr.l_seq) die("corrupt alignment: sub-read start past the end of read " + qname);   // (std::string::substr throws in the reference)
-            const int n = std::max(0, std::min(qe - qs + 1, rr.l_seq - qs));
-            const uint8_t* sq = rr.seq4();
-            std::string sub((size_t)n, 'N');
-            for (int i = 0; i < n; ++i) { const int q = qs + i; sub[(size_t)i] = NT16[(sq[q >> 1] >> ((~q & 1) << 2)) & 0xf]; }
-            ev.name = qname;
-            ev.sub = std::move(sub);
-          }
-          sink(ev);
-        }
-      };
-      bool from_store = false;
-      if (!stores.empty()) {
-        // Round 6: the records are in HBM since pass 1 (svdss_bam_store_t; --gpus N: the store of every region in its GPU's).
-        // Per stored batch a kernel keeps those that overlap a (merged) cluster region; they come down slim, in file order,
-        // and go through `process` on a few threads, what they do to the clusters applied batch after batch -- the order
-        // of the single scan.
-        struct Item { svdss_bam_store_t* st; int64_t key; size_t dev; };
-        std::vector<Item> items;
-        bool complete_all = true;
-        int64_t n_rec_st = 0, n_bytes_st = 0;
-        const int n_phys = std::max(1, svdss_device_count());
-        for (size_t g = 0; g < stores.size(); ++g) {
-          int32_t complete = 0;
-          int64_t nr = 0, nb = 0;
-          if (g > 0 && g < region_seam.size() && region_seam[g]) {
-            (void)svdss_bam_store_batches(seam_stores[g], &complete, &nr, &nb);
-            complete_all = complete_all && complete;
-            n_rec_st += nr; n_bytes_st += nb;
-            items.push_back(Item{seam_stores[g], 0, g % (size_t)n_phys});
-          }
-          const int64_t n_b = svdss_bam_store_batches(stores[g], &complete, &nr, &nb);
-          complete_all = complete_all && complete && n_b == (g < region_batches.size() ? region_batches[g] : -1);
-          n_rec_st += nr; n_bytes_st += nb;
-          for (int64_t k = 0; k < n_b; ++k) items.push_back(Item{stores[g], k, g % (size_t)n_phys});
-        }
-        if (complete_all) {
-          from_store = true;
-          std::vector<int32_t> rt, rb, re;
-          for (size_t t = 0; t < ref_names.size(); ++t) {
-            if (!tid_clusters[t]) continue;
-            int64_t cb = -1, ce = -1;
-            for (size_t ci : *tid_clusters[t]) {
-              const int64_t b0 = std::max(min_s[ci] - 1, 0), e0 = max_e[ci];
-              if (ce >= 0 && b0 <= ce) { ce = std::max(ce, e0); continue; }
-              if (ce >= 0) { rt.push_back((int32_t)t); rb.push_back((int32_t)cb); re.push_back((int32_t)ce); }
-              cb = b0; ce = e0;
-            }
-            if (ce >= 0) { rt.push_back((int32_t)t); rb.push_back((int32_t)cb); re.push_back((int32_t)ce); }
-          }
-          uint64_t n_down = 0, bytes_down = 0;
-          if (!rt.empty() && !items.empty()) {
-            std::vector<svdss_bam_filter_t*> rf((size_t)std::min<size_t>((size_t)n_phys, stores.size()), nullptr);   // the regions, on every GPU that holds a store
-            for (size_t d = 0; d < rf.size(); ++d)
-              check(svdss_bam_filter_create((int32_t)d, (int32_t)std::min<unsigned>(o.min_mapq, 256u), (int32_t)ref_names.size(), nullptr, nullptr, 0, rt.data(), rb.data(),
-                                            re.data(), (int64_t)rt.size(), &rf[d]), "svdss_bam_filter_create");
-            std::vector<std::vector<Ev>> evs(items.size());
-            std::atomic<size_t> next(0);
-            std::atomic<uint64_t> a_down(0), a_bytes(0);
-            std::mutex err_m;
-            std::string err;
-            auto work = [&]() {
-              std::vector<svdss_bam_batch_t*> batch(rf.size(), nullptr);      // (a batch object belongs to one device)
-              std::string nm;
-              BamReader::RawView rr;
-              for (;;) {
-                const size_t k = next.fetch_add(1);
-                if (k >= items.size()) break;
-                const Item& it = items[k];
-                const int rc = svdss_bam_store_select(it.st, it.key, rf[it.dev], &batch[it.dev]);
-                if (rc != SVDSS_OK) { std::lock_guard<std::mutex> lk(err_m); if (err.empty()) err = std::string(svdss_strerror(rc)) + " " + svdss_last_hip_error(); break; }
-                svdss_bam_selection_t r;
-                (void)svdss_bam_batch_selection(batch[it.dev], &r);
-                auto sink = [&](Ev& e) { evs[k].push_back(std::move(e)); };
-                for (int64_t i = 0; i < r.n_selected; ++i) {
-                  if (!view_of_record(r.bytes + r.rec_off[i], (size_t)(r.rec_off[i + 1] - r.rec_off[i]), rr, true)) {
-                    std::lock_guard<std::mutex> lk(err_m); if (err.empty()) err = "corrupt record in the store"; break;
-                  }
-                  process(rr, nm, sink);
-                }
-                a_down += (uint64_t)r.n_selected; a_bytes += (uint64_t)r.n_bytes;
-              }
-              for (svdss_bam_batch_t* b : batch) if (b) svdss_bam_batch_free(b);
-            };
-            const size_t Wt = std::max<size_t>(1, std::min<size_t>({(size_t)effective_cpus(), (size_t)8, items.size()}));
-            std::vector<std::thread> pool;
-            for (size_t w = 1; w < Wt; ++w) pool.emplace_back(work);
-            work();
-            for (std::thread& th : pool) th.join();
-            for (svdss_bam_filter_t* f : rf) svdss_bam_filter_free(f);
-            if (!err.empty()) die("pass 2 from the record store: " + err);
-            for (size_t k = 0; k < items.size(); ++k)
-              for (Ev& e : evs[k]) apply(e);
-            n_down = a_down.load(); bytes_down = a_bytes.load();
-          }
-          logmsg("debug", "pass 2 from the records kept in HBM: " + std::to_string(n_rec_st) + " records (" + std::to_string(n_bytes_st >> 20) + " MB) in " +
-                              std::to_string(items.size()) + " batches" + (stores.size() > 1 ? " of " + std::to_string(stores.size()) + " stores" : "") + ", " +
-                              std::to_string(rt.size()) + " regions, " + std::to_string(n_down) + " records (" + std::to_string(bytes_down >> 20) + " MB) came down");
-        } else
-          logmsg("debug", "the record store is incomplete (" + std::to_string(n_bytes_st >> 20) + " MB kept): pass 2 reads the file again");
-        // (tens of GB of HBM stay allocated until the run ends: memory handed back is cleared by the driver beside whatever
-        // runs next -- here the POA batches -- and `call` has room to spare: it holds no index)
-      }
-      if (from_store) {
-      } else if (cache_ok) {
+    const ClusterRegions R(clusters, ref_names, o.min_cluster_weight, o.min_mapq);
+    C.small += R.n_small;
+    std::vector<std::vector<int>> cov(clusters.size(), std::vector<int>(3, 0));
+    // what the records do to the clusters, in BAM order
+    auto apply = [&](Ev& e) {
+      if (e.hp >= 0 && e.hp < 3) ++cov[e.ci][(size_t)e.hp];
+      clusters[e.ci].reads.emplace_back(e.in_reads ? 1 : 0, e.hp == 0 ? 3 : e.hp);
+      if (!e.in_reads) return;
+      if (e.unext) ++C.unextended;
+      else clusters[e.ci].subreads.push_back(SubRead{std::move(e.name), std::move(e.sub), e.hp});
+    };
+    auto apply_units = [&](std::vector<std::vector<Ev>> evs) {
+      for (std::vector<Ev>& unit : evs)
+        for (Ev& e : unit) apply(e);
+    };
+    const Pass2Plan p = plan_pass2(R);
+    switch (p.src) {
+      case Pass2::store: apply_units(pass2_store(R, p)); break;
+      case Pass2::cache: {   // contiguous ranges of records, one per thread
         stage("pass 2: setup");
         const size_t n = cache_views.size();
         const size_t W = std::max<size_t>(1, std::min<size_t>({(size_t)effective_cpus(), (size_t)32, n / 4096 + 1}));
-        std::vector<std::vector<Ev>> evs(W);
-        auto range = [&](size_t w) {
-          std::string nm;
-          auto sink = [&](Ev& e) { evs[w].push_back(std::move(e)); };
-          for (size_t i = n * w / W; i < n * (w + 1) / W; ++i) process(cache_views[i], nm, sink);
-        };
-        std::vector<std::thread> pool;
-        for (size_t w = 1; w < W; ++w) pool.emplace_back(range, w);
-        range(0);
-        for (std::thread& th : pool) th.join();
+        std::vector<std::vector<Ev>> evs = scan_units<std::string>(W, W, "", [&](std::string& nm, size_t w, auto& sink) {
+          for (size_t i = n * w / W; i < n * (w + 1) / W; ++i) R.process(cache_views[i], nm, sink);
+          return std::string();
+        });
         stage("pass 2: scan");
-        for (size_t w = 0; w < W; ++w)
-          for (Ev& e : evs[w]) apply(e);
+        apply_units(std::move(evs));
         stage("pass 2: apply");
         // (gigabytes of inflated records: released while the DP batches run)
         cache_release = std::thread([v = std::move(cache_views), c = std::move(cache_chunks)]() mutable { v.clear(); c.clear(); });
-      } else {
-        // the records of pass 1 did not fit in memory.  With a BAI index beside the file (what the reference requires:
-        // sam_index_load + one sam_itr_querys per cluster, clusterer.cpp:495-527) only the file chunks around the
-        // clusters are read -- all regions turned into one sorted, merged chunk list, read once in file order, which
-        // visits the same records in the same order as the full scan below does among those that touch a cluster
-        BaiIndex bai;
-        bool have_bai = false;
-        if (!getenv("SVDSS_CALL_NO_BAI")) {
-          // (x.bam.bai, x.bai, x.bam.csi, x.csi: the names htslib's sam_index_load looks for)
-          const std::string stem = o.bam.size() > 4 && o.bam.compare(o.bam.size() - 4, 4, ".bam") == 0 ? o.bam.substr(0, o.bam.size() - 4) : std::string();
-          have_bai = bai.load(o.bam + ".bai") || (!stem.empty() && bai.load(stem + ".bai")) || bai.load(o.bam + ".csi") ||
-                     (!stem.empty() && bai.load(stem + ".csi"));
-          if (have_bai && bai.refs.size() != ref_names.size()) have_bai = false;
-        }
-        std::vector<std::pair<uint64_t, uint64_t>> chunks;
-        size_t n_regions = 0;
-        if (have_bai) {
-          for (size_t t = 0; t < ref_names.size(); ++t) {
-            if (!tid_clusters[t]) continue;
-            int64_t rb = -1, re = -1;   // current merged region
-            for (size_t ci : *tid_clusters[t]) {
-              const int64_t b0 = std::max(min_s[ci] - 1, 0), e0 = max_e[ci];
-              if (re >= 0 && b0 <= re) { re = std::max(re, e0); continue; }
-              if (re >= 0) { bai.query((int)t, rb, re, chunks); ++n_regions; }
-              rb = b0; re = e0;
-            }
-            if (re >= 0) { bai.query((int)t, rb, re, chunks); ++n_regions; }
-          }
-          BaiIndex::merge(chunks);
-          // The index names the file chunks around the clusters; host threads inflate them (~0.3 GB/s each; second session
-          // of round 5: all of them, until then one).  When the chunks are a large part of the file, reading ALL of it
-          // through the device path (tens of GB/s, only the overlapping records come back) is quicker: beyond 8 % of the
-          // file per thread that scans.  SVDSS_CALL_PASS2 = bai | device overrides the estimate.
-          if (dev_pass) {
-            uint64_t chunk_bytes = 0;
-            for (const auto& ch : chunks) chunk_bytes += (ch.second >> 16) - (ch.first >> 16) + 65536;
-            struct stat st;
-            const uint64_t file_bytes = stat(o.bam.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
-            const char* p2 = getenv("SVDSS_CALL_PASS2");
-            const double share = std::min(0.6, 0.08 * (double)pass2_threads(chunks.size()));
-            if (p2 && !strcmp(p2, "device")) have_bai = false;
-            else if (!(p2 && !strcmp(p2, "bai")) && file_bytes && (double)chunk_bytes > share * (double)file_bytes) have_bai = false;
-          }
-        }
-        if (have_bai) {
-          logmsg("debug", std::string("pass 2 through the ") + (bai.csi ? "CSI" : "BAI") + " index: " + std::to_string(n_regions) + " regions, " + std::to_string(chunks.size()) +
-                              " file chunks");
-          const size_t Wt = pass2_threads(chunks.size());
-          if (Wt <= 1) {
-            const std::string e = bam_scan_chunks(o.bam, chunks, [&](const BamReader::RawView& rr) { process(rr, qname, apply); });
-            if (!e.empty()) die("error reading " + o.bam + ": " + e);
-          } else {
-            // Runs of consecutive chunks of about the same size in the file, a few per thread, taken in turn: every run is
-            // scanned by one thread with a file handle and an inflater of its own (bam_scan_chunks), what its records do
-            // to the clusters is collected and applied run after run -- the order of the single scan.
-            std::vector<std::pair<size_t, size_t>> runs;
-            {
-              uint64_t total = 0;
-              for (const auto& ch : chunks) total += (ch.second >> 16) - (ch.first >> 16) + 65536;
-              const uint64_t per = std::max<uint64_t>(1, total / (4 * Wt));
-              size_t a = 0;
-              uint64_t acc = 0;
-              for (size_t k = 0; k < chunks.size(); ++k) {
-                acc += (chunks[k].second >> 16) - (chunks[k].first >> 16) + 65536;
-                if (acc >= per || k + 1 == chunks.size()) { runs.emplace_back(a, k + 1); a = k + 1; acc = 0; }
-              }
-            }
-            std::vector<std::vector<Ev>> evs(runs.size());
-            std::vector<std::string> errs(runs.size());
-            std::atomic<size_t> next(0);
-            auto work = [&]() {
-              std::string nm;
-              for (;;) {
-                const size_t g = next.fetch_add(1);
-                if (g >= runs.size()) return;
-                const std::vector<std::pair<uint64_t, uint64_t>> sub(chunks.begin() + (ptrdiff_t)runs[g].first, chunks.begin() + (ptrdiff_t)runs[g].second);
-                auto sink = [&](Ev& e) { evs[g].push_back(std::move(e)); };
-                errs[g] = bam_scan_chunks(o.bam, sub, [&](const BamReader::RawView& rr) { process(rr, nm, sink); });
-              }
-            };
-            std::vector<std::thread> pool;
-            for (size_t w = 1; w < Wt; ++w) pool.emplace_back(work);
-            work();
-            for (std::thread& th : pool) th.join();
-            for (size_t g = 0; g < runs.size(); ++g) {
-              if (!errs[g].empty()) die("error reading " + o.bam + ": " + errs[g]);
-              for (Ev& e : evs[g]) apply(e);
-            }
-          }
-        } else if (dev_pass) {
-          // no index: the file again through the device path, the (merged) cluster regions as the filter -- the records
-          // that overlap a cluster come back, in file order
-          std::vector<int32_t> rt, rb, re;
-          for (size_t t = 0; t < ref_names.size(); ++t) {
-            if (!tid_clusters[t]) continue;
-            int64_t cb = -1, ce = -1;
-            for (size_t ci : *tid_clusters[t]) {
-              const int64_t b0 = std::max(min_s[ci] - 1, 0), e0 = max_e[ci];
-              if (ce >= 0 && b0 <= ce) { ce = std::max(ce, e0); continue; }
-              if (ce >= 0) { rt.push_back((int32_t)t); rb.push_back((int32_t)cb); re.push_back((int32_t)ce); }
-              cb = b0; ce = e0;
-            }
-            if (ce >= 0) { rt.push_back((int32_t)t); rb.push_back((int32_t)cb); re.push_back((int32_t)ce); }
-          }
-          if (!rt.empty()) {
-            const int n_phys = std::max(1, svdss_device_count());
-            if (bam_cuts.empty()) bam_cuts = plan_bam_regions(o.bam, 1, bam_skip);
-            std::vector<svdss_bam_filter_t*> filters;
-            std::vector<ShardedBamSelect<SelectedBatch>::Shard> shards;
-            for (size_t g = 0; g + 1 < bam_cuts.size(); ++g) {
-              svdss_bam_filter_t* f = nullptr;
-              check(svdss_bam_filter_create((int32_t)(g % (size_t)n_phys), (int32_t)std::min<unsigned>(o.min_mapq, 256u), (int32_t)ref_names.size(), nullptr, nullptr, 0,
-                                            rt.data(), rb.data(), re.data(), (int64_t)rt.size(), &f), "svdss_bam_filter_create");
-              filters.push_back(f);
-              ShardedBamSelect<SelectedBatch>::Shard sh;
-              sh.filter = f;
-              shards.push_back(sh);
-            }
-            {
-              ShardedBamSelect<SelectedBatch> sel(o.bam, shards, (int32_t)ref_names.size(), bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts);
-              BamReader::RawView rr;
-              while (std::unique_ptr<SelectedBatch> sb = sel.next())
-                for (size_t k = 0; k + 1 < sb->off.size(); ++k) {
-                  if (!view_of_record(sb->bytes.data() + sb->off[k], (size_t)(sb->off[k + 1] - sb->off[k]), rr, sb->slim)) die("error reading " + o.bam + ": corrupt record");
-                  process(rr, qname, apply);
-                }
-              if (!sel.error().empty()) die("error reading " + o.bam + ": " + sel.error());
-            }
-            for (svdss_bam_filter_t* f : filters) svdss_bam_filter_free(f);
-          }
-        } else {
-          BamReader bam(o.bam);
-          svdss_enable_gpu_inflate(bam);
-          if (!bam.ok() || !bam.read_header()) die("cannot read " + o.bam + ": " + bam.error());
-          BamReader::RawView rr;   // zero-copy: the record is used where it was inflated, within this iteration only
-          int rc;
-          while ((rc = bam.next_view(rr)) > 0) process(rr, qname, apply);
-          if (rc < 0) die("error reading " + o.bam + ": " + bam.error());
-        }
+        break;
       }
-      for (size_t i = 0; i < clusters.size(); ++i) {
-        if (!live[i]) { clusters[i].reads.clear(); clusters[i].subreads.clear(); continue; }
-        if (clusters[i].size() >= (size_t)o.min_cluster_weight) {
-          clusters[i].cov0 = cov[i][0]; clusters[i].cov1 = cov[i][1]; clusters[i].cov2 = cov[i][2];
-          clusters[i].cov = cov[i][0] + cov[i][1] + cov[i][2];
-        } else ++C.small2;
+      case Pass2::index: apply_units(pass2_index(R, p.chunks)); break;
+      case Pass2::device: case Pass2::host: {
+        // the whole file again, records applied as they come: through the device path with the merged cluster regions as
+        // the filter (the records that overlap a cluster come back, in file order), or through the host reader
+        if (p.src == Pass2::device && R.rt.empty()) break;
+        RecordFeed feed;
+        if (p.src == Pass2::host) open_reader(feed, 1);
+        else open_select(feed, (int32_t)ref_names.size(), false, [&](int32_t dev) { return R.filter(dev); });
+        std::string qname;
+        BamReader::RawView rr;   // zero-copy: the record is used where it was inflated, within this iteration only
+        int rc;
+        while ((rc = feed.next(rr)) > 0) R.process(rr, qname, apply);
+        if (rc < 0) die("error reading " + o.bam + ": " + feed.err);
       }
+    }
+    for (size_t i = 0; i < clusters.size(); ++i) {
+      if (!R.live[i]) { clusters[i].reads.clear(); clusters[i].subreads.clear(); continue; }
+      if (clusters[i].size() >= (size_t)o.min_cluster_weight) {
+        clusters[i].cov0 = cov[i][0]; clusters[i].cov1 = cov[i][1]; clusters[i].cov2 = cov[i][2];
+        clusters[i].cov = cov[i][0] + cov[i][1] + cov[i][2];
+      } else ++C.small2;
     }
     stage("pass 2: fill_clusters");
   }
@@ -1287,9 +1282,6 @@ struct CallRun {
       fclose(f);
     }
     logmsg("info", "Calling SVs from " + std::to_string(clusters.size()) + " clusters..");
-    // (SVDSS_GPUS_OVERSUBSCRIBE: more shards than GPUs, shard g on GPU g % count -- exercises the sharding on a one-GPU box)
-    n_dev = std::max(1, svdss_device_count());
-    G = std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, n_dev));
     // ---- pcall (caller.cpp:311-406): split, then the three GPU batches
     for (size_t i = 0; i < clusters.size(); ++i) {
       if (clusters[i].size() < (size_t)o.min_cluster_weight) continue;
