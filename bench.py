@@ -12,15 +12,21 @@ A "step" = one pass of the hot path over one batch of 1,048,576 reads per GPU (a
           svdss_poa_consensus_batch (caller.cpp:257-308), svdss_align_global_batch of every consensus against its
           reference window (caller.cpp:332-355), svdss_indel_ratio_batch on adjacent alleles (caller.cpp:456-458).
           The sub-reads are handed over as host buffers (~120 MB per step), as `pcall` hands them to abPOA.
-value = reads / wall time of the steps.  In the same run the index is checked row by row against its text
-(svdss_index_verify_device: `index_verified_rows`), the first reads of the batch are searched by the CPU oracle and a
-sample of the step's sub-clusters goes through the oracle's POA / realignment / ratio (cpu_baseline: search, call and
-the combined rate), and the GPU's results for those reads (counts / starts / lengths / extension counts) and
-sub-clusters (consensus lengths, alignment scores, CIGAR lengths, ratios) are compared with them: `verified_reads`,
-`verified_subclusters`; the bench fails on a mismatch.  Then the binaries run end to end (file- and PCIe-inclusive,
-never `value`): `SVDSS search` on a BAM against a chr20-length and against the whole-genome index, `SVDSS call`.
+value = reads / wall time of the steps.  A plain run does only what that figure needs: it builds the reference, the
+index and the step's inputs, runs the search and the call side once alone (the set-up of their device buffers, which
+also gives `roofline` and the `*_on_idle_gpu` figures), warms up, times the steps, writes --dump-outputs if asked and
+prints the result line.
 
-  python bench.py --gpus 1 --steps K --warmup W
+With --full the same run also checks its results and runs what lies around them.  The index is checked row by row
+against its text (svdss_index_verify_device: `index_verified_rows`); the first reads of the batch are searched by the
+CPU oracle and a sample of the step's sub-clusters goes through the oracle's POA / realignment / ratio (cpu_baseline:
+search, call and the combined rate), and the GPU's results for those reads (counts / starts / lengths / extension
+counts) and sub-clusters (consensus lengths, alignment scores, CIGAR lengths, ratios) are compared with them:
+`verified_reads`, `verified_subclusters`; the bench fails on a mismatch.  Then the binaries run end to end (file- and
+PCIe-inclusive, never `value`): `SVDSS search` on a BAM against a chr20-length and against the whole-genome index,
+`SVDSS call`.
+
+  python bench.py --gpus 1 --steps K --warmup W [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU (config 5): the index is replicated (every rank builds its own replica in its HBM, svdss_index_build_device),
@@ -312,6 +318,11 @@ def main():
     ap.add_argument("--read-len", type=int, default=15000)
     ap.add_argument("--err", type=float, default=0.005)
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verify the index, run the CPU baseline that checks the GPU's results "
+                         "and the end-to-end runs of the binaries (--no-cpu-baseline and the --no-e2e* options leave "
+                         "legs of it out).  Off: set up, warm up, time the steps, write --dump-outputs, print the "
+                         "result line")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (also skips verification)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end run of the SVDSS binary on a BAM file")
@@ -393,15 +404,16 @@ def main():
     t0 = time.time()
     ix = svdss_amd.FMDIndex.build(ref, device=local_rank)
     t_index = time.time() - t0
-    # the index against its own text, row by row, by code that shares nothing with the builder (csrc/index_verify.hip):
-    # the oracle below is built from this index's BWT and must not inherit an unchecked index
-    t0 = time.time()
-    iv = ix.verify()
-    t_verify = time.time() - t0
-    if iv["rows"] != ix.size or iv["first_bad"] != -1 or any(iv[k] for k in ("bad_order", "bad_bwt", "bad_range", "bad_block", "bad_dollar")):
-        raise SystemExit(f"INDEX VERIFICATION FAILED: {iv}")
+    # --full: the index against its own text, row by row, by code that shares nothing with the builder
+    # (csrc/index_verify.hip): the oracle below is built from this index's BWT and must not inherit an unchecked index
+    if args.full:
+        t0 = time.time()
+        iv = ix.verify()
+        t_verify = time.time() - t0
+        if iv["rows"] != ix.size or iv["first_bad"] != -1 or any(iv[k] for k in ("bad_order", "bad_bwt", "bad_range", "bad_block", "bad_dollar")):
+            raise SystemExit(f"INDEX VERIFICATION FAILED: {iv}")
     e2e_dir, e2e_error = None, None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         # (the end-to-end legs are auxiliary: whatever goes wrong there -- a full /tmp, a missing binary -- is reported
         # in the JSON line and must not cost the run its headline measurement)
         import shutil
@@ -599,7 +611,9 @@ def main():
     gw = workers[0][1] if workers else None
 
     # raw (unassembled) SFS count: the N_sfs of SURVEY 8(d)'s reference-model bytes; and the search kernel on an
-    # otherwise idle GPU
+    # otherwise idle GPU.  These runs are part of every run's set-up, not of --full alone: the raw search leaves result
+    # buffers of ~6 GB in the batch object, and the call side sizes its POA and realignment workspaces by the HBM still
+    # free at each batch object's first call -- the timed steps see the device as these runs leave it
     search(assemble=False)
     n_sfs_raw = pp.last_total
     alone_ms = []
@@ -647,8 +661,9 @@ def main():
     dumped = None
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, last_step["search"], last_step["call"])
-    search(assemble=True)     # leave the assembled results of one more search in the batch object for the verification
-    finish_gathers()
+    if args.full:
+        search(assemble=True)     # leave the assembled results of one more search in the batch object for the verification
+        finish_gathers()
 
     n_ext = pp.last_total_ext
     n_sfs_asm = pp.last_total
@@ -689,7 +704,7 @@ def main():
                                    else "no data-path collective")),
                 "ext_per_read": n_ext / n_reads, "raw_sfs_per_read": n_sfs_raw / n_reads,
                 "assembled_sfs_per_read": n_sfs_asm / n_reads, "reference_build_s": round(t_ref, 1),
-                "index_build_s": round(t_index, 1), "index_verify_s": round(t_verify, 2), "kmer_table_k": ix.kmer_k, "segments_per_read": pp.last_segments,
+                "index_build_s": round(t_index, 1), "kmer_table_k": ix.kmer_k, "segments_per_read": pp.last_segments,
                 "reads_redone_unsegmented": pp.last_fallbacks,
                 "search_ms_per_step": float(np.mean(pipeline_ms)),
                 "search_kernel_ms_on_idle_gpu": float(np.mean(alone_ms)),
@@ -699,12 +714,13 @@ def main():
             },
         }
         oracle_fm = None
-        out["index_verified_rows"] = iv["rows"]
+        if args.full:
+            out["config"]["index_verify_s"] = round(t_verify, 2)
+            out["index_verified_rows"] = iv["rows"]
         out["roofline"] = search_roofline(ref_total, n_reads, L, ix.kmer_k, k_ms, n_ext, total_syms, n_sfs_raw,
                                           float(np.mean(pipeline_ms)), float(np.mean(alone_ms)),
                                           tag=(f"_families{args.divergence:g}" if families else ""))
         if cw is not None:
-            okc, n_alt = cw.svs_recovered()
             # per STEP: the batches of the timed region covered call_steps steps each
             n_call_steps = float(sum(stats["call_steps"]))
             poa_k, aln_k = float(np.sum(poa_ms)) / n_call_steps, float(np.sum(aln_ms)) / n_call_steps
@@ -728,22 +744,24 @@ def main():
                 "realign_kernel_ms": round(aln_k, 3), "realign_cells": cw.last["realign_cells"],
                 "realign_gcups": cw.last["realign_cells"] / (aln_k * 1e-3) / 1e9,
                 "ratio_wall_ms": round(cw.last["ratio_wall_ms"], 3),
-                "alt_subclusters_with_the_implanted_sv_in_the_cigar": f"{okc}/{n_alt}",
                 # integer DP, not HBM- and not MFMA-bound: cell updates x VALU lane-operations per cell
                 # against the int32 issue rate of 256 CUs x 4 SIMD-32 x 2.4 GHz
             }
+            if args.full:
+                okc, n_alt = cw.svs_recovered()
+                out["config"]["call_dp"]["alt_subclusters_with_the_implanted_sv_in_the_cigar"] = f"{okc}/{n_alt}"
             # (hoisted out of config.call_dp, which the driver's record truncates: the call-side kernels against their bound,
             # measured alone on an idle GPU; poa_kernel_ms / realign_kernel_ms in call_dp are per step inside the pipeline)
             out["roofline"]["call_side"] = call_rooflines(cw.last["poa_cells"], call_alone["poa_kernel_ms"], cw.last["realign_cells"],
                                                           call_alone["realign_kernel_ms"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["verified_reads"], out["verified_subclusters"], oracle_fm = cpu_baseline_and_verify(
                 ix, pp, d_reads, L, n_reads, args.cpu_seconds, cw)
         if dumped is not None:
             out["dumped_outputs"] = dumped
         if e2e_error:
             out["e2e_error"] = e2e_error
-        if world == 1 and not args.no_e2e and e2e_dir:
+        if args.full and world == 1 and not args.no_e2e and e2e_dir:
             # the end-to-end run is a process of its own on the same GPU: this one lets go of the index (127 GB), the
             # reads and the call-side arenas first
             for sp, _ in searchers:

@@ -5,7 +5,7 @@
 # Summaries are written to gpurun_out/final_kernel_stats.csv and gpurun_out/final_pmc.csv for profiles/.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-CMD="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-call-dp"
+CMD="python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-call-dp"
 # counters: the same workload and launches without the torch kernels of the read simulator around them
 PMC_CMD="python $R/tools/sweep_search.py 0 0 128888"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/final_stats -- $CMD > $R/gpurun_out/final_bench_under_rocprof.json 2>/dev/null

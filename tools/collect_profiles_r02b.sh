@@ -11,7 +11,7 @@ mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q --durations=5 > $O/gpu_suite.log 2>&1
 tail -4 $O/gpu_suite.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 1500 $O/bench_default.json
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-e2e > $O/bench_under_rocprof.json 2>/dev/null

@@ -12,7 +12,7 @@ mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q --durations=5 > $O/gpu_suite.log 2>&1
 grep -E "passed|failed" $O/gpu_suite.log | tail -1
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
 tail -c 300 $O/bench_driver_command.json
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R

@@ -41,7 +41,7 @@ rm -rf $O/pmccall_[0-9]*
 tail -3 $O/call_dp_probe_1.log
 # 3. repeat-rich whole-genome references (45 % family repeats), search + call as in the default bench
 for d in 0.15 0.05 0.01; do
-  timeout 900 python $R/bench.py --workload wg-families --divergence $d --steps 8 --warmup 2 --no-e2e --cpu-seconds 6 > $O/bench_wg_families_$d.json 2> $O/bench_wg_families_$d.err
+  timeout 900 python $R/bench.py --full --workload wg-families --divergence $d --steps 8 --warmup 2 --no-e2e --cpu-seconds 6 > $O/bench_wg_families_$d.json 2> $O/bench_wg_families_$d.err
   python - <<PY
 import json
 try:

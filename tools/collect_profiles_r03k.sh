@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -x -q -m gpu --durations=5 > $O/gpu_suite.log 2>&1; tail -9 $O/gpu_suite.log
 timeout 120 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
 tail -c 600 $O/bench_driver_command.json | head -c 300; echo
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
