@@ -432,6 +432,34 @@ typedef struct svdss_bam_smoothed {
   double stage_ms[8];             /* 0-2 as svdss_bam_result_t, 3 filters + CIGAR walk, 4 sizes + records, 5 the output turn, 6 deflate + down */
 } svdss_bam_smoothed_t;
 int svdss_bam_batch_smoothed(const svdss_bam_batch_t* b, svdss_bam_smoothed_t* out);
+/* `smooth --write-index` (csrc/bam_smooth.inc, csrc/bam_index_writer.h): svdss_bam_smooth_set_index(sm, min_shift, depth)
+ * asks every later svdss_bam_smooth_run on sm for the batch's index fragments (min_shift 0: none, the default; BAI is 14 / 5).
+ * They are reduced on the device: one chunk per run of consecutive kept records with the same (tid, bin), one window entry
+ * (16 kb at min_shift 14) per window that a record of the batch reaches into first.  Virtual offsets are relative to the
+ * batch: (compressed offset from the batch's first member) << 16 | offset in the block; a position at or behind the end of
+ * the batch's last member is addressed from the offset right after it (the next member of the output). */
+typedef struct svdss_bam_index_chunk {
+  int32_t tid;
+  uint32_t bin;
+  int64_t n_rec;                  /* records of the run */
+  uint64_t v_beg, v_end;          /* first record's start, last record's end */
+} svdss_bam_index_chunk_t;
+typedef struct svdss_bam_index_window {
+  int32_t tid;
+  int32_t window;                 /* position >> min_shift */
+  uint64_t v_beg;                 /* start of the first record of the batch that reaches into the window */
+} svdss_bam_index_window_t;
+typedef struct svdss_bam_index_frag {
+  int64_t n_chunks;
+  const svdss_bam_index_chunk_t* chunks;    /* in file order */
+  int64_t n_windows;
+  const svdss_bam_index_window_t* windows;  /* in file order */
+  int32_t unsorted;               /* a kept record starts before the one in front of it (tid, then position) */
+  int32_t first_tid, last_tid;    /* the batch's first and last kept record (n_chunks > 0) */
+  int64_t first_beg, last_beg;
+} svdss_bam_index_frag_t;
+int svdss_bam_smooth_set_index(svdss_bam_smooth_t* sm, int32_t min_shift, int32_t depth);
+int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* out);
 const char* svdss_bam_batch_error(const svdss_bam_batch_t* b);
 void svdss_bam_batch_free(svdss_bam_batch_t* b);
 

@@ -808,6 +808,12 @@ struct svdss_bam_batch {
   const uint8_t* sm_bgzf = nullptr;   // where the last run's BGZF members are (the caller's buffer or h_sel)
   std::vector<int64_t> sm_nmx;
   std::vector<uint8_t> sm_fits;
+  // ... with an index asked for (svdss_bam_smooth_set_index): the batch's fragments (svdss_bam_batch_index)
+  DevBuf sm_ix, sm_ixw;
+  bool sm_ix_on = false;
+  std::vector<svdss_bam_index_chunk_t> sm_ix_chunks;
+  std::vector<svdss_bam_index_window_t> sm_ix_windows;
+  int64_t sm_ix_hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   svdss_sfs_batch_t* sfs = nullptr;
   // results of the last run (host side)
   std::vector<int32_t> name_off, hp, sidx, qs, len;
@@ -885,7 +891,7 @@ extern "C" void svdss_bam_batch_free(svdss_bam_batch_t* b) {
     if (d->p) (void)hipFree(d->p);
   if (b->h_pin) (void)hipHostFree(b->h_pin);
   if (b->h_sel) (void)hipHostFree(b->h_sel);
-  for (DevBuf* d : {&b->sel_out, &b->sel_off, &b->sm_rec, &b->sm_out, &b->sm_scratch, &b->sm_members, &b->sm_dense, &b->sm_len})
+  for (DevBuf* d : {&b->sel_out, &b->sel_off, &b->sm_rec, &b->sm_out, &b->sm_scratch, &b->sm_members, &b->sm_dense, &b->sm_len, &b->sm_ix, &b->sm_ixw})
     if (d->p) (void)hipFree(d->p);
   if (b->sfs) svdss_sfs_batch_free(b->sfs);
   if (b->e0) (void)hipEventDestroy(b->e0);

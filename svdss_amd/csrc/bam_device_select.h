@@ -119,6 +119,11 @@ struct SelectedBatch {
   size_t ext_n = 0;
   int ext_slot = -1;              // ... and which one, for its return
   double stage_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, inflate_kernel_s = 0;
+  // smoothing with an index asked for: the batch's index fragments (svdss_bam_batch_index; ix's pointers are set by the
+  // consumer, into the two vectors)
+  std::vector<svdss_bam_index_chunk_t> ix_chunks;
+  std::vector<svdss_bam_index_window_t> ix_windows;
+  svdss_bam_index_frag_t ix{};
 };
 
 // a record's view (BamReader::RawView: the zero-copy form the host readers hand out) over bytes that hold it

@@ -17,6 +17,8 @@
 // record carry; for batch 0: the BAM header of the output), puts it in front of its own records, hands the bytes behind its
 // last full block on, and only then deflates -- so the deflate kernels of different batches overlap.
 
+#include "bam_index_writer.h"
+
 namespace {
 
 enum { E_NCIG = 4 };   // more than 65535 CIGAR operations after smoothing (further bits of hdr[H_ERR])
@@ -391,6 +393,104 @@ __global__ void __launch_bounds__(64) smooth_write_kernel(SmWriteP A) {
   }
 }
 
+// ---- `smooth --write-index` (bam_index_writer.h): the batch's index fragments, reduced before anything comes down
+struct SmIxP {
+  const uint8_t* out;        // the batch's rebuilt records (sm_out + room); record k at ooff[k]
+  const int64_t* ooff;       // n_keep + 1
+  int64_t n_keep;
+  int64_t tail_in, in_len, n_blk;   // the output turn: bytes in front of the records, bytes in full members, members
+  const int64_t* d_off;      // n_blk + 1 compressed offsets of the members (nullptr: n_blk == 0)
+  int32_t min_shift, depth;
+  // per kept record (n_keep + 1)
+  int32_t* tid; uint32_t* bin; int64_t* beg; int64_t* end; uint64_t* vb; uint64_t* ve;
+  uint64_t* key;             // (tid << 32) | (last window + 1): a running maximum of it is the last window reached so far
+  const uint64_t* kmax;      // ... exclusive running maximum
+  int64_t* head; int64_t* own;           // starts a chunk; windows it reaches into first
+  const int64_t* s_head; const int64_t* s_own;
+  svdss_bam_index_chunk_t* chunks; svdss_bam_index_window_t* windows;
+  unsigned long long* err;   // bit 0: records out of coordinate order
+};
+
+// the virtual offset (relative to the batch's first member) of position q of the batch's stream: the member that holds the
+// byte; behind the batch's full members (the carried block, which is the next batch's first member, or the end of the
+// output) the offset right after them
+__device__ __forceinline__ uint64_t sm_ix_voff(const SmIxP& P, int64_t q) {
+  if (q < P.in_len) return ((uint64_t)P.d_off[q / kBgzfBlock] << 16) | (uint64_t)(q % kBgzfBlock);
+  const int64_t after = P.n_blk > 0 ? P.d_off[P.n_blk] : 0;
+  return ((uint64_t)after << 16) | (uint64_t)(q - P.in_len);
+}
+
+__device__ __forceinline__ void sm_ix_core(const SmIxP& P, int64_t k, int32_t& tid, int32_t& pos, int64_t& span) {
+  const int64_t r = P.ooff[k];
+  tid = (int32_t)ld32(P.out, r + 4);
+  pos = (int32_t)ld32(P.out, r + 8);
+  const int64_t l_name = ld32(P.out, r + 12) & 0xffu;
+  const int n_cig = (int)(ld32(P.out, r + 16) & 0xffffu);
+  span = 0;
+  for (int j = 0; j < n_cig; ++j) {
+    const uint32_t c = ld32(P.out, r + 36 + l_name + 4 * (int64_t)j);
+    if (ix_ref_op(c & 0xfu)) span += c >> 4;
+  }
+}
+
+// a thread per kept record: tid, [beg, end) (the span of the CIGAR as written), bin, virtual offsets of start and end
+__global__ void __launch_bounds__(256) sm_ix_rec_kernel(SmIxP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= P.n_keep) return;
+  int32_t tid, pos;
+  int64_t span, beg, end;
+  sm_ix_core(P, k, tid, pos, span);
+  ix_extent(pos, span, P.min_shift, P.depth, beg, end);
+  P.tid[k] = tid; P.beg[k] = beg; P.end[k] = end;
+  P.bin[k] = ix_reg2bin(beg, end, P.min_shift, P.depth);
+  P.vb[k] = sm_ix_voff(P, P.tail_in + P.ooff[k]);
+  P.ve[k] = sm_ix_voff(P, P.tail_in + P.ooff[k + 1]);
+  P.key[k] = ((uint64_t)(uint32_t)tid << 32) | (uint64_t)(((end - 1) >> P.min_shift) + 1);
+  if (k > 0) {
+    const int64_t r = P.ooff[k - 1];
+    const int32_t ptid = (int32_t)ld32(P.out, r + 4);
+    int64_t pbeg, pend;
+    ix_extent((int32_t)ld32(P.out, r + 8), 1, P.min_shift, P.depth, pbeg, pend);
+    if (tid < ptid || (tid == ptid && beg < pbeg)) atomicOr(P.err, 1ull);
+  }
+}
+
+// a thread per kept record (+ the scans' total): does it start a chunk, which windows does it reach into first
+__global__ void __launch_bounds__(256) sm_ix_own_kernel(SmIxP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > P.n_keep) return;
+  if (k == P.n_keep) { P.head[k] = 0; P.own[k] = 0; return; }
+  const uint64_t m = P.kmax[k];
+  const int32_t tid = P.tid[k];
+  const int64_t seen = (m >> 32) == (uint64_t)(uint32_t)tid ? (int64_t)(m & 0xffffffffu) - 1 : -1;   // last window reached before
+  const int64_t w0 = P.beg[k] >> P.min_shift, w1 = (P.end[k] - 1) >> P.min_shift;
+  const int64_t first = w0 > seen + 1 ? w0 : seen + 1;
+  P.own[k] = w1 >= first ? w1 - first + 1 : 0;
+  P.head[k] = (k == 0 || tid != P.tid[k - 1] || P.bin[k] != P.bin[k - 1]) ? 1 : 0;
+}
+
+// a thread per kept record: its chunk's start / end (the record count by two atomics on a zeroed field) and its windows
+__global__ void __launch_bounds__(256) sm_ix_emit_kernel(SmIxP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= P.n_keep) return;
+  const int64_t c = P.s_head[k] + P.head[k] - 1;
+  svdss_bam_index_chunk_t* ch = P.chunks + c;
+  if (P.head[k]) {
+    ch->tid = P.tid[k]; ch->bin = P.bin[k]; ch->v_beg = P.vb[k];
+    atomicAdd((unsigned long long*)&ch->n_rec, (unsigned long long)(-k));
+  }
+  if (k + 1 == P.n_keep || P.head[k + 1]) {
+    ch->v_end = P.ve[k];
+    atomicAdd((unsigned long long*)&ch->n_rec, (unsigned long long)(k + 1));
+  }
+  const int64_t n = P.own[k];
+  if (n > 0) {
+    const int64_t w1 = (P.end[k] - 1) >> P.min_shift;
+    svdss_bam_index_window_t* w = P.windows + P.s_own[k];
+    for (int64_t j = 0; j < n; ++j) { w[j].tid = P.tid[k]; w[j].window = (int32_t)(w1 - n + 1 + j); w[j].v_beg = P.vb[k]; }
+  }
+}
+
 struct FootP { const uint8_t* in; int64_t in_bytes; int32_t block_bytes; uint8_t* members; int64_t stride; const int32_t* len; };
 
 // a wavefront per BGZF block of the output: CRC32 of its bytes and their number into the member's last 8 bytes
@@ -434,6 +534,7 @@ __global__ void __launch_bounds__(64) bgzf_footer_kernel(FootP F) {
 struct svdss_bam_smooth {
   int device = -1;
   int32_t min_mapq = 0, n_ref = 0;
+  int32_t ix_shift = 0, ix_depth = 0;   // svdss_bam_smooth_set_index (0: no index fragments)
   SvdssRefView ref;
   int32_t* d_tidmap = nullptr;
 };
@@ -465,6 +566,13 @@ extern "C" void svdss_bam_smooth_free(svdss_bam_smooth_t* s) {
   if (s->device >= 0) (void)hipSetDevice(s->device);
   if (s->d_tidmap) (void)hipFree(s->d_tidmap);
   delete s;
+}
+
+extern "C" int svdss_bam_smooth_set_index(svdss_bam_smooth_t* sm, int32_t min_shift, int32_t depth) {
+  if (!sm || min_shift < 0 || (min_shift > 0 && (depth < 1 || depth > 10 || min_shift + 3 * depth > 48))) return SVDSS_EINVAL;
+  sm->ix_shift = min_shift;
+  sm->ix_depth = min_shift > 0 ? depth : 0;
+  return SVDSS_OK;
 }
 
 extern "C" int svdss_bam_stream_set_output_prefix(svdss_bam_stream_t* s, const uint8_t* bytes, int64_t n) {
@@ -663,6 +771,7 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
   // ---- BGZF: deflate, footers, back to back, down
   n_blk = (in_len + kBgzfBlock - 1) / kBgzfBlock;
   b->sm_bgzf_bytes = 0;
+  const int64_t* d_off_out = nullptr;   // the members' compressed offsets (for the index fragments)
   if (n_blk > 0) {
     const int64_t stride = svdss_deflate_stride((int32_t)kBgzfBlock);
     RCHK(ensure(b->sm_members, (size_t)(n_blk * stride) + 256));
@@ -670,6 +779,7 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     RCHK(ensure(b->sm_len, sizeof(int32_t) * (size_t)n_blk + sizeof(int64_t) * (size_t)(n_blk + 1) + 256));
     int32_t* d_len = (int32_t*)b->sm_len.p;
     int64_t* d_off = (int64_t*)((uint8_t*)b->sm_len.p + ((sizeof(int32_t) * (size_t)n_blk + 63) & ~(size_t)63));
+    d_off_out = d_off;
     const uint8_t* d_in = (const uint8_t*)b->sm_out.p + b->sm_in0;
     BCHK(hipMemsetAsync(b->sm_members.p, 0, (size_t)(n_blk * stride), st));
     BCHK(svdss_deflate_enqueue(st, d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm_members.p, stride, d_len));
@@ -696,6 +806,75 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     b->sm_bgzf = dst;
     b->sm_bgzf_bytes = total;
   }
+  // ---- index fragments (`smooth --write-index`): chunks and first-reached windows, reduced here; only they come down
+  b->sm_ix_on = sm->ix_shift > 0;
+  b->sm_ix_chunks.clear(); b->sm_ix_windows.clear();
+  for (int64_t& v : b->sm_ix_hdr) v = 0;
+  if (b->sm_ix_on && n_keep > 0) {
+    const size_t nk1 = (size_t)n_keep + 1;
+    RCHK(ensure(b->sm_ix, 80 * nk1 + 8 * nk1 + 256));
+    SmIxP P;
+    P.out = (const uint8_t*)b->sm_out.p + room; P.ooff = d_ooff; P.n_keep = n_keep;
+    P.tail_in = room - b->sm_in0; P.in_len = in_len; P.n_blk = n_blk; P.d_off = d_off_out;
+    P.min_shift = sm->ix_shift; P.depth = sm->ix_depth;
+    int64_t* i64 = (int64_t*)b->sm_ix.p;
+    unsigned long long* d_err = (unsigned long long*)i64;    // 8 bytes, then the per-record arrays
+    P.err = d_err;
+    P.beg = i64 + 1; P.end = P.beg + nk1; P.head = P.end + nk1; P.own = P.head + nk1;
+    int64_t* s_head = P.own + nk1; int64_t* s_own = s_head + nk1;
+    P.s_head = s_head; P.s_own = s_own;
+    P.vb = (uint64_t*)(s_own + nk1); P.ve = P.vb + nk1; P.key = P.ve + nk1;
+    uint64_t* kmax = P.key + nk1;
+    P.kmax = kmax;
+    P.tid = (int32_t*)(kmax + nk1); P.bin = (uint32_t*)(P.tid + nk1);
+    P.chunks = nullptr; P.windows = nullptr;
+    const unsigned g = (unsigned)((n_keep + 1 + 255) / 256);
+    BCHK(hipMemsetAsync(d_err, 0, 8, st));
+    hipLaunchKernelGGL(sm_ix_rec_kernel, dim3(g), dim3(256), 0, st, P);
+    BCHK(hipGetLastError());
+    {
+      size_t t0 = 0, t1 = 0;
+      BCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, t0, P.key, kmax, hipcub::Max(), (uint64_t)0, (int)n_keep, st));
+      BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, P.head, s_head, (int)nk1, st));
+      RCHK(ensure(b->tmp, std::max(t0, t1) + 256));
+      t0 = b->tmp.cap;
+      BCHK(hipcub::DeviceScan::ExclusiveScan(b->tmp.p, t0, P.key, kmax, hipcub::Max(), (uint64_t)0, (int)n_keep, st));
+      hipLaunchKernelGGL(sm_ix_own_kernel, dim3(g), dim3(256), 0, st, P);
+      BCHK(hipGetLastError());
+      t0 = b->tmp.cap;
+      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t0, P.head, s_head, (int)nk1, st));
+      t0 = b->tmp.cap;
+      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t0, P.own, s_own, (int)nk1, st));
+    }
+    // counts, order flag, the first and last record's (tid, beg)
+    int64_t cnt[2] = {0, 0}, be[2] = {0, 0};
+    int32_t td[2] = {0, 0};
+    unsigned long long h_err = 0;
+    BCHK(hipMemcpyAsync(&cnt[0], s_head + n_keep, 8, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&cnt[1], s_own + n_keep, 8, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&td[0], P.tid, 4, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&td[1], P.tid + (n_keep - 1), 4, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&be[0], P.beg, 8, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&be[1], P.beg + (n_keep - 1), 8, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
+    b->sm_ix_hdr[2] = td[0]; b->sm_ix_hdr[3] = td[1]; b->sm_ix_hdr[4] = be[0]; b->sm_ix_hdr[5] = be[1];
+    if (h_err & 1) b->sm_ix_hdr[6] = 1;      // out of order: the builder refuses; nothing else comes down
+    else {
+      const int64_t n_ch = cnt[0], n_win = cnt[1];
+      const size_t ch_bytes = sizeof(svdss_bam_index_chunk_t) * (size_t)n_ch;
+      RCHK(ensure(b->sm_ixw, ch_bytes + sizeof(svdss_bam_index_window_t) * (size_t)n_win + 256));
+      P.chunks = (svdss_bam_index_chunk_t*)b->sm_ixw.p;
+      P.windows = (svdss_bam_index_window_t*)((uint8_t*)b->sm_ixw.p + ((ch_bytes + 255) & ~(size_t)255));
+      try { b->sm_ix_chunks.resize((size_t)n_ch); b->sm_ix_windows.resize((size_t)n_win); } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
+      BCHK(hipMemsetAsync(P.chunks, 0, ch_bytes, st));
+      hipLaunchKernelGGL(sm_ix_emit_kernel, dim3(g), dim3(256), 0, st, P);
+      BCHK(hipGetLastError());
+      if (n_ch) BCHK(hipMemcpyAsync(b->sm_ix_chunks.data(), P.chunks, ch_bytes, hipMemcpyDeviceToHost, st));
+      if (n_win) BCHK(hipMemcpyAsync(b->sm_ix_windows.data(), P.windows, sizeof(svdss_bam_index_window_t) * (size_t)n_win, hipMemcpyDeviceToHost, st));
+      BCHK(hipStreamSynchronize(st));
+    }
+  }
   lap(6);
   return SVDSS_OK;
 }
@@ -712,6 +891,16 @@ extern "C" int svdss_bam_smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t 
                                     const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
                                     svdss_bam_batch_t** out) {
   return smooth_run(s, seq, is_last, skip, sm, 1, max_mismatch_rate, host_out, host_cap, n_chunks, comp, comp_bytes, blocks, crc, n_blocks, out);
+}
+
+extern "C" int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* f) {
+  if (!b || !f) return SVDSS_EINVAL;
+  f->n_chunks = (int64_t)b->sm_ix_chunks.size(); f->chunks = b->sm_ix_chunks.data();
+  f->n_windows = (int64_t)b->sm_ix_windows.size(); f->windows = b->sm_ix_windows.data();
+  f->unsorted = (int32_t)b->sm_ix_hdr[6];
+  f->first_tid = (int32_t)b->sm_ix_hdr[2]; f->last_tid = (int32_t)b->sm_ix_hdr[3];
+  f->first_beg = b->sm_ix_hdr[4]; f->last_beg = b->sm_ix_hdr[5];
+  return SVDSS_OK;
 }
 
 extern "C" int svdss_bam_batch_smoothed(const svdss_bam_batch_t* b, svdss_bam_smoothed_t* r) {

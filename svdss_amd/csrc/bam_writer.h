@@ -55,7 +55,12 @@ class BgzfWriter {
       buf_.reserve(BLOCK * batch_);
     }
   }
+  // the compressed size of every member written from now on, in order (the EOF marker's included): where each block
+  // starts in the file, for an index of it
+  void record_members(std::vector<uint32_t>* sizes) { members_ = sizes; }
+  uint64_t bytes_in() const { return in_bytes_; }   // uncompressed bytes written so far
   void write(const void* p, size_t n) {
+    in_bytes_ += n;
     const uint8_t* s = (const uint8_t*)p;
     if (pin_) {
       while (n) {
@@ -181,6 +186,8 @@ class BgzfWriter {
     work(0);
     for (std::thread& th : pool) th.join();
     if (fwrite(out, 1, off[nblocks], f_) != off[nblocks]) ok_ = false;
+    if (members_)
+      for (size_t i = 0; i < nblocks; ++i) members_->push_back((uint32_t)l32[i]);
     return true;
   }
 
@@ -207,6 +214,8 @@ class BgzfWriter {
     }
     for (size_t i = 0; i < nblocks; ++i)
       if (fwrite(out.data() + i * OUT, 1, len[i], f_) != len[i]) ok_ = false;
+    if (members_)
+      for (size_t i = 0; i < nblocks; ++i) members_->push_back((uint32_t)len[i]);
   }
 
   void flush_full_blocks() {
@@ -221,6 +230,8 @@ class BgzfWriter {
   std::vector<uint8_t> buf_;
   std::vector<std::unique_ptr<Deflater>> deflaters_;   // one per worker of emit()
   bool ok_ = true;
+  uint64_t in_bytes_ = 0;
+  std::vector<uint32_t>* members_ = nullptr;
 };
 
 inline void bam_write_header(BgzfWriter& w, const std::string& text, const std::vector<std::string>& names,

@@ -29,6 +29,7 @@
 #include "gpu_deflate_hook.h"
 #include "gpu_inflate_hook.h"
 #include "bam_writer.h"
+#include "bam_index_writer.h"
 #include "call_host.h"
 #include "fastx_reader.h"
 
@@ -213,6 +214,17 @@ int main_smooth(const CallOptions& o) {
   }
   gpu_warm.join();
   header_pre.join();
+  // --write-index FILE: the scheme from the header's references, refused before anything is written; the index goes to
+  // FILE only once the BAM's EOF marker is out (any failure before leaves no index)
+  bool ix_csi = false;
+  int ix_shift = 14, ix_depth = 5;
+  if (!o.write_index.empty()) {
+    if (!hp.err.empty()) die(hp.err);
+    std::string err;
+    if (!bam_index_scheme(o.write_index, hp.lens, ix_csi, ix_shift, ix_depth, err)) die(err);
+  }
+  std::unique_ptr<BamIndexBuilder> ixb;
+  if (!o.write_index.empty()) ixb.reset(new BamIndexBuilder((int32_t)hp.lens.size(), ix_csi, ix_shift, ix_depth));
   const double fasta_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_fasta0).count();
   auto eligible = [&](const BamRecord& r, const std::vector<std::string>& names) {
     if (r.flag & (4 | 2048 | 256)) return false;
@@ -336,6 +348,11 @@ int main_smooth(const CallOptions& o) {
       tl_slot = -1;
       for (int k = 0; k < 8; ++k) out->stage_s[k] = r.stage_ms[k] * 1e-3;
       out->inflate_kernel_s = r.inflate_kernel_ms * 1e-3;
+      if (ixb) {
+        (void)svdss_bam_batch_index(b, &out->ix);
+        out->ix_chunks.assign(out->ix.chunks, out->ix.chunks + out->ix.n_chunks);
+        out->ix_windows.assign(out->ix.windows, out->ix.windows + out->ix.n_windows);
+      }
       return out;
     };
     if (dbg) fprintf(stderr, "[smooth] BAM header read, output prefix set at +%.3f s\n", since());
@@ -368,6 +385,7 @@ int main_smooth(const CallOptions& o) {
       auto upload = [&](size_t d) {
         rcs[d] = svdss_ref_upload_parts(parts.data(), plen.data(), (int32_t)parts.size(), (int)d, &drefs[d]);
         if (rcs[d] == SVDSS_OK) rcs[d] = svdss_bam_smooth_create(drefs[d], tid_map.data(), (int32_t)tid_map.size(), (int32_t)o.min_mapq, &sms[d]);
+        if (rcs[d] == SVDSS_OK && ixb) rcs[d] = svdss_bam_smooth_set_index(sms[d], ix_shift, ix_depth);
       };
       for (size_t d = 1; d < n_sm; ++d) up.emplace_back(upload, d);
       upload(0);
@@ -461,6 +479,10 @@ int main_smooth(const CallOptions& o) {
       while (std::unique_ptr<SelectedBatch> b = rd ? rd->next() : rds->next()) {
         const auto t0 = std::chrono::steady_clock::now();
         const size_t nb = b->ext ? b->ext_n : b->bytes.size();
+        if (ixb) {   // (the batches come in file order, reruns included: the batch's members start at out_bytes)
+          b->ix.chunks = b->ix_chunks.data(); b->ix.windows = b->ix_windows.data();
+          ixb->add_fragment(b->ix, (uint64_t)out_bytes);
+        }
         n_rec += b->n_records; n_kept += b->n_kept; out_bytes += nb;
         for (int k = 0; k < 4; ++k) n_xf[k] += b->n_xf[k];
         for (int k = 0; k < 8; ++k) st_s[k] += b->stage_s[k];
@@ -504,6 +526,10 @@ int main_smooth(const CallOptions& o) {
     for (svdss_bam_smooth_t* q : sms) svdss_bam_smooth_free(q);
     for (svdss_ref_t* q : drefs) svdss_ref_free(q);
     if (!write_ok) die("error writing the BAM to stdout");
+    if (ixb) {
+      std::string err;
+      if (!ixb->write(o.write_index, err)) die(err);
+    }
     if (dbg) fprintf(stderr, "[smooth] done at +%.3f s\n", since());
     if (!getenv("SVDSS_CLEAN_EXIT")) {
       fprintf(stderr, "[smooth] [info] All done!\n");
@@ -546,6 +572,12 @@ int main_smooth(const CallOptions& o) {
   const int T = std::max(1, o.threads);
   BgzfWriter w(stdout, T);
   svdss_enable_gpu_deflate(w);   // (csrc/deflate.hip; SVDSS_GPU_DEFLATE=0: libdeflate / zlib on the host)
+  // --write-index: every record's (tid, pos, reference span) and where it starts and ends in the inflated stream; the
+  // blocks' compressed sizes turn those into virtual offsets once the stream is complete
+  struct HostIxRec { int32_t tid, pos; int64_t span; uint64_t u0, u1; };
+  std::vector<HostIxRec> hix;
+  std::vector<uint32_t> members;
+  if (ixb) w.record_members(&members);
   bam_write_header(w, bam.header_text(), bam.ref_names(), bam.ref_lens());
   // smooth_read (smoother.cpp:84-232) of one record into its serialised BAM bytes
   auto smooth_one = [&](const BamRecord& r, ByteSink& sink) {
@@ -671,7 +703,24 @@ int main_smooth(const CallOptions& o) {
   std::thread writer([&] {
     while (std::unique_ptr<Item> it = q_write.pop()) {
       const auto t0 = std::chrono::steady_clock::now();
-      for (const ByteSink& sk : it->outs) w.write(sk.v.data(), sk.v.size());
+      for (const ByteSink& sk : it->outs) {
+        if (ixb && sk.v.size() >= 36) {
+          HostIxRec x;
+          const uint8_t* p = sk.v.data();
+          uint32_t l_name = p[12], w4;
+          memcpy(&x.tid, p + 4, 4); memcpy(&x.pos, p + 8, 4); memcpy(&w4, p + 16, 4);
+          if ((w4 >> 16) & 4u) die("--write-index: an unmapped record in the output");   // (eligible() drops them)
+          x.span = 0;
+          for (uint32_t j = 0; j < (w4 & 0xffffu) && 36 + l_name + 4 * (size_t)j + 4 <= sk.v.size(); ++j) {
+            uint32_t c;
+            memcpy(&c, p + 36 + l_name + 4 * (size_t)j, 4);
+            if (ix_ref_op(c & 0xfu)) x.span += c >> 4;
+          }
+          x.u0 = w.bytes_in(); x.u1 = x.u0 + sk.v.size();
+          hix.push_back(x);
+        }
+        w.write(sk.v.data(), sk.v.size());
+      }
       t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     write_ok = w.finish();
@@ -797,6 +846,17 @@ int main_smooth(const CallOptions& o) {
   svdss_ref_free(dref);
   if (rc < 0) die("error reading " + o.bam + ": " + bam.error());
   if (!write_ok) die("error writing the BAM to stdout");
+  if (ixb) {
+    // position u of the stream: the member that holds its byte; the end of the stream: the EOF marker's offset
+    const uint64_t total = w.bytes_in(), n_data = (total + 0xff00 - 1) / 0xff00;
+    if (members.size() < n_data + 1) die("--write-index: the writer's block table is incomplete");
+    std::vector<uint64_t> coff(members.size() + 1, 0);
+    for (size_t i = 0; i < members.size(); ++i) coff[i + 1] = coff[i] + members[i];
+    auto voff = [&](uint64_t u) { return u < total ? coff[u / 0xff00] << 16 | (u % 0xff00) : coff[n_data] << 16; };
+    for (const HostIxRec& x : hix) ixb->add_record(x.tid, x.pos, x.span, voff(x.u0), voff(x.u1));
+    std::string err;
+    if (!ixb->write(o.write_index, err)) die(err);
+  }
   if (!getenv("SVDSS_CLEAN_EXIT")) {   // (see main_search: the teardown of page-locked buffers is left to the OS)
     bam.report();
     fprintf(stderr, "[smooth] [info] All done!\n");

@@ -9,7 +9,7 @@
 //   SVDSS --version                                     (main.cpp:45-47)
 // SFS text goes to stdout exactly as PingPong::output_batch prints it
 // (ping_pong.cpp:213-236), logs to stderr, fatal conditions exit(1).
-// Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings.
+// Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth).
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -53,7 +53,10 @@ static const char* MAIN_USAGE =
 static const char* SMOOTH_USAGE =
     "Usage: SVDSS smooth --reference <FASTA> --bam <BAM> > smoothed.bam\n"
     "      --min-mapq <int>   minimum mapping quality (default: 20)\n"
-    "      --accp <float>     accuracy percentile (default: 0.98)\n";
+    "      --accp <float>     accuracy percentile (default: 0.98)\n"
+    "      --write-index <FILE>  also write the output's index: CSI if FILE ends in .csi, else BAI (as `samtools index`\n"
+    "                            of a BAM written to a new file or a pipe; appended to a non-empty file, it indexes the\n"
+    "                            appended stream only)\n";
 
 static const char* CALL_USAGE =
     "Usage: SVDSS call --reference <FASTA> --bam <BAM> --sfs <SFS>\n"
@@ -1203,6 +1206,8 @@ int main(int argc, char** argv) {
             !strcmp(argv[1], "smooth") ? SMOOTH_USAGE : MAIN_USAGE, stderr);
       return EXIT_SUCCESS;
     }
+    if (!o.write_index.empty() && strcmp(argv[1], "smooth") != 0)
+      die(std::string("--write-index is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
     if (!strcmp(argv[1], "search")) {
       if (o.index.empty() || (o.fastx.empty() && o.bam.empty())) { fputs(SEARCH_USAGE, stderr); return EXIT_FAILURE; }
       main_search(o);
@@ -1218,6 +1223,7 @@ int main(int argc, char** argv) {
       if (o.reference.empty() || o.bam.empty()) { fputs(SMOOTH_USAGE, stderr); return EXIT_FAILURE; }   // main.cpp:73-76
       CallOptions c;
       c.reference = o.reference; c.bam = o.bam; c.threads = o.threads; c.min_mapq = o.min_mapq; c.accp = o.accp; c.gpus = o.gpus;
+      c.write_index = o.write_index;
       main_smooth(c);
     } else {
       fputs(MAIN_USAGE, stderr);
