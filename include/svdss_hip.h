@@ -389,7 +389,7 @@ int svdss_bam_select_store_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_la
                                const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
                                svdss_bam_batch_t** out);
 int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const svdss_bam_filter_t* f, svdss_bam_batch_t** out);
-/* `SVDSS smooth` on the same front end (csrc/bam_smooth.inc): BGZF blocks in, BGZF blocks out; the inflated records never
+/* `SVDSS smooth` on the same front end (csrc/bam_smooth.hip): BGZF blocks in, BGZF blocks out; the inflated records never
  * leave the device.  Stands where smoother.cpp:349-571 stand (loader :498-571 with the filters of :509-537, smooth_read
  * :84-232, rebuild_bam_entry :50-82, the writer :441-494).  A svdss_bam_smooth_t names the reference (svdss_ref_upload:
  * upper-case ASCII), tid_map[t] = chromosome of BAM reference t in it or -1 (records on it are dropped, like every record
@@ -432,7 +432,7 @@ typedef struct svdss_bam_smoothed {
   double stage_ms[8];             /* 0-2 as svdss_bam_result_t, 3 filters + CIGAR walk, 4 sizes + records, 5 the output turn, 6 deflate + down */
 } svdss_bam_smoothed_t;
 int svdss_bam_batch_smoothed(const svdss_bam_batch_t* b, svdss_bam_smoothed_t* out);
-/* `smooth --write-index` (csrc/bam_smooth.inc, csrc/bam_index_writer.h): svdss_bam_smooth_set_index(sm, min_shift, depth)
+/* `smooth --write-index` (csrc/bam_smooth.hip, csrc/bam_index_writer.h): svdss_bam_smooth_set_index(sm, min_shift, depth)
  * asks every later svdss_bam_smooth_run on sm for the batch's index fragments (min_shift 0: none, the default; BAI is 14 / 5).
  * They are reduced on the device: one chunk per run of consecutive kept records with the same (tid, bin), one window entry
  * (16 kb at min_shift 14) per window that a record of the batch reaches into first.  Virtual offsets are relative to the

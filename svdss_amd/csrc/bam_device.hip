@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "bam_device_internal.h"
 #include "hip_check.h"
 #include "index_host.h"
 #include "inflate_dev.h"
@@ -58,45 +59,8 @@ constexpr int64_t kHeadDefault = (int64_t)16 << 20;   // room in front of a batc
 constexpr int kMaxSeg = 2048;
 constexpr int64_t kMinRec = 36;                        // block_size field + the 32 core bytes
 
-// error bits a batch's kernels raise (hdr[H_ERR])
-enum { E_CORRUPT = 1, E_TID = 2 };
-enum { H_NREC = 0, H_TAIL = 1, H_ERR = 2, H_REWALK = 3, H_PRE = 4, H_SHORT = 5, H_START = 6, H_N = 8 };
-
-__device__ __forceinline__ uint32_t ld32(const uint8_t* base, int64_t off) {
-  const uint32_t* w = (const uint32_t*)(base + (off & ~(int64_t)3));
-  return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(off & 3));
-}
-
 // ------------------------------------------------------------------ CRC32 of the inflated blocks
-// a(x) * b(x) mod P in the reflected representation zlib uses (bit 31 = x^0); P = 0xEDB88320
-__host__ __device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-  for (int i = 0; i < 32; ++i) {
-    p ^= (a & 0x80000000u) ? b : 0u;
-    a <<= 1;
-    b = (b >> 1) ^ ((b & 1u) ? 0xEDB88320u : 0u);
-  }
-  return p;
-}
-// x^(8 n) mod P
-__host__ __device__ inline uint32_t gf_xpow8(uint32_t n) {
-  uint32_t r = 0x80000000u;            // x^0
-  uint32_t sq = 0x00800000u;           // x^8
-  while (n) {
-    if (n & 1u) r = gf_mul(r, sq);
-    sq = gf_mul(sq, sq);
-    n >>= 1;
-  }
-  return r;
-}
-
 struct CrcBlk { int64_t uoff; int32_t isize; uint32_t crc; };
-
-// Tables of the kernel below, computed once on the host and copied to every device that asks:
-//   [0]      the byte table of the CRC (state * x^8 for the state's low byte)
-//   [1..4]   byte k of a state times x^2048: state * x^2048 = [1][b0] ^ [2][b1] ^ [3][b2] ^ [4][b3]
-//   [5][l]   x^(32 (64 - l)), lane l's weight (entries 0..63)
-__device__ uint32_t g_crc_tab[6][256];
 
 // One wavefront per BGZF block.  The state of a CRC after words w_0 .. w_(m-1) is the sum of w_i x^(32 (m - i)) (the
 // initial value folded into w_0): lane l takes the words l, l + 64, l + 128, ... -- every load of the wave is 256
@@ -138,47 +102,9 @@ __global__ void __launch_bounds__(64) crc32_kernel(const uint8_t* __restrict__ d
   }
 }
 
-// the tables, on the current device (once per device and process)
-static hipError_t crc_tables_ready() {
-  static std::mutex m;
-  static bool done[64] = {false};
-  static uint32_t h[6][256];
-  static bool built = false;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lk(m);
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  if (!built) {
-    memset(h, 0, sizeof h);
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
-      h[0][i] = c;
-    }
-    const uint32_t x2048 = gf_xpow8(256);
-    for (int k = 0; k < 4; ++k)
-      for (uint32_t i = 0; i < 256; ++i) h[1 + k][i] = gf_mul(i << (8 * k), x2048);
-    for (uint32_t l = 0; l < 64; ++l) h[5][l] = gf_xpow8(4 * (64 - l));
-    built = true;
-  }
-  e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc_tab), h, sizeof h);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
-
 // ------------------------------------------------------------------ the chain of records
-struct WalkP {
-  const uint8_t* buf;
-  int64_t lo, hi;          // fresh data of this batch: [lo, hi) (lo = head room [+ BAM header in the first batch])
-  int64_t seg_bytes;
-  int32_t n_seg, n_ref;
-  uint32_t* seg_start;     // guessed first record of the segment (0xffffffff: none found)
-  uint32_t* seg_end;       // where the chain from there left the segment (or stopped: tail / nonsense)
-  int32_t* seg_cnt;
-  uint32_t* lists;         // n_seg lists of list_cap offsets
-  int64_t list_cap;
-};
+// (SegWalk under the name and in the unnamed namespace the kernels have always taken it by: their symbols stay what they were)
+struct WalkP : SegWalk {};
 
 // necessary conditions on the 36 bytes at p (and the name's terminator) for a record of a file htslib reads
 __device__ __forceinline__ bool plausible(const uint8_t* buf, int64_t p, int64_t hi, int32_t n_ref) {
@@ -692,36 +618,12 @@ __global__ void __launch_bounds__(64) export_kernel(const uint8_t* __restrict__ 
   for (uint32_t k = threadIdx.x; k < (n + 3) / 4; k += 64) dst[k] = ld32(buf, p + 4 * (int64_t)k);
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
 struct OffDiff {   // length of searched read k
   const int64_t* o;
   __host__ __device__ int64_t operator()(int64_t k) const { return o[k + 1] - o[k]; }
 };
 
 }  // namespace
-
-struct svdss_bam_stream {
-  int32_t n_ref = 0;
-  std::mutex m;
-  std::condition_variable cv;
-  int64_t next_seq = 0;
-  int failed = 0;
-  std::string err;
-  std::vector<uint8_t> carry;      // the bytes behind the last complete record of the batch that had its turn last
-  // a region of a file (svdss_bam_stream_region): open_start = batch 0 begins somewhere inside a record, `head` = its bytes
-  // in front of the first record the chain was started at; open_end = the last batch may end inside a record (carry stays)
-  bool open_start = false, open_end = false;
-  std::vector<uint8_t> head;
-  int64_t n_rewalked = 0, n_segments = 0;
-  // smoothing (bam_smooth.inc): the output stream's turn, and the bytes behind its last full BGZF block (at first: the
-  // BAM header of the output)
-  int64_t next_out = 0;
-  std::vector<uint8_t> out_tail;
-};
 
 // What `SVDSS call` keeps of its first pass over the BAM for the second one (svdss_bam_store_t): the slim records of every
 // batch, in HBM, batch by batch in arenas allocated as they are needed.
@@ -782,68 +684,6 @@ struct svdss_bam_park {
   bool closed = false;
 };
 
-struct svdss_bam_batch {
-  int device = -1;
-  hipStream_t st = nullptr;
-  // what the front half left for the search half (svdss_bam_batch_front / _search)
-  const uint8_t* cur_reads = nullptr;
-  const int64_t* cur_off = nullptr;
-  int64_t cur_syms = 0, name_bytes = 0;
-  int32_t cur_flags = 0;
-  bool front_done = false;
-  int64_t park_group = -1, park_first = 0;   // -1: not parked (reads in this object), -2: nothing to search, >= 0: group
-  DevBuf comp, blks, crcb, status, buf, seg, lists, pre, hdr, rpos, flags, scans, d_hp, tmp, o_small, d_names, sym_off, seq_src, reads, totals;
-  uint8_t* h_pin = nullptr;        // page-locked staging: block tables up, small results down
-  size_t h_pin_cap = 0;
-  DevBuf sel_out, sel_off;         // svdss_bam_select_run: the kept records, their offsets
-  uint8_t* h_sel = nullptr;        // ... on the host (page-locked)
-  size_t h_sel_cap = 0;
-  std::vector<int64_t> h_sel_off;
-  int64_t n_selected = 0, sel_bytes = 0;
-  bool sel_slim = false;           // the kept records are slim ones (svdss_bam_store_select)
-  std::vector<int32_t> h_status;
-  // svdss_bam_smooth_run / _measure (bam_smooth.inc)
-  DevBuf sm_rec, sm_out, sm_scratch, sm_members, sm_dense, sm_len;
-  int64_t sm_kept = 0, sm_out_bytes = 0, sm_bgzf_bytes = 0, sm_in0 = 0, sm_xf[4] = {0, 0, 0, 0};
-  const uint8_t* sm_bgzf = nullptr;   // where the last run's BGZF members are (the caller's buffer or h_sel)
-  std::vector<int64_t> sm_nmx;
-  std::vector<uint8_t> sm_fits;
-  // ... with an index asked for (svdss_bam_smooth_set_index): the batch's fragments (svdss_bam_batch_index)
-  DevBuf sm_ix, sm_ixw;
-  bool sm_ix_on = false;
-  std::vector<svdss_bam_index_chunk_t> sm_ix_chunks;
-  std::vector<svdss_bam_index_window_t> sm_ix_windows;
-  int64_t sm_ix_hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  svdss_sfs_batch_t* sfs = nullptr;
-  // results of the last run (host side)
-  std::vector<int32_t> name_off, hp, sidx, qs, len;
-  std::vector<char> names;
-  std::vector<int64_t> counts;
-  int64_t n_records = 0, n_slots = 0, n_searched = 0, n_short = 0, total_sfs = 0;
-  double inflate_ms = 0;
-  double stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host clock between the waits of the last run (svdss_bam_result_t::stage_ms)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::string err;
-};
-
-static int ensure(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap && b.p) return SVDSS_OK;
-  if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-  const size_t want = bytes + (bytes >> 3) + 4096;
-  HIPCHK(hipMalloc(&b.p, want));
-  b.cap = want;
-  return SVDSS_OK;
-}
-
-static int ensure_pin(svdss_bam_batch* b, size_t bytes) {
-  if (bytes <= b->h_pin_cap && b->h_pin) return SVDSS_OK;
-  if (b->h_pin) { (void)hipHostFree(b->h_pin); b->h_pin = nullptr; b->h_pin_cap = 0; }
-  const size_t want = bytes + (bytes >> 2) + 4096;
-  HIPCHK(hipHostMalloc((void**)&b->h_pin, want, hipHostMallocDefault));
-  b->h_pin_cap = want;
-  return SVDSS_OK;
-}
-
 extern "C" int svdss_bam_stream_create(int32_t n_ref, svdss_bam_stream_t** out) {
   if (!out || n_ref < 0) return SVDSS_EINVAL;
   svdss_bam_stream* s = new (std::nothrow) svdss_bam_stream();
@@ -886,93 +726,25 @@ extern "C" int64_t svdss_bam_stream_rewalked(const svdss_bam_stream_t* s, int64_
 extern "C" void svdss_bam_batch_free(svdss_bam_batch_t* b) {
   if (!b) return;
   if (b->device >= 0) (void)hipSetDevice(b->device);
-  for (DevBuf* d : {&b->comp, &b->blks, &b->crcb, &b->status, &b->buf, &b->seg, &b->lists, &b->pre, &b->hdr, &b->rpos, &b->flags,
-                    &b->scans, &b->d_hp, &b->tmp, &b->o_small, &b->d_names, &b->sym_off, &b->seq_src, &b->reads, &b->totals})
-    if (d->p) (void)hipFree(d->p);
-  if (b->h_pin) (void)hipHostFree(b->h_pin);
-  if (b->h_sel) (void)hipHostFree(b->h_sel);
-  for (DevBuf* d : {&b->sel_out, &b->sel_off, &b->sm_rec, &b->sm_out, &b->sm_scratch, &b->sm_members, &b->sm_dense, &b->sm_len, &b->sm_ix, &b->sm_ixw})
-    if (d->p) (void)hipFree(d->p);
-  if (b->sfs) svdss_sfs_batch_free(b->sfs);
   if (b->e0) (void)hipEventDestroy(b->e0);
   if (b->e1) (void)hipEventDestroy(b->e1);
   if (b->st) (void)hipStreamDestroy(b->st);
-  delete b;
+  if (b->search.sfs) svdss_sfs_batch_free(b->search.sfs);
+  delete b;   // (its buffers: ~DevBuf / ~PinBuf, on the device made current above)
 }
 
-// the turn of batch `seq` at the carry: taken by wait_turn, given up by done_turn (on every path)
-static bool wait_turn(svdss_bam_stream* s, int64_t seq) {
-  std::unique_lock<std::mutex> lk(s->m);
-  s->cv.wait(lk, [&] { return s->next_seq == seq || s->failed; });
-  return !s->failed;
-}
-static void done_turn(svdss_bam_stream* s, int fail_code, const std::string& msg) {
-  {
-    std::lock_guard<std::mutex> lk(s->m);
-    if (fail_code && !s->failed) { s->failed = fail_code; s->err = msg; }
-    ++s->next_seq;
-  }
-  s->cv.notify_all();
-}
-
-// What both entry points do first: the batch's blocks up, inflated, checked; the record chain of its segments; the batch's
-// turn at the carry.  On success the records of the batch are listed (F.W / F.seg_base / pre, F.hdr) and the turn is over.
-struct Front {
-  WalkP W;
-  int32_t* seg_base = nullptr;
-  int64_t hdr[H_N];
-  int64_t total_inf = 0, HEAD = 0;
-};
-
-#define BCHK(expr)                                                                                    \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
-      return fail(e_ == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);            \
-    }                                                                                                 \
-  } while (0)
-#define RCHK(expr) do { const int rc_ = (expr); if (rc_ != SVDSS_OK) return fail(rc_, g_svdss_hip_err); } while (0)
-
-static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, int device,
-                       int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
-                       const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
-                       svdss_bam_batch_t** out, Front& F) {
-  // a failure before the batch had its turn still has to pass the turn on: the batches behind it wait for it
-  bool had_turn = false;
-  auto fail = [&](int code, const std::string& msg) {
-    if (!had_turn) {
-      if (wait_turn(s, seq)) done_turn(s, code, msg);   // (a stream that already failed has let everybody through)
-      had_turn = true;
-    }
-    if (*out) {
-      (*out)->err = msg;
-      // the caller recycles its page-locked slabs as soon as this returns: no copy out of them may still be under way
-      if ((*out)->st) (void)hipStreamSynchronize((*out)->st);
-    }
-    return code;
-  };
-  if (n_chunks > 0 && (!comp || !comp_bytes || !blocks || !crc || !n_blocks)) return fail(SVDSS_EINVAL, "bad argument");
+int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, int device,
+                int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
+                const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                svdss_bam_batch_t** out, Front& F) {
+  BatchRun run(*out);
+  run.release = [&](int code, const std::string& msg) { pass_turn(s, &svdss_bam_stream::next_seq, seq, code, msg); };
+  if (n_chunks > 0 && (!comp || !comp_bytes || !blocks || !crc || !n_blocks)) return run.fail(SVDSS_EINVAL, "bad argument");
   BCHK(hipSetDevice(device));
-  svdss_bam_batch* b = *out;
-  if (!b) {
-    b = new (std::nothrow) svdss_bam_batch();
-    if (!b) return fail(SVDSS_ENOMEM, "out of memory");
-    b->device = device;
-    *out = b;
-  }
-  if (b->device != device) return fail(SVDSS_EINVAL, "batch object of another device");
-  if (!b->st) BCHK(svdss_make_stream(&b->st, "SVDSS_SEARCH_CUS"));
-  if (!b->e0) { BCHK(hipEventCreate(&b->e0)); BCHK(hipEventCreate(&b->e1)); }
-  const hipStream_t st = b->st;
-  b->n_records = b->n_slots = b->n_searched = b->n_short = b->total_sfs = 0;
-  b->err.clear();
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    b->stage_ms[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
-    t_prev = t;
-  };
+  RCHK(run.batch_object(out, device));
+  svdss_bam_batch* b = run.b;
+  const hipStream_t st = run.st;
+  b->n_records = b->search.n_slots = b->search.n_searched = b->search.n_short = b->search.total_sfs = 0;
   static const int64_t HEAD = [] {
     const char* e = getenv("SVDSS_BAM_HEADROOM_MB");
     const int64_t mb = e && *e ? atoll(e) : 0;
@@ -982,33 +754,33 @@ static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int6
   // ---- the batch's blocks: compressed bytes back to back, inflated bytes back to back behind the head room
   int64_t total_blocks = 0, total_comp = 0, total_inf = 0;
   for (int32_t c = 0; c < n_chunks; ++c) {
-    if (comp_bytes[c] < 0 || n_blocks[c] < 0 || (n_blocks[c] > 0 && (!comp[c] || !blocks[c] || !crc[c]))) return fail(SVDSS_EINVAL, "bad chunk");
+    if (comp_bytes[c] < 0 || n_blocks[c] < 0 || (n_blocks[c] > 0 && (!comp[c] || !blocks[c] || !crc[c]))) return run.fail(SVDSS_EINVAL, "bad chunk");
     total_blocks += n_blocks[c];
     total_comp += (comp_bytes[c] + 15) & ~(int64_t)15;
     for (int64_t i = 0; i < n_blocks[c]; ++i) {
       const svdss_bgzf_block_t& k = blocks[c][i];
-      if (k.coff < 0 || k.clen < 0 || k.isize < 0 || k.isize > 65536 || k.coff + k.clen > comp_bytes[c]) return fail(SVDSS_EINVAL, "bad block");
+      if (k.coff < 0 || k.clen < 0 || k.isize < 0 || k.isize > 65536 || k.coff + k.clen > comp_bytes[c]) return run.fail(SVDSS_EINVAL, "bad block");
       total_inf += k.isize;
     }
   }
-  if (HEAD + total_inf + skip >= ((int64_t)1 << 32) - 65536) return fail(SVDSS_ERANGE, "batch too large");
-  if (skip > total_inf) return fail(SVDSS_EIO, "truncated header");
-  RCHK(ensure(b->comp, (size_t)total_comp + 8192));
-  RCHK(ensure(b->blks, sizeof(svdss_bgzf_block_t) * (size_t)(total_blocks + 1)));
-  RCHK(ensure(b->crcb, sizeof(CrcBlk) * (size_t)(total_blocks + 1)));
-  RCHK(ensure(b->status, sizeof(int32_t) * (size_t)(total_blocks + 2)));
-  RCHK(ensure(b->buf, (size_t)(HEAD + total_inf) + 4096));
-  RCHK(ensure(b->hdr, sizeof(int64_t) * H_N));
-  RCHK(ensure(b->pre, 64));
-  RCHK(ensure(b->totals, 64));
+  if (HEAD + total_inf + skip >= ((int64_t)1 << 32) - 65536) return run.fail(SVDSS_ERANGE, "batch too large");
+  if (skip > total_inf) return run.fail(SVDSS_EIO, "truncated header");
+  RCHK(b->front.comp.ensure((size_t)total_comp + 8192));
+  RCHK(b->front.blks.ensure(sizeof(svdss_bgzf_block_t) * (size_t)(total_blocks + 1)));
+  RCHK(b->front.crcb.ensure(sizeof(CrcBlk) * (size_t)(total_blocks + 1)));
+  RCHK(b->front.status.ensure(sizeof(int32_t) * (size_t)(total_blocks + 2)));
+  RCHK(b->front.buf.ensure((size_t)(HEAD + total_inf) + 4096));
+  RCHK(b->front.hdr.ensure(sizeof(int64_t) * H_N));
+  RCHK(b->front.pre.ensure(64));
+  RCHK(b->totals.ensure(64));
   const size_t tab_bytes = (sizeof(svdss_bgzf_block_t) + sizeof(CrcBlk)) * (size_t)(total_blocks + 1);
-  RCHK(ensure_pin(b, tab_bytes + 4096));
-  svdss_bgzf_block_t* h_blk = (svdss_bgzf_block_t*)b->h_pin;
-  CrcBlk* h_crc = (CrcBlk*)(b->h_pin + sizeof(svdss_bgzf_block_t) * (size_t)(total_blocks + 1));
+  RCHK(b->front.pin.ensure(tab_bytes + 4096));
+  svdss_bgzf_block_t* h_blk = (svdss_bgzf_block_t*)b->front.pin.p;
+  CrcBlk* h_crc = (CrcBlk*)(h_blk + (total_blocks + 1));
   {
     int64_t k = 0, coff = 0, uoff = 0;
     for (int32_t c = 0; c < n_chunks; ++c) {
-      if (comp_bytes[c] > 0) BCHK(hipMemcpyAsync((uint8_t*)b->comp.p + coff, comp[c], (size_t)comp_bytes[c], hipMemcpyHostToDevice, st));
+      if (comp_bytes[c] > 0) BCHK(hipMemcpyAsync((uint8_t*)b->front.comp.p + coff, comp[c], (size_t)comp_bytes[c], hipMemcpyHostToDevice, st));
       for (int64_t i = 0; i < n_blocks[c]; ++i, ++k) {
         h_blk[k] = blocks[c][i];
         h_blk[k].coff += coff;
@@ -1019,23 +791,23 @@ static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int6
       coff += (comp_bytes[c] + 15) & ~(int64_t)15;
     }
   }
-  BCHK(hipMemsetAsync(b->status.p, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
-  BCHK(hipMemsetAsync(b->hdr.p, 0, sizeof(int64_t) * H_N, st));
-  int32_t* d_status = (int32_t*)b->status.p;
+  BCHK(hipMemsetAsync(b->front.status.p, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
+  BCHK(hipMemsetAsync(b->front.hdr.p, 0, sizeof(int64_t) * H_N, st));
+  int32_t* d_status = (int32_t*)b->front.status.p;
   int32_t* d_crcbad = d_status + total_blocks;
   if (total_blocks > 0) {
-    BCHK(hipMemcpyAsync(b->blks.p, h_blk, sizeof(svdss_bgzf_block_t) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    BCHK(hipMemcpyAsync(b->crcb.p, h_crc, sizeof(CrcBlk) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
+    BCHK(hipMemcpyAsync(b->front.blks.p, h_blk, sizeof(svdss_bgzf_block_t) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
+    BCHK(hipMemcpyAsync(b->front.crcb.p, h_crc, sizeof(CrcBlk) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
     BCHK(hipEventRecord(b->e0, st));
-    BCHK(svdss_inflate_enqueue(st, (const uint8_t*)b->comp.p, (const svdss_bgzf_block_t*)b->blks.p, total_blocks, (uint8_t*)b->buf.p, d_status));
+    BCHK(svdss_inflate_enqueue(st, (const uint8_t*)b->front.comp.p, (const svdss_bgzf_block_t*)b->front.blks.p, total_blocks, (uint8_t*)b->front.buf.p, d_status));
     BCHK(hipEventRecord(b->e1, st));
     BCHK(crc_tables_ready());
-    hipLaunchKernelGGL(crc32_kernel, dim3((unsigned)total_blocks), dim3(64), 0, st, (const uint8_t*)b->buf.p, (const CrcBlk*)b->crcb.p, d_crcbad);
+    hipLaunchKernelGGL(crc32_kernel, dim3((unsigned)total_blocks), dim3(64), 0, st, (const uint8_t*)b->front.buf.p, (const CrcBlk*)b->front.crcb.p, d_crcbad);
     BCHK(hipGetLastError());
   }
   // ---- the chain of records, guessed per segment (does not need the carry)
-  WalkP W;
-  W.buf = (const uint8_t*)b->buf.p;
+  SegWalk W;
+  W.buf = (const uint8_t*)b->front.buf.p;
   W.lo = HEAD + (seq == 0 ? skip : 0);
   W.hi = HEAD + total_inf;
   W.n_ref = s->n_ref;
@@ -1049,31 +821,32 @@ static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int6
     W.seg_bytes = std::max<int64_t>(64, ((fresh + n_seg - 1) / n_seg + 63) & ~(int64_t)63);
     W.list_cap = W.seg_bytes / kMinRec + 4;
   }
-  RCHK(ensure(b->seg, (size_t)W.n_seg * 16 + 64));
-  RCHK(ensure(b->lists, (size_t)W.n_seg * (size_t)W.list_cap * sizeof(uint32_t)));
-  W.seg_start = (uint32_t*)b->seg.p;
+  RCHK(b->front.seg.ensure((size_t)W.n_seg * 16 + 64));
+  RCHK(b->front.lists.ensure((size_t)W.n_seg * (size_t)W.list_cap * sizeof(uint32_t)));
+  W.seg_start = (uint32_t*)b->front.seg.p;
   W.seg_end = W.seg_start + W.n_seg;
   W.seg_cnt = (int32_t*)(W.seg_end + W.n_seg);
   int32_t* seg_base = W.seg_cnt + W.n_seg;
-  W.lists = (uint32_t*)b->lists.p;
-  hipLaunchKernelGGL(walk_kernel, dim3((unsigned)W.n_seg), dim3(64), 0, st, W);
+  W.lists = (uint32_t*)b->front.lists.p;
+  hipLaunchKernelGGL(walk_kernel, dim3((unsigned)W.n_seg), dim3(64), 0, st, WalkP{W});
   BCHK(hipGetLastError());
-  b->h_status.resize((size_t)total_blocks + 2);
-  BCHK(hipMemcpyAsync(b->h_status.data(), d_status, sizeof(int32_t) * (size_t)(total_blocks + 2), hipMemcpyDeviceToHost, st));
+  b->front.h_status.resize((size_t)total_blocks + 2);
+  BCHK(hipMemcpyAsync(b->front.h_status.data(), d_status, sizeof(int32_t) * (size_t)(total_blocks + 2), hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
   if (total_blocks > 0) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, b->e0, b->e1) == hipSuccess) b->inflate_ms = ms;
   }
-  lap(0);   // buffers, upload, inflate, CRC, segment walk
+  run.lap(0);   // buffers, upload, inflate, CRC, segment walk
   for (int64_t i = 0; i < total_blocks; ++i)
-    if (b->h_status[(size_t)i] != 0) return fail(SVDSS_EIO, "BGZF inflate failed");
-  if (b->h_status[(size_t)total_blocks] != 0) return fail(SVDSS_EIO, "BGZF block CRC mismatch");
+    if (b->front.h_status[(size_t)i] != 0) return run.fail(SVDSS_EIO, "BGZF inflate failed");
+  if (b->front.h_status[(size_t)total_blocks] != 0) return run.fail(SVDSS_EIO, "BGZF block CRC mismatch");
 
   // ---- this batch's turn: carry in, the chain proved and completed, carry out
-  if (!wait_turn(s, seq)) { had_turn = true; return fail(s->failed, s->err); }
-  had_turn = true;
-  lap(1);   // waiting for the turn
+  const bool my_turn = wait_turn(s, &svdss_bam_stream::next_seq, seq);
+  run.release = nullptr;   // (taken, or let through by a stream that failed: nothing to pass on any more)
+  if (!my_turn) return run.fail(s->failed, s->err);
+  run.lap(1);   // waiting for the turn
   int turn_code = SVDSS_OK;
   std::string turn_msg;
   int64_t hdr[H_N] = {0};
@@ -1083,14 +856,14 @@ static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int6
     hipError_t e = hipSuccess;
     if (carry_len > HEAD) turn_fail(SVDSS_ERANGE, "a record larger than the head room (SVDSS_BAM_HEADROOM_MB)");
     if (!turn_code && carry_len > 0)
-      e = hipMemcpyAsync((uint8_t*)b->buf.p + (HEAD - carry_len), s->carry.data(), (size_t)carry_len, hipMemcpyHostToDevice, st);
+      e = hipMemcpyAsync((uint8_t*)b->front.buf.p + (HEAD - carry_len), s->carry.data(), (size_t)carry_len, hipMemcpyHostToDevice, st);
     if (!turn_code && e == hipSuccess) {
       // (SVDSS_REGION_TEST, for the tests of the caller's second run: 1 = start at a guess that is no record, 2 = a head one byte short)
       static const int region_test = getenv("SVDSS_REGION_TEST") ? atoi(getenv("SVDSS_REGION_TEST")) : 0;
       const int64_t start = seq == 0 && s->open_start ? (region_test == 1 ? -2 : -1) : seq == 0 && carry_len == 0 ? W.lo : HEAD - carry_len;
-      hipLaunchKernelGGL(link_kernel, dim3(1), dim3(64), 0, st, W, start, (uint32_t*)b->pre.p, seg_base, (int64_t*)b->hdr.p);
+      hipLaunchKernelGGL(link_kernel, dim3(1), dim3(64), 0, st, WalkP{W}, start, (uint32_t*)b->front.pre.p, seg_base, (int64_t*)b->front.hdr.p);
       e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(hdr, b->hdr.p, sizeof hdr, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(hdr, b->front.hdr.p, sizeof hdr, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
       if (e == hipSuccess) {
         if (hdr[H_ERR] & E_CORRUPT) turn_fail(SVDSS_EIO, "truncated record");   // (a block_size below 32: BamReader says the same)
@@ -1100,14 +873,14 @@ static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int6
             const int64_t head_len = std::max<int64_t>(0, hdr[H_START] - W.lo - (region_test == 2 ? 1 : 0));
             try { s->head.resize((size_t)head_len); } catch (...) { turn_fail(SVDSS_ENOMEM, "out of memory"); }
             if (!turn_code && head_len > 0) {
-              e = hipMemcpyAsync(s->head.data(), (const uint8_t*)b->buf.p + W.lo, (size_t)head_len, hipMemcpyDeviceToHost, st);
+              e = hipMemcpyAsync(s->head.data(), (const uint8_t*)b->front.buf.p + W.lo, (size_t)head_len, hipMemcpyDeviceToHost, st);
               if (e == hipSuccess) e = hipStreamSynchronize(st);
             }
           }
           const int64_t tail = hdr[H_TAIL], tail_len = W.hi - tail;
           try { s->carry.resize((size_t)tail_len); } catch (...) { turn_fail(SVDSS_ENOMEM, "out of memory"); }
           if (!turn_code && tail_len > 0) {
-            e = hipMemcpyAsync(s->carry.data(), (const uint8_t*)b->buf.p + tail, (size_t)tail_len, hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(s->carry.data(), (const uint8_t*)b->front.buf.p + tail, (size_t)tail_len, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
           }
           if (!turn_code && is_last && tail_len > 0 && !s->open_end) turn_fail(SVDSS_EIO, "truncated record");
@@ -1121,9 +894,9 @@ static int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int6
       turn_fail(e == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);
     }
   }
-  done_turn(s, turn_code, turn_msg);
+  done_turn(s, &svdss_bam_stream::next_seq, turn_code, turn_msg);
   if (turn_code) { b->err = turn_msg; return turn_code; }
-  lap(2);   // the turn: carry in, link, carry out
+  run.lap(2);   // the turn: carry in, link, carry out
   F.W = W; F.seg_base = seg_base; F.total_inf = total_inf; F.HEAD = HEAD;
   memcpy(F.hdr, hdr, sizeof hdr);
   return SVDSS_OK;
@@ -1283,83 +1056,68 @@ extern "C" int svdss_bam_batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t
                                      int32_t flags, svdss_bam_batch_t** out) {
   if (!s || !out || seq < 0 || skip < 0 || n_chunks < 0 || device < 0) return SVDSS_EINVAL;
   if (park && park->device != device) return SVDSS_EINVAL;
-  if (*out) (*out)->front_done = false;
+  if (*out) (*out)->search.front_done = false;
   Front F;
   {
     const int rc = batch_front(s, seq, is_last, skip, device, n_chunks, comp, comp_bytes, blocks, crc, n_blocks, out, F);
     if (rc != SVDSS_OK) return rc;
   }
   svdss_bam_batch* b = *out;
-  const hipStream_t st = b->st;
-  const WalkP& W = F.W;
+  BatchRun run(b);
+  const hipStream_t st = run.st;
+  const SegWalk& W = F.W;
   int32_t* seg_base = F.seg_base;
   const int64_t* hdr = F.hdr;
   const int64_t total_inf = F.total_inf, HEAD = F.HEAD;
   int64_t pg = -1, pfirst = 0, psym = 0;      // the park's group this batch reserved room in (-1: none)
   auto unpark = [&]() { if (pg >= 0) { park_done(park, pg); pg = -1; } };
-  // (a failure must not leave the group waiting for this batch)
-  auto fail = [&](int code, const std::string& msg) { b->err = msg; (void)hipStreamSynchronize(st); unpark(); return code; };
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    b->stage_ms[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
-    t_prev = t;
-  };
+  run.release = [&](int, const std::string&) { unpark(); };   // (a failure must not leave the group waiting for this batch)
 
   // ---- fields, filters, tags; where everything goes
   const int64_t n_rec = hdr[H_NREC];
   b->n_records = n_rec;
-  RCHK(ensure(b->rpos, sizeof(uint32_t) * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->flags, sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->scans, sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->d_hp, sizeof(int32_t) * (size_t)(n_rec + 1)));
+  RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));
+  RCHK(b->flags.ensure(sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
+  RCHK(b->scans.ensure(sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
+  RCHK(b->search.d_hp.ensure(sizeof(int32_t) * (size_t)(n_rec + 1)));
   MetaP M;
-  M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = seg_base; M.pre = (const uint32_t*)b->pre.p;
+  M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = seg_base; M.pre = (const uint32_t*)b->front.pre.p;
   M.n_seg = W.n_seg; M.putative = (flags & SVDSS_BAM_PUTATIVE) ? 1 : 0; M.n_rec = n_rec;
   M.rpos = (uint32_t*)b->rpos.p;
   M.f_pass = (int64_t*)b->flags.p; M.f_srch = M.f_pass + (n_rec + 1); M.f_name = M.f_srch + (n_rec + 1); M.f_sym = M.f_name + (n_rec + 1);
-  M.hp = (int32_t*)b->d_hp.p; M.hdr = (int64_t*)b->hdr.p;
+  M.hp = (int32_t*)b->search.d_hp.p; M.hdr = (int64_t*)b->front.hdr.p;
   hipLaunchKernelGGL(meta_kernel, dim3((unsigned)W.n_seg + 1), dim3(64), 0, st, M);
   BCHK(hipGetLastError());
   int64_t* sc = (int64_t*)b->scans.p;
-  {
-    size_t tb = 0;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, M.f_pass, sc, (int)(n_rec + 1), st));
-    RCHK(ensure(b->tmp, tb + 256));
-    for (int k = 0; k < 4; ++k) {
-      size_t t2 = b->tmp.cap;
-      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t2, M.f_pass + (int64_t)k * (n_rec + 1), sc + (int64_t)k * (n_rec + 1), (int)(n_rec + 1), st));
-    }
-  }
+  RCHK(run.scan_rows(M.f_pass, sc, n_rec + 1, 4));
   // (sizes of the outputs are not known yet: bounded by the records / the inflated bytes)
-  RCHK(ensure(b->o_small, sizeof(int32_t) * 3 * (size_t)(n_rec + 2)));
-  RCHK(ensure(b->d_names, (size_t)n_rec * 255 + 64 < (size_t)total_inf + (size_t)HEAD ? (size_t)n_rec * 255 + 64 : (size_t)total_inf + (size_t)HEAD + 64));
-  RCHK(ensure(b->sym_off, sizeof(int64_t) * (size_t)(n_rec + 2)));
-  RCHK(ensure(b->seq_src, sizeof(int64_t) * (size_t)(n_rec + 2)));
+  RCHK(b->search.o_small.ensure(sizeof(int32_t) * 3 * (size_t)(n_rec + 2)));
+  RCHK(b->search.d_names.ensure((size_t)n_rec * 255 + 64 < (size_t)total_inf + (size_t)HEAD ? (size_t)n_rec * 255 + 64 : (size_t)total_inf + (size_t)HEAD + 64));
+  RCHK(b->search.sym_off.ensure(sizeof(int64_t) * (size_t)(n_rec + 2)));
+  RCHK(b->search.seq_src.ensure(sizeof(int64_t) * (size_t)(n_rec + 2)));
   ScatP S;
   S.buf = W.buf; S.n_rec = n_rec; S.rpos = M.rpos; S.f_pass = M.f_pass; S.f_srch = M.f_srch;
   S.s_pass = sc; S.s_srch = sc + (n_rec + 1); S.s_name = sc + 2 * (n_rec + 1); S.s_sym = sc + 3 * (n_rec + 1);
   S.hp = M.hp;
-  S.o_name_off = (int32_t*)b->o_small.p; S.o_hp = S.o_name_off + (n_rec + 2); S.o_sidx = S.o_hp + (n_rec + 2);
-  S.o_names = (char*)b->d_names.p; S.sym_off = (int64_t*)b->sym_off.p; S.seq_src = (int64_t*)b->seq_src.p;
+  S.o_name_off = (int32_t*)b->search.o_small.p; S.o_hp = S.o_name_off + (n_rec + 2); S.o_sidx = S.o_hp + (n_rec + 2);
+  S.o_names = (char*)b->search.d_names.p; S.sym_off = (int64_t*)b->search.sym_off.p; S.seq_src = (int64_t*)b->search.seq_src.p;
   S.totals = (int64_t*)b->totals.p;
   hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, st, S);
   BCHK(hipGetLastError());
   int64_t totals[4] = {0, 0, 0, 0}, hdr2[H_N] = {0};
   BCHK(hipMemcpyAsync(totals, b->totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
-  BCHK(hipMemcpyAsync(hdr2, b->hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
+  BCHK(hipMemcpyAsync(hdr2, b->front.hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
-  lap(3);   // fields / filters / tags, scans, scatter
-  if (hdr2[H_ERR] & E_CORRUPT) return fail(SVDSS_EIO, "corrupt record");
-  if (hdr2[H_ERR] & E_TID) return fail(SVDSS_EIO, "core.tid < 0. Why are we here? Please check");
+  run.lap(3);   // fields / filters / tags, scans, scatter
+  if (const char* bad = record_error(hdr2[H_ERR])) return run.fail(SVDSS_EIO, bad);
   const int64_t n_slots = totals[0], n_srch = totals[1], name_bytes = totals[2], total_syms = totals[3];
-  b->n_slots = n_slots; b->n_searched = n_srch; b->n_short = hdr2[H_SHORT];
-  if (total_syms >= ((int64_t)1 << 40)) return fail(SVDSS_ERANGE, "batch too large");
+  b->search.n_slots = n_slots; b->search.n_searched = n_srch; b->search.n_short = hdr2[H_SHORT];
+  if (total_syms >= ((int64_t)1 << 40)) return run.fail(SVDSS_ERANGE, "batch too large");
 
   // ---- bases, search
   const size_t padded = (size_t)((total_syms + 15) & ~(int64_t)15) + 16;
-  b->park_group = n_srch > 0 ? -1 : -2;
-  b->park_first = 0;
+  b->search.park_group = n_srch > 0 ? -1 : -2;
+  b->search.park_first = 0;
   uint8_t* reads_out = nullptr;
   const int64_t* off_out = (const int64_t*)S.sym_off;
   if (n_srch > 0 && park && park_reserve(park, n_srch, total_syms, pg, pfirst, psym)) {
@@ -1370,14 +1128,14 @@ extern "C" int svdss_bam_batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t
     int64_t* po = A.d_off + G.off0 + pfirst;
     hipLaunchKernelGGL(rebase_offsets_kernel, dim3((unsigned)((n_srch + 1 + 255) / 256)), dim3(256), 0, st, (const int64_t*)S.sym_off, n_srch + 1, psym, po);
     off_out = po;
-    b->park_group = pg; b->park_first = pfirst;
+    b->search.park_group = pg; b->search.park_first = pfirst;
     BCHK(hipGetLastError());
   } else {
-    RCHK(ensure(b->reads, padded + 16));
-    reads_out = (uint8_t*)b->reads.p;
+    RCHK(b->search.reads.ensure(padded + 16));
+    reads_out = (uint8_t*)b->search.reads.p;
   }
   if (n_srch > 0) {
-    if (b->park_group < 0) BCHK(hipMemsetAsync((uint8_t*)b->reads.p + (padded >= 32 ? padded - 32 : 0), 0, padded >= 32 ? 32 : padded, st));
+    if (b->search.park_group < 0) BCHK(hipMemsetAsync((uint8_t*)b->search.reads.p + (padded >= 32 ? padded - 32 : 0), 0, padded >= 32 ? 32 : padded, st));
     // (the longest read decides the grid's width: the scan's inputs hold the lengths, the host does not -- bounded by
     // the largest record of the batch, i.e. by the batch itself; a second pass over the symbol offsets would cost more)
     int64_t max_len = 0;
@@ -1388,13 +1146,13 @@ extern "C" int svdss_bam_batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t
       hipcub::TransformInputIterator<int64_t, OffDiff, hipcub::CountingInputIterator<int64_t>> it(cnt, OffDiff{S.sym_off});
       int64_t* d_max = (int64_t*)b->totals.p + 4;
       BCHK(hipcub::DeviceReduce::Max(nullptr, tb, it, d_max, (int)n_srch, st));
-      RCHK(ensure(b->tmp, tb + 256));
+      RCHK(run.scan_tmp(tb));
       tb = b->tmp.cap;
       BCHK(hipcub::DeviceReduce::Max(b->tmp.p, tb, it, d_max, (int)n_srch, st));
       BCHK(hipMemcpyAsync(&max_len, d_max, sizeof max_len, hipMemcpyDeviceToHost, st));
       BCHK(hipStreamSynchronize(st));
     }
-    if (max_len >= (int64_t)0x7fffffff) return fail(SVDSS_ERANGE, "read too long");
+    if (max_len >= (int64_t)0x7fffffff) return run.fail(SVDSS_ERANGE, "read too long");
     if (max_len > 0) {
       const unsigned gx = (unsigned)((max_len + 15 + 256 * 16 - 1) / (256 * 16) + 1);
       for (int64_t y0 = 0; y0 < n_srch; y0 += 65535) {
@@ -1405,72 +1163,66 @@ extern "C" int svdss_bam_batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t
     }
   }
   // ---- what the host needs of the slots: names and tags
-  b->name_bytes = name_bytes;
+  b->search.name_bytes = name_bytes;
   try {
-    b->name_off.resize((size_t)n_slots + 1); b->hp.resize((size_t)n_slots); b->sidx.resize((size_t)n_slots);
-    b->names.resize((size_t)name_bytes + 1); b->counts.clear(); b->qs.clear(); b->len.clear();
-  } catch (...) { unpark(); return fail(SVDSS_ENOMEM, "out of memory"); }
+    b->search.name_off.resize((size_t)n_slots + 1); b->search.hp.resize((size_t)n_slots); b->search.sidx.resize((size_t)n_slots);
+    b->search.names.resize((size_t)name_bytes + 1); b->search.counts.clear(); b->search.qs.clear(); b->search.len.clear();
+  } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
   {
-    hipError_t e = hipMemcpyAsync(b->name_off.data(), S.o_name_off, sizeof(int32_t) * (size_t)(n_slots + 1), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_slots > 0) e = hipMemcpyAsync(b->hp.data(), S.o_hp, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_slots > 0) e = hipMemcpyAsync(b->sidx.data(), S.o_sidx, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && name_bytes > 0) e = hipMemcpyAsync(b->names.data(), S.o_names, (size_t)name_bytes, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(b->search.name_off.data(), S.o_name_off, sizeof(int32_t) * (size_t)(n_slots + 1), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && n_slots > 0) e = hipMemcpyAsync(b->search.hp.data(), S.o_hp, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && n_slots > 0) e = hipMemcpyAsync(b->search.sidx.data(), S.o_sidx, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && name_bytes > 0) e = hipMemcpyAsync(b->search.names.data(), S.o_names, (size_t)name_bytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     unpark();     // (the unpack has run: the group may be searched)
-    if (e != hipSuccess) { g_svdss_hip_err = std::string("bam batch front: ") + hipGetErrorString(e); return fail(e == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err); }
+    if (e != hipSuccess) { g_svdss_hip_err = std::string("bam batch front: ") + hipGetErrorString(e); return run.fail(e == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err); }
   }
-  lap(4);   // unpack; names and tags down
-  b->cur_reads = reads_out; b->cur_off = off_out; b->cur_syms = total_syms; b->cur_flags = flags;
+  run.lap(4);   // unpack; names and tags down
+  b->search.cur_reads = reads_out; b->search.cur_off = off_out; b->search.cur_syms = total_syms; b->search.cur_flags = flags;
   b->stage_ms[5] = b->stage_ms[6] = 0;
-  b->front_done = true;
+  b->search.front_done = true;
   return SVDSS_OK;
 }
 
 extern "C" int svdss_bam_batch_parked(const svdss_bam_batch_t* b, int64_t* group, int64_t* first, int64_t* n_reads) {
-  if (!b || !b->front_done) return SVDSS_EINVAL;
-  if (group) *group = b->park_group;
-  if (first) *first = b->park_first;
-  if (n_reads) *n_reads = b->n_searched;
+  if (!b || !b->search.front_done) return SVDSS_EINVAL;
+  if (group) *group = b->search.park_group;
+  if (first) *first = b->search.park_first;
+  if (n_reads) *n_reads = b->search.n_searched;
   return SVDSS_OK;
 }
 
 // The search half, for a batch whose front half left the reads in the batch object (not parked): search, counts and SFS down.
 extern "C" int svdss_bam_batch_search(svdss_bam_batch_t* b, const svdss_index_t* ix) {
-  if (!b || !ix || !b->front_done || b->park_group >= 0) return SVDSS_EINVAL;
+  if (!b || !ix || !b->search.front_done || b->search.park_group >= 0) return SVDSS_EINVAL;
   if (ix->device != b->device || !ix->d_blocks) return SVDSS_ENODEV;
-  const hipStream_t st = b->st;
-  const int32_t flags = b->cur_flags;
-  const int64_t n_srch = b->n_searched, total_syms = b->cur_syms;
-  auto fail = [&](int code, const std::string& msg) { b->err = msg; (void)hipStreamSynchronize(st); return code; };
+  BatchRun run(b);
+  const hipStream_t st = run.st;
+  const int32_t flags = b->search.cur_flags;
+  const int64_t n_srch = b->search.n_searched, total_syms = b->search.cur_syms;
   BCHK(hipSetDevice(b->device));
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    b->stage_ms[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
-    t_prev = t;
-  };
-  b->front_done = false;
+  b->search.front_done = false;
   {
-    const int rc = svdss_sfs_search_batch_device(ix, b->cur_reads, b->cur_off, n_srch, total_syms,
-                                                 (flags & SVDSS_SFS_ASSEMBLE), (void*)st, &b->sfs);
-    if (rc != SVDSS_OK) return fail(rc, std::string("search: ") + svdss_last_hip_error());
+    const int rc = svdss_sfs_search_batch_device(ix, b->search.cur_reads, b->search.cur_off, n_srch, total_syms,
+                                                 (flags & SVDSS_SFS_ASSEMBLE), (void*)st, &b->search.sfs);
+    if (rc != SVDSS_OK) return run.fail(rc, std::string("search: ") + svdss_last_hip_error());
   }
-  lap(5);   // search
-  b->total_sfs = svdss_sfs_batch_total(b->sfs);
+  run.lap(5);   // search
+  b->search.total_sfs = svdss_sfs_batch_total(b->search.sfs);
   try {
-    b->counts.resize((size_t)n_srch); b->qs.resize((size_t)b->total_sfs); b->len.resize((size_t)b->total_sfs);
-  } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
+    b->search.counts.resize((size_t)n_srch); b->search.qs.resize((size_t)b->search.total_sfs); b->search.len.resize((size_t)b->search.total_sfs);
+  } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
   if (n_srch > 0) {
     void *d_counts = nullptr, *d_qs = nullptr, *d_len = nullptr;
-    RCHK(svdss_sfs_batch_device_ptrs(b->sfs, &d_counts, &d_qs, &d_len, nullptr));
-    BCHK(hipMemcpyAsync(b->counts.data(), d_counts, sizeof(int64_t) * (size_t)n_srch, hipMemcpyDeviceToHost, st));
-    if (b->total_sfs > 0) {
-      BCHK(hipMemcpyAsync(b->qs.data(), d_qs, sizeof(int32_t) * (size_t)b->total_sfs, hipMemcpyDeviceToHost, st));
-      BCHK(hipMemcpyAsync(b->len.data(), d_len, sizeof(int32_t) * (size_t)b->total_sfs, hipMemcpyDeviceToHost, st));
+    RCHK(svdss_sfs_batch_device_ptrs(b->search.sfs, &d_counts, &d_qs, &d_len, nullptr));
+    BCHK(hipMemcpyAsync(b->search.counts.data(), d_counts, sizeof(int64_t) * (size_t)n_srch, hipMemcpyDeviceToHost, st));
+    if (b->search.total_sfs > 0) {
+      BCHK(hipMemcpyAsync(b->search.qs.data(), d_qs, sizeof(int32_t) * (size_t)b->search.total_sfs, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->search.len.data(), d_len, sizeof(int32_t) * (size_t)b->search.total_sfs, hipMemcpyDeviceToHost, st));
     }
   }
   BCHK(hipStreamSynchronize(st));
-  lap(6);   // results down
+  run.lap(6);   // results down
   return SVDSS_OK;
 }
 
@@ -1655,64 +1407,50 @@ extern "C" int svdss_bam_select_store_run(svdss_bam_stream_t* s, int64_t seq, in
     if (rc != SVDSS_OK) return rc;
   }
   svdss_bam_batch* b = *out;
-  const hipStream_t st = b->st;
-  const WalkP& W = F.W;
-  auto fail = [&](int code, const std::string& msg) { b->err = msg; (void)hipStreamSynchronize(st); return code; };
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    b->stage_ms[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
-    t_prev = t;
-  };
+  BatchRun run(b);
+  const hipStream_t st = run.st;
+  const SegWalk& W = F.W;
   const int64_t n_rec = F.hdr[H_NREC];
   b->n_records = n_rec;
-  b->n_selected = 0; b->sel_bytes = 0; b->sel_slim = false;
-  RCHK(ensure(b->rpos, sizeof(uint32_t) * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->flags, sizeof(int64_t) * 5 * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->scans, sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
+  b->sel.n = 0; b->sel.bytes = 0; b->sel.slim = false;
+  RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));
+  RCHK(b->flags.ensure(sizeof(int64_t) * 5 * (size_t)(n_rec + 1)));
+  RCHK(b->scans.ensure(sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
   SelP M;
-  M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = F.seg_base; M.pre = (const uint32_t*)b->pre.p;
+  M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = F.seg_base; M.pre = (const uint32_t*)b->front.pre.p;
   M.n_seg = W.n_seg; M.min_mapq = f->min_mapq; M.n_ref = f->n_ref; M.n_rec = n_rec;
   M.hash = f->d_hash; M.hash_mask = f->hash_mask; M.reg_off = f->d_reg_off; M.reg_beg = f->d_reg_beg; M.reg_runmax = f->d_reg_runmax;
   M.rpos = (uint32_t*)b->rpos.p;
   M.f_sel = (int64_t*)b->flags.p; M.f_bytes = M.f_sel + (n_rec + 1);
   M.f_keep = store ? M.f_bytes + (n_rec + 1) : nullptr; M.f_kbytes = store ? M.f_keep + (n_rec + 1) : nullptr; M.hpv = store ? M.f_kbytes + (n_rec + 1) : nullptr;
-  M.hdr = (int64_t*)b->hdr.p;
+  M.hdr = (int64_t*)b->front.hdr.p;
   hipLaunchKernelGGL(select_kernel, dim3((unsigned)W.n_seg + 1), dim3(64), 0, st, M);
   BCHK(hipGetLastError());
   int64_t* sc = (int64_t*)b->scans.p;
-  {
-    size_t tb = 0;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, M.f_sel, sc, (int)(n_rec + 1), st));
-    RCHK(ensure(b->tmp, tb + 256));
-    for (int k = 0; k < (store ? 4 : 2); ++k) {
-      size_t t2 = b->tmp.cap;
-      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t2, M.f_sel + (int64_t)k * (n_rec + 1), sc + (int64_t)k * (n_rec + 1), (int)(n_rec + 1), st));
-    }
-  }
+  RCHK(run.scan_rows(M.f_sel, sc, n_rec + 1, store ? 4 : 2));
   // (how much is kept is only known on the device: bounded by the batch itself)
-  RCHK(ensure(b->sel_out, (size_t)(F.total_inf + F.HEAD) + 4 * (size_t)(n_rec + 1) + 64));
-  RCHK(ensure(b->sel_off, sizeof(int64_t) * (size_t)(n_rec + 2)));
+  RCHK(b->sel.out.ensure((size_t)(F.total_inf + F.HEAD) + 4 * (size_t)(n_rec + 1) + 64));
+  RCHK(b->sel.off.ensure(sizeof(int64_t) * (size_t)(n_rec + 2)));
   if (store)
     hipLaunchKernelGGL(slim_export_kernel, dim3((unsigned)(n_rec + 1)), dim3(64), 0, st, W.buf, n_rec, (const uint32_t*)M.rpos, (const int64_t*)M.f_sel,
-                       (const int64_t*)sc, (const int64_t*)(sc + (n_rec + 1)), (const int64_t*)M.hpv, (uint8_t*)b->sel_out.p, (int64_t*)b->sel_off.p,
+                       (const int64_t*)sc, (const int64_t*)(sc + (n_rec + 1)), (const int64_t*)M.hpv, (uint8_t*)b->sel.out.p, (int64_t*)b->sel.off.p,
                        (int64_t*)b->totals.p);
   else
     hipLaunchKernelGGL(export_kernel, dim3((unsigned)(n_rec + 1)), dim3(64), 0, st, W.buf, n_rec, (const uint32_t*)M.rpos, (const int64_t*)M.f_sel,
-                       (const int64_t*)sc, (const int64_t*)(sc + (n_rec + 1)), (uint8_t*)b->sel_out.p, (int64_t*)b->sel_off.p, (int64_t*)b->totals.p);
+                       (const int64_t*)sc, (const int64_t*)(sc + (n_rec + 1)), (uint8_t*)b->sel.out.p, (int64_t*)b->sel.off.p, (int64_t*)b->totals.p);
   BCHK(hipGetLastError());
-  b->sel_slim = store != nullptr;
+  b->sel.slim = store != nullptr;
   int64_t totals[2] = {0, 0}, hdr2[H_N] = {0};
   BCHK(hipMemcpyAsync(totals, b->totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
-  BCHK(hipMemcpyAsync(hdr2, b->hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
+  BCHK(hipMemcpyAsync(hdr2, b->front.hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
   int64_t kept[2] = {0, 0};       // the store's share: records, bytes (the last entries of the third and fourth scan)
   if (store) {
     BCHK(hipMemcpyAsync(&kept[0], sc + 2 * (n_rec + 1) + n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     BCHK(hipMemcpyAsync(&kept[1], sc + 3 * (n_rec + 1) + n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   }
   BCHK(hipStreamSynchronize(st));
-  lap(3);
-  if (hdr2[H_ERR] & E_CORRUPT) return fail(SVDSS_EIO, "corrupt record");
+  run.lap(3);
+  if (const char* bad = record_error(hdr2[H_ERR])) return run.fail(SVDSS_EIO, bad);   // (select_kernel raises E_CORRUPT only)
   if (store) {
     StoreBatch B;
     uint8_t* base = nullptr;
@@ -1723,19 +1461,14 @@ extern "C" int svdss_bam_select_store_run(svdss_bam_stream_t* s, int64_t seq, in
       BCHK(hipGetLastError());
     }
   }
-  b->n_selected = totals[0];
-  b->sel_bytes = totals[1];
-  if ((size_t)totals[1] + 64 > b->h_sel_cap || !b->h_sel) {
-    if (b->h_sel) { (void)hipHostFree(b->h_sel); b->h_sel = nullptr; b->h_sel_cap = 0; }
-    const size_t want = (size_t)totals[1] + ((size_t)totals[1] >> 2) + ((size_t)1 << 20);
-    BCHK(hipHostMalloc((void**)&b->h_sel, want, hipHostMallocDefault));
-    b->h_sel_cap = want;
-  }
-  try { b->h_sel_off.resize((size_t)totals[0] + 1); } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
-  BCHK(hipMemcpyAsync(b->h_sel_off.data(), b->sel_off.p, sizeof(int64_t) * (size_t)(totals[0] + 1), hipMemcpyDeviceToHost, st));
-  if (totals[1] > 0) BCHK(hipMemcpyAsync(b->h_sel, b->sel_out.p, (size_t)totals[1], hipMemcpyDeviceToHost, st));
+  b->sel.n = totals[0];
+  b->sel.bytes = totals[1];
+  RCHK(b->sel.host.ensure((size_t)totals[1]));
+  try { b->sel.host_off.resize((size_t)totals[0] + 1); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
+  BCHK(hipMemcpyAsync(b->sel.host_off.data(), b->sel.off.p, sizeof(int64_t) * (size_t)(totals[0] + 1), hipMemcpyDeviceToHost, st));
+  if (totals[1] > 0) BCHK(hipMemcpyAsync(b->sel.host.p, b->sel.out.p, (size_t)totals[1], hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
-  lap(6);
+  run.lap(6);
   return SVDSS_OK;
 }
 
@@ -1754,25 +1487,17 @@ extern "C" int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const s
     base = t->arenas[(size_t)B.arena].p;
   }
   HIPCHK(hipSetDevice(t->device));
-  svdss_bam_batch* b = *out;
-  if (!b) {
-    b = new (std::nothrow) svdss_bam_batch();
-    if (!b) return SVDSS_ENOMEM;
-    b->device = t->device;
-    *out = b;
-  }
-  if (b->device != t->device) return SVDSS_EINVAL;
-  auto fail = [&](int code, const std::string& msg) { b->err = msg; if (b->st) (void)hipStreamSynchronize(b->st); return code; };
-  if (!b->st) BCHK(svdss_make_stream(&b->st, "SVDSS_SEARCH_CUS"));
-  const hipStream_t st = b->st;
-  b->err.clear();
+  BatchRun run;
+  RCHK(run.batch_object(out, t->device));
+  svdss_bam_batch* b = run.b;
+  const hipStream_t st = run.st;
   const int64_t n = B.n;
-  b->n_records = n; b->n_selected = 0; b->sel_bytes = 0; b->sel_slim = true; b->inflate_ms = 0;
+  b->n_records = n; b->sel.n = 0; b->sel.bytes = 0; b->sel.slim = true; b->inflate_ms = 0;
   for (int k = 0; k < 8; ++k) b->stage_ms[k] = 0;
   const auto t0 = std::chrono::steady_clock::now();
-  RCHK(ensure(b->flags, sizeof(int64_t) * 2 * (size_t)(n + 1)));
-  RCHK(ensure(b->scans, sizeof(int64_t) * 2 * (size_t)(n + 1)));
-  RCHK(ensure(b->totals, 64));
+  RCHK(b->flags.ensure(sizeof(int64_t) * 2 * (size_t)(n + 1)));
+  RCHK(b->scans.ensure(sizeof(int64_t) * 2 * (size_t)(n + 1)));
+  RCHK(b->totals.ensure(64));
   StoreSelP M;
   M.recs = base + B.at; M.off = (const int64_t*)(base + B.off_at); M.n = n; M.n_ref = f->n_ref;
   M.reg_off = f->d_reg_off; M.reg_beg = f->d_reg_beg; M.reg_runmax = f->d_reg_runmax;
@@ -1780,34 +1505,21 @@ extern "C" int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const s
   hipLaunchKernelGGL(store_select_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, M);
   BCHK(hipGetLastError());
   int64_t* sc = (int64_t*)b->scans.p;
-  {
-    size_t tb = 0;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, M.f_sel, sc, (int)(n + 1), st));
-    RCHK(ensure(b->tmp, tb + 256));
-    for (int k = 0; k < 2; ++k) {
-      size_t t2 = b->tmp.cap;
-      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t2, M.f_sel + (int64_t)k * (n + 1), sc + (int64_t)k * (n + 1), (int)(n + 1), st));
-    }
-  }
-  RCHK(ensure(b->sel_out, (size_t)B.bytes + 64));
-  RCHK(ensure(b->sel_off, sizeof(int64_t) * (size_t)(n + 2)));
+  RCHK(run.scan_rows(M.f_sel, sc, n + 1, 2));
+  RCHK(b->sel.out.ensure((size_t)B.bytes + 64));
+  RCHK(b->sel.off.ensure(sizeof(int64_t) * (size_t)(n + 2)));
   hipLaunchKernelGGL(store_export_kernel, dim3((unsigned)(n + 1)), dim3(64), 0, st, M.recs, M.off, n, (const int64_t*)M.f_sel, (const int64_t*)sc,
-                     (const int64_t*)(sc + (n + 1)), (uint8_t*)b->sel_out.p, (int64_t*)b->sel_off.p, (int64_t*)b->totals.p);
+                     (const int64_t*)(sc + (n + 1)), (uint8_t*)b->sel.out.p, (int64_t*)b->sel.off.p, (int64_t*)b->totals.p);
   BCHK(hipGetLastError());
   int64_t totals[2] = {0, 0};
   BCHK(hipMemcpyAsync(totals, b->totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
-  b->n_selected = totals[0];
-  b->sel_bytes = totals[1];
-  if ((size_t)totals[1] + 64 > b->h_sel_cap || !b->h_sel) {
-    if (b->h_sel) { (void)hipHostFree(b->h_sel); b->h_sel = nullptr; b->h_sel_cap = 0; }
-    const size_t want = (size_t)totals[1] + ((size_t)totals[1] >> 2) + ((size_t)1 << 20);
-    BCHK(hipHostMalloc((void**)&b->h_sel, want, hipHostMallocDefault));
-    b->h_sel_cap = want;
-  }
-  try { b->h_sel_off.resize((size_t)totals[0] + 1); } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
-  BCHK(hipMemcpyAsync(b->h_sel_off.data(), b->sel_off.p, sizeof(int64_t) * (size_t)(totals[0] + 1), hipMemcpyDeviceToHost, st));
-  if (totals[1] > 0) BCHK(hipMemcpyAsync(b->h_sel, b->sel_out.p, (size_t)totals[1], hipMemcpyDeviceToHost, st));
+  b->sel.n = totals[0];
+  b->sel.bytes = totals[1];
+  RCHK(b->sel.host.ensure((size_t)totals[1]));
+  try { b->sel.host_off.resize((size_t)totals[0] + 1); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
+  BCHK(hipMemcpyAsync(b->sel.host_off.data(), b->sel.off.p, sizeof(int64_t) * (size_t)(totals[0] + 1), hipMemcpyDeviceToHost, st));
+  if (totals[1] > 0) BCHK(hipMemcpyAsync(b->sel.host.p, b->sel.out.p, (size_t)totals[1], hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
   b->stage_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return SVDSS_OK;
@@ -1815,9 +1527,9 @@ extern "C" int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const s
 
 extern "C" int svdss_bam_batch_selection(const svdss_bam_batch_t* b, svdss_bam_selection_t* r) {
   if (!b || !r) return SVDSS_EINVAL;
-  r->n_records = b->n_records; r->n_selected = b->n_selected; r->n_bytes = b->sel_bytes;
-  r->rec_off = b->h_sel_off.data(); r->bytes = b->h_sel;
-  r->slim = b->sel_slim ? 1 : 0;
+  r->n_records = b->n_records; r->n_selected = b->sel.n; r->n_bytes = b->sel.bytes;
+  r->rec_off = b->sel.host_off.data(); r->bytes = (const uint8_t*)b->sel.host.p;
+  r->slim = b->sel.slim ? 1 : 0;
   r->inflate_kernel_ms = b->inflate_ms;
   for (int k = 0; k < 8; ++k) r->stage_ms[k] = b->stage_ms[k];
   return SVDSS_OK;
@@ -1825,10 +1537,10 @@ extern "C" int svdss_bam_batch_selection(const svdss_bam_batch_t* b, svdss_bam_s
 
 extern "C" int svdss_bam_batch_result(const svdss_bam_batch_t* b, svdss_bam_result_t* r) {
   if (!b || !r) return SVDSS_EINVAL;
-  r->n_records = b->n_records; r->n_slots = b->n_slots; r->n_searched = b->n_searched; r->n_short = b->n_short;
-  r->total_sfs = b->total_sfs;
-  r->name_off = b->name_off.data(); r->names = b->names.data(); r->hp = b->hp.data(); r->sidx = b->sidx.data();
-  r->counts = b->counts.data(); r->qs = b->qs.data(); r->len = b->len.data();
+  r->n_records = b->n_records; r->n_slots = b->search.n_slots; r->n_searched = b->search.n_searched; r->n_short = b->search.n_short;
+  r->total_sfs = b->search.total_sfs;
+  r->name_off = b->search.name_off.data(); r->names = b->search.names.data(); r->hp = b->search.hp.data(); r->sidx = b->search.sidx.data();
+  r->counts = b->search.counts.data(); r->qs = b->search.qs.data(); r->len = b->search.len.data();
   r->inflate_kernel_ms = b->inflate_ms;
   for (int k = 0; k < 8; ++k) r->stage_ms[k] = b->stage_ms[k];
   return SVDSS_OK;
@@ -1836,7 +1548,3 @@ extern "C" int svdss_bam_batch_result(const svdss_bam_batch_t* b, svdss_bam_resu
 
 extern "C" const char* svdss_bam_batch_error(const svdss_bam_batch_t* b) { return b ? b->err.c_str() : ""; }
 
-#include "bam_smooth.inc"
-
-#undef BCHK
-#undef RCHK

@@ -1,0 +1,296 @@
+// bam_device_internal.h -- what the units of the BAM device path share (bam_device.hip: front end, search, select, store;
+// bam_smooth.hip: `SVDSS smooth`): the stream and batch objects, the front end's result, the scope an entry point runs a
+// batch in (BatchRun) and the few device helpers the kernels of both units use.  Kernels stay in the unit that launches them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <chrono>
+#include <condition_variable>
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/svdss_hip.h"
+#include "dev_buf.h"
+#include "hip_check.h"
+
+// error bits a batch's kernels raise (hdr[H_ERR]; bam_smooth.hip adds one of its own)
+enum { E_CORRUPT = 1, E_TID = 2 };
+enum { H_NREC = 0, H_TAIL = 1, H_ERR = 2, H_REWALK = 3, H_PRE = 4, H_SHORT = 5, H_START = 6, H_N = 8 };
+
+// what the host says about them: the words of the host path (BamReader::next_view, ping_pong.cpp:76-79)
+static inline const char* record_error(int64_t bits) {
+  return (bits & E_CORRUPT) ? "corrupt record" : (bits & E_TID) ? "core.tid < 0. Why are we here? Please check" : nullptr;
+}
+
+namespace {   // (every unit its own copy: no device-side linking)
+
+__device__ __forceinline__ uint32_t ld32(const uint8_t* base, int64_t off) {
+  const uint32_t* w = (const uint32_t*)(base + (off & ~(int64_t)3));
+  return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(off & 3));
+}
+
+// ------------------------------------------------------------------ CRC32 of BGZF blocks (crc32_kernel, bgzf_footer_kernel)
+// a(x) * b(x) mod P in the reflected representation zlib uses (bit 31 = x^0); P = 0xEDB88320
+__host__ __device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (int i = 0; i < 32; ++i) {
+    p ^= (a & 0x80000000u) ? b : 0u;
+    a <<= 1;
+    b = (b >> 1) ^ ((b & 1u) ? 0xEDB88320u : 0u);
+  }
+  return p;
+}
+// x^(8 n) mod P
+__host__ __device__ inline uint32_t gf_xpow8(uint32_t n) {
+  uint32_t r = 0x80000000u;            // x^0
+  uint32_t sq = 0x00800000u;           // x^8
+  while (n) {
+    if (n & 1u) r = gf_mul(r, sq);
+    sq = gf_mul(sq, sq);
+    n >>= 1;
+  }
+  return r;
+}
+
+// Tables of the CRC kernels, computed once on the host and copied to every device that asks:
+//   [0]      the byte table of the CRC (state * x^8 for the state's low byte)
+//   [1..4]   byte k of a state times x^2048: state * x^2048 = [1][b0] ^ [2][b1] ^ [3][b2] ^ [4][b3]
+//   [5][l]   x^(32 (64 - l)), lane l's weight (entries 0..63)
+__device__ uint32_t g_crc_tab[6][256];
+
+// the tables, on the current device (once per device, unit and process)
+hipError_t crc_tables_ready() {
+  static std::mutex m;
+  static bool done[64] = {false};
+  static uint32_t h[6][256];
+  static bool built = false;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lk(m);
+  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
+  if (!built) {
+    memset(h, 0, sizeof h);
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+      h[0][i] = c;
+    }
+    const uint32_t x2048 = gf_xpow8(256);
+    for (int k = 0; k < 4; ++k)
+      for (uint32_t i = 0; i < 256; ++i) h[1 + k][i] = gf_mul(i << (8 * k), x2048);
+    for (uint32_t l = 0; l < 64; ++l) h[5][l] = gf_xpow8(4 * (64 - l));
+    built = true;
+  }
+  e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc_tab), h, sizeof h);
+  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
+  return e;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ the stream of a file's batches
+struct svdss_bam_stream {
+  int32_t n_ref = 0;
+  std::mutex m;
+  std::condition_variable cv;
+  int64_t next_seq = 0;
+  int failed = 0;
+  std::string err;
+  std::vector<uint8_t> carry;      // the bytes behind the last complete record of the batch that had its turn last
+  // a region of a file (svdss_bam_stream_region): open_start = batch 0 begins somewhere inside a record, `head` = its bytes
+  // in front of the first record the chain was started at; open_end = the last batch may end inside a record (carry stays)
+  bool open_start = false, open_end = false;
+  std::vector<uint8_t> head;
+  int64_t n_rewalked = 0, n_segments = 0;
+  // smoothing (bam_smooth.hip): the output stream's turn, and the bytes behind its last full BGZF block (at first: the
+  // BAM header of the output)
+  int64_t next_out = 0;
+  std::vector<uint8_t> out_tail;
+};
+
+// Batches take turns in file order: at the carry (`turn` = &svdss_bam_stream::next_seq) and, when smoothing, at the output
+// stream (next_out).  The turn of batch `seq` is taken by wait_turn and given up by done_turn, on every path.
+static inline bool wait_turn(svdss_bam_stream* s, int64_t svdss_bam_stream::*turn, int64_t seq) {
+  std::unique_lock<std::mutex> lk(s->m);
+  s->cv.wait(lk, [&] { return s->*turn == seq || s->failed; });
+  return !s->failed;
+}
+static inline void done_turn(svdss_bam_stream* s, int64_t svdss_bam_stream::*turn, int fail_code, const std::string& msg) {
+  {
+    std::lock_guard<std::mutex> lk(s->m);
+    if (fail_code && !s->failed) { s->failed = fail_code; s->err = msg; }
+    ++(s->*turn);
+  }
+  s->cv.notify_all();
+}
+// a batch that fails before its turn still passes the turn on: the batches behind it wait for it (a stream that already
+// failed has let everybody through)
+static inline void pass_turn(svdss_bam_stream* s, int64_t svdss_bam_stream::*turn, int64_t seq, int code, const std::string& msg) {
+  if (wait_turn(s, turn, seq)) done_turn(s, turn, code, msg);
+}
+
+// ------------------------------------------------------------------ the batch object
+// One object for every job (callers reuse it across jobs); the members are grouped by the job that owns them.
+using BamBuf = DevBuf<3, 4096>;   // grows to n + n / 8 + 4096
+
+struct svdss_bam_batch {
+  int device = -1;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  std::string err;
+  int64_t n_records = 0;
+  double inflate_ms = 0;
+  double stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host clock between the waits of the last run (svdss_bam_result_t::stage_ms)
+  // shared on purpose: record offsets, the flags and their scans, hipcub's temporary storage, small totals
+  BamBuf rpos, flags, scans, tmp, totals;
+  // batch_front: the blocks, the inflated bytes, the record chain (pre and hdr are read by the job that follows)
+  struct {
+    BamBuf comp, blks, crcb, status, buf, seg, lists, pre, hdr;
+    PinBuf<2, 4096> pin;             // page-locked staging of the block tables (grows to n + n / 4 + 4096)
+    std::vector<int32_t> h_status;
+  } front;
+  // svdss_bam_batch_front / _search: what the front half left for the search half, and the results on the host
+  struct {
+    const uint8_t* cur_reads = nullptr;
+    const int64_t* cur_off = nullptr;
+    int64_t cur_syms = 0, name_bytes = 0;
+    int32_t cur_flags = 0;
+    bool front_done = false;
+    int64_t park_group = -1, park_first = 0;   // -1: not parked (reads in this object), -2: nothing to search, >= 0: group
+    BamBuf d_hp, o_small, d_names, sym_off, seq_src, reads;
+    svdss_sfs_batch_t* sfs = nullptr;
+    std::vector<int32_t> name_off, hp, sidx, qs, len;
+    std::vector<char> names;
+    std::vector<int64_t> counts;
+    int64_t n_slots = 0, n_searched = 0, n_short = 0, total_sfs = 0;
+  } search;
+  // svdss_bam_select_run / _select_store_run / svdss_bam_store_select: the kept records and their offsets, device and host
+  struct {
+    BamBuf out, off;
+    PinBuf<2, (size_t)1 << 20, 64> host;   // page-locked (grows to n + n / 4 + 1 MB); smoothing's BGZF members land here too
+    std::vector<int64_t> host_off;
+    int64_t n = 0, bytes = 0;
+    bool slim = false;               // the kept records are slim ones (svdss_bam_store_select)
+  } sel;
+  // svdss_bam_smooth_run / _measure (bam_smooth.hip)
+  struct {
+    BamBuf rec, out, scratch, members, dense, len;
+    int64_t kept = 0, out_bytes = 0, bgzf_bytes = 0, in0 = 0, xf[4] = {0, 0, 0, 0};
+    const uint8_t* bgzf = nullptr;   // where the last run's BGZF members are (the caller's buffer or sel.host)
+    std::vector<int64_t> nmx;
+    std::vector<uint8_t> fits;
+  } sm;
+  // ... with an index asked for (svdss_bam_smooth_set_index): the batch's fragments (svdss_bam_batch_index)
+  struct {
+    BamBuf rec, frag;                // per kept record; the chunks and windows
+    bool on = false;
+    std::vector<svdss_bam_index_chunk_t> chunks;
+    std::vector<svdss_bam_index_window_t> windows;
+    int64_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  } sm_ix;
+};
+
+// ------------------------------------------------------------------ the front end's result
+// the chain of records of a batch, per segment (the argument of walk_kernel / link_kernel)
+struct SegWalk {
+  const uint8_t* buf;
+  int64_t lo, hi;          // fresh data of this batch: [lo, hi) (lo = head room [+ BAM header in the first batch])
+  int64_t seg_bytes;
+  int32_t n_seg, n_ref;
+  uint32_t* seg_start;     // guessed first record of the segment (0xffffffff: none found)
+  uint32_t* seg_end;       // where the chain from there left the segment (or stopped: tail / nonsense)
+  int32_t* seg_cnt;
+  uint32_t* lists;         // n_seg lists of list_cap offsets
+  int64_t list_cap;
+};
+
+struct Front {
+  SegWalk W;
+  int32_t* seg_base = nullptr;
+  int64_t hdr[H_N];
+  int64_t total_inf = 0, HEAD = 0;
+};
+
+// ------------------------------------------------------------------ the scope an entry point runs a batch in
+// The batch, its stream, the stage clock and the one way out on failure.  Entry points differ in a single thing: what else
+// a failure must let go of (the input turn, the park group, the output turn) -- `release`, set where it is owed and
+// cleared where it has been settled.  BCHK / RCHK return through fail() of the BatchRun named `run` of the calling function.
+struct BatchRun {
+  svdss_bam_batch* b = nullptr;
+  hipStream_t st = nullptr;
+  std::function<void(int, const std::string&)> release;
+  std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+
+  explicit BatchRun(svdss_bam_batch* b_ = nullptr) : b(b_), st(b_ ? b_->st : nullptr) {}
+
+  void lap(int k) {
+    const auto t = std::chrono::steady_clock::now();
+    b->stage_ms[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
+    t_prev = t;
+  }
+  int fail(int code, const std::string& msg) {
+    if (b) {
+      b->err = msg;
+      // the caller recycles its page-locked slabs as soon as this returns: no copy out of them may still be under way
+      if (b->st) (void)hipStreamSynchronize(b->st);
+    }
+    if (release) { release(code, msg); release = nullptr; }
+    return code;
+  }
+  // The helpers below return a code and leave the message in the thread's error string (RCHK passes both to fail()).
+  // the batch object, created on first use: of this device, with its stream and events
+  int batch_object(svdss_bam_batch_t** out, int device) {
+    if (!*out) {
+      *out = new (std::nothrow) svdss_bam_batch();
+      if (!*out) { g_svdss_hip_err = "out of memory"; return SVDSS_ENOMEM; }
+      (*out)->device = device;
+    }
+    b = *out;
+    if (b->device != device) { g_svdss_hip_err = "batch object of another device"; return SVDSS_EINVAL; }
+    if (!b->st) HIPCHK(svdss_make_stream(&b->st, "SVDSS_SEARCH_CUS"));
+    if (!b->e0) { HIPCHK(hipEventCreate(&b->e0)); HIPCHK(hipEventCreate(&b->e1)); }
+    st = b->st;
+    b->err.clear();
+    t_prev = std::chrono::steady_clock::now();   // (the stage clock runs from here)
+    return SVDSS_OK;
+  }
+  // room for a hipcub call that asked for `bytes` of temporary storage (b->tmp.cap is what the call may then be told)
+  int scan_tmp(size_t bytes) { return b->tmp.ensure(bytes + 256); }
+  // exclusive sums of `rows` consecutive rows of n entries (the last entry of a row: its total)
+  int scan_rows(int64_t* in, int64_t* out, int64_t n, int rows) {
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, st));
+    if (const int rc = scan_tmp(tb)) return rc;
+    for (int k = 0; k < rows; ++k) {
+      tb = b->tmp.cap;
+      HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, tb, in + (int64_t)k * n, out + (int64_t)k * n, (int)n, st));
+    }
+    return SVDSS_OK;
+  }
+};
+
+#define BCHK(expr)                                                                                    \
+  do {                                                                                                \
+    hipError_t e_ = (expr);                                                                           \
+    if (e_ != hipSuccess) {                                                                           \
+      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
+      return run.fail(e_ == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);        \
+    }                                                                                                 \
+  } while (0)
+#define RCHK(expr) do { const int rc_ = (expr); if (rc_ != SVDSS_OK) return run.fail(rc_, g_svdss_hip_err); } while (0)
+
+// What every entry point that reads BGZF blocks does first: the batch's blocks up, inflated, checked; the record chain of
+// its segments; the batch's turn at the carry.  On success the records of the batch are listed (F.W / F.seg_base /
+// front.pre, F.hdr) and the turn is over.  (bam_device.hip)
+__attribute__((visibility("hidden")))
+int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, int device,
+                int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
+                const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                svdss_bam_batch_t** out, Front& F);

@@ -1,7 +1,7 @@
 // bam_index_writer.h -- the BAI / CSI index of the BAM `SVDSS smooth` writes (`smooth --write-index FILE`, what
 // `samtools index` of the output gives; SAM specification 5.2 / 5.3).
 //
-// The device path reduces every batch on the GPU (csrc/bam_smooth.inc: chunks = runs of consecutive records with the same
+// The device path reduces every batch on the GPU (csrc/bam_smooth.hip: chunks = runs of consecutive records with the same
 // (tid, bin), the 16 kb windows the batch's records reach into first) and BamIndexBuilder folds those fragments in file
 // order; the host paths feed it one record at a time.  Both give the same bytes for the same BAM.
 //

@@ -1,4 +1,4 @@
-// bam_smooth.inc -- `SVDSS smooth` on the device path (part of bam_device.hip: same front end, same batch objects).
+// bam_smooth.hip -- `SVDSS smooth` on the device path (beside bam_device.hip: same front end, same batch objects).
 //
 // Stands where smoother.cpp's batch loop stands (:349-494 driver, :498-571 loader, :84-232 smooth_read, :50-82
 // rebuild_bam_entry, :441-494 writer): BGZF blocks in, BGZF blocks out.  The inflated records never leave HBM: the front end
@@ -17,15 +17,27 @@
 // record carry; for batch 0: the BAM header of the output), puts it in front of its own records, hands the bytes behind its
 // last full block on, and only then deflates -- so the deflate kernels of different batches overlap.
 
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstdint>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/svdss_hip.h"
+#include "bam_device_internal.h"
 #include "bam_index_writer.h"
+#include "deflate_dev.h"
+#include "ref_dev.h"
 
 namespace {
 
 enum { E_NCIG = 4 };   // more than 65535 CIGAR operations after smoothing (further bits of hdr[H_ERR])
 constexpr int kSmMinIndel = 20;          // config.hpp:95
 constexpr int64_t kBgzfBlock = 0xff00;
-
-__device__ __forceinline__ uint8_t sm_ld8(const uint8_t* buf, int64_t off) { return buf[off]; }
 
 struct SmMetaP {
   const uint8_t* buf;
@@ -102,10 +114,6 @@ struct CigIter {
 __device__ __forceinline__ char sm4_base(const uint8_t* buf, int64_t sq, int64_t i) {
   const uint8_t b = buf[sq + (i >> 1)];
   return "=ACMGRSVTWYHKDBN"[(i & 1) ? (b & 15) : (b >> 4)];
-}
-__device__ __forceinline__ uint32_t sm4_code(const uint8_t* buf, int64_t sq, int64_t i) {
-  const uint8_t b = buf[sq + (i >> 1)];
-  return (i & 1) ? (b & 15u) : (uint32_t)(b >> 4);
 }
 __device__ __forceinline__ uint32_t sm_code_of(char c) {   // the table write_record (smooth_host.cpp) packs with
   switch (c) {
@@ -582,87 +590,52 @@ extern "C" int svdss_bam_stream_set_output_prefix(svdss_bam_stream_t* s, const u
   return SVDSS_OK;
 }
 
-// the turn of batch `seq` at the output stream (second turn of a smoothing batch)
-static bool wait_out_turn(svdss_bam_stream* s, int64_t seq) {
-  std::unique_lock<std::mutex> lk(s->m);
-  s->cv.wait(lk, [&] { return s->next_out == seq || s->failed; });
-  return !s->failed;
-}
-static void done_out_turn(svdss_bam_stream* s, int fail_code, const std::string& msg) {
-  {
-    std::lock_guard<std::mutex> lk(s->m);
-    if (fail_code && !s->failed) { s->failed = fail_code; s->err = msg; }
-    ++s->next_out;
-  }
-  s->cv.notify_all();
-}
-
 // mode 0: measure (smoother.cpp:259-346 on the batch: matches / mismatches of the kept records come down);
 // mode 1: smooth, rebuild, deflate
 static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, const svdss_bam_smooth_t* sm, int mode, double acc,
                       uint8_t* host_out, int64_t host_cap, int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes, const svdss_bgzf_block_t* const* blocks,
                       const uint32_t* const* crc, const int64_t* n_blocks, svdss_bam_batch_t** out) {
   if (!s || !sm || !out || seq < 0 || skip < 0 || n_chunks < 0) return SVDSS_EINVAL;
-  // (a batch that fails before its output turn still has to pass that turn on)
-  bool had_out_turn = mode == 0;
+  constexpr auto out_turn = &svdss_bam_stream::next_out;
+  const bool owes_out_turn = mode != 0;   // (a batch that fails before its output turn still has to pass that turn on)
   Front F;
   {
     const int rc = batch_front(s, seq, is_last, skip, sm->device, n_chunks, comp, comp_bytes, blocks, crc, n_blocks, out, F);
     if (rc != SVDSS_OK) {
-      if (!had_out_turn && wait_out_turn(s, seq)) done_out_turn(s, rc, *out ? (*out)->err : std::string("batch failed"));
+      if (owes_out_turn) pass_turn(s, out_turn, seq, rc, *out ? (*out)->err : std::string("batch failed"));
       return rc;
     }
   }
   svdss_bam_batch* b = *out;
-  const hipStream_t st = b->st;
-  const WalkP& W = F.W;
-  auto fail = [&](int code, const std::string& msg) {
-    if (!had_out_turn) {
-      if (wait_out_turn(s, seq)) done_out_turn(s, code, msg);
-      had_out_turn = true;
-    }
-    b->err = msg;
-    (void)hipStreamSynchronize(st);
-    return code;
-  };
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    b->stage_ms[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
-    t_prev = t;
-  };
+  BatchRun run(b);
+  if (owes_out_turn) run.release = [&](int code, const std::string& msg) { pass_turn(s, out_turn, seq, code, msg); };
+  const hipStream_t st = run.st;
+  const SegWalk& W = F.W;
   const int64_t n_rec = F.hdr[H_NREC];
   b->n_records = n_rec;
-  b->sm_kept = 0; b->sm_out_bytes = 0; b->sm_bgzf_bytes = 0; b->sm_bgzf = nullptr;
-  for (int k = 0; k < 4; ++k) b->sm_xf[k] = 0;
-  RCHK(ensure(b->rpos, sizeof(uint32_t) * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->flags, sizeof(int64_t) * 2 * (size_t)(n_rec + 1)));
-  RCHK(ensure(b->scans, sizeof(int64_t) * 2 * (size_t)(n_rec + 1)));
+  b->sm.kept = 0; b->sm.out_bytes = 0; b->sm.bgzf_bytes = 0; b->sm.bgzf = nullptr;
+  for (int k = 0; k < 4; ++k) b->sm.xf[k] = 0;
+  RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));
+  RCHK(b->flags.ensure(sizeof(int64_t) * 2 * (size_t)(n_rec + 1)));
+  RCHK(b->scans.ensure(sizeof(int64_t) * 2 * (size_t)(n_rec + 1)));
   SmMetaP M;
-  M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = F.seg_base; M.pre = (const uint32_t*)b->pre.p;
+  M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = F.seg_base; M.pre = (const uint32_t*)b->front.pre.p;
   M.n_seg = W.n_seg; M.min_mapq = sm->min_mapq; M.n_ref = sm->n_ref; M.n_rec = n_rec; M.tidmap = sm->d_tidmap;
-  M.rpos = (uint32_t*)b->rpos.p; M.f_keep = (int64_t*)b->flags.p; M.hdr = (int64_t*)b->hdr.p;
+  M.rpos = (uint32_t*)b->rpos.p; M.f_keep = (int64_t*)b->flags.p; M.hdr = (int64_t*)b->front.hdr.p;
   hipLaunchKernelGGL(smooth_meta_kernel, dim3((unsigned)W.n_seg + 1), dim3(64), 0, st, M);
   BCHK(hipGetLastError());
   int64_t* s_keep = (int64_t*)b->scans.p;
-  {
-    size_t tb = 0;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, M.f_keep, s_keep, (int)(n_rec + 1), st));
-    RCHK(ensure(b->tmp, tb + 256));
-    size_t t2 = b->tmp.cap;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t2, M.f_keep, s_keep, (int)(n_rec + 1), st));
-  }
+  RCHK(run.scan_rows(M.f_keep, s_keep, n_rec + 1, 1));
   int64_t n_keep = 0, hdr2[H_N] = {0};
   BCHK(hipMemcpyAsync(&n_keep, s_keep + n_rec, sizeof n_keep, hipMemcpyDeviceToHost, st));
-  BCHK(hipMemcpyAsync(hdr2, b->hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
+  BCHK(hipMemcpyAsync(hdr2, b->front.hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
-  if (hdr2[H_ERR] & E_CORRUPT) return fail(SVDSS_EIO, "corrupt record");
-  if (hdr2[H_ERR] & E_TID) return fail(SVDSS_EIO, "core.tid < 0. Why are we here? Please check");
-  b->sm_kept = n_keep;
+  if (const char* bad = record_error(hdr2[H_ERR])) return run.fail(SVDSS_EIO, bad);
+  b->sm.kept = n_keep;
   // per kept record: kpos u32 | nlen i32 | ncig i32 | xf_at i32 | xf_sz i32 | nmx 2 x i64 | osize, ssize, ooff, soff (n + 1) x i64 | kflags u8 | xfv u8
   const size_t nk = (size_t)n_keep + 1;
-  RCHK(ensure(b->sm_rec, 20 * nk + 16 * nk + 32 * nk + 2 * nk + 256));
-  uint8_t* base = (uint8_t*)b->sm_rec.p;
+  RCHK(b->sm.rec.ensure(20 * nk + 16 * nk + 32 * nk + 2 * nk + 256));
+  uint8_t* base = (uint8_t*)b->sm.rec.p;
   int64_t* d_nmx = (int64_t*)base;                    // 16 nk
   int64_t* d_osize = d_nmx + 2 * nk;                  // 8 nk each
   int64_t* d_ssize = d_osize + nk;
@@ -683,62 +656,57 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     hipLaunchKernelGGL(smooth_walk_kernel, dim3((unsigned)n_rec), dim3(64), 0, st, A);
     BCHK(hipGetLastError());
   }
-  lap(3);
+  run.lap(3);
   if (mode == 0) {
-    try { b->sm_nmx.resize(2 * (size_t)n_keep); b->sm_fits.resize((size_t)n_keep); } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
+    try { b->sm.nmx.resize(2 * (size_t)n_keep); b->sm.fits.resize((size_t)n_keep); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
     if (n_keep > 0) {
-      BCHK(hipMemcpyAsync(b->sm_nmx.data(), d_nmx, 16 * (size_t)n_keep, hipMemcpyDeviceToHost, st));
-      BCHK(hipMemcpyAsync(b->sm_fits.data(), d_kfl, (size_t)n_keep, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->sm.nmx.data(), d_nmx, 16 * (size_t)n_keep, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->sm.fits.data(), d_kfl, (size_t)n_keep, hipMemcpyDeviceToHost, st));
       BCHK(hipStreamSynchronize(st));
-      for (uint8_t& f : b->sm_fits) f &= 1;
+      for (uint8_t& f : b->sm.fits) f &= 1;
     }
-    lap(6);
+    run.lap(6);
     return SVDSS_OK;
   }
   // ---- sizes, places, the records
   {
     SmSizeP S;
     S.buf = W.buf; S.n_keep = n_keep; S.kpos = d_kpos; S.nmx = d_nmx; S.nlen = d_nlen; S.ncig = d_ncig; S.kflags = d_kfl; S.xf_at = d_xat;
-    S.acc = acc; S.xfv = d_xfv; S.osize = d_osize; S.ssize = d_ssize; S.hdr = (int64_t*)b->hdr.p;
+    S.acc = acc; S.xfv = d_xfv; S.osize = d_osize; S.ssize = d_ssize; S.hdr = (int64_t*)b->front.hdr.p;
     hipLaunchKernelGGL(smooth_size_kernel, dim3((unsigned)((n_keep + 1 + 255) / 256)), dim3(256), 0, st, S);
     BCHK(hipGetLastError());
-    size_t t2 = 0;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_osize, d_ooff, (int)(n_keep + 1), st));
-    RCHK(ensure(b->tmp, t2 + 256));
-    t2 = b->tmp.cap;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t2, d_osize, d_ooff, (int)(n_keep + 1), st));
-    t2 = b->tmp.cap;
-    BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t2, d_ssize, d_soff, (int)(n_keep + 1), st));
+    RCHK(run.scan_rows(d_osize, d_ooff, n_keep + 1, 2));   // osize -> ooff, ssize -> soff
   }
   int64_t tot[2] = {0, 0};
   BCHK(hipMemcpyAsync(&tot[0], d_ooff + n_keep, 8, hipMemcpyDeviceToHost, st));
   BCHK(hipMemcpyAsync(&tot[1], d_soff + n_keep, 8, hipMemcpyDeviceToHost, st));
-  BCHK(hipMemcpyAsync(hdr2, b->hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
+  BCHK(hipMemcpyAsync(hdr2, b->front.hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
-  if (hdr2[H_ERR] & E_NCIG) return fail(SVDSS_ERANGE, "more than 65535 CIGAR operations (CG tag records are not supported)");
+  if (hdr2[H_ERR] & E_NCIG) return run.fail(SVDSS_ERANGE, "more than 65535 CIGAR operations (CG tag records are not supported)");
   const int64_t out_bytes = tot[0];
-  b->sm_out_bytes = out_bytes;
+  b->sm.out_bytes = out_bytes;
   // the output stream of the batch sits behind room for what the batch before leaves over (batch 0: the BAM header)
   int64_t room = kBgzfBlock;
   if (seq == 0) { std::lock_guard<std::mutex> lk(s->m); room = std::max<int64_t>(room, (int64_t)s->out_tail.size()); }
   room = (room + 255) & ~(int64_t)255;
-  RCHK(ensure(b->sm_out, (size_t)(room + out_bytes) + 4096));
-  RCHK(ensure(b->sm_scratch, (size_t)tot[1] + 4096));
+  RCHK(b->sm.out.ensure((size_t)(room + out_bytes) + 4096));
+  RCHK(b->sm.scratch.ensure((size_t)tot[1] + 4096));
   if (n_keep > 0) {
     SmWriteP A;
     A.buf = W.buf; A.n_keep = n_keep; A.kpos = d_kpos; A.nlen = d_nlen; A.ncig = d_ncig; A.xf_at = d_xat; A.xf_sz = d_xsz; A.xfv = d_xfv;
     A.ooff = d_ooff; A.soff = d_soff; A.ref = sm->ref.d_seq; A.ref_off = sm->ref.d_off; A.tidmap = sm->d_tidmap;
-    A.out = (uint8_t*)b->sm_out.p + room; A.scratch = (uint8_t*)b->sm_scratch.p;
+    A.out = (uint8_t*)b->sm.out.p + room; A.scratch = (uint8_t*)b->sm.scratch.p;
     hipLaunchKernelGGL(smooth_write_kernel, dim3((unsigned)n_keep), dim3(64), 0, st, A);
     BCHK(hipGetLastError());
   }
   std::vector<uint8_t> h_xfv;
-  try { h_xfv.resize((size_t)n_keep); } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
+  try { h_xfv.resize((size_t)n_keep); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
   if (n_keep > 0) BCHK(hipMemcpyAsync(h_xfv.data(), d_xfv, (size_t)n_keep, hipMemcpyDeviceToHost, st));
-  lap(4);
+  run.lap(4);
   // ---- the output turn
-  if (!wait_out_turn(s, seq)) { had_out_turn = true; return fail(s->failed, s->err); }
-  had_out_turn = true;
+  const bool my_turn = wait_turn(s, out_turn, seq);
+  run.release = nullptr;   // (taken, or let through by a stream that failed: nothing to pass on any more)
+  if (!my_turn) return run.fail(s->failed, s->err);
   int turn_code = SVDSS_OK;
   std::string turn_msg;
   int64_t in_len = 0, stream_bytes = 0, n_blk = 0;
@@ -748,76 +716,71 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     hipError_t e = hipSuccess;
     if (tail_in > room) turn_fail(SVDSS_ERANGE, "output tail larger than its room");
     if (!turn_code && tail_in > 0)
-      e = hipMemcpyAsync((uint8_t*)b->sm_out.p + (room - tail_in), s->out_tail.data(), (size_t)tail_in, hipMemcpyHostToDevice, st);
+      e = hipMemcpyAsync((uint8_t*)b->sm.out.p + (room - tail_in), s->out_tail.data(), (size_t)tail_in, hipMemcpyHostToDevice, st);
     stream_bytes = tail_in + out_bytes;
     in_len = is_last ? stream_bytes : stream_bytes / kBgzfBlock * kBgzfBlock;     // the last batch also writes the short block
     const int64_t tail_out = stream_bytes - in_len;
     if (!turn_code && e == hipSuccess) {
       try { s->out_tail.resize((size_t)tail_out); } catch (...) { turn_fail(SVDSS_ENOMEM, "out of memory"); }
       if (!turn_code && tail_out > 0)
-        e = hipMemcpyAsync(s->out_tail.data(), (const uint8_t*)b->sm_out.p + (room - tail_in) + in_len, (size_t)tail_out, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(s->out_tail.data(), (const uint8_t*)b->sm.out.p + (room - tail_in) + in_len, (size_t)tail_out, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     if (e != hipSuccess && !turn_code) {
       g_svdss_hip_err = std::string("smooth output turn: ") + hipGetErrorString(e);
       turn_fail(e == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);
     }
-    b->sm_in0 = room - tail_in;
+    b->sm.in0 = room - tail_in;
   }
-  done_out_turn(s, turn_code, turn_msg);
+  done_turn(s, out_turn, turn_code, turn_msg);
   if (turn_code) { b->err = turn_msg; return turn_code; }
-  for (uint8_t v : h_xfv) ++b->sm_xf[v & 3];
-  lap(5);
+  for (uint8_t v : h_xfv) ++b->sm.xf[v & 3];
+  run.lap(5);
   // ---- BGZF: deflate, footers, back to back, down
   n_blk = (in_len + kBgzfBlock - 1) / kBgzfBlock;
-  b->sm_bgzf_bytes = 0;
+  b->sm.bgzf_bytes = 0;
   const int64_t* d_off_out = nullptr;   // the members' compressed offsets (for the index fragments)
   if (n_blk > 0) {
     const int64_t stride = svdss_deflate_stride((int32_t)kBgzfBlock);
-    RCHK(ensure(b->sm_members, (size_t)(n_blk * stride) + 256));
-    RCHK(ensure(b->sm_dense, (size_t)(n_blk * stride) + 256));
-    RCHK(ensure(b->sm_len, sizeof(int32_t) * (size_t)n_blk + sizeof(int64_t) * (size_t)(n_blk + 1) + 256));
-    int32_t* d_len = (int32_t*)b->sm_len.p;
-    int64_t* d_off = (int64_t*)((uint8_t*)b->sm_len.p + ((sizeof(int32_t) * (size_t)n_blk + 63) & ~(size_t)63));
+    RCHK(b->sm.members.ensure((size_t)(n_blk * stride) + 256));
+    RCHK(b->sm.dense.ensure((size_t)(n_blk * stride) + 256));
+    RCHK(b->sm.len.ensure(sizeof(int32_t) * (size_t)n_blk + sizeof(int64_t) * (size_t)(n_blk + 1) + 256));
+    int32_t* d_len = (int32_t*)b->sm.len.p;
+    int64_t* d_off = (int64_t*)((uint8_t*)b->sm.len.p + ((sizeof(int32_t) * (size_t)n_blk + 63) & ~(size_t)63));
     d_off_out = d_off;
-    const uint8_t* d_in = (const uint8_t*)b->sm_out.p + b->sm_in0;
-    BCHK(hipMemsetAsync(b->sm_members.p, 0, (size_t)(n_blk * stride), st));
-    BCHK(svdss_deflate_enqueue(st, d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm_members.p, stride, d_len));
+    const uint8_t* d_in = (const uint8_t*)b->sm.out.p + b->sm.in0;
+    BCHK(hipMemsetAsync(b->sm.members.p, 0, (size_t)(n_blk * stride), st));
+    BCHK(svdss_deflate_enqueue(st, d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm.members.p, stride, d_len));
     BCHK(crc_tables_ready());
-    FootP Fp{d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm_members.p, stride, d_len};
+    FootP Fp{d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm.members.p, stride, d_len};
     hipLaunchKernelGGL(bgzf_footer_kernel, dim3((unsigned)n_blk), dim3(64), 0, st, Fp);
     BCHK(hipGetLastError());
-    BCHK(svdss_deflate_compact_enqueue(st, (const uint8_t*)b->sm_members.p, stride, d_len, n_blk, d_off, (uint8_t*)b->sm_dense.p));
+    BCHK(svdss_deflate_compact_enqueue(st, (const uint8_t*)b->sm.members.p, stride, d_len, n_blk, d_off, (uint8_t*)b->sm.dense.p));
     int64_t total = 0;
     BCHK(hipMemcpyAsync(&total, d_off + n_blk, 8, hipMemcpyDeviceToHost, st));
     BCHK(hipStreamSynchronize(st));
     uint8_t* dst = host_out;
     if (!dst || total > host_cap) {     // (no buffer of the caller's, or too small a one: the batch object's own)
-      if ((size_t)total + 64 > b->h_sel_cap || !b->h_sel) {
-        if (b->h_sel) { (void)hipHostFree(b->h_sel); b->h_sel = nullptr; b->h_sel_cap = 0; }
-        const size_t want = (size_t)total + ((size_t)total >> 2) + ((size_t)1 << 20);
-        BCHK(hipHostMalloc((void**)&b->h_sel, want, hipHostMallocDefault));
-        b->h_sel_cap = want;
-      }
-      dst = b->h_sel;
+      RCHK(b->sel.host.ensure((size_t)total));
+      dst = (uint8_t*)b->sel.host.p;
     }
-    BCHK(hipMemcpyAsync(dst, b->sm_dense.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(dst, b->sm.dense.p, (size_t)total, hipMemcpyDeviceToHost, st));
     BCHK(hipStreamSynchronize(st));
-    b->sm_bgzf = dst;
-    b->sm_bgzf_bytes = total;
+    b->sm.bgzf = dst;
+    b->sm.bgzf_bytes = total;
   }
   // ---- index fragments (`smooth --write-index`): chunks and first-reached windows, reduced here; only they come down
-  b->sm_ix_on = sm->ix_shift > 0;
-  b->sm_ix_chunks.clear(); b->sm_ix_windows.clear();
-  for (int64_t& v : b->sm_ix_hdr) v = 0;
-  if (b->sm_ix_on && n_keep > 0) {
+  b->sm_ix.on = sm->ix_shift > 0;
+  b->sm_ix.chunks.clear(); b->sm_ix.windows.clear();
+  for (int64_t& v : b->sm_ix.hdr) v = 0;
+  if (b->sm_ix.on && n_keep > 0) {
     const size_t nk1 = (size_t)n_keep + 1;
-    RCHK(ensure(b->sm_ix, 80 * nk1 + 8 * nk1 + 256));
+    RCHK(b->sm_ix.rec.ensure(80 * nk1 + 8 * nk1 + 256));
     SmIxP P;
-    P.out = (const uint8_t*)b->sm_out.p + room; P.ooff = d_ooff; P.n_keep = n_keep;
-    P.tail_in = room - b->sm_in0; P.in_len = in_len; P.n_blk = n_blk; P.d_off = d_off_out;
+    P.out = (const uint8_t*)b->sm.out.p + room; P.ooff = d_ooff; P.n_keep = n_keep;
+    P.tail_in = room - b->sm.in0; P.in_len = in_len; P.n_blk = n_blk; P.d_off = d_off_out;
     P.min_shift = sm->ix_shift; P.depth = sm->ix_depth;
-    int64_t* i64 = (int64_t*)b->sm_ix.p;
+    int64_t* i64 = (int64_t*)b->sm_ix.rec.p;
     unsigned long long* d_err = (unsigned long long*)i64;    // 8 bytes, then the per-record arrays
     P.err = d_err;
     P.beg = i64 + 1; P.end = P.beg + nk1; P.head = P.end + nk1; P.own = P.head + nk1;
@@ -836,15 +799,12 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
       size_t t0 = 0, t1 = 0;
       BCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, t0, P.key, kmax, hipcub::Max(), (uint64_t)0, (int)n_keep, st));
       BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, P.head, s_head, (int)nk1, st));
-      RCHK(ensure(b->tmp, std::max(t0, t1) + 256));
+      RCHK(run.scan_tmp(std::max(t0, t1)));   // (room for the sums below as well: nothing is allocated between the kernels)
       t0 = b->tmp.cap;
       BCHK(hipcub::DeviceScan::ExclusiveScan(b->tmp.p, t0, P.key, kmax, hipcub::Max(), (uint64_t)0, (int)n_keep, st));
       hipLaunchKernelGGL(sm_ix_own_kernel, dim3(g), dim3(256), 0, st, P);
       BCHK(hipGetLastError());
-      t0 = b->tmp.cap;
-      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t0, P.head, s_head, (int)nk1, st));
-      t0 = b->tmp.cap;
-      BCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t0, P.own, s_own, (int)nk1, st));
+      RCHK(run.scan_rows(P.head, s_head, (int64_t)nk1, 2));   // head -> s_head, own -> s_own
     }
     // counts, order flag, the first and last record's (tid, beg)
     int64_t cnt[2] = {0, 0}, be[2] = {0, 0};
@@ -858,24 +818,24 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     BCHK(hipMemcpyAsync(&be[0], P.beg, 8, hipMemcpyDeviceToHost, st));
     BCHK(hipMemcpyAsync(&be[1], P.beg + (n_keep - 1), 8, hipMemcpyDeviceToHost, st));
     BCHK(hipStreamSynchronize(st));
-    b->sm_ix_hdr[2] = td[0]; b->sm_ix_hdr[3] = td[1]; b->sm_ix_hdr[4] = be[0]; b->sm_ix_hdr[5] = be[1];
-    if (h_err & 1) b->sm_ix_hdr[6] = 1;      // out of order: the builder refuses; nothing else comes down
+    b->sm_ix.hdr[2] = td[0]; b->sm_ix.hdr[3] = td[1]; b->sm_ix.hdr[4] = be[0]; b->sm_ix.hdr[5] = be[1];
+    if (h_err & 1) b->sm_ix.hdr[6] = 1;      // out of order: the builder refuses; nothing else comes down
     else {
       const int64_t n_ch = cnt[0], n_win = cnt[1];
       const size_t ch_bytes = sizeof(svdss_bam_index_chunk_t) * (size_t)n_ch;
-      RCHK(ensure(b->sm_ixw, ch_bytes + sizeof(svdss_bam_index_window_t) * (size_t)n_win + 256));
-      P.chunks = (svdss_bam_index_chunk_t*)b->sm_ixw.p;
-      P.windows = (svdss_bam_index_window_t*)((uint8_t*)b->sm_ixw.p + ((ch_bytes + 255) & ~(size_t)255));
-      try { b->sm_ix_chunks.resize((size_t)n_ch); b->sm_ix_windows.resize((size_t)n_win); } catch (...) { return fail(SVDSS_ENOMEM, "out of memory"); }
+      RCHK(b->sm_ix.frag.ensure(ch_bytes + sizeof(svdss_bam_index_window_t) * (size_t)n_win + 256));
+      P.chunks = (svdss_bam_index_chunk_t*)b->sm_ix.frag.p;
+      P.windows = (svdss_bam_index_window_t*)((uint8_t*)b->sm_ix.frag.p + ((ch_bytes + 255) & ~(size_t)255));
+      try { b->sm_ix.chunks.resize((size_t)n_ch); b->sm_ix.windows.resize((size_t)n_win); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
       BCHK(hipMemsetAsync(P.chunks, 0, ch_bytes, st));
       hipLaunchKernelGGL(sm_ix_emit_kernel, dim3(g), dim3(256), 0, st, P);
       BCHK(hipGetLastError());
-      if (n_ch) BCHK(hipMemcpyAsync(b->sm_ix_chunks.data(), P.chunks, ch_bytes, hipMemcpyDeviceToHost, st));
-      if (n_win) BCHK(hipMemcpyAsync(b->sm_ix_windows.data(), P.windows, sizeof(svdss_bam_index_window_t) * (size_t)n_win, hipMemcpyDeviceToHost, st));
+      if (n_ch) BCHK(hipMemcpyAsync(b->sm_ix.chunks.data(), P.chunks, ch_bytes, hipMemcpyDeviceToHost, st));
+      if (n_win) BCHK(hipMemcpyAsync(b->sm_ix.windows.data(), P.windows, sizeof(svdss_bam_index_window_t) * (size_t)n_win, hipMemcpyDeviceToHost, st));
       BCHK(hipStreamSynchronize(st));
     }
   }
-  lap(6);
+  run.lap(6);
   return SVDSS_OK;
 }
 
@@ -895,21 +855,21 @@ extern "C" int svdss_bam_smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t 
 
 extern "C" int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* f) {
   if (!b || !f) return SVDSS_EINVAL;
-  f->n_chunks = (int64_t)b->sm_ix_chunks.size(); f->chunks = b->sm_ix_chunks.data();
-  f->n_windows = (int64_t)b->sm_ix_windows.size(); f->windows = b->sm_ix_windows.data();
-  f->unsorted = (int32_t)b->sm_ix_hdr[6];
-  f->first_tid = (int32_t)b->sm_ix_hdr[2]; f->last_tid = (int32_t)b->sm_ix_hdr[3];
-  f->first_beg = b->sm_ix_hdr[4]; f->last_beg = b->sm_ix_hdr[5];
+  f->n_chunks = (int64_t)b->sm_ix.chunks.size(); f->chunks = b->sm_ix.chunks.data();
+  f->n_windows = (int64_t)b->sm_ix.windows.size(); f->windows = b->sm_ix.windows.data();
+  f->unsorted = (int32_t)b->sm_ix.hdr[6];
+  f->first_tid = (int32_t)b->sm_ix.hdr[2]; f->last_tid = (int32_t)b->sm_ix.hdr[3];
+  f->first_beg = b->sm_ix.hdr[4]; f->last_beg = b->sm_ix.hdr[5];
   return SVDSS_OK;
 }
 
 extern "C" int svdss_bam_batch_smoothed(const svdss_bam_batch_t* b, svdss_bam_smoothed_t* r) {
   if (!b || !r) return SVDSS_EINVAL;
-  r->n_records = b->n_records; r->n_kept = b->sm_kept;
-  r->match_mismatch = b->sm_nmx.data(); r->fits = b->sm_fits.data();
-  r->out_bytes = b->sm_out_bytes;
-  r->bgzf = b->sm_bgzf; r->bgzf_bytes = b->sm_bgzf_bytes;
-  for (int k = 0; k < 4; ++k) r->n_xf[k] = b->sm_xf[k];
+  r->n_records = b->n_records; r->n_kept = b->sm.kept;
+  r->match_mismatch = b->sm.nmx.data(); r->fits = b->sm.fits.data();
+  r->out_bytes = b->sm.out_bytes;
+  r->bgzf = b->sm.bgzf; r->bgzf_bytes = b->sm.bgzf_bytes;
+  for (int k = 0; k < 4; ++k) r->n_xf[k] = b->sm.xf[k];
   r->inflate_kernel_ms = b->inflate_ms;
   for (int k = 0; k < 8; ++k) r->stage_ms[k] = b->stage_ms[k];
   return SVDSS_OK;

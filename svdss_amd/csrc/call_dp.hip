@@ -27,17 +27,6 @@
 #include "dev_arena.h"
 #include "hip_check.h"
 
-extern thread_local std::string g_svdss_hip_err;
-
-#define HIPCHK2(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess) {                                                       \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);        \
-      return (e_ == hipErrorOutOfMemory) ? SVDSS_ENOMEM : SVDSS_EHIP;             \
-    }                                                                             \
-  } while (0)
-
 #define DP_NEG (-0x20000000)
 #define DP_THREADS 256
 
@@ -417,7 +406,7 @@ struct DevMem {
   void* p = nullptr;
   ~DevMem() { if (p) (void)hipFree(p); }
   int alloc(size_t bytes) {
-    HIPCHK2(hipMalloc(&p, bytes ? bytes : 16));
+    HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
     return SVDSS_OK;
   }
 };
@@ -430,7 +419,7 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
                                         svdss_aln_batch_t** out) {
   if (!out || n_pairs < 0 || m < 1 || m > 8 || !mat || device < 0) return SVDSS_EINVAL;
   if (n_pairs > 0 && (!queries || !q_off || !targets || !t_off)) return SVDSS_EINVAL;
-  HIPCHK2(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   svdss_aln_batch* b = *out ? *out : new (std::nothrow) svdss_aln_batch();
   if (!b) return SVDSS_ENOMEM;
   *out = b;
@@ -453,12 +442,12 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
     if (b->stream) { (void)hipStreamDestroy(b->stream); b->stream = nullptr; }
     b->device = device;
   }
-  if (!b->stream) HIPCHK2(svdss_make_stream(&b->stream, "SVDSS_CALL_CUS"));
+  if (!b->stream) HIPCHK(svdss_make_stream(&b->stream, "SVDSS_CALL_CUS"));
   const hipStream_t st = b->stream;
   const GapModel gm{gapo, gape, gapo2, gape2};
   hipEvent_t ev0, ev1;
-  HIPCHK2(hipEventCreate(&ev0));
-  HIPCHK2(hipEventCreate(&ev1));
+  HIPCHK(hipEventCreate(&ev0));
+  HIPCHK(hipEventCreate(&ev1));
   // chunks of pairs whose direction matrices fit the workspace budget (HBM has 288 GB; the index may hold half of it)
   int64_t dir_budget = (int64_t)24 << 30;
   {
@@ -521,7 +510,7 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
                               DevArena::padded(sizeof(AlnPair) * (size_t)np) + DevArena::padded(sizeof(int32_t) * (size_t)ws) +
                               DevArena::padded((size_t)dirb) + DevArena::padded(sizeof(uint32_t) * (size_t)cig) +
                               2 * DevArena::padded(sizeof(int32_t) * (size_t)np) + DevArena::padded(64);
-    HIPCHK2(b->arena.reserve(need_bytes));
+    HIPCHK(b->arena.reserve(need_bytes));
     void* d_q = b->arena.take((size_t)qtot);
     void* d_t = b->arena.take((size_t)ttot);
     void* d_mat = b->arena.take(64);
@@ -532,12 +521,12 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
     void* d_sc = b->arena.take(sizeof(int32_t) * (size_t)np);
     void* d_nc = b->arena.take(sizeof(int32_t) * (size_t)np);
     void* d_abort = b->arena.take(64);
-    if (qtot) HIPCHK2(hipMemcpyAsync(d_q, queries + q_off[0], (size_t)qtot, hipMemcpyHostToDevice, st));
-    if (ttot) HIPCHK2(hipMemcpyAsync(d_t, targets + t_off[0], (size_t)ttot, hipMemcpyHostToDevice, st));
-    HIPCHK2(hipMemcpyAsync(d_mat, mat, (size_t)(m * m), hipMemcpyHostToDevice, st));
-    HIPCHK2(hipMemcpyAsync(d_pairs, hp.data(), sizeof(AlnPair) * (size_t)np, hipMemcpyHostToDevice, st));
-    HIPCHK2(hipMemsetAsync(d_abort, 0, 64, st));
-    HIPCHK2(hipEventRecord(ev0, st));
+    if (qtot) HIPCHK(hipMemcpyAsync(d_q, queries + q_off[0], (size_t)qtot, hipMemcpyHostToDevice, st));
+    if (ttot) HIPCHK(hipMemcpyAsync(d_t, targets + t_off[0], (size_t)ttot, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mat, mat, (size_t)(m * m), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pairs, hp.data(), sizeof(AlnPair) * (size_t)np, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_abort, 0, 64, st));
+    HIPCHK(hipEventRecord(ev0, st));
     if (any_multi && ALN_W == 8)
       hipLaunchKernelGGL(align_wave_kernel<8>, dim3((unsigned)np), dim3(64 * 8), 0, st, (const AlnPair*)d_pairs,
                          (const uint8_t*)d_q, (const uint8_t*)d_t, (int)m, (const int8_t*)d_mat, gm, (int32_t*)d_ws,
@@ -550,12 +539,12 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
       hipLaunchKernelGGL(align_wave_kernel<1>, dim3((unsigned)np), dim3(64), 0, st, (const AlnPair*)d_pairs,
                          (const uint8_t*)d_q, (const uint8_t*)d_t, (int)m, (const int8_t*)d_mat, gm, (int32_t*)d_ws,
                          (uint8_t*)d_dir, (uint32_t*)d_cig, (int32_t*)d_sc, (int32_t*)d_nc, (int32_t*)d_abort);
-    HIPCHK2(hipGetLastError());
-    HIPCHK2(hipEventRecord(ev1, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev1, st));
     if (any_multi) {
       int32_t ab = 0;
-      HIPCHK2(hipMemcpyAsync(&ab, d_abort, sizeof ab, hipMemcpyDeviceToHost, st));
-      HIPCHK2(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(&ab, d_abort, sizeof ab, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
       if (ab) {   // a wavefront gave up waiting for its neighbour (never seen): the chunk again, one wavefront per pair
         fprintf(stderr, "[svdss] realignment: a multi-wavefront pair did not finish; the batch runs again with one wavefront per pair\n");
         multi = false;
@@ -565,12 +554,12 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
       }
     }
     chunk_cigs.emplace_back((size_t)cig);
-    HIPCHK2(hipMemcpyAsync(&b->scores[(size_t)start], d_sc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
-    HIPCHK2(hipMemcpyAsync(&h_nc[(size_t)start], d_nc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
-    if (cig) HIPCHK2(hipMemcpyAsync(chunk_cigs.back().data(), d_cig, sizeof(uint32_t) * (size_t)cig, hipMemcpyDeviceToHost, st));
-    HIPCHK2(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&b->scores[(size_t)start], d_sc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&h_nc[(size_t)start], d_nc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
+    if (cig) HIPCHK(hipMemcpyAsync(chunk_cigs.back().data(), d_cig, sizeof(uint32_t) * (size_t)cig, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     float ms = 0.f;
-    HIPCHK2(hipEventElapsedTime(&ms, ev0, ev1));
+    HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
     b->kernel_ms += ms;
     start = end;
   }
@@ -614,7 +603,7 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
   if (n_pairs < 0 || device < 0) return SVDSS_EINVAL;
   if (n_pairs == 0) return SVDSS_OK;
   if (!a || !a_off || !bsy || !b_off || !ratio_out) return SVDSS_EINVAL;
-  HIPCHK2(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   std::vector<LcsPair> hp((size_t)n_pairs);
   int64_t ws = 0, la_max = 0, lb_max = 0;
   for (int64_t i = 0; i < n_pairs; ++i) {
@@ -645,18 +634,18 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
     if (R.stream) { (void)hipStreamDestroy(R.stream); R.stream = nullptr; }
     R.device = device;
   }
-  if (!R.stream) HIPCHK2(svdss_make_stream(&R.stream, "SVDSS_CALL_CUS"));
+  if (!R.stream) HIPCHK(svdss_make_stream(&R.stream, "SVDSS_CALL_CUS"));
   const hipStream_t st = R.stream;
-  HIPCHK2(R.arena.reserve(DevArena::padded((size_t)atot) + DevArena::padded((size_t)btot) +
+  HIPCHK(R.arena.reserve(DevArena::padded((size_t)atot) + DevArena::padded((size_t)btot) +
                           DevArena::padded(sizeof(LcsPair) * (size_t)n_pairs) + DevArena::padded(sizeof(int32_t) * (size_t)ws) +
                           DevArena::padded(sizeof(int64_t) * (size_t)n_pairs) + DevArena::padded(sizeof(double) * (size_t)n_pairs) +
                           DevArena::padded(256)));
   struct { void* p; } d_a{R.arena.take((size_t)atot)}, d_b{R.arena.take((size_t)btot)},
       d_pairs{R.arena.take(sizeof(LcsPair) * (size_t)n_pairs)}, d_ws{R.arena.take(sizeof(int32_t) * (size_t)ws)},
       d_lcs{R.arena.take(sizeof(int64_t) * (size_t)n_pairs)}, d_ratio{R.arena.take(sizeof(double) * (size_t)n_pairs)};
-  if (atot) HIPCHK2(hipMemcpyAsync(d_a.p, a + a_off[0], (size_t)atot, hipMemcpyHostToDevice, st));
-  if (btot) HIPCHK2(hipMemcpyAsync(d_b.p, bsy + b_off[0], (size_t)btot, hipMemcpyHostToDevice, st));
-  HIPCHK2(hipMemcpyAsync(d_pairs.p, hp.data(), sizeof(LcsPair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
+  if (atot) HIPCHK(hipMemcpyAsync(d_a.p, a + a_off[0], (size_t)atot, hipMemcpyHostToDevice, st));
+  if (btot) HIPCHK(hipMemcpyAsync(d_b.p, bsy + b_off[0], (size_t)btot, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_pairs.p, hp.data(), sizeof(LcsPair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
   // the bit-parallel kernel takes batches over at most 8 distinct symbols whose shorter strings fit 64 x 64 bits
   bool bits_ok = !getenv("SVDSS_RATIO_DP");
   uint8_t sym_id[256];
@@ -680,18 +669,18 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
   }
   if (bits_ok) {
     void* d_map = R.arena.take(256);
-    HIPCHK2(hipMemcpyAsync(d_map, sym_id, 256, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_map, sym_id, 256, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lcs_bits_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, (const LcsPair*)d_pairs.p,
                        (const uint8_t*)d_a.p, (const uint8_t*)d_b.p, (const uint8_t*)d_map, (int64_t*)d_lcs.p, (double*)d_ratio.p);
-    HIPCHK2(hipGetLastError());
-    HIPCHK2(hipMemcpyAsync(ratio_out, d_ratio.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
-    if (lcs_out) HIPCHK2(hipMemcpyAsync(lcs_out, d_lcs.p, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
-    HIPCHK2(hipStreamSynchronize(st));   // (sym_id is a local: the copy must have left it)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ratio_out, d_ratio.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    if (lcs_out) HIPCHK(hipMemcpyAsync(lcs_out, d_lcs.p, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // (sym_id is a local: the copy must have left it)
     return SVDSS_OK;
   }
   const size_t lds_need = sizeof(int32_t) * 3 * (size_t)(la_max + 1) + (size_t)la_max + (size_t)lb_max + 16;
   if (lds_need <= 150 * 1024) {
-    HIPCHK2(hipFuncSetAttribute((const void*)lcs_ratio_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need));
+    HIPCHK(hipFuncSetAttribute((const void*)lcs_ratio_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need));
     hipLaunchKernelGGL(lcs_ratio_kernel<true>, dim3((unsigned)n_pairs), dim3(DP_THREADS), lds_need, st,
                        (const LcsPair*)d_pairs.p, (const uint8_t*)d_a.p, (const uint8_t*)d_b.p, (int32_t*)d_ws.p,
                        (int64_t*)d_lcs.p, (double*)d_ratio.p);
@@ -700,9 +689,9 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
                        (const LcsPair*)d_pairs.p, (const uint8_t*)d_a.p, (const uint8_t*)d_b.p, (int32_t*)d_ws.p,
                        (int64_t*)d_lcs.p, (double*)d_ratio.p);
   }
-  HIPCHK2(hipGetLastError());
-  HIPCHK2(hipMemcpyAsync(ratio_out, d_ratio.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
-  if (lcs_out) HIPCHK2(hipMemcpyAsync(lcs_out, d_lcs.p, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
-  HIPCHK2(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(ratio_out, d_ratio.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+  if (lcs_out) HIPCHK(hipMemcpyAsync(lcs_out, d_lcs.p, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   return SVDSS_OK;
 }

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "dev_buf.h"
 #include "inflate_dev.h"
 
 #define UNI(x) __builtin_amdgcn_readfirstlane(x)
@@ -955,11 +956,6 @@ static unsigned inflate_grid(int64_t n_blocks) {
   return (unsigned)(n_blocks < cap ? n_blocks : cap);
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
 }  // namespace
 
 hipError_t svdss_inflate_enqueue(hipStream_t st, const uint8_t* d_comp, const svdss_bgzf_block_t* d_blocks, int64_t n_blocks,
@@ -972,7 +968,7 @@ hipError_t svdss_inflate_enqueue(hipStream_t st, const uint8_t* d_comp, const sv
 struct svdss_inflate {
   int device = -1;
   hipStream_t st = nullptr;
-  DevBuf comp, blks, status;
+  DevBuf<2, 4096> comp, blks, status;   // grow to n + n / 4 + 4096
   std::vector<int32_t> h_status;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double kernel_ms = 0.0;
@@ -986,15 +982,6 @@ struct svdss_inflate {
       return e_ == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP;                                 \
     }                                                                                               \
   } while (0)
-
-static int ensure(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap && b.p) return SVDSS_OK;
-  if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-  const size_t want = bytes + (bytes >> 2) + 4096;
-  HIPCHK(hipMalloc(&b.p, want));
-  b.cap = want;
-  return SVDSS_OK;
-}
 
 extern "C" int svdss_bgzf_inflate(svdss_inflate_t** obj, int device, const uint8_t* comp, int64_t comp_bytes,
                                   const svdss_bgzf_block_t* blocks, int64_t n_blocks, void* d_out, uint8_t* host_out,
@@ -1023,9 +1010,9 @@ extern "C" int svdss_bgzf_inflate(svdss_inflate_t** obj, int device, const uint8
   if (n_blocks == 0) return SVDSS_OK;
   int rc;
   // (the kernel reads the input in aligned 512-byte pieces, up to 5 KB past a block's last byte)
-  if ((rc = ensure(o->comp, (size_t)comp_bytes + 8192))) return rc;
-  if ((rc = ensure(o->blks, sizeof(svdss_bgzf_block_t) * (size_t)n_blocks))) return rc;
-  if ((rc = ensure(o->status, sizeof(int32_t) * (size_t)n_blocks))) return rc;
+  if ((rc = o->comp.ensure((size_t)comp_bytes + 8192))) return rc;
+  if ((rc = o->blks.ensure(sizeof(svdss_bgzf_block_t) * (size_t)n_blocks))) return rc;
+  if ((rc = o->status.ensure(sizeof(int32_t) * (size_t)n_blocks))) return rc;
   HIPCHK(hipMemcpyAsync(o->comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, o->st));
   HIPCHK(hipMemcpyAsync(o->blks.p, blocks, sizeof(svdss_bgzf_block_t) * (size_t)n_blocks, hipMemcpyHostToDevice, o->st));
   if (!o->ev0) { HIPCHK(hipEventCreate(&o->ev0)); HIPCHK(hipEventCreate(&o->ev1)); }
@@ -1071,8 +1058,6 @@ extern "C" void svdss_inflate_free(svdss_inflate_t* o) {
   if (o->device >= 0) (void)hipSetDevice(o->device);
   if (o->ev0) (void)hipEventDestroy(o->ev0);
   if (o->ev1) (void)hipEventDestroy(o->ev1);
-  for (DevBuf* d : {&o->comp, &o->blks, &o->status})
-    if (d->p) (void)hipFree(d->p);
   if (o->st) (void)hipStreamDestroy(o->st);
   delete o;
 }

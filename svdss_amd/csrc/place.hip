@@ -25,18 +25,8 @@
 
 #include "../../include/svdss_hip.h"
 #include "dev_arena.h"
+#include "hip_check.h"
 #include "ref_dev.h"
-
-extern thread_local std::string g_svdss_hip_err;
-
-#define HIPCHK5(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess) {                                                       \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);        \
-      return (e_ == hipErrorOutOfMemory) ? SVDSS_ENOMEM : SVDSS_EHIP;             \
-    }                                                                             \
-  } while (0)
 
 namespace {
 
@@ -246,7 +236,7 @@ SvdssRefView svdss_ref_view(const svdss_ref_t* ref) {
 
 extern "C" int svdss_ref_upload(const uint8_t* seqs, const int64_t* off, int32_t n_chrom, int32_t device, svdss_ref_t** out) {
   if (!out || n_chrom < 0 || device < 0 || (n_chrom > 0 && (!seqs || !off))) return SVDSS_EINVAL;
-  HIPCHK5(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   svdss_ref* r = new (std::nothrow) svdss_ref();
   if (!r) return SVDSS_ENOMEM;
   r->device = device;
@@ -270,7 +260,7 @@ extern "C" int svdss_ref_upload_parts(const uint8_t* const* seqs, const int64_t*
     if (lens[i] < 0 || (lens[i] > 0 && !seqs[i])) return SVDSS_EINVAL;
     off[(size_t)i + 1] = off[(size_t)i] + lens[i];
   }
-  HIPCHK5(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   svdss_ref* r = new (std::nothrow) svdss_ref();
   if (!r) return SVDSS_ENOMEM;
   r->device = device;
@@ -338,7 +328,7 @@ extern "C" int svdss_place_sfs_batch(svdss_ref_t* ref, const int32_t* tid, const
   if (!ref || n_aln < 0 || !out_count || (n_aln > 0 && (!tid || !pos || !cigar_off || !sfs_off))) return SVDSS_EINVAL;
   if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
   if (n_aln == 0) return SVDSS_OK;
-  HIPCHK5(hipSetDevice(ref->device));
+  HIPCHK(hipSetDevice(ref->device));
   // the prefix tables of the CIGARs (host: O(total operations))
   const int64_t n_sfs = sfs_off[n_aln];
   if (n_sfs > 0 && (!sfs_qs || !sfs_len || !out)) return SVDSS_EINVAL;
@@ -377,7 +367,7 @@ extern "C" int svdss_place_sfs_batch(svdss_ref_t* ref, const int32_t* tid, const
   const size_t need = DevArena::padded(4 * (size_t)n_aln) + 2 * DevArena::padded(8 * (size_t)(n_aln + 1)) +
                       3 * DevArena::padded(4 * (size_t)nw) + DevArena::padded((size_t)nw) + 2 * DevArena::padded(4 * (size_t)n_sfs) +
                       DevArena::padded(4 * (size_t)n_aln) + DevArena::padded(20 * (size_t)n_sfs) + DevArena::padded(32);
-  HIPCHK5(ar.reserve(need));
+  HIPCHK(ar.reserve(need));
   PlaceArgs A;
   const hipStream_t st = ref->stream;
   auto up = [&](const void* src, size_t bytes) -> void* {
@@ -401,14 +391,14 @@ extern "C" int svdss_place_sfs_batch(svdss_ref_t* ref, const int32_t* tid, const
   A.out_count = (int32_t*)ar.take(4 * (size_t)n_aln);
   A.out = (int32_t*)ar.take(20 * (size_t)(n_sfs ? n_sfs : 1));
   A.stats = (unsigned long long*)ar.take(32);
-  HIPCHK5(hipMemsetAsync(A.stats, 0, 32, st));
+  HIPCHK(hipMemsetAsync(A.stats, 0, 32, st));
   hipLaunchKernelGGL(place_sfs_kernel, dim3((unsigned)((n_aln + 63) / 64)), dim3(64), 0, st, A);
-  HIPCHK5(hipGetLastError());
-  HIPCHK5(hipMemcpyAsync(out_count, A.out_count, 4 * (size_t)n_aln, hipMemcpyDeviceToHost, st));
-  if (n_sfs) HIPCHK5(hipMemcpyAsync(out, A.out, 20 * (size_t)n_sfs, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out_count, A.out_count, 4 * (size_t)n_aln, hipMemcpyDeviceToHost, st));
+  if (n_sfs) HIPCHK(hipMemcpyAsync(out, A.out, 20 * (size_t)n_sfs, hipMemcpyDeviceToHost, st));
   unsigned long long hs[4] = {0, 0, 0, 0};
-  HIPCHK5(hipMemcpyAsync(hs, A.stats, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(hs, A.stats, 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (stats) for (int k = 0; k < 4; ++k) stats[k] = (int64_t)hs[k];
   return SVDSS_OK;
 }
@@ -562,7 +552,7 @@ extern "C" int svdss_smooth_batch(svdss_ref_t* ref, const int32_t* tid, const in
   if (!tid || !pos || !cigar || !cigar_off || !seq4 || !seq4_off || !qual || !qual_off || !l_seq || !cap_off || !out_seq4 ||
       !out_qual || !out_cigar || !out_ncig || !out_len || !out_match_mismatch || !out_ignore)
     return SVDSS_EINVAL;
-  HIPCHK5(hipSetDevice(ref->device));
+  HIPCHK(hipSetDevice(ref->device));
   for (int64_t i = 0; i < n; ++i)
     if (tid[i] < 0 || tid[i] >= ref->n_chrom || (cap_off[i] & 1) || cap_off[i + 1] < cap_off[i]) return SVDSS_EINVAL;
   const int64_t n_cig = cigar_off[n], cap = cap_off[n];
@@ -572,7 +562,7 @@ extern "C" int svdss_smooth_batch(svdss_ref_t* ref, const int32_t* tid, const in
     q_bytes = std::max<int64_t>(q_bytes, qual_off[i] + l_seq[i]);
   }
   DevArena& ar = ref->arena;
-  HIPCHK5(ar.reserve(3 * DevArena::padded(4 * (size_t)n) + 4 * DevArena::padded(8 * (size_t)(n + 1)) + 2 * DevArena::padded(4 * (size_t)n_cig) +
+  HIPCHK(ar.reserve(3 * DevArena::padded(4 * (size_t)n) + 4 * DevArena::padded(8 * (size_t)(n + 1)) + 2 * DevArena::padded(4 * (size_t)n_cig) +
                      DevArena::padded((size_t)s4_bytes) + DevArena::padded((size_t)q_bytes) + 2 * DevArena::padded((size_t)cap) +
                      DevArena::padded((size_t)cap / 2 + 8) + 2 * DevArena::padded(4 * (size_t)n) + DevArena::padded(16 * (size_t)n) +
                      DevArena::padded((size_t)n)));
@@ -605,14 +595,14 @@ extern "C" int svdss_smooth_batch(svdss_ref_t* ref, const int32_t* tid, const in
   A.out_nm = (unsigned long long*)ar.take(16 * (size_t)n);
   A.out_ignore = (uint8_t*)ar.take((size_t)n);
   hipLaunchKernelGGL(smooth_kernel, dim3((unsigned)n), dim3(64), 0, st, A);
-  HIPCHK5(hipGetLastError());
-  HIPCHK5(hipMemcpyAsync(out_seq4, A.out_seq4, (size_t)cap / 2, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipMemcpyAsync(out_qual, A.out_qual, (size_t)cap, hipMemcpyDeviceToHost, st));
-  if (n_cig) HIPCHK5(hipMemcpyAsync(out_cigar, A.out_cigar, 4 * (size_t)n_cig, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipMemcpyAsync(out_ncig, A.out_ncig, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipMemcpyAsync(out_len, A.out_len, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipMemcpyAsync(out_match_mismatch, A.out_nm, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipMemcpyAsync(out_ignore, A.out_ignore, (size_t)n, hipMemcpyDeviceToHost, st));
-  HIPCHK5(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out_seq4, A.out_seq4, (size_t)cap / 2, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_qual, A.out_qual, (size_t)cap, hipMemcpyDeviceToHost, st));
+  if (n_cig) HIPCHK(hipMemcpyAsync(out_cigar, A.out_cigar, 4 * (size_t)n_cig, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_ncig, A.out_ncig, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_len, A.out_len, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_match_mismatch, A.out_nm, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_ignore, A.out_ignore, (size_t)n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   return SVDSS_OK;
 }

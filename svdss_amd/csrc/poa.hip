@@ -32,17 +32,6 @@
 #include "poa_wave.h"
 #include "poa_quad.h"
 
-extern thread_local std::string g_svdss_hip_err;
-
-#define HIPCHK3(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess) {                                                       \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);        \
-      return (e_ == hipErrorOutOfMemory) ? SVDSS_ENOMEM : SVDSS_EHIP;             \
-    }                                                                             \
-  } while (0)
-
 #define PNEG (-0x20000000)
 #define P_O1 4
 #define P_E1 2
@@ -402,7 +391,7 @@ namespace {
 struct DevMem3 {
   void* p = nullptr;
   ~DevMem3() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { HIPCHK3(hipMalloc(&p, bytes ? bytes : 16)); return SVDSS_OK; }
+  int alloc(size_t bytes) { HIPCHK(hipMalloc(&p, bytes ? bytes : 16)); return SVDSS_OK; }
 };
 
 }  // namespace
@@ -429,7 +418,7 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
                                          int64_t n_clusters, int32_t device, svdss_poa_batch_t** out) {
   if (!out || n_clusters < 0 || device < 0) return SVDSS_EINVAL;
   if (n_clusters > 0 && (!seq_off || !cluster_off)) return SVDSS_EINVAL;
-  HIPCHK3(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   svdss_poa_batch* b = *out ? *out : new (std::nothrow) svdss_poa_batch();
   if (!b) return SVDSS_ENOMEM;
   *out = b;
@@ -457,7 +446,7 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
     b->device = device;
   }
   const size_t off_bytes = sizeof(int64_t) * (size_t)(n_seqs_total + 1);
-  HIPCHK3(b->in_arena.reserve(DevArena::padded((size_t)total_syms) + DevArena::padded(off_bytes) + DevArena::padded(8)));
+  HIPCHK(b->in_arena.reserve(DevArena::padded((size_t)total_syms) + DevArena::padded(off_bytes) + DevArena::padded(8)));
   struct { void* p; } d_seqs{b->in_arena.take((size_t)total_syms)}, d_off{b->in_arena.take(off_bytes)},
       d_cells{b->in_arena.take(8)};
   // every copy and launch of this call goes to the batch object's own non-blocking streams and every wait is a
@@ -466,16 +455,16 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
   // in order)
   while (b->streams.size() < 6) {   // (the launches of a round run side by side: one stream each while they last)
     hipStream_t st;
-    HIPCHK3(svdss_make_stream(&st, "SVDSS_CALL_CUS"));
+    HIPCHK(svdss_make_stream(&st, "SVDSS_CALL_CUS"));
     b->streams.push_back(st);
   }
   const hipStream_t s0 = b->streams[0];
-  if (total_syms) HIPCHK3(hipMemcpyAsync(d_seqs.p, seqs, (size_t)total_syms, hipMemcpyHostToDevice, s0));
-  HIPCHK3(hipMemcpyAsync(d_off.p, seq_off, off_bytes, hipMemcpyHostToDevice, s0));
-  HIPCHK3(hipMemsetAsync(d_cells.p, 0, 8, s0));
+  if (total_syms) HIPCHK(hipMemcpyAsync(d_seqs.p, seqs, (size_t)total_syms, hipMemcpyHostToDevice, s0));
+  HIPCHK(hipMemcpyAsync(d_off.p, seq_off, off_bytes, hipMemcpyHostToDevice, s0));
+  HIPCHK(hipMemsetAsync(d_cells.p, 0, 8, s0));
   hipEvent_t ev0, ev1;
-  HIPCHK3(hipEventCreate(&ev0));
-  HIPCHK3(hipEventCreate(&ev1));
+  HIPCHK(hipEventCreate(&ev0));
+  HIPCHK(hipEventCreate(&ev1));
   std::vector<std::vector<uint8_t>> results((size_t)n_clusters);
   // fast path: the LDS-resident kernel in up to three rounds of growing generosity -- ring rows of 2w + 33 columns
   // and a graph of ~1.5 x the longest read (what nearly every sub-cluster needs); then the specification's widest
@@ -699,7 +688,7 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
         tot_bytes += groups[gend++]->bytes();
       {
         const auto ta = std::chrono::steady_clock::now();
-        HIPCHK3(b->ws_arena.reserve(tot_bytes));
+        HIPCHK(b->ws_arena.reserve(tot_bytes));
         const double as = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
         if (getenv("SVDSS_DEBUG") && as > 0.005) fprintf(stderr, "[poa] workspace of %.1f GB taken in %.3f s\n", (double)tot_bytes / 1073741824.0, as);
       }
@@ -711,26 +700,26 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
         g.d8 = b->ws_arena.take((size_t)g.w8);
         g.d_len = b->ws_arena.take(sizeof(int32_t) * nt);
         g.d_st = b->ws_arena.take(sizeof(int32_t) * nt);
-        HIPCHK3(hipMemcpyAsync(g.d_tasks, g.tasks.data(), sizeof(PoaWaveTask) * nt, hipMemcpyHostToDevice, s0));
-        HIPCHK3(hipMemsetAsync(g.d_st, 0xff, sizeof(int32_t) * nt, s0));
+        HIPCHK(hipMemcpyAsync(g.d_tasks, g.tasks.data(), sizeof(PoaWaveTask) * nt, hipMemcpyHostToDevice, s0));
+        HIPCHK(hipMemsetAsync(g.d_st, 0xff, sizeof(int32_t) * nt, s0));
       }
-      HIPCHK3(hipStreamSynchronize(s0));
+      HIPCHK(hipStreamSynchronize(s0));
       const auto t0 = std::chrono::steady_clock::now();
       for (size_t gi = gpos; gi < gend; ++gi) {
         Group& g = *groups[gi];
         const hipStream_t gs = b->streams[(gi - gpos) % b->streams.size()];
         if (g.gw) {
-          HIPCHK3(poa_quad_launch(g.gw, g.cols, (const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.max_len, (const uint8_t*)d_seqs.p,
+          HIPCHK(poa_quad_launch(g.gw, g.cols, (const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.max_len, (const uint8_t*)d_seqs.p,
                                   (const int64_t*)d_off.p, (int32_t*)g.d32, (int32_t*)g.d_len, (int32_t*)g.d_st,
                                   (unsigned long long*)d_cells.p, gs));
-          HIPCHK3(poa_bundle_launch((const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.bundle_lds, (int32_t*)g.d32, (uint8_t*)g.d8,
+          HIPCHK(poa_bundle_launch((const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.bundle_lds, (int32_t*)g.d32, (uint8_t*)g.d8,
                                     (int32_t*)g.d_len, (const int32_t*)g.d_st, gs));
         } else
-        HIPCHK3(poa_wave_launch(g.cols, (const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.lds, g.bundle_lds,
+        HIPCHK(poa_wave_launch(g.cols, (const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.lds, g.bundle_lds,
                                 (const uint8_t*)d_seqs.p, (const int64_t*)d_off.p, (int32_t*)g.d32, (uint8_t*)g.d8,
                                 (int32_t*)g.d_len, (int32_t*)g.d_st, (unsigned long long*)d_cells.p, gs));
       }
-      for (size_t k = 0; k < std::min(gend - gpos, b->streams.size()); ++k) HIPCHK3(hipStreamSynchronize(b->streams[k]));
+      for (size_t k = 0; k < std::min(gend - gpos, b->streams.size()); ++k) HIPCHK(hipStreamSynchronize(b->streams[k]));
       const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       b->kernel_ms += ms;   // wall time of the concurrent launches
       int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -741,10 +730,10 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
         n_run += nt;
         std::vector<int32_t> lens((size_t)nt), st((size_t)nt);
         std::vector<uint8_t> h8((size_t)g.w8);
-        HIPCHK3(hipMemcpyAsync(lens.data(), g.d_len, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-        HIPCHK3(hipMemcpyAsync(st.data(), g.d_st, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-        if (g.w8) HIPCHK3(hipMemcpyAsync(h8.data(), g.d8, (size_t)g.w8, hipMemcpyDeviceToHost, s0));
-        HIPCHK3(hipStreamSynchronize(s0));
+        HIPCHK(hipMemcpyAsync(lens.data(), g.d_len, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
+        HIPCHK(hipMemcpyAsync(st.data(), g.d_st, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
+        if (g.w8) HIPCHK(hipMemcpyAsync(h8.data(), g.d8, (size_t)g.w8, hipMemcpyDeviceToHost, s0));
+        HIPCHK(hipStreamSynchronize(s0));
         for (int64_t k = 0; k < nt; ++k) {
           if (st[(size_t)k] == 0) {
             const uint8_t* src = h8.data() + g.tasks[(size_t)k].cons_off;
@@ -817,24 +806,24 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
           (rc = d64.alloc(sizeof(int64_t) * (size_t)w64)) || (rc = d8.alloc((size_t)w8)) ||
           (rc = d_len.alloc(sizeof(int32_t) * (size_t)nt)) || (rc = d_st.alloc(sizeof(int32_t) * (size_t)nt)))
         return rc;
-      HIPCHK3(hipMemcpyAsync(d_tasks.p, tasks.data(), sizeof(PoaTask) * (size_t)nt, hipMemcpyHostToDevice, s0));
-      HIPCHK3(hipMemsetAsync(d_st.p, 0xff, sizeof(int32_t) * (size_t)nt, s0));
-      HIPCHK3(hipEventRecord(ev0, s0));
+      HIPCHK(hipMemcpyAsync(d_tasks.p, tasks.data(), sizeof(PoaTask) * (size_t)nt, hipMemcpyHostToDevice, s0));
+      HIPCHK(hipMemsetAsync(d_st.p, 0xff, sizeof(int32_t) * (size_t)nt, s0));
+      HIPCHK(hipEventRecord(ev0, s0));
       hipLaunchKernelGGL(poa_consensus_kernel, dim3((unsigned)nt), dim3(64), 0, s0, (const PoaTask*)d_tasks.p,
                          (const uint8_t*)d_seqs.p, (const int64_t*)d_off.p, (int32_t*)d32.p, (int64_t*)d64.p,
                          (uint8_t*)d8.p, (int32_t*)d_len.p, (int32_t*)d_st.p, (unsigned long long*)d_cells.p);
-      HIPCHK3(hipGetLastError());
-      HIPCHK3(hipEventRecord(ev1, s0));
-      HIPCHK3(hipStreamSynchronize(s0));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(ev1, s0));
+      HIPCHK(hipStreamSynchronize(s0));
       float ms = 0.f;
-      HIPCHK3(hipEventElapsedTime(&ms, ev0, ev1));
+      HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
       b->kernel_ms += ms;
       std::vector<int32_t> lens((size_t)nt), st((size_t)nt);
       std::vector<uint8_t> h8((size_t)w8);
-      HIPCHK3(hipMemcpyAsync(lens.data(), d_len.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-      HIPCHK3(hipMemcpyAsync(st.data(), d_st.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-      if (w8) HIPCHK3(hipMemcpyAsync(h8.data(), d8.p, (size_t)w8, hipMemcpyDeviceToHost, s0));
-      HIPCHK3(hipStreamSynchronize(s0));
+      HIPCHK(hipMemcpyAsync(lens.data(), d_len.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
+      HIPCHK(hipMemcpyAsync(st.data(), d_st.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
+      if (w8) HIPCHK(hipMemcpyAsync(h8.data(), d8.p, (size_t)w8, hipMemcpyDeviceToHost, s0));
+      HIPCHK(hipStreamSynchronize(s0));
       for (int64_t k = 0; k < nt; ++k) {
         if (st[(size_t)k] == 0) {
           const uint8_t* src = h8.data() + tasks[(size_t)k].cons_off;
@@ -852,8 +841,8 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
   (void)hipEventDestroy(ev0);
   (void)hipEventDestroy(ev1);
   unsigned long long cells = 0;
-  HIPCHK3(hipMemcpyAsync(&cells, d_cells.p, 8, hipMemcpyDeviceToHost, s0));
-  HIPCHK3(hipStreamSynchronize(s0));
+  HIPCHK(hipMemcpyAsync(&cells, d_cells.p, 8, hipMemcpyDeviceToHost, s0));
+  HIPCHK(hipStreamSynchronize(s0));
   b->cells = (int64_t)cells;
   for (int64_t c = 0; c < n_clusters; ++c) {
     b->cons_len[(size_t)c] = (int64_t)results[(size_t)c].size();

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "dev_buf.h"
 #include "fmd_layout.h"
 #include "hip_check.h"
 #include "index_host.h"
@@ -713,10 +714,7 @@ __global__ void __launch_bounds__(256) sfs_gather_kernel(SfsParams p, const int6
 
 // ------------------------------------------------------------------ batch
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
+using SfsBuf = DevBuf<3, 256>;   // grows to n + n / 8 + 256
 
 struct svdss_sfs_batch {
   int device = -1;
@@ -725,8 +723,8 @@ struct svdss_sfs_batch {
   int64_t total_ext = 0;
   double kernel_ms = 0.0;
   double search_ms = 0.0;   // the segmented / one-lane-per-read search kernel of pass 0 alone
-  DevBuf rec, counts, n_ext, out_off, out_qs, out_len, tmp, misc, reads, offsets, base2, sum;
-  DevBuf seg_rec, seg_info, fallback, fallback2, seg_take, order, order_cnt, tiny;
+  SfsBuf rec, counts, n_ext, out_off, out_qs, out_len, tmp, misc, reads, offsets, base2, sum;
+  SfsBuf seg_rec, seg_info, fallback, fallback2, seg_take, order, order_cnt, tiny;
   int64_t n_fallback = 0;   // reads of the last call that were redone unsegmented
   int32_t n_seg = 1;        // segments per read used by the last call
   int32_t used_bs = 0;      // the last call launched the BS instantiation
@@ -735,37 +733,18 @@ struct svdss_sfs_batch {
   // host-buffer entry points: the batch object's own non-blocking stream (copies in, kernels, copies out), so that
   // calls on different batch objects -- e.g. two threads feeding the GPU from a BAM file -- overlap
   hipStream_t own_stream = nullptr;
-  DevBuf packed, byte_off, lens32;   // svdss_sfs_search_batch_bam: the 4-bit bases as they sit in the BAM records
+  SfsBuf packed, byte_off, lens32;   // svdss_sfs_search_batch_bam: the 4-bit bases as they sit in the BAM records
 };
-
-static int ensure(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap && b.p) return SVDSS_OK;
-  if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-  size_t want = bytes + (bytes >> 3) + 256;
-  HIPCHK(hipMalloc(&b.p, want));
-  b.cap = want;
-  return SVDSS_OK;
-}
-
-static void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
 
 extern "C" void svdss_sfs_batch_free(svdss_sfs_batch_t* b) {
   if (!b) return;
   if (b->device >= 0) (void)hipSetDevice(b->device);
-  for (DevBuf* d : {&b->rec, &b->counts, &b->n_ext, &b->out_off, &b->out_qs, &b->out_len, &b->tmp,
-                    &b->misc, &b->reads, &b->offsets, &b->base2, &b->sum, &b->seg_rec, &b->seg_info,
-                    &b->fallback, &b->fallback2, &b->seg_take, &b->order, &b->order_cnt, &b->tiny, &b->packed, &b->byte_off, &b->lens32})
-    release(*d);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   if (b->ek0) (void)hipEventDestroy(b->ek0);
   if (b->ek1) (void)hipEventDestroy(b->ek1);
-  delete b;
+  delete b;   // (its buffers: ~DevBuf, on the device made current above)
 }
 
 extern "C" int64_t svdss_sfs_batch_nreads(const svdss_sfs_batch_t* b) { return b ? b->n_reads : -1; }
@@ -815,12 +794,12 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
 
   int rc;
   const int64_t rec_total = (total_syms >> 3) + 8 * n_reads + 16;
-  if ((rc = ensure(b->rec, (size_t)rec_total * sizeof(uint2)))) return rc;
-  if ((rc = ensure(b->counts, (size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(b->n_ext, (size_t)n_reads * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(b->out_off, (size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(b->misc, 64))) return rc;
-  if ((rc = ensure(b->sum, 64))) return rc;
+  if ((rc = b->rec.ensure((size_t)rec_total * sizeof(uint2)))) return rc;
+  if ((rc = b->counts.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = b->n_ext.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
+  if ((rc = b->out_off.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = b->misc.ensure(64))) return rc;
+  if ((rc = b->sum.ensure(64))) return rc;
 
   SfsParams p;
   p.ix = svdss_device_view(ix);
@@ -868,7 +847,7 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
 
   // (the kernel fetches a read's symbols 64 bytes at a time: a batch smaller than that is searched in a padded copy)
   if (total_syms < 64) {
-    if ((rc = ensure(b->tiny, 96))) return rc;
+    if ((rc = b->tiny.ensure(96))) return rc;
     HIPCHK(hipMemsetAsync(b->tiny.p, 0, 96, stream));
     if (total_syms > 0) HIPCHK(hipMemcpyAsync(b->tiny.p, d_reads, (size_t)total_syms, hipMemcpyDeviceToDevice, stream));
     p.chunks = (const svdss_u4*)b->tiny.p;
@@ -898,10 +877,10 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
   }
   if (n_seg > 1) {
     const int64_t seg_total = (total_syms >> 3) + (8 + 24 * (int64_t)n_seg) * n_reads + 64;
-    if ((rc = ensure(b->seg_rec, (size_t)seg_total * sizeof(uint4)))) return rc;
-    if ((rc = ensure(b->seg_info, (size_t)(n_reads * n_seg) * sizeof(SvSegInfo)))) return rc;
-    if ((rc = ensure(b->fallback, (size_t)n_reads * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(b->seg_take, (size_t)(2 * n_reads * n_seg) * sizeof(int32_t)))) return rc;
+    if ((rc = b->seg_rec.ensure((size_t)seg_total * sizeof(uint4)))) return rc;
+    if ((rc = b->seg_info.ensure((size_t)(n_reads * n_seg) * sizeof(SvSegInfo)))) return rc;
+    if ((rc = b->fallback.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
+    if ((rc = b->seg_take.ensure((size_t)(2 * n_reads * n_seg) * sizeof(int32_t)))) return rc;
     p.seg_rec = (uint4*)b->seg_rec.p;
     p.seg_info = (SvSegInfo*)b->seg_info.p;
     p.fallback_ids = (int64_t*)b->fallback.p;
@@ -923,18 +902,18 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
                                           (int)(n_reads + 1), stream));
   HIPCHK(hipcub::DeviceReduce::Sum(nullptr, tmp2, p.n_ext, (int64_t*)b->sum.p, (int)n_reads, stream));
   if (tmp2 > tmp_bytes) tmp_bytes = tmp2;
-  if ((rc = ensure(b->tmp, tmp_bytes))) return rc;
+  if ((rc = b->tmp.ensure(tmp_bytes))) return rc;
 
   // heavy reads first (see sfs_order_kernel); SVDSS_ORDER=0 keeps the input order
   const char* ord_env = getenv("SVDSS_ORDER");
   const bool use_order = n_reads >= 1024 && p.ix.k >= 8 && !(ord_env && atoi(ord_env) == 0);
   if (use_order) {
-    if ((rc = ensure(b->order, (size_t)n_reads * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(b->order_cnt, (size_t)(2 * n_reads + 2) * sizeof(int64_t)))) return rc;   // flags, their scan
+    if ((rc = b->order.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
+    if ((rc = b->order_cnt.ensure((size_t)(2 * n_reads + 2) * sizeof(int64_t)))) return rc;   // flags, their scan
     size_t t3 = 0;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (int64_t*)b->order_cnt.p, (int64_t*)b->order_cnt.p + n_reads + 1,
                                             (int)(n_reads + 1), stream));
-    if (t3 > b->tmp.cap && (rc = ensure(b->tmp, t3))) return rc;
+    if (t3 > b->tmp.cap && (rc = b->tmp.ensure(t3))) return rc;
   }
   for (int pass = 0; pass < 2; ++pass) {
     HIPCHK(hipMemsetAsync(b->misc.p, 0, 64, stream));
@@ -997,7 +976,7 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
       const unsigned long long direct = getenv("SVDSS_FALLBACK_DIRECT") ? (unsigned long long)atoll(getenv("SVDSS_FALLBACK_DIRECT")) : 64ull;
       while (n_fb > 0) {
         lvl_seg = lvl_seg / 4 < 1 || n_fb <= direct ? 1 : lvl_seg / 4;
-        if ((rc = ensure(b->fallback2, (size_t)n_fb * sizeof(int64_t)))) return rc;
+        if ((rc = b->fallback2.ensure((size_t)n_fb * sizeof(int64_t)))) return rc;
         HIPCHK(hipMemcpyAsync(b->fallback2.p, p.fallback_ids, (size_t)n_fb * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
         SfsParams q = p;
         q.read_ids = (const int64_t*)b->fallback2.p;
@@ -1053,8 +1032,8 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
                           hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (p.n_seg == 1 && getenv("SVDSS_DEBUG")) sfs_report_op_counts();
-    if ((rc = ensure(b->out_qs, (size_t)(total + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(b->out_len, (size_t)(total + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = b->out_qs.ensure((size_t)(total + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = b->out_len.ensure((size_t)(total + 1) * sizeof(int32_t)))) return rc;
     hipLaunchKernelGGL(sfs_gather_kernel, dim3(gblocks), dim3(256), 0, stream, p,
                        (const int64_t*)b->out_off.p, (int32_t*)b->out_qs.p, (int32_t*)b->out_len.p,
                        d_overflow);
@@ -1081,8 +1060,8 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
     // Some read produced more SFS than its default region holds (e.g. a read
     // of N against an N-free reference gives one SFS per base).  The counts
     // are exact, so rerun with regions sized from them.
-    if ((rc = ensure(b->rec, (size_t)(total + 1) * sizeof(uint2)))) return rc;
-    if ((rc = ensure(b->base2, (size_t)(2 * (n_reads + 1)) * sizeof(int64_t)))) return rc;
+    if ((rc = b->rec.ensure((size_t)(total + 1) * sizeof(uint2)))) return rc;
+    if ((rc = b->base2.ensure((size_t)(2 * (n_reads + 1)) * sizeof(int64_t)))) return rc;
     int64_t* base2 = (int64_t*)b->base2.p;
     int64_t* cap2 = base2 + (n_reads + 1);
     HIPCHK(hipMemcpyAsync(base2, b->out_off.p, (size_t)(n_reads + 1) * sizeof(int64_t),
@@ -1131,8 +1110,8 @@ extern "C" int svdss_sfs_search_batch(const svdss_index_t* ix, const uint8_t* re
   }
   const int64_t total = offsets[n_reads];
   const size_t padded = (size_t)((total + 15) & ~(int64_t)15) + 16;
-  if ((rc = ensure(b->reads, padded))) return rc;
-  if ((rc = ensure(b->offsets, (size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = b->reads.ensure(padded))) return rc;
+  if ((rc = b->offsets.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
   const hipStream_t st = b->own_stream;
   HIPCHK(hipMemsetAsync((uint8_t*)b->reads.p + (padded >= 32 ? padded - 32 : 0), 0, padded >= 32 ? 32 : padded, st));   // the bytes past the last read
   if (total > 0) HIPCHK(hipMemcpyAsync(b->reads.p, reads, (size_t)total, hipMemcpyHostToDevice, st));
@@ -1185,10 +1164,10 @@ extern "C" int svdss_sfs_search_batch_bam(const svdss_index_t* ix, const uint8_t
   }
   const int64_t total = sym_off[(size_t)n_reads], pbytes = byte_off[n_reads] - byte_off[0];
   const size_t padded = (size_t)((total + 15) & ~(int64_t)15) + 16;
-  if ((rc = ensure(b->reads, padded))) return rc;
-  if ((rc = ensure(b->offsets, (size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(b->byte_off, (size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(b->packed, (size_t)pbytes + 16))) return rc;
+  if ((rc = b->reads.ensure(padded))) return rc;
+  if ((rc = b->offsets.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = b->byte_off.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = b->packed.ensure((size_t)pbytes + 16))) return rc;
   const hipStream_t st = b->own_stream;
   std::vector<int64_t> rel((size_t)n_reads + 1);
   for (int64_t i = 0; i <= n_reads; ++i) rel[(size_t)i] = byte_off[i] - byte_off[0];

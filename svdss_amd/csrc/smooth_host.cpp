@@ -236,7 +236,7 @@ int main_smooth(const CallOptions& o) {
   auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
   const bool dbg = getenv("SVDSS_DEBUG") != nullptr;
   double t_read = 0, t_proc = 0, t_write = 0;
-  // ---- the device path (csrc/bam_smooth.inc): compressed blocks up, compressed blocks down; the records are filtered,
+  // ---- the device path (csrc/bam_smooth.hip): compressed blocks up, compressed blocks down; the records are filtered,
   // measured, smoothed, rebuilt and deflated in HBM.  SVDSS_BAM_DEVICE=0 (or SVDSS_SMOOTH_HOST=1): the host pipeline below,
   // which writes the same bytes.
   // (SVDSS_GPU_DEFLATE=0 asks for the host's deflate: that is the host pipeline's writer)

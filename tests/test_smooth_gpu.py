@@ -49,7 +49,7 @@ def test_gpu_and_host_smooth_write_the_same_bam(tmp_path):
 
 
 def test_device_path_writes_the_bytes_of_the_host_paths(tmp_path):
-    """Round 5: records filtered, measured, smoothed, rebuilt and deflated in HBM (csrc/bam_smooth.inc) against the host
+    """Round 5: records filtered, measured, smoothed, rebuilt and deflated in HBM (csrc/bam_smooth.hip) against the host
     pipeline with the GPU walk (SVDSS_BAM_DEVICE=0) and the host code (SVDSS_SMOOTH_HOST=1): the same bytes -- with XF tags
     already present in every integer type and as a string, records the filters drop, CIGARs that do not fit, reads on a
     contig the FASTA does not have, and device batches of one megabyte handed round six feeding threads (the output stream's

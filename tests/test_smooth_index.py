@@ -1,5 +1,5 @@
 """`SVDSS smooth --write-index FILE` (csrc/bam_index_writer.h; on the device path the fragments come from
-csrc/bam_smooth.inc): the index of the output BAM, held against the test writer's own BAI / CSI of the same bytes
+csrc/bam_smooth.hip): the index of the output BAM, held against the test writer's own BAI / CSI of the same bytes
 (tests/bam_writer.py) after every virtual offset is turned into a position of the inflated stream, and against region
 queries through the product's reader (csrc/bai_index.h) versus a sequential read."""
 import bisect

@@ -1,4 +1,4 @@
-"""`SVDSS smooth --write-index` on the device path: the index fragments reduced on the GPU (csrc/bam_smooth.inc) and folded
+"""`SVDSS smooth --write-index` on the device path: the index fragments reduced on the GPU (csrc/bam_smooth.hip) and folded
 on the host give the bytes the host paths give, batch size and carried blocks notwithstanding; with --gpus N (regions, other
 member cuts) each run's index describes its own output."""
 import os
