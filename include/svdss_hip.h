@@ -204,10 +204,18 @@ void svdss_inflate_free(svdss_inflate_t* obj);
  * level-1-class encoder for packed bases and qualities; incompressible quarters are stored), and 8 bytes LEFT FOR THE CALLER to fill with CRC32 and ISIZE; out_len[i] = the member's length with
  * those 8 bytes.  out_stride 0: the members are written back to back instead (out needs in_bytes + 64 per block).
  * Any inflater reads the result; it is not the byte stream zlib would write.  Returns when done (the
- * object's own stream: calls on different objects overlap). */
+ * object's own stream: calls on different objects overlap).
+ * svdss_bgzf_deflate_mode: the same with the encoder's mode.  SVDSS_DEFLATE_RUNS (0) is svdss_bgzf_deflate, byte for
+ * byte.  SVDSS_DEFLATE_LZ (1) adds general matches (length 4..258, distance 1..32768, never in front of the member's own
+ * first byte; a distance code of its own per quarter): what a coordinate-sorted BAM repeats from one overlapping read to
+ * the next, a record (~22 KB) back.  A match finder kernel runs in front of the coder; the container is the same. */
 typedef struct svdss_deflate svdss_deflate_t;
+#define SVDSS_DEFLATE_RUNS 0
+#define SVDSS_DEFLATE_LZ 1
 int svdss_bgzf_deflate(svdss_deflate_t** obj, int32_t device, const uint8_t* in, int64_t in_bytes, int32_t block_bytes,
                        uint8_t* out, int64_t out_stride, int32_t* out_len);
+int svdss_bgzf_deflate_mode(svdss_deflate_t** obj, int32_t device, const uint8_t* in, int64_t in_bytes, int32_t block_bytes,
+                            uint8_t* out, int64_t out_stride, int32_t* out_len, int32_t mode);
 double svdss_deflate_kernel_ms(const svdss_deflate_t* obj);
 void svdss_deflate_free(svdss_deflate_t* obj);
 /* plain device memory for the callers of the entry points that take device pointers */
@@ -459,6 +467,10 @@ typedef struct svdss_bam_index_frag {
   int64_t first_beg, last_beg;
 } svdss_bam_index_frag_t;
 int svdss_bam_smooth_set_index(svdss_bam_smooth_t* sm, int32_t min_shift, int32_t depth);
+/* `smooth --compress`: every later svdss_bam_smooth_run on sm deflates its BGZF members in this mode (SVDSS_DEFLATE_RUNS,
+ * the default, or SVDSS_DEFLATE_LZ; see svdss_bgzf_deflate_mode).  The records, the members' inflated bytes and the index
+ * fragments' offsets inside a block do not depend on it; the compressed offsets follow the members' lengths. */
+int svdss_bam_smooth_set_deflate(svdss_bam_smooth_t* sm, int32_t mode);
 int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* out);
 const char* svdss_bam_batch_error(const svdss_bam_batch_t* b);
 void svdss_bam_batch_free(svdss_bam_batch_t* b);

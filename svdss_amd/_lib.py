@@ -80,6 +80,7 @@ SIGNATURES = {
     "svdss_inflate_kernel_ms": (C.c_double, [_p]),
     "svdss_inflate_free": (None, [_p]),
     "svdss_bgzf_deflate": (C.c_int, [C.POINTER(_p), _i32, _p, _i64, _i32, _p, _i64, _p]),
+    "svdss_bgzf_deflate_mode": (C.c_int, [C.POINTER(_p), _i32, _p, _i64, _i32, _p, _i64, _p, _i32]),
     "svdss_deflate_kernel_ms": (C.c_double, [_p]),
     "svdss_deflate_free": (None, [_p]),
     "svdss_device_alloc": (C.c_int, [_i32, _i64, C.POINTER(_p)]),
@@ -130,6 +131,7 @@ SIGNATURES = {
     "svdss_bam_smooth_run": (C.c_int, [_p, _i64, C.c_int32, _i64, _p, C.c_double, _p, _i64, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "svdss_bam_batch_smoothed": (C.c_int, [_p, _p]),
     "svdss_bam_smooth_set_index": (C.c_int, [_p, C.c_int32, C.c_int32]),
+    "svdss_bam_smooth_set_deflate": (C.c_int, [_p, C.c_int32]),
     "svdss_bam_batch_index": (C.c_int, [_p, _p]),
     "svdss_bam_batch_error": (C.c_char_p, [_p]),
     "svdss_bam_filter_create": (C.c_int, [_i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _i64, C.POINTER(_p)]),

@@ -67,11 +67,13 @@ def gpu_inflate(data, blocks, device=0, uoff=None):
     return out[:total]
 
 
-def gpu_deflate(data, block_bytes=0xff00, device=0, return_stats=False, dense=False):
+def gpu_deflate(data, block_bytes=0xff00, device=0, return_stats=False, dense=False, mode=0):
     """BGZF members written by the GPU encoder (svdss_bgzf_deflate, csrc/deflate.hip) for `data` cut into blocks of
     block_bytes; the CRC32 / ISIZE footers are filled in here, as the binary's writer does (csrc/bam_writer.h).
     Returns the concatenated members (bytes) -- a valid BGZF stream without the EOF marker block.  dense: the library
-    writes the members back to back itself (out_stride 0, what the binary's writer asks for) instead of one per stride."""
+    writes the members back to back itself (out_stride 0, what the binary's writer asks for) instead of one per stride.
+    mode: 0 literals and runs (svdss_bgzf_deflate itself), 1 also matches between overlapping reads
+    (svdss_bgzf_deflate_mode, `smooth --compress lz`)."""
     import ctypes as C
     import zlib
     import numpy as np
@@ -86,8 +88,12 @@ def gpu_deflate(data, block_bytes=0xff00, device=0, return_stats=False, dense=Fa
     lens = np.zeros(nb, dtype=np.int32)
     obj = C.c_void_p()
     try:
-        check(lib.svdss_bgzf_deflate(C.byref(obj), device, raw.ctypes.data, n, block_bytes, out.ctypes.data, stride,
-                                     lens.ctypes.data), "svdss_bgzf_deflate")
+        if mode == 0:
+            check(lib.svdss_bgzf_deflate(C.byref(obj), device, raw.ctypes.data, n, block_bytes, out.ctypes.data, stride,
+                                         lens.ctypes.data), "svdss_bgzf_deflate")
+        else:
+            check(lib.svdss_bgzf_deflate_mode(C.byref(obj), device, raw.ctypes.data, n, block_bytes, out.ctypes.data, stride,
+                                              lens.ctypes.data, mode), "svdss_bgzf_deflate_mode")
         ms = lib.svdss_deflate_kernel_ms(obj)
     finally:
         lib.svdss_deflate_free(obj)

@@ -182,6 +182,7 @@ struct svdss_bam_batch {
   // svdss_bam_smooth_run / _measure (bam_smooth.hip)
   struct {
     BamBuf rec, out, scratch, members, dense, len;
+    BamBuf lz;   // the match finder's candidates (svdss_bam_smooth_set_deflate: lz mode only)
     int64_t kept = 0, out_bytes = 0, bgzf_bytes = 0, in0 = 0, xf[4] = {0, 0, 0, 0};
     const uint8_t* bgzf = nullptr;   // where the last run's BGZF members are (the caller's buffer or sel.host)
     std::vector<int64_t> nmx;

@@ -543,6 +543,7 @@ struct svdss_bam_smooth {
   int device = -1;
   int32_t min_mapq = 0, n_ref = 0;
   int32_t ix_shift = 0, ix_depth = 0;   // svdss_bam_smooth_set_index (0: no index fragments)
+  int32_t deflate_mode = SVDSS_DEFLATE_RUNS;   // svdss_bam_smooth_set_deflate
   SvdssRefView ref;
   int32_t* d_tidmap = nullptr;
 };
@@ -580,6 +581,12 @@ extern "C" int svdss_bam_smooth_set_index(svdss_bam_smooth_t* sm, int32_t min_sh
   if (!sm || min_shift < 0 || (min_shift > 0 && (depth < 1 || depth > 10 || min_shift + 3 * depth > 48))) return SVDSS_EINVAL;
   sm->ix_shift = min_shift;
   sm->ix_depth = min_shift > 0 ? depth : 0;
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_bam_smooth_set_deflate(svdss_bam_smooth_t* sm, int32_t mode) {
+  if (!sm || (mode != SVDSS_DEFLATE_RUNS && mode != SVDSS_DEFLATE_LZ)) return SVDSS_EINVAL;
+  sm->deflate_mode = mode;
   return SVDSS_OK;
 }
 
@@ -750,7 +757,10 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     d_off_out = d_off;
     const uint8_t* d_in = (const uint8_t*)b->sm.out.p + b->sm.in0;
     BCHK(hipMemsetAsync(b->sm.members.p, 0, (size_t)(n_blk * stride), st));
-    BCHK(svdss_deflate_enqueue(st, d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm.members.p, stride, d_len));
+    const size_t lz_bytes = (size_t)svdss_deflate_scratch_bytes(in_len, (int32_t)kBgzfBlock, sm->deflate_mode);
+    if (lz_bytes) RCHK(b->sm.lz.ensure(lz_bytes));
+    BCHK(svdss_deflate_enqueue_mode(st, d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm.members.p, stride, d_len, sm->deflate_mode,
+                                    lz_bytes ? b->sm.lz.p : nullptr));
     BCHK(crc_tables_ready());
     FootP Fp{d_in, in_len, (int32_t)kBgzfBlock, (uint8_t*)b->sm.members.p, stride, d_len};
     hipLaunchKernelGGL(bgzf_footer_kernel, dim3((unsigned)n_blk), dim3(64), 0, st, Fp);

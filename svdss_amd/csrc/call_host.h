@@ -12,6 +12,7 @@ struct CallOptions {
   float min_ratio = 0.97f;
   float accp = 0.98f;          // smooth only
   std::string write_index;     // smooth only: --write-index <FILE>, the output's BAI / CSI (bam_index_writer.h)
+  int compress = 0;            // smooth only: --compress runs|lz, the GPU deflate's mode (0 runs, 1 lz; csrc/deflate.hip)
   bool verbose = false;         // stage timings on stderr
   int gpus = 1;                 // --gpus N: POA / realignment batches shard by sub-cluster index
   std::string poa;             // --poa <FILE>: consensus alignments as SAM (caller.cpp:65-75)

@@ -17,7 +17,27 @@
 // for the distance; a lane finds the runs of its own slice alone (dwords whose bytes equal the byte in front of them,
 // even across the slice's start), so the three passes over a slice (count, size, pack) see the same tokens without
 // storing them.
-// No general LZ77: BGZF members are independent 64 KB streams, and bases and qualities do not repeat inside one.
+// TWO MODES (svdss_bgzf_deflate_mode; `smooth --compress runs|lz`).  Mode 0, runs, is what is described above and
+// below: bases and qualities do not repeat inside ONE read.  Mode 1, lz, adds general matches (length 4..258, distance
+// 1..32768, never in front of byte 0 of the member -- members stay independent streams --, free to reach into an
+// earlier deflate block of the member): in a coordinate-sorted BAM at depth consecutive records overlap almost entirely,
+// their packed bases are byte-aligned whenever the two start positions have the same parity, and the copy sits one
+// record (~22 KB) back, inside deflate's window and inside the member.  Mode 1 is two kernels:
+//   * bgzf_lz_find_kernel, 256 threads per member: positions in chunks of 2,048 -- all look up a 16 K-entry head table
+//     (8-byte hash; 64 KB of LDS, two members per CU) that holds positions of earlier chunks, the largest per slot
+//     (atomicMax: the same table in whatever order lanes arrive), verify the 8 bytes, then the chunk's even positions
+//     are inserted.  One verified distance per group of four positions goes to a scratch array (a byte per input byte);
+//   * bgzf_deflate_lz_kernel, one wavefront per member like mode 0: a lane parses its 1/64 of the quarter greedily,
+//     once -- longest of a run, the distance of its last match (behind a match's end and behind a substituted base the
+//     same distance goes on, so one hit at the start of an overlap is enough) and the finder's candidate -- and leaves
+//     the matches in LDS, one word per four positions, for the size and pack passes; the 30 distance codes get a
+//     Huffman code of their own from the same rank / merge / fold machinery (HDIST = the highest code in use, at least
+//     two codes so that the code is complete).  157 VGPRs, 39,340 B of LDS, no scratch: four members per CU (mode 0:
+//     seven by LDS); the finder 20 VGPRs, no scratch.
+// Why two kernels and a head table in LDS: with the member and the heads both in LDS (128 KB) a CU holds one
+// workgroup, and the coder's passes are one-wavefront work; split, the finder runs 8 wavefronts per CU on the table
+// alone and the coder keeps its quarter-block staging, both reading the bytes a match is verified against from L2.
+// Measured: profiles/ (deflate_lz_*), DESIGN.md sections 4c and 7.0.  Mode 0's kernel and output are untouched.
 //   * the quarter block is staged in LDS (coalesced loads), every lane counts the bytes of its 1/64 of it (LDS atomics);
 //   * the 286 symbols (literals, end of block, length codes) are ranked by (count, symbol) -- every lane ranks its symbols against
 //     all others with broadcast LDS reads --, one lane runs the two-queue Huffman merge over the sorted leaves, turns
@@ -136,31 +156,34 @@ __device__ __forceinline__ void put_bits_atomic(uint32_t* w, int64_t pos, uint32
   if (sh + nbits > 32) atomicOr(&w[(pos >> 5) + 1], (uint32_t)(x >> 32));
 }
 
-// Huffman code lengths (1..15) of the symbols with a non-zero count; one lane, everything in LDS.
-__device__ void build_lengths(Lds& S) {
-  const int n = S.n_used;
-  for (int s = 0; s < NSYM; ++s) S.len[s] = 0;
-  if (n == 1) { S.len[S.order[0]] = 1; return; }        // (cannot happen: the end-of-block symbol is always counted)
+// Huffman code lengths (1..15) of the symbols with a non-zero count, for an alphabet of NS symbols (the literal / length
+// alphabet; in lz mode the 30 distance codes too); one lane, everything in LDS.  n = symbols with a non-zero count,
+// order = those symbols, rarest first; weight / parent / depth: work space of 2 * NS entries (enc may lie over weight);
+// bl (40 entries) and next_code (16): the counts per length and the canonical codes' counters, wherever the caller has room.
+template <int NS>
+__device__ __forceinline__ void build_code(int n, const uint32_t* freq, const uint16_t* order, uint32_t* weight, uint16_t* parent,
+                                           uint8_t* depth, uint8_t* len, uint32_t* enc, int* bl, uint32_t* next_code) {
+  for (int s = 0; s < NS; ++s) len[s] = 0;
+  if (n == 1) { len[order[0]] = 1; return; }        // (cannot happen: the end-of-block symbol is always counted)
   // two-queue merge: leaves 0..n-1 in ascending count, internal nodes n.. in creation order (their weights ascend too)
-  for (int i = 0; i < n; ++i) S.weight[i] = S.freq[S.order[i]];
+  for (int i = 0; i < n; ++i) weight[i] = freq[order[i]];
   int li = 0, ii = n, next = n;
   for (int k = 0; k < n - 1; ++k) {
     int a, b;
-    if (li < n && (ii >= next || S.weight[li] <= S.weight[ii])) a = li++; else a = ii++;
-    if (li < n && (ii >= next || S.weight[li] <= S.weight[ii])) b = li++; else b = ii++;
-    S.weight[next] = S.weight[a] + S.weight[b];
-    S.parent[a] = (uint16_t)next;
-    S.parent[b] = (uint16_t)next;
+    if (li < n && (ii >= next || weight[li] <= weight[ii])) a = li++; else a = ii++;
+    if (li < n && (ii >= next || weight[li] <= weight[ii])) b = li++; else b = ii++;
+    weight[next] = weight[a] + weight[b];
+    parent[a] = (uint16_t)next;
+    parent[b] = (uint16_t)next;
     ++next;
   }
-  int bl[40];
   for (int b = 0; b < 40; ++b) bl[b] = 0;
-  S.depth[next - 1] = 0;
+  depth[next - 1] = 0;
   int overflow = 0;
   for (int i = next - 2; i >= 0; --i) {
-    int d = S.depth[S.parent[i]] + 1;
+    int d = depth[parent[i]] + 1;
     if (d > 39) d = 39;
-    S.depth[i] = (uint8_t)d;
+    depth[i] = (uint8_t)d;
     if (i < n) {
       if (d > 15) { ++overflow; d = 15; }
       ++bl[d];
@@ -179,21 +202,26 @@ __device__ void build_lengths(Lds& S) {
   // longest codes to the rarest symbols
   int i = 0;
   for (int bits = 15; bits >= 1; --bits)
-    for (int c = bl[bits]; c > 0; --c) S.len[S.order[i++]] = (uint8_t)bits;
+    for (int c = bl[bits]; c > 0; --c) len[order[i++]] = (uint8_t)bits;
   // canonical codes (RFC 1951 3.2.2), stored reversed: deflate packs Huffman codes most significant bit first
-  uint32_t next_code[16];
   uint32_t code = 0;
   bl[0] = 0;
   for (int bits = 1; bits <= 15; ++bits) {
     code = (code + (uint32_t)bl[bits - 1]) << 1;
     next_code[bits] = code;
   }
-  for (int s = 0; s < NSYM; ++s) {
-    const int l = S.len[s];
-    if (!l) { S.enc[s] = 0; continue; }
+  for (int s = 0; s < NS; ++s) {
+    const int l = len[s];
+    if (!l) { enc[s] = 0; continue; }
     const uint32_t c = next_code[l]++;
-    S.enc[s] = (__builtin_bitreverse32(c) >> (32 - l)) | ((uint32_t)l << 16);
+    enc[s] = (__builtin_bitreverse32(c) >> (32 - l)) | ((uint32_t)l << 16);
   }
+}
+
+__device__ void build_lengths(Lds& S) {
+  int bl[40];
+  uint32_t next_code[16];
+  build_code<NSYM>(S.n_used, S.freq, S.order, S.weight, S.parent, S.depth, S.len, S.enc, bl, next_code);
 }
 
 __global__ void __launch_bounds__(64) bgzf_deflate_kernel(const uint8_t* in, int64_t in_bytes, int32_t block_bytes,
@@ -352,6 +380,348 @@ __global__ void __launch_bounds__(64) bgzf_deflate_kernel(const uint8_t* in, int
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// mode 1 (lz): literals, runs and GENERAL MATCHES (length 4..258, distance 1..32768, never in front of byte 0 of the
+// member).  Two kernels (see the header comment): bgzf_lz_find_kernel leaves one verified candidate per group of four
+// positions in a scratch array, bgzf_deflate_lz_kernel parses and codes.
+
+constexpr int NDSYM = 30;                  // distance codes (RFC 1951 3.2.5)
+constexpr int LZ_MAX_LEN = 258;
+constexpr int LZ_MIN_LEN = 8;              // a match at a distance > 1: a distance code and up to 13 extra bits must pay
+constexpr int LZ_MIN_RUN = 4;              // distance 1, as in runs mode
+constexpr int LZ_MAX_DIST = 32768;
+constexpr int LZ_HASH_BITS = 14;
+constexpr int LZ_FIND_THREADS = 256;
+constexpr int LZ_CHUNK_GROUPS = 2 * LZ_FIND_THREADS;   // 2,048 positions: looked up together, then inserted together
+constexpr int LZ_DROP_AFTER = 16;          // literals in a row after which the last distance is no longer tried
+constexpr int LZ_CAND_WORDS = MAX_IN / 4;  // scratch words per member: one per four positions
+
+__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
+
+// Candidates.  Positions are taken in chunks of 2,048: every position of the chunk hashes its 8 bytes and looks up the
+// head table -- which holds positions of EARLIER chunks only, the largest one per slot (atomicMax: the same table whatever
+// the order the lanes arrive in) --, verifies the 8 bytes and keeps the distance; then the chunk's even positions are
+// inserted.  Matches closer than a chunk are not found here (distance 1 is the coder's own business); 8 bytes that are
+// one byte repeated are neither looked up nor inserted (a run of 15,000 x 0xff would hammer one slot).  One thread owns
+// a group of four positions and keeps the first hit: cand[group] = offset in the group << 16 | distance, 0 for none --
+// the coder tries a match's distance again behind its end, so one hit at the start of an overlap is all it needs.
+__global__ void __launch_bounds__(LZ_FIND_THREADS) bgzf_lz_find_kernel(const uint8_t* in, int64_t in_bytes, int32_t block_bytes,
+                                                                       uint32_t* cand) {
+  __shared__ uint32_t head[1 << LZ_HASH_BITS];   // position + 1 (0: empty)
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int64_t start = b * (int64_t)block_bytes;
+  const int n = (int)(in_bytes - start < block_bytes ? in_bytes - start : block_bytes);
+  const uint8_t* mem = in + start;
+  uint32_t* cd = cand + b * LZ_CAND_WORDS;
+  for (int i = tid; i < (1 << LZ_HASH_BITS); i += LZ_FIND_THREADS) head[i] = 0;
+  __syncthreads();
+  const int ngroups = (n + 3) >> 2;
+  for (int g0 = 0; g0 < ngroups; g0 += LZ_CHUNK_GROUPS) {
+    uint32_t hs[2][4];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int g = g0 + k * LZ_FIND_THREADS + tid;
+      uint32_t entry = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) hs[k][j] = 0xffffffffu;
+      if (g < ngroups) {
+        // (a group's 11 bytes end at most 11 bytes behind the member: inside the 16 bytes of slack of the input)
+        const uint32_t w0 = ld32(mem + 4 * g), w1 = ld32(mem + 4 * g + 4), w2 = ld32(mem + 4 * g + 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int P = 4 * g + j;
+          const uint32_t lo = j ? __builtin_amdgcn_alignbyte(w1, w0, j) : w0, hi = j ? __builtin_amdgcn_alignbyte(w2, w1, j) : w1;
+          const bool one_byte = lo == hi && lo == ((lo >> 8) | (lo << 24));
+          if (P + 8 > n || one_byte) continue;
+          const uint64_t v = (uint64_t)lo | ((uint64_t)hi << 32);
+          const uint32_t h = (uint32_t)((v * 0x9E3779B97F4A7C15ull) >> (64 - LZ_HASH_BITS));
+          hs[k][j] = h;
+          if (entry) continue;
+          const uint32_t c1 = head[h];
+          if (!c1) continue;
+          const int d = P - (int)(c1 - 1);
+          if (d > LZ_MAX_DIST) continue;
+          if (ld64(mem + (c1 - 1)) == v) entry = ((uint32_t)j << 16) | (uint32_t)d;
+        }
+        cd[g] = entry;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; j += 2)
+        if (hs[k][j] != 0xffffffffu) atomicMax(&head[hs[k][j]], (uint32_t)(4 * (g0 + k * LZ_FIND_THREADS + tid) + j + 1));
+    __syncthreads();
+  }
+}
+
+struct LdsLz {
+  Lds L;                                // the literal / length alphabet, as in runs mode
+  uint32_t tok[MAX_SUB / 4 + 8];        // per group of four positions: the finder's candidate, then the match that starts there
+  uint32_t dfreq[NDSYM + 2];
+  uint32_t denc[NDSYM + 2];
+  uint16_t dorder[NDSYM + 2];
+  uint8_t dlen[NDSYM + 2];
+  int32_t dn_used, ndist;
+  int bl[40];                           // build_code's counters: in LDS, the kernel has no scratch
+  uint32_t next_code[16];
+};
+constexpr uint32_t TOK_MATCH = 0x80000000u;   // tok: this bit | offset in the group << 29 | length << 16 | distance - 1
+
+__device__ __forceinline__ int lz_len_symbol(int len, int& ebits, int& eval) {
+  if (len == 258) { ebits = 0; eval = 0; return 285; }
+  return len_symbol(len, ebits, eval);
+}
+// distance 1..32768 -> its distance code (0..29), the number of extra bits and their value
+__device__ __forceinline__ int dist_symbol(int d, int& ebits, int& eval) {
+  const int x = d - 1;
+  ebits = 0; eval = 0;
+  if (x < 4) return x;
+  const int e = (31 - __builtin_clz((unsigned)x)) - 1;
+  ebits = e;
+  eval = x & ((1 << e) - 1);
+  return 2 * e + 2 + ((x >> e) & 1);
+}
+
+// bytes that mem[P ..] and mem[P - d ..] have in common, maxlen at most (reads up to 7 bytes behind P + maxlen)
+__device__ __forceinline__ int match_len(const uint8_t* mem, int P, int d, int maxlen) {
+  int L = 0;
+  while (L < maxlen) {
+    const uint64_t x = ld64(mem + P + L) ^ ld64(mem + P - d + L);
+    if (x) { L += __builtin_ctzll(x) >> 3; break; }
+    L += 8;
+  }
+  return L < maxlen ? L : maxlen;
+}
+
+// the tokens of the slice [c0, c1) as the parse left them in tok[]
+template <class FL, class FM>
+__device__ __forceinline__ void for_lz_tokens(const uint8_t* sb, const uint32_t* tok, int c0, int c1, FL&& lit, FM&& match) {
+  int p = c0;
+  while (p < c1) {
+    const uint32_t g = tok[p >> 2];
+    if ((g & TOK_MATCH) && (int)((g >> 29) & 3u) == (p & 3)) {
+      const int len = (int)((g >> 16) & 0x1ffu);
+      match(len, (int)(g & 0x7fffu) + 1);
+      p += len;
+    } else {
+      lit((uint32_t)sb[p]);
+      ++p;
+    }
+  }
+}
+
+// One wavefront per member, as in runs mode; the quarters are whole dwords here (the candidates come per four positions).
+// A lane parses its 1/64 of the quarter greedily, ONCE, and leaves the matches in tok[] for the two passes that follow:
+// at a position it takes the longest of a run (distance 1, 4 bytes or more), the distance of its last match (8 or more:
+// behind a match's end and behind a substituted base the same distance goes on) and the finder's candidate (8 or more);
+// a match ends at the slice's end at the latest.  The bytes a match is compared with come from the input in HBM / L2 --
+// they may lie in an earlier quarter --, the literals from the staged quarter.
+__global__ void __launch_bounds__(64) bgzf_deflate_lz_kernel(const uint8_t* in, int64_t in_bytes, int32_t block_bytes,
+                                                            uint8_t* out, int64_t out_stride, int32_t* out_len, const uint32_t* cand) {
+  __shared__ LdsLz Z;
+  Lds& S = Z.L;
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int64_t start = b * (int64_t)block_bytes;
+  const int n = (int)(in_bytes - start < block_bytes ? in_bytes - start : block_bytes);
+  const uint8_t* mem = in + start;
+  const uint32_t* cd = cand + b * LZ_CAND_WORDS;
+  uint8_t* const ob = out + b * out_stride;
+  uint32_t* const ow = (uint32_t*)ob;
+  int64_t bitpos = 18 * 8;
+  const int base = ((n + SUBS - 1) / SUBS + 3) & ~3;
+  int prev_last = -1;
+  for (int s0 = 0; s0 < n; s0 += base) {
+    const int m = UNI(n - s0 < base ? n - s0 : base);
+    const bool final_sub = s0 + m >= n;
+    const uint8_t* src = mem + s0;
+    // ---- stage the bytes and the candidates
+    for (int w = lane; w < (m + 3) / 4; w += 64) {
+      S.in[w] = ld32(src + 4 * w);
+      Z.tok[w] = cd[(s0 >> 2) + w];
+    }
+    for (int t = lane; t < NSYM + 6; t += 64) S.freq[t] = 0;
+    if (lane < NDSYM + 2) Z.dfreq[lane] = 0;
+    __syncthreads();
+    const uint8_t* sb = (const uint8_t*)S.in;
+    const int cl = ((m + 63) / 64 + 3) & ~3;
+    const int c0 = lane * cl, c1 = c0 + cl < m ? c0 + cl : m;
+    // ---- parse + count
+    {
+      int p = c0, last_d = 0, lits = 0;
+      while (p < c1) {
+        const int P = s0 + p;
+        const int maxlen = c1 - p < LZ_MAX_LEN ? c1 - p : LZ_MAX_LEN;
+        int bl = 0, bd = 0;
+        if (maxlen >= LZ_MIN_RUN) {
+          const int pb = p > 0 ? (int)sb[p - 1] : prev_last;
+          const uint32_t cur = __builtin_amdgcn_alignbyte(S.in[(p >> 2) + 1], S.in[p >> 2], p & 3);
+          if (pb >= 0 && cur == (uint32_t)pb * 0x01010101u) { bl = match_len(mem, P, 1, maxlen); bd = 1; }
+          if (bl < maxlen && maxlen >= LZ_MIN_LEN) {
+            if (last_d > 1) {
+              const int L = match_len(mem, P, last_d, maxlen);
+              if (L >= LZ_MIN_LEN && L > bl) { bl = L; bd = last_d; }
+            }
+            const uint32_t g = Z.tok[p >> 2];
+            const int d = (int)(g & 0xffffu);
+            if (bl < LZ_MIN_LEN && d > 1 && d != last_d && (int)(g >> 16) == (p & 3)) {
+              const int L = match_len(mem, P, d, maxlen);
+              if (L >= LZ_MIN_LEN && L > bl) { bl = L; bd = d; }
+            }
+          }
+        }
+        if (bl >= LZ_MIN_RUN) {
+          int eb, ev;
+          Z.tok[p >> 2] = TOK_MATCH | ((uint32_t)(p & 3) << 29) | ((uint32_t)bl << 16) | (uint32_t)(bd - 1);
+          atomicAdd(&S.freq[lz_len_symbol(bl, eb, ev)], 1u);
+          atomicAdd(&Z.dfreq[dist_symbol(bd, eb, ev)], 1u);
+          p += bl;
+          if (bd > 1) last_d = bd;
+          lits = 0;
+        } else {
+          atomicAdd(&S.freq[sb[p]], 1u);
+          ++p;
+          if (++lits >= LZ_DROP_AFTER) last_d = 0;
+        }
+      }
+    }
+    if (lane == 0) S.freq[256] = 1;
+    __syncthreads();
+    // ---- the distance code is always a complete one: at least two codes in use (as runs mode's two one-bit codes)
+    if (lane == 0) {
+      int used = 0, top = 1;
+      for (int t = 0; t < NDSYM; ++t)
+        if (Z.dfreq[t]) { ++used; top = t; }
+      if (used < 2 && !Z.dfreq[0]) { Z.dfreq[0] = 1; ++used; }
+      if (used < 2) { Z.dfreq[1] = 1; ++used; }
+      Z.dn_used = used;
+      Z.ndist = top + 1 < 2 ? 2 : top + 1;
+    }
+    __syncthreads();
+    // ---- both alphabets ranked by (count, symbol), zero counts left out
+    {
+      int used = 0;
+      for (int t0 = 0; t0 < NSYM; t0 += 64) {
+        const int t = t0 + lane;
+        const uint32_t f = t < NSYM ? S.freq[t] : 0;
+        int rank = 0;
+        if (f) {
+          for (int u = 0; u < NSYM; ++u) {
+            const uint32_t g = S.freq[u];
+            rank += (g != 0 && (g < f || (g == f && u < t))) ? 1 : 0;
+          }
+          S.order[rank] = (uint16_t)t;
+        }
+        used += (int)__popcll(__ballot(f != 0));
+      }
+      if (lane == 0) S.n_used = used;
+      const uint32_t f = lane < NDSYM ? Z.dfreq[lane] : 0;
+      if (f) {
+        int rank = 0;
+        for (int u = 0; u < NDSYM; ++u) {
+          const uint32_t g = Z.dfreq[u];
+          rank += (g != 0 && (g < f || (g == f && u < lane))) ? 1 : 0;
+        }
+        Z.dorder[rank] = (uint16_t)lane;
+      }
+    }
+    __syncthreads();
+    if (lane == 0) {   // (the distance code first: it borrows the work space that the literal codes end up in)
+      build_code<NDSYM>(Z.dn_used, Z.dfreq, Z.dorder, S.weight, S.parent, S.depth, Z.dlen, Z.denc, Z.bl, Z.next_code);
+      build_code<NSYM>(S.n_used, S.freq, S.order, S.weight, S.parent, S.depth, S.len, S.enc, Z.bl, Z.next_code);
+    }
+    __syncthreads();
+    // ---- sizes
+    int my_bits = 0;
+    for_lz_tokens(sb, Z.tok, c0, c1,
+                  [&](uint32_t v) { my_bits += (int)(S.enc[v] >> 16); },
+                  [&](int len, int d) {
+                    int eb, ev, db, dv;
+                    my_bits += (int)(S.enc[lz_len_symbol(len, eb, ev)] >> 16) + eb;
+                    my_bits += (int)(Z.denc[dist_symbol(d, db, dv)] >> 16) + db;
+                  });
+    const int incl = wave_scan_add(my_bits);
+    const int body_bits = __builtin_amdgcn_readlane(incl, 63);
+    const int eob = (int)S.enc[256];
+    const int ndist = UNI(Z.ndist);
+    const int hdr_bits = 3 + 5 + 5 + 4 + 19 * 3 + (NSYM + ndist) * 4;
+    const int total_bits = hdr_bits + body_bits + (eob >> 16);
+    if (total_bits > 8 * (m + 5)) {
+      // ---- stored (later matches may still reach into it: the window is the inflated bytes)
+      if (lane == 0) put_bits_atomic(ow, bitpos, final_sub ? 1u : 0u, 3);
+      const int64_t byte0 = (bitpos + 3 + 7) >> 3;
+      if (lane == 0) {
+        ob[byte0] = (uint8_t)(m & 0xff); ob[byte0 + 1] = (uint8_t)(m >> 8);
+        ob[byte0 + 2] = (uint8_t)(~m & 0xff); ob[byte0 + 3] = (uint8_t)((~m >> 8) & 0xff);
+      }
+      for (int i = lane; i < m; i += 64) ob[byte0 + 4 + i] = sb[i];
+      bitpos = (byte0 + 4 + m) * 8;
+    } else {
+      // ---- header: as runs mode's, with HDIST = the highest distance code in use
+      if (lane == 0) {
+        int64_t p = bitpos;
+        put_bits_atomic(ow, p, (final_sub ? 1u : 0u) | (2u << 1), 3); p += 3;
+        put_bits_atomic(ow, p, (uint32_t)(NSYM - 257), 5); p += 5;
+        put_bits_atomic(ow, p, (uint32_t)(ndist - 1), 5); p += 5;
+        put_bits_atomic(ow, p, 15u, 4); p += 4;
+        for (int k = 0; k < 19; ++k) { put_bits_atomic(ow, p, k < 3 ? 0u : 4u, 3); p += 3; }
+        for (int t = 0; t < NSYM + ndist; ++t) {
+          const uint32_t v = t < NSYM ? S.len[t] : Z.dlen[t - NSYM];
+          put_bits_atomic(ow, p, __builtin_bitreverse32(v) >> 28, 4);
+          p += 4;
+        }
+      }
+      // ---- body
+      int64_t p = bitpos + hdr_bits + (incl - my_bits);
+      if (c1 > c0 || lane == 63) {
+        uint64_t acc = 0;
+        int have = (int)(p & 31);
+        int64_t w = p >> 5;
+        bool first = true;
+        auto flush = [&](bool last) {
+          const uint32_t v = (uint32_t)acc;
+          if (first || last) atomicOr(&ow[w], v); else ow[w] = v;
+          first = false;
+          acc >>= 32; have -= 32; ++w;
+        };
+        auto put = [&](uint32_t v, int nbits) {      // at most 15 bits at a time: have stays below 64
+          acc |= (uint64_t)v << have;
+          have += nbits;
+          if (have >= 32) flush(false);
+        };
+        for_lz_tokens(sb, Z.tok, c0, c1,
+                      [&](uint32_t v) { const uint32_t e = S.enc[v]; put(e & 0xffffu, (int)(e >> 16)); },
+                      [&](int len, int d) {
+                        int eb, ev, db, dv;
+                        const uint32_t e = S.enc[lz_len_symbol(len, eb, ev)];
+                        put(e & 0xffffu, (int)(e >> 16));
+                        put((uint32_t)ev, eb);
+                        const uint32_t f = Z.denc[dist_symbol(d, db, dv)];
+                        put(f & 0xffffu, (int)(f >> 16));
+                        put((uint32_t)dv, db);
+                      });
+        if (lane == 63) put((uint32_t)eob & 0xffffu, eob >> 16);
+        if (have > 0) flush(true);
+      }
+      bitpos += total_bits;
+    }
+    prev_last = (int)sb[m - 1];
+    __syncthreads();
+  }
+  if (lane == 0) {
+    const int clen = n > 0 ? (int)((bitpos - 18 * 8 + 7) >> 3) : 0;
+    const uint8_t hdr[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+    for (int i = 0; i < 16; ++i) ob[i] = hdr[i];
+    const int bsize = clen + 25;
+    ob[16] = (uint8_t)(bsize & 0xff); ob[17] = (uint8_t)(bsize >> 8);
+    out_len[b] = clen + 26;
+  }
+}
+
 // exclusive prefix sum of the members' lengths (one wavefront; a launch has a few thousand blocks at most)
 __global__ void __launch_bounds__(64) deflate_offsets_kernel(const int32_t* len, int64_t nb, int64_t* off) {
   const int lane = threadIdx.x;
@@ -400,6 +770,23 @@ hipError_t svdss_deflate_enqueue(hipStream_t st, const uint8_t* d_in, int64_t in
   return hipGetLastError();
 }
 
+int64_t svdss_deflate_scratch_bytes(int64_t in_bytes, int32_t block_bytes, int32_t mode) {
+  if (mode != SVDSS_DEFLATE_LZ || in_bytes <= 0 || block_bytes <= 0) return 0;
+  return (in_bytes + block_bytes - 1) / block_bytes * (int64_t)LZ_CAND_WORDS * 4;
+}
+
+hipError_t svdss_deflate_enqueue_mode(hipStream_t st, const uint8_t* d_in, int64_t in_bytes, int32_t block_bytes, uint8_t* d_out,
+                                      int64_t stride, int32_t* d_len, int32_t mode, void* d_scratch) {
+  if (mode == SVDSS_DEFLATE_RUNS) return svdss_deflate_enqueue(st, d_in, in_bytes, block_bytes, d_out, stride, d_len);
+  if (mode != SVDSS_DEFLATE_LZ || !d_scratch) return hipErrorInvalidValue;
+  if (in_bytes <= 0 || block_bytes <= 0 || block_bytes > MAX_IN || stride < svdss_deflate_stride(block_bytes)) return hipErrorInvalidValue;
+  const int64_t nb = (in_bytes + block_bytes - 1) / block_bytes;
+  hipLaunchKernelGGL(bgzf_lz_find_kernel, dim3((unsigned)nb), dim3(LZ_FIND_THREADS), 0, st, d_in, in_bytes, block_bytes, (uint32_t*)d_scratch);
+  hipLaunchKernelGGL(bgzf_deflate_lz_kernel, dim3((unsigned)nb), dim3(64), 0, st, d_in, in_bytes, block_bytes, d_out, stride, d_len,
+                     (const uint32_t*)d_scratch);
+  return hipGetLastError();
+}
+
 hipError_t svdss_deflate_compact_enqueue(hipStream_t st, const uint8_t* d_strided, int64_t stride, const int32_t* d_len, int64_t nb,
                                          int64_t* d_off, uint8_t* d_dense) {
   hipLaunchKernelGGL(deflate_offsets_kernel, dim3(1), dim3(64), 0, st, d_len, nb, d_off);
@@ -416,6 +803,7 @@ struct svdss_deflate {
   int32_t* d_len = nullptr; size_t len_cap = 0;
   uint8_t* d_dense = nullptr; size_t dense_cap = 0;   // compact mode: the members back to back
   int64_t* d_off = nullptr; size_t off_cap = 0;
+  void* d_scratch = nullptr; size_t scratch_cap = 0;  // lz mode: the match finder's candidates
   double kernel_ms = 0;
 };
 
@@ -427,6 +815,7 @@ extern "C" void svdss_deflate_free(svdss_deflate_t* o) {
   if (o->d_len) (void)hipFree(o->d_len);
   if (o->d_dense) (void)hipFree(o->d_dense);
   if (o->d_off) (void)hipFree(o->d_off);
+  if (o->d_scratch) (void)hipFree(o->d_scratch);
   if (o->e0) (void)hipEventDestroy(o->e0);
   if (o->e1) (void)hipEventDestroy(o->e1);
   if (o->stream) (void)hipStreamDestroy(o->stream);
@@ -437,7 +826,13 @@ extern "C" double svdss_deflate_kernel_ms(const svdss_deflate_t* o) { return o ?
 
 extern "C" int svdss_bgzf_deflate(svdss_deflate_t** obj, int32_t device, const uint8_t* in, int64_t in_bytes,
                                   int32_t block_bytes, uint8_t* out, int64_t out_stride, int32_t* out_len) {
+  return svdss_bgzf_deflate_mode(obj, device, in, in_bytes, block_bytes, out, out_stride, out_len, SVDSS_DEFLATE_RUNS);
+}
+
+extern "C" int svdss_bgzf_deflate_mode(svdss_deflate_t** obj, int32_t device, const uint8_t* in, int64_t in_bytes,
+                                       int32_t block_bytes, uint8_t* out, int64_t out_stride, int32_t* out_len, int32_t mode) {
   if (!obj || !in || !out || !out_len || in_bytes <= 0 || block_bytes <= 0 || block_bytes > MAX_IN) return SVDSS_EINVAL;
+  if (mode != SVDSS_DEFLATE_RUNS && mode != SVDSS_DEFLATE_LZ) return SVDSS_EINVAL;
   // out_stride 0: the members back to back in `out` (room for in_bytes + 64 per block), out_len gives their lengths
   const bool dense = out_stride == 0;
   if (dense) out_stride = ((int64_t)block_bytes + 26 + 6 * SUBS + 4 + 63) & ~(int64_t)63;
@@ -474,13 +869,24 @@ extern "C" int svdss_bgzf_deflate(svdss_deflate_t** obj, int32_t device, const u
     HIPCHK(hipMalloc((void**)&o->d_len, len_need * 2 + 64));
     o->len_cap = len_need * 2 + 64;
   }
+  const size_t scratch_need = (size_t)svdss_deflate_scratch_bytes(in_bytes, block_bytes, mode);
+  if (o->scratch_cap < scratch_need) {
+    if (o->d_scratch) (void)hipFree(o->d_scratch);
+    o->d_scratch = nullptr; o->scratch_cap = 0;
+    HIPCHK(hipMalloc(&o->d_scratch, scratch_need + scratch_need / 4));
+    o->scratch_cap = scratch_need + scratch_need / 4;
+  }
   HIPCHK(hipMemcpyAsync(o->d_in, in, (size_t)in_bytes, hipMemcpyHostToDevice, o->stream));
   HIPCHK(hipMemsetAsync(o->d_in + in_bytes, 0, 64, o->stream));
   HIPCHK(hipMemsetAsync(o->d_out, 0, out_need, o->stream));
   HIPCHK(hipEventRecord(o->e0, o->stream));
-  hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)nb), dim3(64), 0, o->stream, o->d_in, in_bytes, block_bytes, o->d_out,
-                     out_stride, o->d_len);
-  HIPCHK(hipGetLastError());
+  if (mode == SVDSS_DEFLATE_RUNS) {
+    hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)nb), dim3(64), 0, o->stream, o->d_in, in_bytes, block_bytes, o->d_out,
+                       out_stride, o->d_len);
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(svdss_deflate_enqueue_mode(o->stream, o->d_in, in_bytes, block_bytes, o->d_out, out_stride, o->d_len, mode, o->d_scratch));
+  }
   HIPCHK(hipEventRecord(o->e1, o->stream));
   if (dense) {
     if (o->dense_cap < out_need) {

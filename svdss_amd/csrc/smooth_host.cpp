@@ -386,6 +386,7 @@ int main_smooth(const CallOptions& o) {
         rcs[d] = svdss_ref_upload_parts(parts.data(), plen.data(), (int32_t)parts.size(), (int)d, &drefs[d]);
         if (rcs[d] == SVDSS_OK) rcs[d] = svdss_bam_smooth_create(drefs[d], tid_map.data(), (int32_t)tid_map.size(), (int32_t)o.min_mapq, &sms[d]);
         if (rcs[d] == SVDSS_OK && ixb) rcs[d] = svdss_bam_smooth_set_index(sms[d], ix_shift, ix_depth);
+        if (rcs[d] == SVDSS_OK) rcs[d] = svdss_bam_smooth_set_deflate(sms[d], o.compress);
       };
       for (size_t d = 1; d < n_sm; ++d) up.emplace_back(upload, d);
       upload(0);

@@ -9,7 +9,8 @@
 //   SVDSS --version                                     (main.cpp:45-47)
 // SFS text goes to stdout exactly as PingPong::output_batch prints it
 // (ping_pong.cpp:213-236), logs to stderr, fatal conditions exit(1).
-// Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth).
+// Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth),
+// --compress runs|lz (smooth).
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -56,7 +57,10 @@ static const char* SMOOTH_USAGE =
     "      --accp <float>     accuracy percentile (default: 0.98)\n"
     "      --write-index <FILE>  also write the output's index: CSI if FILE ends in .csi, else BAI (as `samtools index`\n"
     "                            of a BAM written to a new file or a pipe; appended to a non-empty file, it indexes the\n"
-    "                            appended stream only)\n";
+    "                            appended stream only)\n"
+    "      --compress <runs|lz>  how the GPU deflates the output (default: runs): runs codes literals and runs of equal\n"
+    "                            bytes; lz also finds matches between overlapping reads (a smaller file, more GPU time).\n"
+    "                            No effect where the host deflates (SVDSS_GPU_DEFLATE=0, SVDSS_SMOOTH_HOST=1)\n";
 
 static const char* CALL_USAGE =
     "Usage: SVDSS call --reference <FASTA> --bam <BAM> --sfs <SFS>\n"
@@ -1223,7 +1227,7 @@ int main(int argc, char** argv) {
       if (o.reference.empty() || o.bam.empty()) { fputs(SMOOTH_USAGE, stderr); return EXIT_FAILURE; }   // main.cpp:73-76
       CallOptions c;
       c.reference = o.reference; c.bam = o.bam; c.threads = o.threads; c.min_mapq = o.min_mapq; c.accp = o.accp; c.gpus = o.gpus;
-      c.write_index = o.write_index;
+      c.write_index = o.write_index; c.compress = o.compress;
       main_smooth(c);
     } else {
       fputs(MAIN_USAGE, stderr);
