@@ -27,7 +27,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/svdss_hip.h"
+#define SVDSS_LOG_TAG "call"
+#include "host_common.h"
 #include "bai_index.h"
 #include "bam_reader.h"
 #include "bam_device_select.h"
@@ -38,12 +39,6 @@
 #include "fastx_reader.h"
 
 namespace {
-
-void logmsg(const char* lvl, const std::string& m) { fprintf(stderr, "[call] [%s] %s\n", lvl, m.c_str()); }
-[[noreturn]] void die(const std::string& m) { logmsg("critical", m); exit(EXIT_FAILURE); }
-void check(int rc, const char* what) {
-  if (rc != SVDSS_OK) die(std::string(what) + ": " + svdss_strerror(rc) + " " + svdss_last_hip_error());
-}
 
 
 struct ESFS {   // SFS after placement (sfs.hpp:52-62)
@@ -745,9 +740,9 @@ struct CallRun {
     // the record store(s) of the ONE pass over the BAM (round 6, align_and_extend / fill_clusters below): the memory is taken
     // NOW, on a thread of its own, beside the FASTA and the SFS file -- tens of GB that the driver clears before it hands them out
     {
-      // (SVDSS_GPUS_OVERSUBSCRIBE: more shards than GPUs, shard g on GPU g % count -- exercises the sharding on a one-GPU box)
+      // (effective_gpus: oversubscribed, more shards than GPUs, shard g on GPU g % count -- exercises the sharding on a one-GPU box)
       n_dev = std::max(1, svdss_device_count());
-      G = std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, n_dev));
+      G = effective_gpus(o.gpus);
       // Records handled on the GPU (csrc/bam_device.hip, svdss_bam_select_run; the default when there is a GPU and the
       // input is a regular file): only the primary, mapq-ok alignments of reads that HAVE SFS come back to the host --
       // the records clusterer.cpp:108-145 keeps -- instead of every inflated byte.  No record cache then: pass 2 takes the
@@ -805,7 +800,7 @@ struct CallRun {
   }
 
   // Pass 1 through the device path: the records of reads that have SFS.  --gpus N: the file's regions, one per GPU
-  // (SVDSS_GPUS_OVERSUBSCRIBE puts the N shards on the GPUs there are -- the code path of N devices on a one-GPU box): every
+  // (oversubscribed, effective_gpus puts the N shards on the GPUs there are -- the code path of N devices on a one-GPU box): every
   // region has its own scanner, batcher, feeding threads, record stream and filter; the slim form of every record that
   // passes the flag / mapq filters stays in that GPU's HBM for pass 2 (load_inputs took the memory; all of it or none is
   // used).  SVDSS_CALL_STORE=0: two passes over the file.
@@ -857,7 +852,7 @@ struct CallRun {
       if (dev_pass) open_pass1_select(feed);
       else {
         // (--gpus N: the chunks of pass 1 are inflated on all N GPUs in turn, as `search` does -- on GPUs that are there,
-        // whatever SVDSS_GPUS_OVERSUBSCRIBE says)
+        // whatever the oversubscribe knob says)
         open_reader(feed, std::max(1, std::min(o.gpus, n_dev)));
         ref_names = feed.bam->ref_names();
         feed.on_chunk = [this](const std::shared_ptr<BamReader::Bytes>& chunk) {

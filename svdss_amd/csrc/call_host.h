@@ -1,5 +1,7 @@
-// call_host.h -- options of the `call` and `smooth` sub-commands (config.hpp:68-103 defaults).
+// call_host.h -- options of the `call` and `smooth` sub-commands (config.hpp:68-103 defaults), and the entry points of the
+// sub-commands that have a file of their own.
 #pragma once
+#include <ctime>
 #include <string>
 
 struct CallOptions {
@@ -20,5 +22,8 @@ struct CallOptions {
   bool clipped = false;        // --clipped: imprecise SVs from soft-clipped alignments (clipper.cpp; EXPERIMENTAL)
 };
 
+struct Options;   // cli_options.h
+
+int main_search(const Options& o, time_t process_start);   // search_host.cpp
 int main_call(const CallOptions& o);
 int main_smooth(const CallOptions& o);

@@ -23,7 +23,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/svdss_hip.h"
+#define SVDSS_LOG_TAG "smooth"
+#include "host_common.h"
 #include "bam_reader.h"
 #include "bam_device_select.h"
 #include "gpu_deflate_hook.h"
@@ -34,8 +35,6 @@
 #include "fastx_reader.h"
 
 namespace {
-[[noreturn]] void die(const std::string& m) { fprintf(stderr, "[smooth] [critical] %s\n", m.c_str()); exit(EXIT_FAILURE); }
-
 const int MIN_INDEL = 20;   // config.hpp:95
 
 bool is_m(uint32_t op) { return op == 0 || op == 7 || op == 8; }
@@ -252,12 +251,12 @@ int main_smooth(const CallOptions& o) {
     const int per_gpu = getenv("SVDSS_SEARCH_FEEDERS") ? std::max(1, atoi(getenv("SVDSS_SEARCH_FEEDERS"))) : 6;
     // --gpus N (round 6): the file's regions, one per GPU (ShardedBamSelect, bam_device_select.h: the machinery of `SVDSS call
     // --gpus N`) -- every region has its own loaders, feeding threads and record stream, and every GPU its copy of the
-    // chromosomes; SVDSS_GPUS_OVERSUBSCRIBE puts the N regions on the GPUs there are.  The records and their order are those
+    // chromosomes; oversubscribed (effective_gpus), it puts the N regions on the GPUs there are.  The records and their order are those
     // of one GPU's run; the BGZF members are not cut at the same bytes: a region ends with a short member where one GPU's
     // stream would have gone on filling it, and the record a seam completes is a member of its own (`gzip -dc` of the two
     // files is the same).
     const int n_phys = std::max(1, svdss_device_count());
-    const int n_g = std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? o.gpus : std::min(o.gpus, n_phys));
+    const int n_g = effective_gpus(o.gpus);
     const std::vector<size_t> cuts = n_g > 1 ? plan_bam_regions(o.bam, n_g, skip) : std::vector<size_t>{0, 0};
     const size_t n_regions = cuts.size() - 1;
     const size_t n_sm = std::min<size_t>(n_regions, (size_t)n_phys);

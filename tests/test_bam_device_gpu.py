@@ -273,6 +273,11 @@ def test_binary_device_path_writes_the_host_paths_bytes(case, tmp_path):
                 assert int(m.group(3)) < 3000          # (the park was full: not every read fitted)
             assert early.stdout == host.stdout, env
             assert early.stderr.count("Alignment filtered due to l_qseq") == 8
+        # the early path once more with the orderly teardown (SVDSS_CLEAN_EXIT=1: the park and the index are freed, the
+        # process returns through main instead of _exit): the same bytes, exit 0 (run() asserts it)
+        clean = run({"SVDSS_CLEAN_EXIT": "1", "SVDSS_PARK_GROUP_READS": "300", "SVDSS_PARK_ARENA_MB": "1", "SVDSS_SEARCH_EARLY": "1",
+                     "SVDSS_EARLY_HOLD_MS": "1500", "SVDSS_BAM_SLAB_KB": "64", "SVDSS_BAM_BATCH_MB": "1"}, *extra)
+        assert "front end beside the index restore" in clean.stderr and clean.stdout == host.stdout
         # round 5: --gpus N cuts the file into N regions, each with its own scanner / batcher / feeders; a region's first
         # record is guessed and proved at the seam.  SVDSS_REGION_TEST: 1 = every guess is no record (the regions fail
         # and run again from the region before), 2 = the seams do not fit (the regions run again)

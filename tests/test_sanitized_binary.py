@@ -1,4 +1,4 @@
-"""The host side of the SVDSS binary (svdss_main.cpp, call_host.cpp, smooth_host.cpp: option parsing, FASTA / BAM
+"""The host side of the SVDSS binary (svdss_main.cpp, search_host.cpp, call_host.cpp, smooth_host.cpp: option parsing, FASTA / BAM
 reading and writing, the smoothing rules and the record rebuild, the host index builder behind `SVDSS index`) under
 AddressSanitizer + UndefinedBehaviorSanitizer: the process-level CPU tests of this directory once more, against a
 sanitized build of the binary.  Opt-in (SVDSS_RUN_SANITIZED_BINARY=1): the build and the slower runs take three minutes,
@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "svdss_amd", "csrc")
 
 @pytest.mark.skipif(os.environ.get("SVDSS_RUN_SANITIZED_BINARY") != "1", reason="opt-in: SVDSS_RUN_SANITIZED_BINARY=1")
 def test_process_level_tests_against_the_sanitized_binary():
-    srcs = [os.path.join(CSRC, f) for f in ("svdss_main.cpp", "call_host.cpp", "smooth_host.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("svdss_main.cpp", "search_host.cpp", "call_host.cpp", "smooth_host.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     if not os.path.exists(SAN) or any(os.path.getmtime(d) > os.path.getmtime(SAN) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined",
