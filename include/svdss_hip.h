@@ -437,7 +437,8 @@ typedef struct svdss_bam_smoothed {
   int64_t bgzf_bytes;
   int64_t n_xf[4];                /* run: records by XF value */
   double inflate_kernel_ms;
-  double stage_ms[8];             /* 0-2 as svdss_bam_result_t, 3 filters + CIGAR walk, 4 sizes + records, 5 the output turn, 6 deflate + down */
+  double stage_ms[8];             /* 0-2 as svdss_bam_result_t, 3 filters + CIGAR walk, 4 sizes + records, 5 the output turn, 6 deflate + down,
+                                     7 the reads exported for a search, and searched (svdss_bam_smooth_set_search) */
 } svdss_bam_smoothed_t;
 int svdss_bam_batch_smoothed(const svdss_bam_batch_t* b, svdss_bam_smoothed_t* out);
 /* `smooth --write-index` (csrc/bam_smooth.hip, csrc/bam_index_writer.h): svdss_bam_smooth_set_index(sm, min_shift, depth)
@@ -472,6 +473,22 @@ int svdss_bam_smooth_set_index(svdss_bam_smooth_t* sm, int32_t min_shift, int32_
  * fragments' offsets inside a block do not depend on it; the compressed offsets follow the members' lengths. */
 int svdss_bam_smooth_set_deflate(svdss_bam_smooth_t* sm, int32_t mode);
 int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* out);
+/* `smooth --index --sfs` (csrc/bam_smooth.hip): one pass over the original BAM yields what `SVDSS search` would find in the
+ * smoothed one.  Seam: ping_pong.cpp:53-128 read the smoothed file back (load_batch_bam :66-104: flag and l_qseq filters,
+ * qname, HP, XF, seq_nt16 -> nt6); here those fields are taken from the rebuilt records while they are in HBM.
+ *   svdss_bam_smooth_set_search  flags >= 0 (SVDSS_SFS_ASSEMBLE, SVDSS_BAM_PUTATIVE): every later svdss_bam_smooth_run on sm
+ *                                also leaves what svdss_bam_batch_front leaves -- names / HP / slots of the kept records with
+ *                                a rebuilt l_seq >= 100 on the host (svdss_bam_batch_result; n_short: the shorter ones), the
+ *                                searched reads as nt6 in `park` (svdss_bam_batch_parked: group >= 0) or, with park = NULL,
+ *                                no room in it or closed, in the batch object (group -1; -2: nothing to search).
+ *                                flags = -1, park = NULL: off (the default).
+ *   svdss_bam_smooth_search      finishes a batch of group -1 against a resident index, like svdss_bam_batch_search; the
+ *                                smoothing run's stage_ms stay, the search is added to stage 7.
+ *   svdss_bam_smooth_set_output  write_bam = 0 (`--nobam`): later runs take and pass on the output turn but keep no tail,
+ *                                deflate nothing and bring nothing down (bgzf_bytes = 0, no index fragments); 1: the default. */
+int svdss_bam_smooth_set_search(svdss_bam_smooth_t* sm, int32_t flags, svdss_bam_park_t* park);
+int svdss_bam_smooth_set_output(svdss_bam_smooth_t* sm, int32_t write_bam);
+int svdss_bam_smooth_search(svdss_bam_batch_t* b, const svdss_index_t* ix);
 const char* svdss_bam_batch_error(const svdss_bam_batch_t* b);
 void svdss_bam_batch_free(svdss_bam_batch_t* b);
 

@@ -132,6 +132,9 @@ SIGNATURES = {
     "svdss_bam_batch_smoothed": (C.c_int, [_p, _p]),
     "svdss_bam_smooth_set_index": (C.c_int, [_p, C.c_int32, C.c_int32]),
     "svdss_bam_smooth_set_deflate": (C.c_int, [_p, C.c_int32]),
+    "svdss_bam_smooth_set_search": (C.c_int, [_p, C.c_int32, _p]),
+    "svdss_bam_smooth_set_output": (C.c_int, [_p, C.c_int32]),
+    "svdss_bam_smooth_search": (C.c_int, [_p, _p]),
     "svdss_bam_batch_index": (C.c_int, [_p, _p]),
     "svdss_bam_batch_error": (C.c_char_p, [_p]),
     "svdss_bam_filter_create": (C.c_int, [_i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _i64, C.POINTER(_p)]),

@@ -260,45 +260,6 @@ struct MetaP {
   int64_t* hdr;
 };
 
-// bam_aux_get + bam_aux2i for one two-letter tag, as BamReader::aux_int reads it (csrc/bam_reader.h): integer types
-// only, anything unexpected ends the scan with "absent"
-__device__ bool aux_int(const uint8_t* p, const uint8_t* e, char a, char b, int64_t& out) {
-  while (p + 3 <= e) {
-    const char t0 = (char)p[0], t1 = (char)p[1], ty = (char)p[2];
-    p += 3;
-    int64_t sz = 0;
-    switch (ty) {
-      case 'A': case 'c': case 'C': sz = 1; break;
-      case 's': case 'S': sz = 2; break;
-      case 'i': case 'I': case 'f': sz = 4; break;
-      case 'Z': case 'H': { const uint8_t* z = p; while (z < e && *z) ++z; sz = (int64_t)(z - p) + 1; break; }
-      case 'B': {
-        if (p + 5 > e) return false;
-        const char st = (char)p[0];
-        const int32_t cnt = (int32_t)((uint32_t)p[1] | ((uint32_t)p[2] << 8) | ((uint32_t)p[3] << 16) | ((uint32_t)p[4] << 24));
-        const int64_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-        sz = 5 + es * (int64_t)(uint32_t)cnt;     // (size_t arithmetic on the host: a negative count is a huge one)
-        break;
-      }
-      default: return false;
-    }
-    if (sz > (int64_t)(e - p)) return false;
-    if (t0 == a && t1 == b) {
-      switch (ty) {
-        case 'c': out = (int8_t)p[0]; return true;
-        case 'C': out = p[0]; return true;
-        case 's': out = (int16_t)((uint16_t)p[0] | ((uint16_t)p[1] << 8)); return true;
-        case 'S': out = (uint16_t)((uint16_t)p[0] | ((uint16_t)p[1] << 8)); return true;
-        case 'i': out = (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24)); return true;
-        case 'I': out = (uint32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24)); return true;
-        default: return false;
-      }
-    }
-    p += sz;
-  }
-  return false;
-}
-
 // block s < n_seg: the records of segment s; block n_seg: those that begin in the carried bytes
 __global__ void __launch_bounds__(64) meta_kernel(MetaP M) {
   const int s = blockIdx.x;
@@ -396,30 +357,7 @@ __global__ void __launch_bounds__(256) unpack_kernel(const uint8_t* __restrict__
   const int64_t c = (s >> 4) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t o0 = c << 4;
   if (o0 >= e) return;
-  const int64_t a = o0 < s ? s : o0, b = o0 + 16 < e ? o0 + 16 : e;    // output bytes [a, b)
-  const int64_t i0 = a - s;                                            // first symbol of the read this lane writes
-  const int64_t sb = seq_src[r] + (i0 >> 1);
-  const uint64_t lo = (uint64_t)ld32(buf, sb) | ((uint64_t)ld32(buf, sb + 4) << 32);
-  const uint32_t hi = ld32(buf, sb + 8);
-  // "=ACMGRSVTWYHKDBN": A=1 C=2 G=4 T=8 -> nt6 1..4, every other code (IUPAC, '=') -> 5 like seq_nt6_table
-  const uint64_t lut = 0x5555555455535215ull;
-  uint32_t w[4] = {0, 0, 0, 0};
-  const int n = (int)(b - a);
-  const int odd = (int)(i0 & 1);
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int ni = k + odd;                        // nibble index from the first loaded byte
-    const int by = ni >> 1;
-    const uint32_t byte = by < 8 ? (uint32_t)(lo >> (8 * by)) & 0xffu : (hi >> (8 * (by - 8))) & 0xffu;
-    const uint32_t v = (ni & 1) ? (byte & 15u) : (byte >> 4);
-    const uint32_t sym = (uint32_t)(lut >> (4 * v)) & 15u;
-    w[k >> 2] |= sym << (8 * (k & 3));
-  }
-  if (n == 16) {
-    *(uint4*)(out + a) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else {
-    for (int k = 0; k < n; ++k) out[a + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-  }
+  nt6_chunk16(buf, seq_src[r], s, e, o0, out);
 }
 
 // ------------------------------------------------------------------ records selected for `call` (svdss_bam_select_run)
@@ -654,36 +592,6 @@ struct svdss_bam_filter {
   int32_t *d_reg_beg = nullptr, *d_reg_runmax = nullptr;
 };
 
-// Reads unpacked while no index is resident yet (`SVDSS search` restores its index for seconds; the BAM front end runs
-// meanwhile): an arena of nt6 bytes + one of offsets, cut into GROUPS of consecutive reservations that are searched as one
-// large launch each (one lane per read) once the index is there.  A group's reads are contiguous from a 16-byte aligned
-// start, its offsets relative to that start.
-struct ParkGroup {
-  int32_t arena = 0;
-  int64_t sym0 = 0, n_syms = 0;      // where its reads begin in its arena (16-aligned), symbols so far
-  int64_t off0 = 0, n_reads = 0;     // where its offsets begin, reads so far (offsets: n_reads + 1 entries)
-  int32_t n_batches = 0, pending = 0;
-  bool closed = false;
-};
-// (arenas are allocated one at a time, the first before the index restore starts: a process that searches 1 % of its reads --
-// `SVDSS search` on a smoothed BAM -- never needs a second one, and memory the driver hands out is cleared first, 30-50 GB/s)
-struct ParkArena {
-  uint8_t* d_reads = nullptr;
-  int64_t* d_off = nullptr;
-  int64_t cap_bytes = 0, cap_off = 0;
-};
-struct svdss_bam_park {
-  int device = -1;
-  std::vector<ParkArena> arenas;
-  int64_t arena_bytes = (int64_t)8 << 30, max_bytes = 0, reads_per_arena = 0;
-  int64_t group_reads = 262144, group_bytes = (int64_t)4 << 30;
-  hipStream_t st = nullptr;
-  std::mutex m;
-  std::condition_variable cv;
-  std::vector<ParkGroup> groups;
-  bool closed = false;
-};
-
 extern "C" int svdss_bam_stream_create(int32_t n_ref, svdss_bam_stream_t** out) {
   if (!out || n_ref < 0) return SVDSS_EINVAL;
   svdss_bam_stream* s = new (std::nothrow) svdss_bam_stream();
@@ -908,22 +816,6 @@ __global__ void __launch_bounds__(256) rebase_offsets_kernel(const int64_t* __re
 }
 
 // ---- the park (see struct svdss_bam_park)
-static hipError_t park_new_arena(svdss_bam_park* p) {
-  ParkArena A;
-  A.cap_bytes = std::min(p->arena_bytes, p->max_bytes - (int64_t)p->arenas.size() * p->arena_bytes);
-  if (A.cap_bytes < 4096) return hipErrorOutOfMemory;
-  A.cap_off = p->reads_per_arena + 64;
-  hipError_t e = hipMalloc((void**)&A.d_reads, (size_t)A.cap_bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&A.d_off, sizeof(int64_t) * (size_t)A.cap_off);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (A.d_reads) (void)hipFree(A.d_reads);
-    return e;
-  }
-  p->arenas.push_back(A);
-  return hipSuccess;
-}
-
 extern "C" int svdss_bam_park_create(int32_t device, int64_t read_bytes, int64_t max_reads, svdss_bam_park_t** out) {
   if (!out || device < 0 || read_bytes < 4096 || max_reads < 1) return SVDSS_EINVAL;
   HIPCHK(hipSetDevice(device));
@@ -986,43 +878,6 @@ extern "C" int svdss_bam_park_group(svdss_bam_park_t* p, int64_t g, int64_t* n_b
   if (n_reads) *n_reads = G.n_reads;
   if (n_syms) *n_syms = G.n_syms;
   return SVDSS_OK;
-}
-
-// room for n reads / syms symbols: group, index of the first read and symbol offset inside it; false = not parked
-static bool park_reserve(svdss_bam_park* p, int64_t n, int64_t syms, int64_t& g, int64_t& first, int64_t& sym_first) {
-  std::lock_guard<std::mutex> lk(p->m);
-  if (p->closed) return false;
-  auto fits = [&](const ParkGroup& G) {
-    const ParkArena& A = p->arenas[(size_t)G.arena];
-    return G.sym0 + G.n_syms + syms + 64 <= A.cap_bytes && G.off0 + G.n_reads + n + 2 <= A.cap_off;
-  };
-  if (!p->groups.empty() && !p->groups.back().closed && !fits(p->groups.back())) p->groups.back().closed = true;
-  if (p->groups.empty() || p->groups.back().closed) {
-    ParkGroup G;
-    if (!p->groups.empty()) {
-      const ParkGroup& L = p->groups.back();
-      G.arena = L.arena;
-      G.sym0 = ((L.sym0 + L.n_syms + 15) & ~(int64_t)15) + 32;
-      G.off0 = L.off0 + L.n_reads + 1;
-    }
-    if (!fits(G)) {
-      // the next arena (what is parked stays where it is); none to be had: the rest of the file waits for the index
-      if (syms + 64 > p->arena_bytes || n + 2 > p->reads_per_arena || park_new_arena(p) != hipSuccess) { p->closed = true; return false; }
-      G.arena = (int32_t)p->arenas.size() - 1; G.sym0 = 0; G.off0 = 0;
-      if (!fits(G)) { p->closed = true; return false; }
-    }
-    p->groups.push_back(G);
-  }
-  ParkGroup& G = p->groups.back();
-  g = (int64_t)p->groups.size() - 1;
-  first = G.n_reads; sym_first = G.n_syms;
-  G.n_reads += n; G.n_syms += syms; ++G.n_batches; ++G.pending;
-  if (G.n_reads >= p->group_reads || G.n_syms >= p->group_bytes) G.closed = true;
-  return true;
-}
-static void park_done(svdss_bam_park* p, int64_t g) {
-  { std::lock_guard<std::mutex> lk(p->m); --p->groups[(size_t)g].pending; }
-  p->cv.notify_all();
 }
 
 // One group searched as ONE launch (one lane per read: the large-batch regime).  Waits until the group is closed and all

@@ -499,6 +499,101 @@ __global__ void __launch_bounds__(256) sm_ix_emit_kernel(SmIxP P) {
   }
 }
 
+// ---- `smooth --index --sfs`: what `SVDSS search` would read from the smoothed BAM, taken from the rebuilt records while
+// they are in HBM (the fields, filters and tags of bam_device.hip's meta_kernel / scatter_kernel / unpack_kernel, on the
+// OUTPUT records: names, HP and XF as search's aux walk finds them, l_seq as rebuilt)
+struct SmSfsP {
+  const uint8_t* out;        // the batch's rebuilt records (sm_out + room); record k at ooff[k]
+  const int64_t* ooff;       // n_keep + 1
+  int64_t n_keep;
+  int32_t putative;
+  int64_t *f_pass, *f_srch, *f_name, *f_sym, *f_short;   // n_keep + 1 each, consecutive rows: inputs of the scans
+  const int64_t *s_pass, *s_srch, *s_name, *s_sym;       // their exclusive sums (the last entry of a row: its total)
+  int32_t* hp;               // n_keep
+  // host-bound block, per read of the sequence ("slot": kept, l_seq >= 100)
+  int32_t* o_name_off;       // slots + 1
+  char* o_names;
+  int32_t* o_hp;
+  int32_t* o_sidx;           // index among the searched reads, -1: keeps its place but is not searched (XF != 0, putative)
+  // per searched read
+  int64_t* sym_off;          // searched + 1: where its symbols go, from the destination's start (sym_base: the park group's fill)
+  int64_t sym_base;
+  int64_t* seq_src;          // where its packed bases sit in `out`
+};
+
+__device__ __forceinline__ void sm_sfs_fields(const SmSfsP& P, int64_t k, int64_t& r, uint32_t& bs, uint32_t& l_name, uint32_t& n_cig, uint32_t& flag, int32_t& l_seq) {
+  r = P.ooff[k];
+  bs = ld32(P.out, r);
+  const uint32_t w3 = ld32(P.out, r + 12), w4 = ld32(P.out, r + 16);
+  l_seq = (int32_t)ld32(P.out, r + 20);
+  l_name = w3 & 0xffu; n_cig = w4 & 0xffffu; flag = w4 >> 16;
+}
+
+// a thread per kept record: in the sequence (ping_pong.cpp:66-75)?  searched (:196-203)?  name bytes, symbols, HP
+__global__ void __launch_bounds__(256) sm_sfs_flag_kernel(SmSfsP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > P.n_keep) return;
+  if (k == P.n_keep) { P.f_pass[k] = 0; P.f_srch[k] = 0; P.f_name[k] = 0; P.f_sym[k] = 0; P.f_short[k] = 0; return; }
+  int64_t r; uint32_t bs, l_name, n_cig, flag; int32_t l_seq;
+  sm_sfs_fields(P, k, r, bs, l_name, n_cig, flag, l_seq);
+  const int64_t head = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + l_seq;
+  bool keep = !(flag & (4u | 2048u | 256u)) && l_seq >= 0 && head <= (int64_t)bs;
+  const bool is_short = keep && l_seq < 100;
+  keep = keep && !is_short;
+  bool srch = false;
+  int64_t hp = 0;
+  if (keep) {
+    const uint8_t* aux = P.out + r + 4 + head;
+    const uint8_t* end = P.out + r + 4 + (int64_t)bs;
+    int64_t xf = 0;
+    (void)aux_int(aux, end, 'X', 'F', xf);
+    (void)aux_int(aux, end, 'H', 'P', hp);
+    srch = !(P.putative && xf != 0);
+  }
+  P.f_pass[k] = keep ? 1 : 0;
+  P.f_srch[k] = srch ? 1 : 0;
+  P.f_name[k] = keep ? (int64_t)(l_name ? l_name - 1 : 0) : 0;
+  P.f_sym[k] = srch ? (int64_t)l_seq : 0;
+  P.f_short[k] = is_short ? 1 : 0;
+  P.hp[k] = (int32_t)hp;
+}
+
+// a thread per kept record (+ the totals' entry): the host-bound block and where the searched reads' symbols go
+__global__ void __launch_bounds__(256) sm_sfs_scatter_kernel(SmSfsP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > P.n_keep) return;
+  if (k == P.n_keep) {
+    P.o_name_off[P.s_pass[k]] = (int32_t)P.s_name[k];
+    P.sym_off[P.s_srch[k]] = P.sym_base + P.s_sym[k];
+    return;
+  }
+  if (!P.f_pass[k]) return;
+  int64_t r; uint32_t bs, l_name, n_cig, flag; int32_t l_seq;
+  sm_sfs_fields(P, k, r, bs, l_name, n_cig, flag, l_seq);
+  const int64_t slot = P.s_pass[k];
+  P.o_name_off[slot] = (int32_t)P.s_name[k];
+  P.o_hp[slot] = P.hp[k];
+  const uint8_t* nm = P.out + r + 36;
+  char* dst = P.o_names + P.s_name[k];
+  for (uint32_t i = 0; i + 1 < l_name; ++i) dst[i] = (char)nm[i];
+  if (P.f_srch[k]) {
+    const int64_t j = P.s_srch[k];
+    P.o_sidx[slot] = (int32_t)j;
+    P.sym_off[j] = P.sym_base + P.s_sym[k];
+    P.seq_src[j] = r + 36 + (int64_t)l_name + 4 * (int64_t)n_cig;
+  } else P.o_sidx[slot] = -1;
+}
+
+// a workgroup per searched read: its packed bases -> nt6 at its place in the park's arena or the batch's buffer, a lane per
+// 16 aligned output bytes (nt6_chunk16: dword loads of the packed bases, one 16-byte store)
+__global__ void __launch_bounds__(256) sm_sfs_nt6_kernel(const uint8_t* __restrict__ recs, const int64_t* __restrict__ seq_src,
+                                                         const int64_t* __restrict__ sym_off, uint8_t* out) {
+  const int64_t j = blockIdx.x;
+  const int64_t s = sym_off[j], e = sym_off[j + 1];
+  const int64_t src = seq_src[j];
+  for (int64_t c = (s >> 4) + threadIdx.x; (c << 4) < e; c += 256) nt6_chunk16(recs, src, s, e, c << 4, out);
+}
+
 struct FootP { const uint8_t* in; int64_t in_bytes; int32_t block_bytes; uint8_t* members; int64_t stride; const int32_t* len; };
 
 // a wavefront per BGZF block of the output: CRC32 of its bytes and their number into the member's last 8 bytes
@@ -544,6 +639,9 @@ struct svdss_bam_smooth {
   int32_t min_mapq = 0, n_ref = 0;
   int32_t ix_shift = 0, ix_depth = 0;   // svdss_bam_smooth_set_index (0: no index fragments)
   int32_t deflate_mode = SVDSS_DEFLATE_RUNS;   // svdss_bam_smooth_set_deflate
+  int32_t search_flags = -1;            // svdss_bam_smooth_set_search (-1: the reads are not exported for a search)
+  svdss_bam_park* park = nullptr;       // ... where they wait for the index (nullptr: in the batch object)
+  bool write_bam = true;                // svdss_bam_smooth_set_output (false: no BGZF members)
   SvdssRefView ref;
   int32_t* d_tidmap = nullptr;
 };
@@ -590,6 +688,20 @@ extern "C" int svdss_bam_smooth_set_deflate(svdss_bam_smooth_t* sm, int32_t mode
   return SVDSS_OK;
 }
 
+extern "C" int svdss_bam_smooth_set_search(svdss_bam_smooth_t* sm, int32_t flags, svdss_bam_park_t* park) {
+  if (!sm || flags < -1 || (flags >= 0 && (flags & ~(SVDSS_SFS_ASSEMBLE | SVDSS_BAM_PUTATIVE))) || (flags < 0 && park)) return SVDSS_EINVAL;
+  if (park && park->device != sm->device) return SVDSS_EINVAL;
+  sm->search_flags = flags;
+  sm->park = park;
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_bam_smooth_set_output(svdss_bam_smooth_t* sm, int32_t write_bam) {
+  if (!sm || (write_bam != 0 && write_bam != 1)) return SVDSS_EINVAL;
+  sm->write_bam = write_bam != 0;
+  return SVDSS_OK;
+}
+
 extern "C" int svdss_bam_stream_set_output_prefix(svdss_bam_stream_t* s, const uint8_t* bytes, int64_t n) {
   if (!s || n < 0 || (n > 0 && !bytes)) return SVDSS_EINVAL;
   std::lock_guard<std::mutex> lk(s->m);
@@ -623,8 +735,11 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
   b->sm.kept = 0; b->sm.out_bytes = 0; b->sm.bgzf_bytes = 0; b->sm.bgzf = nullptr;
   for (int k = 0; k < 4; ++k) b->sm.xf[k] = 0;
   RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));
-  RCHK(b->flags.ensure(sizeof(int64_t) * 2 * (size_t)(n_rec + 1)));
-  RCHK(b->scans.ensure(sizeof(int64_t) * 2 * (size_t)(n_rec + 1)));
+  const bool sfs_on = mode != 0 && sm->search_flags >= 0;
+  b->search.front_done = false;
+  // (with the reads exported for a search, five rows of flags over the kept records follow the two over all records)
+  RCHK(b->flags.ensure(sizeof(int64_t) * (sfs_on ? 5 : 2) * (size_t)(n_rec + 1)));
+  RCHK(b->scans.ensure(sizeof(int64_t) * (sfs_on ? 5 : 2) * (size_t)(n_rec + 1)));
   SmMetaP M;
   M.buf = W.buf; M.lists = W.lists; M.list_cap = W.list_cap; M.seg_cnt = W.seg_cnt; M.seg_base = F.seg_base; M.pre = (const uint32_t*)b->front.pre.p;
   M.n_seg = W.n_seg; M.min_mapq = sm->min_mapq; M.n_ref = sm->n_ref; M.n_rec = n_rec; M.tidmap = sm->d_tidmap;
@@ -710,10 +825,99 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
   try { h_xfv.resize((size_t)n_keep); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
   if (n_keep > 0) BCHK(hipMemcpyAsync(h_xfv.data(), d_xfv, (size_t)n_keep, hipMemcpyDeviceToHost, st));
   run.lap(4);
+  // ---- `smooth --index --sfs`: the reads `SVDSS search` would take from these records -- names, HP and slots to the host,
+  // the searched reads' bases as nt6 into the park (svdss_bam_batch_parked says where) or, without room there, into the
+  // batch object (svdss_bam_smooth_search finishes it).  Before the output turn: the wait for it hides this.
+  b->stage_ms[7] = 0;
+  if (sfs_on) {
+    int64_t pg = -1, pfirst = 0, psym = 0;      // the park's group this batch reserved room in (-1: none)
+    auto unpark = [&]() { if (pg >= 0) { park_done(sm->park, pg); pg = -1; } };
+    // (a failure must neither leave the group waiting for this batch nor keep the output turn)
+    run.release = [&](int code, const std::string& msg) { unpark(); pass_turn(s, out_turn, seq, code, msg); };
+    RCHK(b->search.d_hp.ensure(sizeof(int32_t) * nk));
+    RCHK(b->search.o_small.ensure(sizeof(int32_t) * 3 * (nk + 1)));
+    RCHK(b->search.d_names.ensure(std::min<size_t>((size_t)n_keep * 255, (size_t)out_bytes) + 64));
+    RCHK(b->search.sym_off.ensure(sizeof(int64_t) * (nk + 1)));
+    RCHK(b->search.seq_src.ensure(sizeof(int64_t) * (nk + 1)));
+    SmSfsP P;
+    P.out = (const uint8_t*)b->sm.out.p + room; P.ooff = d_ooff; P.n_keep = n_keep; P.putative = (sm->search_flags & SVDSS_BAM_PUTATIVE) ? 1 : 0;
+    P.f_pass = (int64_t*)b->flags.p; P.f_srch = P.f_pass + nk; P.f_name = P.f_srch + nk; P.f_sym = P.f_name + nk; P.f_short = P.f_sym + nk;
+    int64_t* sc = (int64_t*)b->scans.p;
+    P.s_pass = sc; P.s_srch = sc + nk; P.s_name = sc + 2 * nk; P.s_sym = sc + 3 * nk;
+    P.hp = (int32_t*)b->search.d_hp.p;
+    P.o_name_off = (int32_t*)b->search.o_small.p; P.o_hp = P.o_name_off + (nk + 1); P.o_sidx = P.o_hp + (nk + 1);
+    P.o_names = (char*)b->search.d_names.p; P.sym_off = (int64_t*)b->search.sym_off.p; P.seq_src = (int64_t*)b->search.seq_src.p;
+    P.sym_base = 0;
+    const unsigned g = (unsigned)((nk + 255) / 256);
+    hipLaunchKernelGGL(sm_sfs_flag_kernel, dim3(g), dim3(256), 0, st, P);
+    BCHK(hipGetLastError());
+    RCHK(run.scan_rows(P.f_pass, sc, (int64_t)nk, 5));
+    int64_t totals[5] = {0, 0, 0, 0, 0};     // slots, searched, name bytes, symbols, short
+    for (int k = 0; k < 5; ++k) BCHK(hipMemcpyAsync(&totals[k], sc + (size_t)k * nk + (size_t)n_keep, 8, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
+    const int64_t n_slots = totals[0], n_srch = totals[1], name_bytes = totals[2], total_syms = totals[3];
+    b->search.n_slots = n_slots; b->search.n_searched = n_srch; b->search.n_short = totals[4]; b->search.total_sfs = 0;
+    if (total_syms >= ((int64_t)1 << 40)) return run.fail(SVDSS_ERANGE, "batch too large");
+    const size_t padded = (size_t)((total_syms + 15) & ~(int64_t)15) + 16;
+    b->search.park_group = n_srch > 0 ? -1 : -2;
+    b->search.park_first = 0;
+    uint8_t* reads_out = nullptr;
+    const int64_t* off_out = P.sym_off;
+    if (n_srch > 0 && sm->park && park_reserve(sm->park, n_srch, total_syms, pg, pfirst, psym)) {
+      // the reads go behind those of the batches that reserved before this one; the offsets are the group's
+      ParkArena A;
+      const ParkGroup G = [&] { std::lock_guard<std::mutex> lk(sm->park->m); A = sm->park->arenas[(size_t)sm->park->groups[(size_t)pg].arena]; return sm->park->groups[(size_t)pg]; }();
+      reads_out = A.d_reads + G.sym0;
+      P.sym_off = A.d_off + G.off0 + pfirst;
+      P.sym_base = psym;
+      off_out = P.sym_off;
+      b->search.park_group = pg; b->search.park_first = pfirst;
+    } else if (n_srch > 0) {
+      RCHK(b->search.reads.ensure(padded + 16));
+      reads_out = (uint8_t*)b->search.reads.p;
+      BCHK(hipMemsetAsync(reads_out + (padded >= 32 ? padded - 32 : 0), 0, padded >= 32 ? 32 : padded, st));
+    }
+    hipLaunchKernelGGL(sm_sfs_scatter_kernel, dim3(g), dim3(256), 0, st, P);
+    BCHK(hipGetLastError());
+    if (n_srch > 0) {
+      hipLaunchKernelGGL(sm_sfs_nt6_kernel, dim3((unsigned)n_srch), dim3(256), 0, st, P.out, (const int64_t*)P.seq_src, off_out, reads_out);
+      BCHK(hipGetLastError());
+    }
+    b->search.name_bytes = name_bytes;
+    try {
+      b->search.name_off.resize((size_t)n_slots + 1); b->search.hp.resize((size_t)n_slots); b->search.sidx.resize((size_t)n_slots);
+      b->search.names.resize((size_t)name_bytes + 1); b->search.counts.clear(); b->search.qs.clear(); b->search.len.clear();
+    } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
+    {
+      hipError_t e = hipMemcpyAsync(b->search.name_off.data(), P.o_name_off, sizeof(int32_t) * (size_t)(n_slots + 1), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && n_slots > 0) e = hipMemcpyAsync(b->search.hp.data(), P.o_hp, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && n_slots > 0) e = hipMemcpyAsync(b->search.sidx.data(), P.o_sidx, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && name_bytes > 0) e = hipMemcpyAsync(b->search.names.data(), P.o_names, (size_t)name_bytes, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      unpark();     // (the bases are in place: the group may be searched)
+      if (e != hipSuccess) { g_svdss_hip_err = std::string("smooth sfs export: ") + hipGetErrorString(e); return run.fail(e == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err); }
+    }
+    b->search.cur_reads = reads_out; b->search.cur_off = off_out; b->search.cur_syms = total_syms; b->search.cur_flags = sm->search_flags;
+    b->search.front_done = true;
+    run.release = [&](int code, const std::string& msg) { pass_turn(s, out_turn, seq, code, msg); };
+    run.lap(7);
+  }
   // ---- the output turn
   const bool my_turn = wait_turn(s, out_turn, seq);
   run.release = nullptr;   // (taken, or let through by a stream that failed: nothing to pass on any more)
   if (!my_turn) return run.fail(s->failed, s->err);
+  if (!sm->write_bam) {
+    // --nobam: nothing of the output stream is kept -- no tail handed on, no members; the turn itself is passed on in order
+    const hipError_t e = hipStreamSynchronize(st);   // (the XF values are down)
+    if (e != hipSuccess) g_svdss_hip_err = std::string("smooth output turn: ") + hipGetErrorString(e);
+    done_turn(s, out_turn, e == hipSuccess ? SVDSS_OK : SVDSS_EHIP, e == hipSuccess ? std::string() : g_svdss_hip_err);
+    if (e != hipSuccess) { b->err = g_svdss_hip_err; return SVDSS_EHIP; }
+    for (uint8_t v : h_xfv) ++b->sm.xf[v & 3];
+    b->sm_ix.on = false; b->sm_ix.chunks.clear(); b->sm_ix.windows.clear();
+    run.lap(5);
+    b->stage_ms[6] = 0;
+    return SVDSS_OK;
+  }
   int turn_code = SVDSS_OK;
   std::string turn_msg;
   int64_t in_len = 0, stream_bytes = 0, n_blk = 0;
@@ -883,4 +1087,16 @@ extern "C" int svdss_bam_batch_smoothed(const svdss_bam_batch_t* b, svdss_bam_sm
   r->inflate_kernel_ms = b->inflate_ms;
   for (int k = 0; k < 8; ++k) r->stage_ms[k] = b->stage_ms[k];
   return SVDSS_OK;
+}
+
+// A batch whose reads stayed in the batch object (svdss_bam_batch_parked: group -1): searched here, counts and SFS down
+// (svdss_bam_batch_result).  The smoothing run's stage clock stays as it was; the search is added to its stage 7.
+extern "C" int svdss_bam_smooth_search(svdss_bam_batch_t* b, const svdss_index_t* ix) {
+  if (!b || !ix) return SVDSS_EINVAL;
+  double keep[8];
+  for (int k = 0; k < 8; ++k) keep[k] = b->stage_ms[k];
+  const int rc = svdss_bam_batch_search(b, ix);
+  if (rc == SVDSS_OK) keep[7] += b->stage_ms[5] + b->stage_ms[6];
+  for (int k = 0; k < 8; ++k) b->stage_ms[k] = keep[k];
+  return rc;
 }

@@ -15,6 +15,11 @@ struct CallOptions {
   float accp = 0.98f;          // smooth only
   std::string write_index;     // smooth only: --write-index <FILE>, the output's BAI / CSI (bam_index_writer.h)
   int compress = 0;            // smooth only: --compress runs|lz, the GPU deflate's mode (0 runs, 1 lz; csrc/deflate.hip)
+  // smooth only: --index FMD --sfs FILE, the text `SVDSS search` would write for the smoothed BAM (sfs above is FILE), with
+  // search's own --bsize / --noputative / --noassemble; --nobam: no BAM on stdout
+  std::string index;
+  int bsize = 10000;
+  bool putative = true, assemble = true, nobam = false;
   bool verbose = false;         // stage timings on stderr
   int gpus = 1;                 // --gpus N: POA / realignment batches shard by sub-cluster index
   std::string poa;             // --poa <FILE>: consensus alignments as SAM (caller.cpp:65-75)

@@ -29,261 +29,9 @@
 #include "cli_options.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "sfs_units.h"
 
 namespace {
-
-typedef std::chrono::steady_clock::time_point TimePoint;
-TimePoint now() { return std::chrono::steady_clock::now(); }
-double secs(TimePoint a, TimePoint b) { return std::chrono::duration<double>(b - a).count(); }
-struct Stopwatch {   // seconds since the run began, for the --verbose lines
-  TimePoint t0 = now();
-  std::string since() const { return std::to_string(secs(t0, now())); }
-};
-
-// ---- the knobs: every SVDSS_* variable this file reads, read once at the top of main_search (README.md has the table).
-// Not here: SVDSS_KMER / SVDSS_NO_KMER_LIMIT (the library's; choose_kmer_order SETS the first), the oversubscribe knob of
-// effective_gpus (host_common.h), and what bam_device_select.h, bam_reader.h and the library read themselves.
-// the value if it is set and at least `least` / if it is set, raised to `least` / -1 not set, 0 off, 1 on
-int64_t env_from(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e && atoll(e) >= least ? atoll(e) : dflt; }
-int64_t env_raised(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e ? std::max<int64_t>(least, atoll(e)) : dflt; }
-int env_switch(const char* name) { const char* e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }
-struct SearchKnobs {
-  int64_t batch_bytes = env_from("SVDSS_BAM_BATCH_MB", 1, 192) << 20;         // inflated bytes per device batch (192 MB; `smooth` has its own default)
-  size_t slab_bytes = (size_t)env_from("SVDSS_BAM_SLAB_KB", 64, 16 << 10) << 10;   // the scanners' read unit (16 MB, at least 64 KB)
-  int loaders = (int)env_raised("SVDSS_BAM_LOADERS", 1, 8);                   // file-reading threads per scanner (8)
-  int feeders = (int)env_raised("SVDSS_SEARCH_FEEDERS", 1, 6);                // feeding threads per GPU, both paths (6)
-  int format_threads = (int)env_raised("SVDSS_FORMAT_THREADS", 1, 0);         // device path's text formatters (0: five per GPU, as the cores allow)
-  // what may be parked at most, in arenas allocated as they are needed: SVDSS_PARK_GB (32), or SVDSS_PARK_MB (tests)
-  int64_t park_bytes = env_from("SVDSS_PARK_MB", 1, env_from("SVDSS_PARK_GB", 1, 32) << 10) << 20;
-  bool bam_device = env_switch("SVDSS_BAM_DEVICE") != 0;                      // 0: the host path (BamReader) although there is a GPU
-  int early = env_switch("SVDSS_SEARCH_EARLY");                               // front end beside the restore: 1 forces it, 0 forbids it
-  int64_t early_min_mb = getenv("SVDSS_EARLY_MIN_MB") ? atoll(getenv("SVDSS_EARLY_MIN_MB")) : 800;   // ... else from this index size on (800)
-  int early_hold_ms = (int)env_from("SVDSS_EARLY_HOLD_MS", 1, 0);             // tests: the index held back as if its restore took that long
-  int lf = env_switch("SVDSS_SEARCH_LF");                                     // the rank blocks alone: 1 forces, 0 forbids
-  bool lf_max_set = getenv("SVDSS_SEARCH_LF_MAX") != nullptr;                 // ... else up to this many reads to search
-  double lf_max = lf_max_set ? atof(getenv("SVDSS_SEARCH_LF_MAX")) : 0;       //     (default: 2e6 per 6.18e9 BWT symbols)
-  bool prewarm = !getenv("SVDSS_NO_PREWARM");                                 // page-locked buffers allocated beside the restore
-  bool clean_exit = getenv("SVDSS_CLEAN_EXIT") != nullptr;                    // orderly teardown instead of _exit (leak checkers)
-};
-
-// ---- batches
-
-struct Read {
-  std::string name;
-  int hp = 0;
-  int64_t len = 0;
-  int64_t first = 0, count = 0;  // into the result arrays (-1: not searched)
-};
-// page-locked staging buffers (svdss_host_alloc), recycled between batches
-struct PinnedPool {
-  std::mutex m;
-  std::vector<std::pair<uint8_t*, size_t>> free_;
-  uint8_t* get(size_t bytes, size_t& cap) {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      for (size_t i = 0; i < free_.size(); ++i)
-        if (free_[i].second >= bytes) {
-          uint8_t* p = free_[i].first;
-          cap = free_[i].second;
-          free_.erase(free_.begin() + (long)i);
-          return p;
-        }
-    }
-    void* p = nullptr;
-    cap = bytes + bytes / 8 + 4096;
-    check(svdss_host_alloc((int64_t)cap, &p), "svdss_host_alloc");
-    return (uint8_t*)p;
-  }
-  void put(uint8_t* p, size_t cap) {
-    if (!p) return;
-    std::lock_guard<std::mutex> lk(m);
-    free_.emplace_back(p, cap);
-  }
-  ~PinnedPool() { for (auto& f : free_) svdss_host_free(f.first); }
-};
-
-struct SearchBatch {
-  uint64_t seq = 0;              // position in the input: batches are written in this order
-  std::vector<Read> reads;
-  std::vector<uint8_t> gbuf;     // nt6 bases of the searched reads, back to back (FASTX mode)
-  // BAM mode: the 4-bit bases exactly as the records hold them, in page-locked memory; the GPU expands them
-  uint8_t* seq4 = nullptr;
-  size_t seq4_cap = 0;
-  std::vector<int64_t> boff;     // byte offset of every searched read in seq4 (+ end)
-  std::vector<int32_t> lseq;
-  std::vector<int64_t> goff;
-  std::vector<size_t> gidx;      // searched read -> index into reads
-  std::vector<int32_t> qs, ln;   // results
-  std::vector<int64_t> counts;
-  std::string text;              // the batch's lines, formatted by the thread that searched it
-  uint64_t n_lines = 0;
-};
-// batch objects go round: their vectors and text buffers keep their capacity (tens of MB each; a fresh allocation of
-// that size is an mmap, a page fault per 4 KB and a munmap that stalls every other thread of the process)
-class BatchPool {
- public:
-  explicit BatchPool(size_t cap) : cap_(cap) {}
-  std::unique_ptr<SearchBatch> get() {
-    std::unique_ptr<SearchBatch> b;
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      if (!free_.empty()) { b = std::move(free_.back()); free_.pop_back(); }
-    }
-    if (!b) b.reset(new SearchBatch);
-    b->reads.clear(); b->gbuf.clear(); b->boff.clear(); b->lseq.clear();
-    b->goff.clear(); b->gidx.clear(); b->qs.clear(); b->ln.clear(); b->text.clear(); b->counts.clear();
-    b->n_lines = 0; b->seq = 0;
-    return b;
-  }
-  void put(std::unique_ptr<SearchBatch> b) {
-    std::lock_guard<std::mutex> lk(m_);
-    if (free_.size() < cap_) free_.push_back(std::move(b));
-  }
- private:
-  const size_t cap_;
-  std::mutex m_;
-  std::vector<std::unique_ptr<SearchBatch>> free_;
-};
-// Formatted batches arrive out of order (several threads finish them) and are written to stdout in the order of their
-// `seq`; a written batch goes back to the pool.
-class OrderedWriter {
- public:
-  explicit OrderedWriter(BatchPool& pool) : pool_(pool), thread_([this] { run(); }) {}
-  // (bounded: a finished batch waits until fewer than 8 are waiting -- or it is in front of all of them)
-  void put(std::unique_ptr<SearchBatch> b) {
-    std::unique_lock<std::mutex> lk(m_);
-    const uint64_t sq = b->seq;
-    cv_.wait(lk, [&] { return done_.size() < 8 || done_.begin()->first > sq; });
-    done_[sq] = std::move(b);
-    lk.unlock();
-    cv_.notify_all();
-  }
-  // nothing more will be put: returns when everything is written and flushed
-  void finish() {
-    { std::lock_guard<std::mutex> lk(m_); finished_ = true; }
-    cv_.notify_all();
-    thread_.join();
-  }
-  uint64_t lines() const { return lines_; }         // (after finish)
-  double busy_seconds() const { return seconds_; }
- private:
-  void run() {
-    uint64_t want = 0;
-    for (;;) {
-      std::unique_ptr<SearchBatch> bt;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&] { return done_.count(want) || (finished_ && done_.empty()); });
-        auto it = done_.find(want);
-        if (it == done_.end()) break;
-        bt = std::move(it->second);
-        done_.erase(it);
-        ++want;
-      }
-      cv_.notify_all();
-      const auto tw0 = now();
-      fwrite(bt->text.data(), 1, bt->text.size(), stdout);
-      lines_ += bt->n_lines;
-      seconds_ += secs(tw0, now());
-      pool_.put(std::move(bt));
-    }
-    fflush(stdout);
-  }
-  BatchPool& pool_;
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::map<uint64_t, std::unique_ptr<SearchBatch>> done_;
-  bool finished_ = false;
-  uint64_t lines_ = 0;
-  double seconds_ = 0;
-  std::thread thread_;   // (the last member: it runs from the constructor on)
-};
-// busy seconds of the stages, summed over their threads (--verbose)
-struct StageSeconds {
-  std::mutex m;   // for the sums several threads add to:
-  double gpu = 0, inflate_ms = 0, unpack = 0, format = 0, device[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t n_seen = 0, n_batches = 0;
-  double assemble = 0, slice = 0, decode = 0;   // (one thread each: no lock)
-};
-// decimal text of v at w, returns the end
-inline char* put_int(char* w, int64_t v) {
-  if (v < 0) { *w++ = '-'; v = -v; }
-  char tmp[24];
-  int n = 0;
-  do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-  while (n) *w++ = tmp[--n];
-  return w;
-}
-
-template <class T>
-class BoundedQueue {
- public:
-  explicit BoundedQueue(size_t cap) : cap_(cap) {}
-  void push(std::unique_ptr<T> v) {
-    std::unique_lock<std::mutex> lk(m_);
-    not_full_.wait(lk, [&] { return q_.size() < cap_; });
-    q_.push_back(std::move(v));
-    not_empty_.notify_one();
-  }
-  // nullptr = the producer closed the queue and it is drained
-  std::unique_ptr<T> pop() {
-    std::unique_lock<std::mutex> lk(m_);
-    not_empty_.wait(lk, [&] { return !q_.empty() || closed_; });
-    if (q_.empty()) return nullptr;
-    std::unique_ptr<T> v = std::move(q_.front());
-    q_.pop_front();
-    not_full_.notify_one();
-    return v;
-  }
-  void close() {
-    std::lock_guard<std::mutex> lk(m_);
-    closed_ = true;
-    not_empty_.notify_all();
-  }
- private:
-  size_t cap_;
-  std::deque<std::unique_ptr<T>> q_;
-  std::mutex m_;
-  std::condition_variable not_full_, not_empty_;
-  bool closed_ = false;
-};
-// the text of one batch.  output_batch order: reference batches of bsize reads -> thread t takes reads n with
-// n % T == t (ping_pong.cpp:59,101-104) -> std::map<qname, vector<SFS>> order (:217)
-void format_batch(const Options& o, SearchBatch& b) {
-  const std::vector<Read>& reads = b.reads;
-  std::string& out = b.text;
-  out.reserve(b.qs.size() * 24 + 1024);
-  char num[64];
-  for (size_t b0 = 0; b0 < reads.size(); b0 += (size_t)o.bsize) {
-    const size_t b1 = std::min(reads.size(), b0 + (size_t)o.bsize);
-    for (int t = 0; t < o.threads; ++t) {
-      std::map<std::string, std::vector<size_t>> by_name;
-      for (size_t n = b0 + (size_t)t; n < b1; n += (size_t)o.threads)
-        if (reads[n].count >= 0) by_name[reads[n].name].push_back(n);
-      for (const auto& kv : by_name) {
-        bool first = true;
-        for (size_t n : kv.second) {
-          const Read& r = reads[n];
-          for (int64_t k = 0; k < r.count; ++k) {
-            if (first) out += r.name; else out += '*';
-            char* w = num;                      // "\t<qs>\t<len>\t<hp>\t\n" without printf (11 M lines per GB of reads)
-            *w++ = '\t'; w = put_int(w, b.qs[(size_t)(r.first + k)]);
-            *w++ = '\t'; w = put_int(w, b.ln[(size_t)(r.first + k)]);
-            *w++ = '\t'; w = put_int(w, r.hp);
-            *w++ = '\t'; *w++ = '\n';
-            out.append(num, (size_t)(w - num));
-            first = false;
-            ++b.n_lines;
-          }
-        }
-      }
-    }
-  }
-}
-// One GPU launch covers many reference-sized batches; the text is still emitted batch by
-// batch, thread slice by thread slice, read names in std::map order (ping_pong.cpp:215-217).
-// (32 k reads keep the GPU efficient and let parsing, search and output of successive batches overlap)
-int64_t reads_per_unit(const Options& o) { return std::max<int64_t>(o.bsize, 32768 / o.bsize * (int64_t)o.bsize); }
 
 // ---- `search --bam` with the records handled where they are inflated (csrc/bam_device.hip): the host reads the file,
 // finds the BGZF members, hands runs of them to the GPUs and gets names, tags and SFS back -- through the front end that
@@ -297,7 +45,6 @@ int64_t reads_per_unit(const Options& o) { return std::max<int64_t>(o.bsize, 327
 // (ShardedBamSelect: a region's first record is guessed, and proved at the seam or the region runs again).  The reads of a
 // region are dealt into units when everything before it has been (the unit a read belongs to depends on the reads in front
 // of it), so the later regions' results wait in memory (~0.6 KB per read).
-struct DevOut { std::vector<Read> reads; std::vector<int32_t> qs, ln; int64_t n_short = 0; std::vector<int32_t> sidx; };
 // the file as the device path reads it: its regions (plan_bam_regions) and one scanner per region, opened before the index is
 // restored and kept open to the end (the process ends with _exit: their page-locked slabs are never handed back one by one)
 struct DeviceBamInput {
@@ -308,104 +55,18 @@ struct DeviceBamInput {
   int64_t skip = 0;
   size_t n_regions() const { return cuts.size() - 1; }
 };
-// `SVDSS search` with the BAM front end started BEFORE the index is resident (include/svdss_hip.h, svdss_bam_park_*): while
-// the feeders have no index they run the front half of their batches and park the unpacked reads in HBM; when the index is
-// there the parked groups are searched one large launch each (the drain thread), and the feeders go on with whole batches.
-//
-// Who touches what: `park` and `file_bytes` are set before the first feeder runs and only read then; the four counters are
-// atomics, added to by the feeders and read by anyone; everything private is under `m_`, reached through the methods alone,
-// and `cv_` is notified on every change somebody may wait for.
-class EarlySearch {
- public:
-  struct Pending { uint64_t seq; std::unique_ptr<DevOut> out; int64_t first, n; };
-  svdss_bam_park_t* park = nullptr;
-  int64_t file_bytes = 0;
-  // what the front end has seen so far (the order of the k-mer table is chosen from it: svdss_index_kmer_limit)
-  std::atomic<int64_t> records{0}, searched{0}, comp_bytes{0}, index_n{0};
-
-  // feeder, before a batch: the index if the feeders have it (a whole batch) -- null: the front half, the reads parked
-  svdss_index_t* index_for_feeders() { std::lock_guard<std::mutex> lk(m_); return ready_ ? ix_ : nullptr; }
-  // how many reads there will be to search, from what has been seen (-1: nothing seen yet); both cost models use it
-  double estimate_reads_to_search() const {
-    const int64_t recs = records.load(), srch = searched.load(), cb = comp_bytes.load();
-    return recs > 0 && cb > 0 ? (double)srch / (double)recs * ((double)recs * (double)file_bytes / (double)cb) : -1;
-  }
-  // feeder, after a front half: the counters, and from them the order of the k-mer table (its build begins when the suffix
-  // array is sorted; the limit is read then)
-  void note_batch(int64_t n_records, int64_t n_searched, int64_t batch_comp_bytes) {
-    const int64_t recs = (records += n_records);
-    searched += n_searched; comp_bytes += batch_comp_bytes;
-    if (index_n.load() < ((int64_t)1 << 31) || recs < 50000 || getenv("SVDSS_KMER") || getenv("SVDSS_NO_KMER_LIMIT")) return;
-    const double est = estimate_reads_to_search();
-    if (est < 0) return;
-    // build: 1.6 s at K = 16, a quarter of that per step down; kernel: 16 M reads/s at K = 16, half of that per step down
-    // (profiles/r05i_restore_by_table_order.txt); its seconds count double, as in choose_kmer_order
-    auto cost = [&](int k) { return 1.6 * std::pow(4.0, k - 16) + 2 * est / 16e6 * std::pow(2.2, 16 - k); };
-    int best = 16;
-    for (int k = 15; k >= 12; --k) if (cost(k) < cost(best)) best = k;
-    if (cost(best) > 0.8 * cost(16)) best = 16;     // (a clear gain or none)
-    std::lock_guard<std::mutex> lk(m_);
-    if (best != kmer_limit_) { kmer_limit_ = best; svdss_index_kmer_limit(best == 16 ? 0 : best); }
-  }
-  // feeder whose batch found no room in the park (or it has just been closed): the batch waits here for the index
-  svdss_index_t* wait_for_index() {
-    std::unique_lock<std::mutex> lk(m_);
-    park_full_ = true;
-    cv_.notify_all();
-    return wait_for(lk, [&] { return ready_; });
-  }
-  // a parked batch's names and tags wait for its group's search / the drain thread takes a group's `n` batches
-  void add_pending(int64_t group, Pending p) { change([&] { by_group_[group].push_back(std::move(p)); }); }
-  std::vector<Pending> take_group(int64_t group, int64_t n) {
-    std::unique_lock<std::mutex> lk(m_);
-    wait_for(lk, [&] { return (int64_t)by_group_[group].size() == n; });
-    return std::move(by_group_[group]);
-  }
-  // main thread: the index is resident but held back from the feeders (the rank blocks alone, resident long before the file
-  // has been read) until the front end is through -- or the park is full --, so that what is parked goes in large launches,
-  // one lane per read, instead of a small segmented launch per batch.  The drain thread has it at once and searches the
-  // groups as they close.
-  void offer_index_held_back(svdss_index_t* ix) {
-    std::unique_lock<std::mutex> lk(m_);
-    ix_ = ix; ix_avail_ = true;
-    cv_.notify_all();
-    wait_for(lk, [&] { return front_done_ || park_full_; });
-  }
-  // main thread: from now on the feeders run whole batches
-  void release_index(svdss_index_t* ix) { change([&] { ix_ = ix; ready_ = true; }); }
-  // every feeding thread has ended
-  void front_finished() { change([&] { front_done_ = true; }); }
-  bool front_is_finished() { std::lock_guard<std::mutex> lk(m_); return front_done_; }
-  // drain thread: the index once it is offered or released; whether the feeders have it; a short wait for news
-  svdss_index_t* wait_for_offered_index() { std::unique_lock<std::mutex> lk(m_); return wait_for(lk, [&] { return ready_ || ix_avail_; }); }
-  bool released() { std::lock_guard<std::mutex> lk(m_); return ready_; }
-  void nap() { std::unique_lock<std::mutex> lk(m_); cv_.wait_for(lk, std::chrono::milliseconds(2)); }
- private:
-  template <class F> void change(F f) { { std::lock_guard<std::mutex> lk(m_); f(); } cv_.notify_all(); }
-  template <class P> svdss_index_t* wait_for(std::unique_lock<std::mutex>& lk, P pred) { cv_.wait(lk, pred); return ix_; }
-  std::mutex m_;
-  std::condition_variable cv_;
-  svdss_index_t* ix_ = nullptr;      // set once, with ready_ -- or before it, with ix_avail_
-  bool ready_ = false, ix_avail_ = false;
-  std::map<int64_t, std::vector<Pending>> by_group_;
-  bool front_done_ = false, park_full_ = false;
-  int kmer_limit_ = 0;               // the last limit given
-};
-
 class DevicePath {
  public:
   DevicePath(const Options& o, const SearchKnobs& knobs, const std::vector<svdss_index_t*>& replicas, const DeviceBamInput& in,
              const Stopwatch& clock, EarlySearch* early = nullptr)
-      : o_(o), knobs_(knobs), replicas_(replicas), in_(in), clock_(clock), early_(early), super_(reads_per_unit(o)),
+      : o_(o), knobs_(knobs), replicas_(replicas), in_(in), clock_(clock), early_(early),
         flags_((o.assemble ? SVDSS_SFS_ASSEMBLE : 0) | (o.putative ? SVDSS_BAM_PUTATIVE : 0)) {}
   void run();
  private:
   BamRunFn run_on(size_t r);
   std::unique_ptr<DevOut> collect(const svdss_bam_batch_t* batch, uint64_t seq);
   std::unique_ptr<DevOut> next() { return one_ ? one_->next() : sharded_->next(); }
-  void deal(DevOut& d);
   void assemble();
-  void format_units();
   void drain_park();
   void report();
 
@@ -415,14 +76,10 @@ class DevicePath {
   const DeviceBamInput& in_;
   const Stopwatch& clock_;
   EarlySearch* const early_;
-  const int64_t super_;
   const int32_t flags_;
   StageSeconds t_;
   // units of whole reference batches, formatted by a few threads, written in order
-  BoundedQueue<SearchBatch> units_{4};
-  BatchPool pool_{16};
-  std::unique_ptr<SearchBatch> unit_;   // (the assembler's: the unit being filled)
-  uint64_t unit_seq_ = 0;
+  UnitAssembler units_{o_, t_};
   // the file's batches in file order: one region (every replica's feeders take its batches) or one region per replica
   std::unique_ptr<DeviceBamSelect<DevOut>> one_;
   std::unique_ptr<ShardedBamSelect<DevOut>> sharded_;
@@ -461,26 +118,7 @@ std::unique_ptr<DevOut> DevicePath::collect(const svdss_bam_batch_t* batch, uint
   const bool parked = early_ && svdss_bam_batch_parked(batch, &grp, &first, &n_srch) == SVDSS_OK && grp >= 0;
   svdss_bam_result_t r;
   check(svdss_bam_batch_result(batch, &r), "svdss_bam_batch_result");
-  std::unique_ptr<DevOut> out(new DevOut);
-  out->n_short = r.n_short;
-  out->reads.resize((size_t)r.n_slots);
-  if (parked) {
-    // the front half only: names and tags; counts and SFS follow when the batch's group has been searched
-    out->sidx.assign(r.sidx, r.sidx + r.n_slots);
-  } else {
-    out->qs.assign(r.qs, r.qs + r.total_sfs);
-    out->ln.assign(r.len, r.len + r.total_sfs);
-  }
-  // (searched reads are numbered in slot order, so their SFS follow each other in slot order too)
-  int64_t acc = 0;
-  for (int64_t i = 0; i < r.n_slots; ++i) {
-    Read& rd = out->reads[(size_t)i];
-    rd.name.assign(r.names + r.name_off[i], (size_t)(r.name_off[i + 1] - r.name_off[i]));
-    rd.hp = r.hp[i];
-    rd.first = acc;
-    rd.count = r.sidx[i] < 0 ? -1 : parked ? 0 : r.counts[r.sidx[i]];
-    if (rd.count > 0) acc += rd.count;
-  }
+  std::unique_ptr<DevOut> out = unpack_result(r, parked);
   {
     std::lock_guard<std::mutex> lk(t_.m);
     t_.unpack += secs(t1, now()); t_.inflate_ms += r.inflate_kernel_ms;
@@ -491,38 +129,16 @@ std::unique_ptr<DevOut> DevicePath::collect(const svdss_bam_batch_t* batch, uint
   early_->add_pending(grp, EarlySearch::Pending{seq, std::move(out), first, n_srch});
   return nullptr;
 }
-// the reads of a device batch into the unit being filled; full units go to the formatters
-void DevicePath::deal(DevOut& d) {
-  const auto ta = now();
-  // (said when the batch is dealt, not when it was read: a region that runs twice says it once)
-  for (int64_t k = 0; k < d.n_short; ++k) logmsg("warning", "Alignment filtered due to l_qseq. Why are we here? Please check");   // :70-75
-  for (Read& r : d.reads) {
-    const int64_t first = r.first;
-    r.first = (int64_t)unit_->qs.size();
-    if (r.count > 0) {
-      unit_->qs.insert(unit_->qs.end(), d.qs.begin() + first, d.qs.begin() + first + r.count);
-      unit_->ln.insert(unit_->ln.end(), d.ln.begin() + first, d.ln.begin() + first + r.count);
-    }
-    unit_->reads.push_back(std::move(r));
-    if ((int64_t)unit_->reads.size() == super_) {
-      unit_->seq = unit_seq_++;
-      units_.push(std::move(unit_));
-      unit_ = pool_.get();
-    }
-  }
-  t_.assemble += secs(ta, now());
-}
 void DevicePath::assemble() {
-  unit_ = pool_.get();
-  while (std::unique_ptr<DevOut> d = next()) deal(*d);
+  units_.begin();
+  while (std::unique_ptr<DevOut> d = next()) units_.deal(*d);
   const BamRunError e = one_ ? one_->failure() : sharded_->failure();
   if (e.failed()) {
     if (e.msg.find("core.tid") != std::string::npos) die(e.msg);                       // ping_pong.cpp:76-79
     if (e.rc == SVDSS_EIO) die("error reading " + o_.bam + ": " + e.msg);
     die(std::string("svdss_bam_batch_run: ") + svdss_strerror(e.rc) + " " + e.msg + " " + e.hip);
   }
-  if (!unit_->reads.empty()) { unit_->seq = unit_seq_++; units_.push(std::move(unit_)); }
-  units_.close();
+  units_.end();
 }
 // early: once the index is resident, the parked groups -- ONE launch each, one lane per read -- and their batches' results
 void DevicePath::drain_park() {
@@ -558,19 +174,7 @@ void DevicePath::drain_park() {
     prefix.assign((size_t)nr + 1, 0);
     for (int64_t i = 0; i < nr; ++i) prefix[(size_t)i + 1] = prefix[(size_t)i] + counts[(size_t)i];
     for (EarlySearch::Pending& P : early_->take_group(g, nb)) {
-      DevOut& d = *P.out;
-      int64_t acc = 0;
-      for (size_t i = 0; i < d.reads.size(); ++i) {
-        Read& rd = d.reads[i];
-        rd.first = acc;
-        if (d.sidx[i] < 0) { rd.count = -1; continue; }
-        const size_t k = (size_t)(P.first + d.sidx[i]);
-        rd.count = counts[k];
-        d.qs.insert(d.qs.end(), qs.begin() + prefix[k], qs.begin() + prefix[k + 1]);
-        d.ln.insert(d.ln.end(), ln.begin() + prefix[k], ln.begin() + prefix[k + 1]);
-        acc += rd.count;
-      }
-      d.sidx.clear();
+      fill_parked(P, counts, prefix, qs, ln);
       one_->deliver(P.seq, std::move(P.out));
     }
     n_parked += nr; n_parked_batches += nb;
@@ -582,14 +186,6 @@ void DevicePath::drain_park() {
                         " records) had been read when the index was resident; their " + std::to_string(n_parked) + " reads searched in " +
                         std::to_string(n_groups) + " launch(es), " + std::to_string(t_search) + " s" +
                         (n_early_groups ? " (" + std::to_string(n_early_groups) + " of them while the file was still being read)" : "") + ", done at +" + clock_.since() + " s");
-}
-void DevicePath::format_units() {
-  while (std::unique_ptr<SearchBatch> u = units_.pop()) {
-    const auto tf = now();
-    format_batch(o_, *u);
-    { std::lock_guard<std::mutex> lk(t_.m); t_.format += secs(tf, now()); }
-    writer_->put(std::move(u));
-  }
 }
 void DevicePath::run() {
   const size_t pending = 8;       // (results of the region being dealt that may wait for the assembler)
@@ -610,11 +206,11 @@ void DevicePath::run() {
     sharded_.reset(new ShardedBamSelect<DevOut>(o_.bam, hk, in_.n_ref, in_.skip, knobs_.feeders, knobs_.batch_bytes, in_.cuts, pending, in_.scanner_ptrs));
   }
   std::thread assembler([this] { assemble(); });
-  writer_.reset(new OrderedWriter(pool_));
+  writer_.reset(new OrderedWriter(units_.pool()));
   // (formatting the text costs about one core-second per million reads: five threads per GPU, as many as the cores allow)
   const int n_fmt = knobs_.format_threads ? knobs_.format_threads : (int)std::max<size_t>(5, std::min<size_t>(5 * replicas_.size(), effective_cpus()));
   std::vector<std::thread> fmt;
-  for (int k = 0; k < n_fmt; ++k) fmt.emplace_back([this] { format_units(); });
+  for (int k = 0; k < n_fmt; ++k) fmt.emplace_back([this] { units_.format_units(*writer_); });
   if (early_) {
     std::thread drain([this] { drain_park(); });
     one_->wait_finished();
@@ -933,56 +529,9 @@ void SearchRun::load_index() {
   if (early) early->index_n.store(svdss_index_size(ix));
   if (o.verbose) logmsg("debug", "index file read at +" + clock.since() + " s");
 }
-void SearchRun::choose_kmer_order() {
-  user_kmer = getenv("SVDSS_KMER") != nullptr;      // (this function may set the variable itself)
-  if (user_kmer) return;
-  // The order K of the k-mer table trades its build time (4^K entries: 1.6 s at K = 16, a quarter of that per step
-  // down) against the search kernel's speed (about a third slower per step down).  The library's own choice (K = 16
-  // from 64 Mb on) is the one for a resident index that searches batch after batch; a process that restores the
-  // index for ONE input knows roughly how many reads are coming (a BAM is ~1 byte per base, a FASTQ ~2) and takes the
-  // K that minimises build + search.  Results never depend on K (tests/test_sfs_gpu.py, tests/test_scale_gpu.py).
-  struct stat st;
-  const std::string& input = bam_mode ? o.bam : o.fastx;
-  // (references above 2^31 symbols keep the library's K: nothing below 16 was measured there)
-  const int64_t n = svdss_index_size(ix);
-  if (stat(input.c_str(), &st) != 0 || st.st_size <= 0 || n >= ((int64_t)1 << 31)) return;
-  const double est_reads = (double)st.st_size / (bam_mode ? 15000.0 : 30000.0);
-  int k_auto = 1;
-  while (k_auto < 16 && ((int64_t)1 << (2 * k_auto)) <= n) ++k_auto;
-  k_auto = std::min(16, k_auto + 2);
-  int best = k_auto;
-  double best_cost = 1e300;
-  for (int k = k_auto; k >= std::max(8, k_auto - 5); --k) {
-    // (the kernel's seconds count double: they are GPU time the BGZF inflate of the stream wants too)
-    const double build = 1.6 * std::pow(4.0, k - 16), kernel = est_reads / 15e6 * std::pow(1.35, 16 - k);
-    if (build + 2 * kernel < best_cost) { best_cost = build + 2 * kernel; best = k; }
-  }
-  if (best == k_auto) return;
-  setenv("SVDSS_KMER", std::to_string(best).c_str(), 0);
-  if (o.verbose) logmsg("debug", "k-mer table of order " + std::to_string(best) + " for ~" + std::to_string((long long)est_reads) + " reads");
-}
-// Few reads to search (the front end has seen enough to say: `search` on a smoothed BAM skips what `smooth` tagged XF != 0)
-// and the sidecar carries the rank blocks: the index as a rank structure ALONE -- 3 GB uploaded instead of six billion
-// suffixes sorted for a text, a suffix array and a k-mer table; ~1 M reads/s instead of 8 - 24 M, results identical
-// (svdss_index_attach_blocks).  SVDSS_SEARCH_LF=0|1 forces the choice, SVDSS_SEARCH_LF_MAX moves the threshold (reads).
+void SearchRun::choose_kmer_order() { user_kmer = ::choose_kmer_order(bam_mode ? o.bam : o.fastx, bam_mode, ix, o.verbose); }   // (sfs_units.h)
 void SearchRun::choose_rank_blocks_alone() {
-  if (!early || user_kmer || knobs.lf == 0) return;
-  const bool forced = knobs.lf == 1;
-  const auto w0 = now();
-  while (!forced && !early->front_is_finished() && early->records.load() < 50000 && secs(w0, now()) <= 1.5)
-    std::this_thread::sleep_for(std::chrono::milliseconds(5));
-  const double est = early->estimate_reads_to_search();
-  const std::string t_est = clock.since();
-  // (what the rank structure alone saves is the rest of the restore -- ~4.5 s at GRCh38 lengths, in proportion for a
-  // smaller reference --, what it costs is the search at ~1 M reads/s instead of 8 - 24 M: worth it below ~2 M reads
-  // per 6.2e9 BWT symbols; profiles/r06q_*)
-  const double lf_max = knobs.lf_max_set ? knobs.lf_max : 2e6 * (double)svdss_index_size(ix) / 6.18e9;
-  if (!forced && !(est >= 0 && est <= lf_max)) return;
-  const int rc = svdss_index_attach_blocks(ix, o.index.c_str());
-  if (rc == SVDSS_OK) {
-    lf_only = true;
-    if (o.verbose) logmsg("debug", "~" + std::to_string((long long)std::max(0.0, est)) + " reads to search (known at +" + t_est + " s): the index as a rank structure alone (blocks read at +" + clock.since() + " s)");
-  } else if (rc != SVDSS_EINVAL) check(rc, "svdss_index_attach_blocks");
+  if (early) lf_only = ::choose_rank_blocks_alone(knobs, *early, ix, o.index, user_kmer, o.verbose, clock);   // (sfs_units.h)
 }
 void SearchRun::index_to_device() {
   check(svdss_index_to_device(ix, 0), "svdss_index_to_device");

@@ -33,6 +33,7 @@
 #include "bam_index_writer.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "sfs_units.h"
 
 namespace {
 const int MIN_INDEL = 20;   // config.hpp:95
@@ -174,11 +175,196 @@ void write_record(ByteSink& w, const BamRecord& r, const std::vector<uint32_t>& 
   for (int32_t i = 0; i < l_seq; ++i) packed[(size_t)i >> 1] |= (uint8_t)(lut[(uint8_t)seq[(size_t)i]] << ((~i & 1) << 2));
   write_record_packed(w, r, cigar.data(), cigar.size(), packed.data(), l_seq, qual.data(), aux);
 }
+
+// ---- `smooth --index FMD --sfs FILE`: the search of the smoothed reads beside the smoothing.  The device path leaves, per
+// batch, what `search`'s front end would have read from the smoothed BAM (svdss_bam_smooth_set_search): names and tags on
+// the host, the reads to search in a park in HBM.  A side thread makes the index resident from process start on; until it
+// is, the reads wait in the park (a full park: the feeding threads wait for the index); a drain thread searches the park's
+// groups, one launch each; batches that found the index resident are searched by their feeding thread.  Finished batches
+// go to the assembler in file order -- whenever they finish, without a bound: the BAM's hand-over never waits for a search
+// -- and from there through search's own units, format_batch and ordered writer into FILE.
+class SfsSide {
+ public:
+  SfsSide(const CallOptions& c, FILE* sink) : sink_(sink) {
+    o_.index = c.index; o_.bam = c.bam; o_.threads = std::max(1, c.threads); o_.bsize = c.bsize; o_.putative = c.putative; o_.assemble = c.assemble;
+    o_.verbose = c.verbose || getenv("SVDSS_DEBUG") != nullptr;
+    flags_ = (o_.assemble ? SVDSS_SFS_ASSEMBLE : 0) | (o_.putative ? SVDSS_BAM_PUTATIVE : 0);
+    struct stat stb;
+    early_.file_bytes = stat(c.bam.c_str(), &stb) == 0 ? (int64_t)stb.st_size : 0;
+    index_thread_ = std::thread([this] { make_index_resident(); });
+  }
+  int32_t flags() const { return flags_; }
+  // the park, allocated before the stream starts (the device's context must be up)
+  svdss_bam_park_t* create_park() {
+    check(svdss_bam_park_create(0, knobs_.park_bytes, knobs_.park_bytes / 512 + 4096, &early_.park), "svdss_bam_park_create");
+    return early_.park;
+  }
+  // the stream starts: the threads behind the feeders
+  void begin() {
+    writer_.reset(new OrderedWriter(units_.pool(), sink_));
+    drain_ = std::thread([this] { drain_park(); });
+    assembler_ = std::thread([this] { assemble(); });
+    for (int k = 0; k < (knobs_.format_threads ? knobs_.format_threads : 5); ++k) fmt_.emplace_back([this] { units_.format_units(*writer_); });
+  }
+  // feeding thread, after a batch's smoothing run: a batch that found no room in the park waits for the index and is searched here
+  int after_run(svdss_bam_batch_t* batch, int64_t comp_bytes) {
+    int64_t grp = -1;
+    check(svdss_bam_batch_parked(batch, &grp, nullptr, nullptr), "svdss_bam_batch_parked");
+    svdss_bam_result_t r0;
+    check(svdss_bam_batch_result(batch, &r0), "svdss_bam_batch_result");
+    early_.note_batch(r0.n_records, r0.n_searched, comp_bytes);
+    if (grp != -1) return SVDSS_OK;     // (parked, or nothing to search)
+    ++n_direct_;
+    return svdss_bam_smooth_search(batch, early_.wait_for_index());
+  }
+  // feeding thread, with the batch's results: to the assembler, or to wait for its group's search
+  void collect(const svdss_bam_batch_t* batch, uint64_t seq) {
+    int64_t grp = -1, first = 0, n_srch = 0;
+    // (a batch its feeding thread has searched no longer answers svdss_bam_batch_parked: its front half is used up, it is
+    // complete -- as in DevicePath::collect of search_host.cpp)
+    const bool parked = svdss_bam_batch_parked(batch, &grp, &first, &n_srch) == SVDSS_OK && grp >= 0;
+    svdss_bam_result_t r;
+    check(svdss_bam_batch_result(batch, &r), "svdss_bam_batch_result");
+    std::unique_ptr<DevOut> out = unpack_result(r, parked);
+    if (parked) early_.add_pending(grp, EarlySearch::Pending{seq, std::move(out), first, n_srch});
+    else deliver(seq, std::move(out));
+  }
+  // every batch of the file (n_batches of them) has been collected: the rest of the park, the rest of the text
+  void finish(uint64_t n_batches) {
+    early_.front_finished();
+    index_thread_.join();
+    drain_.join();
+    { std::lock_guard<std::mutex> lk(m_); total_ = n_batches; total_known_ = true; }
+    cv_.notify_all();
+    assembler_.join();
+    for (std::thread& t : fmt_) t.join();
+    writer_->finish();
+    if (writer_->failed() || fclose(sink_) != 0) die("error writing the SFS file");
+    if (o_.verbose) {
+      char buf[400];
+      snprintf(buf, sizeof buf, "sfs: %lld reads parked in %lld batch(es), %lld group(s) searched (%.3f s), %lld batch(es) searched by their feeding thread; index resident "
+               "at +%.3f s (%s); %llu SFS lines written; re-dealing %.3f s, format %.3f s, write %.3f s", (long long)n_parked_, (long long)n_parked_batches_,
+               (long long)n_groups_, t_park_search_, (long long)n_direct_.load(), t_resident_, lf_only_ ? "rank blocks alone" : "full restore",
+               (unsigned long long)writer_->lines(), t_.assemble, t_.format, writer_->busy_seconds());
+      logmsg("debug", buf);
+    }
+  }
+ private:
+  // the side thread: the index file, the form it becomes resident in (SVDSS_KMER, SVDSS_SEARCH_LF, SVDSS_SEARCH_LF_MAX as
+  // for `search`; the estimate of the reads to search runs on the XF counts the batches bring), then to the feeders
+  void make_index_resident() {
+    svdss_index_t* ix = nullptr;
+    check(svdss_index_load(o_.index.c_str(), &ix), "svdss_index_load");
+    early_.index_n.store(svdss_index_size(ix));
+    const bool user_kmer = choose_kmer_order(o_.bam, true, ix, o_.verbose);
+    lf_only_ = choose_rank_blocks_alone(knobs_, early_, ix, o_.index, user_kmer, o_.verbose, clock_);
+    check(svdss_index_to_device(ix, 0), "svdss_index_to_device");
+    t_resident_ = secs(clock_.t0, now());
+    // (the rank blocks alone: held back from the feeders until the file is through or the park is full, so that what is
+    // parked goes in large launches; the drain thread has the index at once)
+    if (lf_only_) early_.offer_index_held_back(ix);
+    if (knobs_.early_hold_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(knobs_.early_hold_ms));
+    early_.release_index(ix);
+  }
+  void deliver(uint64_t seq, std::unique_ptr<DevOut> out) {
+    { std::lock_guard<std::mutex> lk(m_); ready_[seq] = std::move(out); }
+    cv_.notify_all();
+  }
+  void assemble() {
+    units_.begin();
+    for (uint64_t want = 0;; ++want) {
+      std::unique_ptr<DevOut> d;
+      {
+        std::unique_lock<std::mutex> lk(m_);
+        cv_.wait(lk, [&] { return ready_.count(want) || (total_known_ && want >= total_); });
+        auto it = ready_.find(want);
+        if (it == ready_.end()) break;
+        d = std::move(it->second);
+        ready_.erase(it);
+      }
+      units_.deal(*d);
+    }
+    units_.end();
+  }
+  // the park's groups, ONE launch each: those that close while the index is held back from the feeders, and -- once the
+  // feeders have it and the park is closed -- whatever is left (DevicePath::drain_park of search_host.cpp)
+  void drain_park() {
+    svdss_index_t* ix = early_.wait_for_offered_index();
+    svdss_sfs_batch_t* sfs = nullptr;
+    std::vector<int64_t> counts, prefix;
+    std::vector<int32_t> qs, ln;
+    bool closed = false;
+    int64_t n_groups = 0;
+    for (int64_t g = 0;; ++g) {
+      for (;;) {
+        if (!closed && early_.released()) {
+          check(svdss_bam_park_close(early_.park), "svdss_bam_park_close");
+          closed = true;
+          n_groups = svdss_bam_park_groups(early_.park);
+        }
+        if (closed || svdss_bam_park_group_ready(early_.park, g)) break;
+        early_.nap();
+      }
+      if (closed && g >= n_groups) break;
+      int64_t nb = 0, nr = 0, ns = 0;
+      check(svdss_bam_park_group(early_.park, g, &nb, &nr, &ns), "svdss_bam_park_group");
+      const auto t0 = now();
+      check(svdss_bam_park_search(early_.park, g, ix, flags_, &sfs), "svdss_bam_park_search");
+      const int64_t total = svdss_sfs_batch_total(sfs);
+      counts.resize((size_t)nr); qs.resize((size_t)total); ln.resize((size_t)total);
+      check(svdss_sfs_batch_fetch(sfs, counts.data(), qs.data(), ln.data(), nullptr), "svdss_sfs_batch_fetch");
+      t_park_search_ += secs(t0, now());
+      prefix.assign((size_t)nr + 1, 0);
+      for (int64_t i = 0; i < nr; ++i) prefix[(size_t)i + 1] = prefix[(size_t)i] + counts[(size_t)i];
+      for (EarlySearch::Pending& P : early_.take_group(g, nb)) {
+        fill_parked(P, counts, prefix, qs, ln);
+        deliver(P.seq, std::move(P.out));
+      }
+      n_parked_ += nr; n_parked_batches_ += nb; ++n_groups_;
+    }
+    if (sfs) svdss_sfs_batch_free(sfs);
+  }
+
+  Options o_;
+  const SearchKnobs knobs_{};
+  const Stopwatch clock_{};
+  FILE* const sink_;
+  int32_t flags_ = 0;
+  EarlySearch early_;
+  StageSeconds t_;
+  UnitAssembler units_{o_, t_};
+  std::unique_ptr<OrderedWriter> writer_;
+  std::mutex m_;
+  std::condition_variable cv_;
+  std::map<uint64_t, std::unique_ptr<DevOut>> ready_;   // finished batches the assembler has not reached yet
+  uint64_t total_ = 0;
+  bool total_known_ = false;
+  bool lf_only_ = false;
+  double t_resident_ = 0, t_park_search_ = 0;
+  int64_t n_parked_ = 0, n_parked_batches_ = 0, n_groups_ = 0;
+  std::atomic<int64_t> n_direct_{0};
+  std::thread index_thread_, drain_, assembler_;
+  std::vector<std::thread> fmt_;
+};
 }  // namespace
 
 int main_smooth(const CallOptions& o) {
   std::unordered_map<std::string, std::string> chrom;
   const auto t_fasta0 = std::chrono::steady_clock::now();
+  // --index FMD --sfs FILE: what it cannot run on is said before FILE or anything else is created; then the index is on its
+  // way from the first moment
+  std::unique_ptr<SfsSide> side;
+  if (!o.sfs.empty()) {
+    if (o.gpus != 1) die("smooth --index --sfs with --gpus other than 1 is out of scope: run it on one GPU");
+    if (getenv("SVDSS_SMOOTH_HOST") || (getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0) ||
+        (getenv("SVDSS_GPU_DEFLATE") && atoi(getenv("SVDSS_GPU_DEFLATE")) == 0))
+      die("smooth --index --sfs needs the device path: it does not run with SVDSS_SMOOTH_HOST=1, SVDSS_BAM_DEVICE=0 or SVDSS_GPU_DEFLATE=0");
+    if (svdss_device_count() <= 0) die("no GPU found: smooth --index --sfs searches the smoothed reads on the GPU");
+    if (o.bsize <= 0) die("batch size smaller than the number of threads");
+    FILE* f = fopen(o.sfs.c_str(), "wb");
+    if (!f) die("cannot write " + o.sfs);
+    side.reset(new SfsSide(o, f));
+  }
   // the HIP runtime and the device's context come up (a few tenths of a second) while the FASTA is read
   std::thread gpu_warm([] {
     void* q = nullptr;
@@ -213,6 +399,7 @@ int main_smooth(const CallOptions& o) {
   }
   gpu_warm.join();
   header_pre.join();
+  svdss_bam_park_t* const park = side ? side->create_park() : nullptr;
   // --write-index FILE: the scheme from the header's references, refused before anything is written; the index goes to
   // FILE only once the BAM's EOF marker is out (any failure before leaves no index)
   bool ix_csi = false;
@@ -327,13 +514,19 @@ int main_smooth(const CallOptions& o) {
                                        svdss_bam_batch_t** batch) {
         { std::unique_lock<std::mutex> lk(gate.m); gate.cv.wait(lk, [&] { return gate.open; }); }
         tl_slot = use_pool ? pool.take() : -1;
-        const int rc = svdss_bam_smooth_run(st, seq, last, sk, sms[g % sms.size()], al_accuracy, tl_slot >= 0 ? pool.buf[(size_t)tl_slot] : nullptr,
+        int rc = svdss_bam_smooth_run(st, seq, last, sk, sms[g % sms.size()], al_accuracy, tl_slot >= 0 ? pool.buf[(size_t)tl_slot] : nullptr,
                                             tl_slot >= 0 ? (int64_t)pool.cap : 0, nc, comp, cb, blocks, crc, nb, batch);
+        if (rc == SVDSS_OK && side) {
+          int64_t job_comp = 0;
+          for (int32_t k = 0; k < nc; ++k) job_comp += cb[k];
+          rc = side->after_run(*batch, job_comp);
+        }
         if (rc != SVDSS_OK && tl_slot >= 0) { pool.give(tl_slot); tl_slot = -1; }
         return rc;
       });
     };
-    DeviceBamSelect<SelectedBatch>::CollectFn collect = [&](const svdss_bam_batch_t* b, uint64_t) {
+    DeviceBamSelect<SelectedBatch>::CollectFn collect = [&](const svdss_bam_batch_t* b, uint64_t seq) {
+      if (side) side->collect(b, seq);
       std::unique_ptr<SelectedBatch> out(new SelectedBatch);
       svdss_bam_smoothed_t r;
       (void)svdss_bam_batch_smoothed(b, &r);
@@ -357,7 +550,7 @@ int main_smooth(const CallOptions& o) {
     if (dbg) fprintf(stderr, "[smooth] BAM header read, output prefix set at +%.3f s\n", since());
     std::unique_ptr<DeviceBamSelect<SelectedBatch>> rd;
     std::unique_ptr<ShardedBamSelect<SelectedBatch>> rds;
-    if (n_regions == 1) rd.reset(new DeviceBamSelect<SelectedBatch>(o.bam, 1, n_ref, skip, per_gpu, target, run_for(0, true), collect, stream));
+    if (n_regions == 1) rd.reset(new DeviceBamSelect<SelectedBatch>(o.bam, 1, n_ref, skip, per_gpu, target, run_for(0, !o.nobam), collect, stream));
     else {
       ShardedBamSelect<SelectedBatch>::Hooks hk;
       hk.run = [&](size_t g, bool seam) { return run_for(g, g == 0 && !seam); };
@@ -386,6 +579,8 @@ int main_smooth(const CallOptions& o) {
         if (rcs[d] == SVDSS_OK) rcs[d] = svdss_bam_smooth_create(drefs[d], tid_map.data(), (int32_t)tid_map.size(), (int32_t)o.min_mapq, &sms[d]);
         if (rcs[d] == SVDSS_OK && ixb) rcs[d] = svdss_bam_smooth_set_index(sms[d], ix_shift, ix_depth);
         if (rcs[d] == SVDSS_OK) rcs[d] = svdss_bam_smooth_set_deflate(sms[d], o.compress);
+        if (rcs[d] == SVDSS_OK && side) rcs[d] = svdss_bam_smooth_set_search(sms[d], side->flags(), park);
+        if (rcs[d] == SVDSS_OK && o.nobam) rcs[d] = svdss_bam_smooth_set_output(sms[d], 0);
       };
       for (size_t d = 1; d < n_sm; ++d) up.emplace_back(upload, d);
       upload(0);
@@ -430,8 +625,10 @@ int main_smooth(const CallOptions& o) {
       }
     }
     if (dbg) fprintf(stderr, "[smooth] accuracy threshold %.6g at +%.3f s\n", al_accuracy, since());
+    if (side) side->begin();
     { std::lock_guard<std::mutex> lk(gate.m); gate.open = true; }
     gate.cv.notify_all();
+    uint64_t n_batches = 0;
     uint64_t n_rec = 0, n_kept = 0, n_xf[4] = {0, 0, 0, 0}, out_bytes = 0;
     std::atomic<bool> write_ok{true};   // (set by several writer threads)
     {
@@ -442,7 +639,7 @@ int main_smooth(const CallOptions& o) {
       // (pwrite ignores its offset on an O_APPEND descriptor -- `SVDSS smooth ... >> out.bam` -- and the batches would land in
       // completion order: such a stdout takes the ordered path)
       const int fl = fcntl(STDOUT_FILENO, F_GETFL);
-      const bool seekable = pos0 >= 0 && fstat(STDOUT_FILENO, &sb) == 0 && S_ISREG(sb.st_mode) && fl >= 0 && !(fl & O_APPEND) &&
+      const bool seekable = !o.nobam && pos0 >= 0 && fstat(STDOUT_FILENO, &sb) == 0 && S_ISREG(sb.st_mode) && fl >= 0 && !(fl & O_APPEND) &&
                             !getenv("SVDSS_SMOOTH_SERIAL_WRITE");
       struct WJob { std::unique_ptr<SelectedBatch> b; off_t at; };
       std::mutex wm; std::condition_variable wcv;
@@ -479,6 +676,7 @@ int main_smooth(const CallOptions& o) {
       while (std::unique_ptr<SelectedBatch> b = rd ? rd->next() : rds->next()) {
         const auto t0 = std::chrono::steady_clock::now();
         const size_t nb = b->ext ? b->ext_n : b->bytes.size();
+        ++n_batches;
         if (ixb) {   // (the batches come in file order, reruns included: the batch's members start at out_bytes)
           b->ix.chunks = b->ix_chunks.data(); b->ix.windows = b->ix_windows.data();
           ixb->add_fragment(b->ix, (uint64_t)out_bytes);
@@ -514,15 +712,22 @@ int main_smooth(const CallOptions& o) {
       rds.reset();
       for (uint8_t* q : pool.buf) if (q) svdss_host_free(q);
       if (!rerr.empty()) die("error reading " + o.bam + ": " + rerr);
-      if (dbg)
+      if (side) side->finish(n_batches);
+      if (dbg && !side)
         fprintf(stderr, "[smooth] device path: %llu records, %llu kept (XF 0/1/2/3: %llu %llu %llu %llu), %llu BGZF bytes; feeder seconds: front %.3f "
                 "turn wait %.3f turn %.3f walk %.3f rebuild %.3f output turn %.3f deflate + down %.3f (inflate kernels %.3f); writing %.3f\n",
                 (unsigned long long)n_rec, (unsigned long long)n_kept, (unsigned long long)n_xf[0], (unsigned long long)n_xf[1],
                 (unsigned long long)n_xf[2], (unsigned long long)n_xf[3], (unsigned long long)out_bytes, st_s[0], st_s[1], st_s[2], st_s[3],
                 st_s[4], st_s[5], st_s[6], inf_s, t_write);
+      if (side && (dbg || o.verbose))
+        fprintf(stderr, "[smooth] device path: %llu records, %llu kept (XF 0/1/2/3: %llu %llu %llu %llu), %llu BGZF bytes; feeder seconds: front %.3f "
+                "turn wait %.3f turn %.3f walk %.3f rebuild %.3f sfs export + search %.3f output turn %.3f deflate + down %.3f (inflate kernels %.3f); writing %.3f\n",
+                (unsigned long long)n_rec, (unsigned long long)n_kept, (unsigned long long)n_xf[0], (unsigned long long)n_xf[1],
+                (unsigned long long)n_xf[2], (unsigned long long)n_xf[3], (unsigned long long)out_bytes, st_s[0], st_s[1], st_s[2], st_s[3],
+                st_s[4], st_s[7], st_s[5], st_s[6], inf_s, t_write);
     }
     static const uint8_t eof_marker[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (fwrite(eof_marker, 1, 28, stdout) != 28 || fflush(stdout) != 0) write_ok = false;
+    if (!o.nobam && (fwrite(eof_marker, 1, 28, stdout) != 28 || fflush(stdout) != 0)) write_ok = false;
     for (svdss_bam_smooth_t* q : sms) svdss_bam_smooth_free(q);
     for (svdss_ref_t* q : drefs) svdss_ref_free(q);
     if (!write_ok) die("error writing the BAM to stdout");

@@ -10,7 +10,7 @@
 // This file: the usage texts, the command line, `index`; the other sub-commands have a file each.
 // Logs go to stderr (host_common.h), fatal conditions exit(1).
 // Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth),
-// --compress runs|lz (smooth).
+// --compress runs|lz (smooth), --index FMD --sfs FILE [--nobam] (smooth: the search of the smoothed reads in the same pass).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -48,7 +48,11 @@ static const char* SMOOTH_USAGE =
     "                            appended stream only)\n"
     "      --compress <runs|lz>  how the GPU deflates the output (default: runs): runs codes literals and runs of equal\n"
     "                            bytes; lz also finds matches between overlapping reads (a smaller file, more GPU time).\n"
-    "                            No effect where the host deflates (SVDSS_GPU_DEFLATE=0, SVDSS_SMOOTH_HOST=1)\n";
+    "                            No effect where the host deflates (SVDSS_GPU_DEFLATE=0, SVDSS_SMOOTH_HOST=1)\n"
+    "      --index <FMD> --sfs <FILE>  also search the smoothed reads while they are on the GPU: FILE receives what\n"
+    "                            `SVDSS search --index FMD --bam smoothed.bam` writes to stdout, with the same --threads,\n"
+    "                            --bsize, --noputative and --noassemble (one GPU, the device path)\n"
+    "      --nobam               with --index --sfs: write FILE only, nothing to stdout\n";
 
 static const char* CALL_USAGE =
     "Usage: SVDSS call --reference <FASTA> --bam <BAM> --sfs <SFS>\n"
@@ -205,6 +209,7 @@ int main(int argc, char** argv) {
             !strcmp(argv[1], "smooth") ? SMOOTH_USAGE : MAIN_USAGE, stderr);
       return EXIT_SUCCESS;
     }
+    if (o.nobam && strcmp(argv[1], "smooth") != 0) die(std::string("--nobam is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
     if (!o.write_index.empty() && strcmp(argv[1], "smooth") != 0)
       die(std::string("--write-index is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
     if (!strcmp(argv[1], "search")) {
@@ -220,9 +225,15 @@ int main(int argc, char** argv) {
       main_call(c);
     } else if (!strcmp(argv[1], "smooth")) {
       if (o.reference.empty() || o.bam.empty()) { fputs(SMOOTH_USAGE, stderr); return EXIT_FAILURE; }   // main.cpp:73-76
+      // --index FMD --sfs FILE [--nobam]: refused here, before anything is opened or written
+      if (o.sfs.empty() != o.index.empty()) die("smooth: --index and --sfs go together (--index <FMD> --sfs <FILE>)");
+      if (o.nobam && o.sfs.empty()) die("smooth: --nobam needs --index <FMD> --sfs <FILE> (there would be no output at all)");
+      if (o.nobam && !o.write_index.empty()) die("smooth: --nobam writes no BAM, so there is nothing for --write-index to index");
       CallOptions c;
       c.reference = o.reference; c.bam = o.bam; c.threads = o.threads; c.min_mapq = o.min_mapq; c.accp = o.accp; c.gpus = o.gpus;
       c.write_index = o.write_index; c.compress = o.compress;
+      c.index = o.index; c.sfs = o.sfs; c.bsize = o.bsize; c.putative = o.putative; c.assemble = o.assemble; c.nobam = o.nobam;
+      c.verbose = o.verbose;
       main_smooth(c);
     } else {
       fputs(MAIN_USAGE, stderr);
