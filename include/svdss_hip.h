@@ -551,6 +551,10 @@ int64_t svdss_aln_batch_npairs(const svdss_aln_batch_t* b);
 int64_t svdss_aln_batch_total_cigar(const svdss_aln_batch_t* b);   /* sum of n_cigar */
 int64_t svdss_aln_batch_cells(const svdss_aln_batch_t* b);         /* sum of tlen*qlen */
 double svdss_aln_batch_kernel_ms(const svdss_aln_batch_t* b);
+/* how the last call ran (tests assert the path they were written for): out[0] chunks launched, out[1] pairs laid out
+ * with more than one wavefront, out[2] the kernel's wavefronts per workgroup, the largest over the chunks (1, 4 or 8),
+ * out[3] chunks run again with one wavefront per pair after a wait that did not end.  All 0 after an empty batch. */
+int svdss_aln_batch_launch_info(const svdss_aln_batch_t* b, int64_t out[4]);
 /* scores int32[n_pairs], n_cigar int64[n_pairs], cigar uint32[total_cigar] (pairs concatenated) */
 int svdss_aln_batch_fetch(const svdss_aln_batch_t* b, int32_t* scores, int64_t* n_cigar, uint32_t* cigar);
 void svdss_aln_batch_free(svdss_aln_batch_t* b);
@@ -592,6 +596,9 @@ void svdss_poa_batch_free(svdss_poa_batch_t* b);
  * a/b: concatenated byte strings with offsets[n_pairs+1].  lcs_out may be NULL. */
 int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off,
                             int64_t n_pairs, int32_t device, double* ratio_out, int64_t* lcs_out);
+/* the kernel the calling thread's last non-empty svdss_indel_ratio_batch launched: 0 bit-parallel, 1 anti-diagonals
+ * in LDS, 2 anti-diagonals in HBM, -1 none yet */
+int32_t svdss_indel_ratio_last_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -389,6 +389,7 @@ struct svdss_aln_batch {
   int64_t total_cigar = 0;
   int64_t cells = 0;
   double kernel_ms = 0.0;
+  int64_t info[4] = {0, 0, 0, 0};   // the last call: chunks, pairs with several wavefronts, largest W, chunks run again
   std::vector<int32_t> scores;
   std::vector<int64_t> n_cigar;
   std::vector<uint32_t> cigar;   // per pair, forward order, concatenated
@@ -427,6 +428,7 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
   b->total_cigar = 0;
   b->cells = 0;
   b->kernel_ms = 0.0;
+  b->info[0] = b->info[1] = b->info[2] = b->info[3] = 0;
   b->scores.assign((size_t)n_pairs, 0);
   b->n_cigar.assign((size_t)n_pairs, 0);
   b->cigar.clear();
@@ -455,6 +457,8 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
       dir_budget = std::min<int64_t>(dir_budget, (int64_t)((free_b + b->arena.cap) / 2));
     if (dir_budget < ((int64_t)1 << 30)) dir_budget = (int64_t)1 << 30;
+    // SVDSS_ALIGN_DIR_MB: the budget in MB, no floor (tests: several chunks from a small batch)
+    if (getenv("SVDSS_ALIGN_DIR_MB") && atoll(getenv("SVDSS_ALIGN_DIR_MB")) > 0) dir_budget = atoll(getenv("SVDSS_ALIGN_DIR_MB")) << 20;
   }
   std::vector<int32_t> h_nc((size_t)n_pairs, 0);
   std::vector<std::pair<int64_t, int64_t>> cig_at((size_t)n_pairs);   // (chunk-local offset, chunk index)
@@ -548,11 +552,15 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
       if (ab) {   // a wavefront gave up waiting for its neighbour (never seen): the chunk again, one wavefront per pair
         fprintf(stderr, "[svdss] realignment: a multi-wavefront pair did not finish; the batch runs again with one wavefront per pair\n");
         multi = false;
+        ++b->info[3];
         b->cells -= [&] { int64_t c = 0; for (const AlnPair& a : hp) c += (int64_t)a.ql * a.tl; return c; }();
         for (int64_t k = start; k < end; ++k) cig_at[(size_t)k] = {0, 0};
         continue;   // (same `start`: the chunk is laid out again with waves = 1)
       }
     }
+    ++b->info[0];
+    for (const AlnPair& a : hp) b->info[1] += a.waves > 1;
+    b->info[2] = std::max<int64_t>(b->info[2], any_multi ? ALN_W : 1);
     chunk_cigs.emplace_back((size_t)cig);
     HIPCHK(hipMemcpyAsync(&b->scores[(size_t)start], d_sc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&h_nc[(size_t)start], d_nc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
@@ -586,6 +594,12 @@ extern "C" int64_t svdss_aln_batch_total_cigar(const svdss_aln_batch_t* b) { ret
 extern "C" int64_t svdss_aln_batch_cells(const svdss_aln_batch_t* b) { return b ? b->cells : -1; }
 extern "C" double svdss_aln_batch_kernel_ms(const svdss_aln_batch_t* b) { return b ? b->kernel_ms : -1.0; }
 
+extern "C" int svdss_aln_batch_launch_info(const svdss_aln_batch_t* b, int64_t out[4]) {
+  if (!b || !out) return SVDSS_EINVAL;
+  memcpy(out, b->info, sizeof b->info);
+  return SVDSS_OK;
+}
+
 extern "C" int svdss_aln_batch_fetch(const svdss_aln_batch_t* b, int32_t* scores, int64_t* n_cigar,
                                      uint32_t* cigar) {
   if (!b) return SVDSS_EINVAL;
@@ -596,6 +610,11 @@ extern "C" int svdss_aln_batch_fetch(const svdss_aln_batch_t* b, int32_t* scores
 }
 
 extern "C" void svdss_aln_batch_free(svdss_aln_batch_t* b) { delete b; }
+
+// the kernel of the calling thread's last svdss_indel_ratio_batch that launched one: 0 bit-parallel, 1 diagonals in LDS,
+// 2 diagonals in HBM, -1 none yet
+static thread_local int32_t g_ratio_last_kernel = -1;
+extern "C" int32_t svdss_indel_ratio_last_kernel(void) { return g_ratio_last_kernel; }
 
 extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, const uint8_t* bsy,
                                        const int64_t* b_off, int64_t n_pairs, int32_t device,
@@ -670,6 +689,7 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
   if (bits_ok) {
     void* d_map = R.arena.take(256);
     HIPCHK(hipMemcpyAsync(d_map, sym_id, 256, hipMemcpyHostToDevice, st));
+    g_ratio_last_kernel = 0;
     hipLaunchKernelGGL(lcs_bits_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, (const LcsPair*)d_pairs.p,
                        (const uint8_t*)d_a.p, (const uint8_t*)d_b.p, (const uint8_t*)d_map, (int64_t*)d_lcs.p, (double*)d_ratio.p);
     HIPCHK(hipGetLastError());
@@ -681,10 +701,12 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
   const size_t lds_need = sizeof(int32_t) * 3 * (size_t)(la_max + 1) + (size_t)la_max + (size_t)lb_max + 16;
   if (lds_need <= 150 * 1024) {
     HIPCHK(hipFuncSetAttribute((const void*)lcs_ratio_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need));
+    g_ratio_last_kernel = 1;
     hipLaunchKernelGGL(lcs_ratio_kernel<true>, dim3((unsigned)n_pairs), dim3(DP_THREADS), lds_need, st,
                        (const LcsPair*)d_pairs.p, (const uint8_t*)d_a.p, (const uint8_t*)d_b.p, (int32_t*)d_ws.p,
                        (int64_t*)d_lcs.p, (double*)d_ratio.p);
   } else {
+    g_ratio_last_kernel = 2;
     hipLaunchKernelGGL(lcs_ratio_kernel<false>, dim3((unsigned)n_pairs), dim3(DP_THREADS), 0, st,
                        (const LcsPair*)d_pairs.p, (const uint8_t*)d_a.p, (const uint8_t*)d_b.p, (int32_t*)d_ws.p,
                        (int64_t*)d_lcs.p, (double*)d_ratio.p);

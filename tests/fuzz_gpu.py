@@ -276,38 +276,86 @@ def fuzz_poa(rng, out_dir, it):
 
 # ------------------------------------------------------------------------------------------------ extd2 / ratio
 
-def fuzz_extd2(rng, out_dir, it):
+ALIGN_KNOBS = ("SVDSS_ALIGN_WAVES", "SVDSS_ALIGN_FRAC", "SVDSS_ALIGN_DIR_MB")
+
+
+def _with_env(env, knobs, fn):
+    """fn() with exactly `env` of `knobs` set; the environment is put back afterwards"""
+    old = {k: os.environ.pop(k, None) for k in knobs}
+    os.environ.update(env)
+    try:
+        return fn()
+    finally:
+        for k in knobs:
+            os.environ.pop(k, None)
+            if old[k] is not None:
+                os.environ[k] = old[k]
+
+
+def _extd2_case(rng):
+    """-> (queries, targets, m, mat, (q, e, q2, e2), env): a batch, its scoring parameters (half of the time the product's,
+    otherwise an alphabet, matrix and gap model of tests/calldp_cases.py) and the launch settings it runs under"""
     from svdss_amd import calldp
+    from tests import calldp_cases as K
+    env = {}
+    w = rng.choice(["", "1", "8"])
+    if w:
+        env["SVDSS_ALIGN_WAVES"] = str(w)
+    if rng.random() < 0.3:
+        env["SVDSS_ALIGN_DIR_MB"] = "1"
+    if rng.random() < 0.5:
+        m, mat, gm = 5, calldp.KSW_MAT, K.GAP_MODELS[0]
+    else:
+        m = int(rng.choice([4, 5, 8]))
+        mat = K.matrix(str(rng.choice(K.MATRIX_KINDS + ("extreme",))), m, rng)
+        gm = K.GAP_MODELS[int(rng.integers(0, len(K.GAP_MODELS)))]
+    top = min(m, 4)
     qs, ts = [], []
     for _ in range(int(rng.integers(8, 120))):
         kind = int(rng.integers(0, 5))
         tl = int(rng.choice([0, 1, 3, 50, 300, 1200, 2500]))
         tl = int(rng.integers(0, tl + 1))
+        if rng.random() < 0.2:
+            tl = int(rng.choice(K.STRIPE_EDGE_TL))
         if kind == 1:
-            u = rng.integers(0, 4, size=int(rng.integers(1, 7)), dtype=np.uint8)
+            u = rng.integers(0, top, size=int(rng.integers(1, 7)), dtype=np.uint8)
             t = np.tile(u, tl // len(u) + 1)[:tl]
         elif kind == 2:
-            t = np.repeat(rng.integers(0, 4, size=tl + 1, dtype=np.uint8), rng.geometric(0.3, size=tl + 1))[:tl]
+            t = np.repeat(rng.integers(0, top, size=tl + 1, dtype=np.uint8), rng.geometric(0.3, size=tl + 1))[:tl]
         else:
-            t = rng.integers(0, 5 if kind == 3 else 4, size=tl, dtype=np.uint8)
+            t = rng.integers(0, m if kind == 3 else top, size=tl, dtype=np.uint8)
         q = _mutate(rng, t, float(rng.choice([0, 0.01, 0.1, 0.3])))
         if len(q) > 4 and rng.random() < 0.6:
             at = int(rng.integers(0, len(q)))
             ln = int(rng.integers(1, 500))
-            q = np.concatenate([q[:at], rng.integers(0, 4, size=ln, dtype=np.uint8), q[at:]]) if rng.random() < 0.5 else np.concatenate([q[:at], q[at + ln:]])
+            q = np.concatenate([q[:at], rng.integers(0, top, size=ln, dtype=np.uint8), q[at:]]) if rng.random() < 0.5 else np.concatenate([q[:at], q[at + ln:]])
         if rng.random() < 0.05:
-            q = rng.integers(0, 4, size=int(rng.integers(0, 400)), dtype=np.uint8)
+            q = rng.integers(0, top, size=int(rng.integers(0, 400)), dtype=np.uint8)
+        if rng.random() < 0.1 and tl > 0:                 # unbalanced: a few bases of the target against all of it, or the reverse
+            n = int(rng.choice([1, 2, 5, 40, 63, 64, 65]))
+            at = int(rng.choice([0, max(0, tl - n) // 2, max(0, tl - n)]))
+            q = t[at:at + n].copy()
+            if rng.random() < 0.3:
+                q, t = t, q
         qs.append(np.ascontiguousarray(q, dtype=np.uint8)); ts.append(np.ascontiguousarray(t, dtype=np.uint8))
-    scores, cigars, stats = calldp.ksw_extd2_global(qs, ts)
+    return qs, ts, m, mat, gm, env
+
+
+def fuzz_extd2(rng, out_dir, it):
+    from svdss_amd import calldp
+    qs, ts, m, mat, gm, env = _extd2_case(rng)
+    scores, cigars, stats = _with_env(env, ALIGN_KNOBS, lambda: calldp.ksw_extd2_global(qs, ts, mat=mat, gapo=gm[0], gape=gm[1], gapo2=gm[2], gape2=gm[3]))
     for k, (q, t, s, c) in enumerate(zip(qs, ts, scores.tolist(), cigars)):
-        es, ec = O.ksw_extd2_global(q, t, calldp.KSW_MAT)
+        es, ec = O.ksw_extd2_global(q, t, mat, *gm)
         if s != es or c.tolist() != ec.tolist():
-            raise Mismatch(f"extd2 differs (pair {k}: score {s} vs {es}): " + _dump(out_dir, f"extd2_{it}", q=q, t=t, got=np.asarray(c), want=np.asarray(ec)))
+            raise Mismatch(f"extd2 differs (pair {k}: score {s} vs {es}; m {m}, gaps {gm}, env {env}): " +
+                           _dump(out_dir, f"extd2_{it}", q=q, t=t, got=np.asarray(c), want=np.asarray(ec), mat=np.asarray(mat),
+                                 gaps=np.asarray(gm), env=str(env)))
     return int(stats["cells"]), len(qs)
 
 
-def fuzz_ratio(rng, out_dir, it):
-    from svdss_amd import calldp
+def _ratio_case(rng):
+    """-> (a strings, b strings, alphabet size, env)"""
     a_list, b_list = [], []
     alpha = int(rng.choice([1, 2, 4, 5, 8, 9, 30, 256]))
     syms = rng.choice(256, size=alpha, replace=False).astype(np.uint8)
@@ -328,16 +376,26 @@ def fuzz_ratio(rng, out_dir, it):
                 at = int(rng.integers(0, len(b)))
                 b = np.delete(b, slice(at, at + int(rng.integers(0, 300)))) if x == 2 else np.insert(b, at, rng.choice(syms, size=int(rng.integers(0, 300))))
         a_list.append(bytes(a.astype(np.uint8))); b_list.append(bytes(b.astype(np.uint8)))
-    if rng.random() < 0.3:
-        os.environ["SVDSS_RATIO_DP"] = "1"
-    try:
-        ratio, lcs = calldp.fuzz_ratio(a_list, b_list)
-    finally:
-        os.environ.pop("SVDSS_RATIO_DP", None)
+    if rng.random() < 0.25:                               # one long string against a short one: too long for the diagonals in LDS
+        a = rng.choice(syms, size=int(rng.integers(11900, 16000)))
+        at = int(rng.integers(0, len(a) - 200))
+        b = a[at:at + int(rng.integers(1, 200))].copy()
+        b[int(rng.integers(0, len(b)))] = rng.choice(syms)
+        a, b = (a, b) if rng.random() < 0.5 else (b, a)
+        k = int(rng.integers(0, len(a_list) + 1))
+        a_list.insert(k, bytes(a.astype(np.uint8))); b_list.insert(k, bytes(b.astype(np.uint8)))
+    env = {"SVDSS_RATIO_DP": "1"} if rng.random() < 0.3 else {}
+    return a_list, b_list, alpha, env
+
+
+def fuzz_ratio(rng, out_dir, it):
+    from svdss_amd import calldp
+    a_list, b_list, alpha, env = _ratio_case(rng)
+    ratio, lcs = _with_env(env, ("SVDSS_RATIO_DP",), lambda: calldp.fuzz_ratio(a_list, b_list))
     for k, (a, b, r, l) in enumerate(zip(a_list, b_list, ratio.tolist(), lcs.tolist())):
         if l != O.lcs(a, b) or r != O.fuzz_ratio(a, b):
-            raise Mismatch(f"ratio differs (pair {k}, {len(a)} x {len(b)}, alphabet {alpha}): " +
-                           _dump(out_dir, f"ratio_{it}", a=np.frombuffer(a, np.uint8), b=np.frombuffer(b, np.uint8)))
+            raise Mismatch(f"ratio differs (pair {k}, {len(a)} x {len(b)}, alphabet {alpha}, env {env}): " +
+                           _dump(out_dir, f"ratio_{it}", a=np.frombuffer(a, np.uint8), b=np.frombuffer(b, np.uint8), env=str(env)))
     return sum(len(a) * len(b) for a, b in zip(a_list, b_list)), len(a_list)
 
 

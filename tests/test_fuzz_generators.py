@@ -44,3 +44,29 @@ def test_byte_mixtures_and_the_zlib_verdict():
     assert F._zlib_inflate(raw, len(data) - 1)[0] is False          # wrong ISIZE
     assert F._zlib_inflate(raw[:len(raw) // 2], len(data))[0] is False
     assert F._zlib_inflate(b"\x07" + raw[1:], len(data))[0] is False  # block type 3
+
+
+def test_alignment_and_ratio_batches_are_taken_by_the_oracle():
+    """what fuzz_extd2 / fuzz_ratio draw: symbols below m, an m x m matrix, a gap model whose first piece is the cheaper
+    one at length 1, launch settings the library knows -- unbalanced pairs, every wave setting, several chunks and a
+    pair for the LCS kernel with its diagonals in HBM among them -- and the oracle scores them"""
+    seen_env, seen_m, unbalanced, long_ratio = set(), set(), 0, 0
+    for it in range(40):
+        rng = np.random.default_rng([8, it])
+        qs, ts, m, mat, gm, env = F._extd2_case(rng)
+        assert len(qs) == len(ts) >= 8 and len(mat) == m * m and np.asarray(mat).dtype == np.int8
+        assert all(len(s) == 0 or s.max() < m for s in qs + ts)
+        assert gm[0] + gm[1] <= gm[2] + gm[3] and set(env) <= set(F.ALIGN_KNOBS)
+        seen_env.update(env.items())
+        seen_m.add(m)
+        unbalanced += sum(1 for q, t in zip(qs, ts) if 0 < len(q) <= 65 and len(t) >= 8 * len(q) or 0 < len(t) <= 65 and len(q) >= 8 * len(t))
+        if it < 6:
+            k = int(np.argmin([len(q) * len(t) if len(q) * len(t) > 100 else 1 << 40 for q, t in zip(qs, ts)]))
+            sc, cg = O.ksw_extd2_global(qs[k], ts[k], mat, *gm)
+            assert O.cigar_score(qs[k], ts[k], mat, cg, *gm) == sc
+        a_list, b_list, alpha, renv = F._ratio_case(rng)
+        assert len(a_list) == len(b_list) and set(renv) <= {"SVDSS_RATIO_DP"}
+        long_ratio += sum(1 for a, b in zip(a_list, b_list) if max(len(a), len(b)) >= 11900)
+    assert seen_env >= {("SVDSS_ALIGN_WAVES", "1"), ("SVDSS_ALIGN_WAVES", "8"), ("SVDSS_ALIGN_DIR_MB", "1")}
+    assert seen_m == {4, 5, 8} and unbalanced > 0 and long_ratio > 0
+    assert O.lcs(b"AGGTAB", b"GXTXAYB") == 4

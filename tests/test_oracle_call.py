@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests.mirror import caller
+from tests import calldp_cases as K
 from tests import oracle_lib as O
 
 MAT = caller.KSW_MAT
@@ -37,6 +38,25 @@ def test_score_is_the_optimum_and_cigar_attains_it(seed):
         assert sc == O.global_score_general(q, t, MAT)
         assert O.cigar_score(q, t, MAT, cg) == sc
         # CIGAR consumes exactly the two sequences and never has two adjacent ops of one kind
+        assert sum(int(c) >> 4 for c in cg if (c & 0xf) in (0, 1)) == len(q)
+        assert sum(int(c) >> 4 for c in cg if (c & 0xf) in (0, 2)) == len(t)
+        assert all((a & 0xf) != (b & 0xf) for a, b in zip(cg, cg[1:]))
+
+
+@pytest.mark.parametrize("kind", K.MATRIX_KINDS)
+@pytest.mark.parametrize("m", (4, 5, 8))
+@pytest.mark.parametrize("gm", K.GAP_MODELS, ids=lambda g: "-".join(map(str, g)))
+def test_score_and_cigar_pins_hold_for_every_model(gm, m, kind):
+    """the same pins at the alphabets, matrices and gap models the GPU tests pass (tests/test_call_dp_shapes_gpu.py):
+    targets below 60 symbols, with and without one indel of up to 30"""
+    rng = np.random.default_rng([11, m, K.MATRIX_KINDS.index(kind), K.GAP_MODELS.index(gm)])
+    assert gm[0] + gm[1] <= gm[2] + gm[3]
+    for k in range(30):
+        mat = K.matrix(kind, m, rng)
+        q, t = K.small_pair(rng, m, indel=bool(k % 2))
+        sc, cg = O.ksw_extd2_global(q, t, mat, *gm)
+        assert sc == O.global_score_general(q, t, mat, *gm), (k, len(q), len(t))
+        assert O.cigar_score(q, t, mat, cg, *gm) == sc
         assert sum(int(c) >> 4 for c in cg if (c & 0xf) in (0, 1)) == len(q)
         assert sum(int(c) >> 4 for c in cg if (c & 0xf) in (0, 2)) == len(t)
         assert all((a & 0xf) != (b & 0xf) for a, b in zip(cg, cg[1:]))
