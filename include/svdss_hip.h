@@ -492,6 +492,60 @@ int svdss_bam_smooth_search(svdss_bam_batch_t* b, const svdss_index_t* ix);
 const char* svdss_bam_batch_error(const svdss_bam_batch_t* b);
 void svdss_bam_batch_free(svdss_bam_batch_t* b);
 
+/* ---- FASTA / FASTQ records found on the device (csrc/fastx_device.hip) ------------------------------------------
+ * Replaces the kseq loop of PingPong::load_batch_fastq (ping_pong.cpp:130-173: kseq_read per record, rb3_char2nt6 per
+ * base) for a run of text at once, followed by the search of svdss_sfs_search_batch_device.
+ * A svdss_fastx_stream_t is one input being read: it holds the bytes behind a batch's last complete record (the carry,
+ * at most carry_cap bytes) and gives the batches their turn in file order; everything else of a batch -- upload,
+ * inflate, CRC, names, bases, search -- overlaps with the other batches, each on its own svdss_fastx_batch_t.
+ * svdss_fastx_batch_run, batch number seq = 0, 1, 2, ... (every number exactly once, from any thread; is_last on the
+ * final one).  The batch's bytes are either BGZF members (n_chunks pieces as for svdss_bam_batch_run, CRC32 checked) or
+ * plain text (plain, plain_bytes; n_chunks = 0).  ix = NULL: parse only, on the stream's device (the result then holds
+ * the reads); else on the index's device, searched with flags (SVDSS_SFS_ASSEMBLE).
+ * The parser delivers a batch in one of two shapes and proves that the host's FastxReader returns the same records:
+ * FASTA (first byte '>': no '\r', no NUL, no line beginning with '@') and FASTQ in groups of four lines (first byte
+ * '@': no '\r', no NUL; '@' line, a line beginning with neither '>' nor '+', '+' line, a line as long as the second;
+ * empty lines only at the end of the stream).  Anything else -- a record longer than carry_cap as well -- is declined:
+ * the batch holds the records proved in front of that point and the text from its first unparsed byte on; every later
+ * batch of the stream is declined too and holds its text alone (the caller reads on with FastxReader).
+ * Errors: SVDSS_EIO with svdss_fastx_batch_error() = "BGZF inflate failed" | "BGZF block CRC mismatch"; once a batch
+ * failed every later batch of the stream returns its error. */
+typedef struct svdss_fastx_stream svdss_fastx_stream_t;
+typedef struct svdss_fastx_batch svdss_fastx_batch_t;
+int svdss_fastx_stream_create(int32_t device, int64_t carry_cap, svdss_fastx_stream_t** out);
+void svdss_fastx_stream_free(svdss_fastx_stream_t* s);
+const char* svdss_fastx_stream_error(const svdss_fastx_stream_t* s);
+int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32_t is_last, const svdss_index_t* ix,
+                          int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
+                          const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                          const uint8_t* plain, int64_t plain_bytes, int32_t flags, svdss_fastx_batch_t** out);
+/* What the last run of a batch object left on the host (valid until its next run / svdss_fastx_batch_free). */
+typedef struct svdss_fastx_result {
+  int64_t n_records;        /* records delivered: proved, in file order */
+  const int32_t* name_off;  /* n_records + 1: record i is called names[name_off[i] .. name_off[i + 1]) */
+  const char* names;
+  const int32_t* seq_len;   /* n_records */
+  const int64_t* counts;    /* n_records: SFS per record (ix given) */
+  const int32_t* qs;        /* total_sfs, record after record */
+  const int32_t* len;
+  int64_t total_sfs;
+  const uint8_t* reads;     /* parse only: the nt6 reads back to back ... */
+  const int64_t* offsets;   /* ... read i = reads[offsets[i] .. offsets[i + 1]) */
+  int32_t declined;         /* 1: the text from the first unparsed byte on is in `text` */
+  int64_t n_text_bytes;     /* carry + this batch's bytes */
+  const uint8_t* text;
+  int64_t text_bytes;
+  double inflate_kernel_ms; /* HIP events */
+  double parse_kernel_ms;   /* the parse kernels and their scans, HIP events */
+  double stage_ms[8];       /* host clock: 0 upload + inflate + CRC, 1 waiting for the turn, 2 the turn (lines, shape, carry),
+                               3 records + names + bases, 5 search, 6 results down */
+} svdss_fastx_result_t;
+int svdss_fastx_batch_result(const svdss_fastx_batch_t* b, svdss_fastx_result_t* out);
+const char* svdss_fastx_batch_error(const svdss_fastx_batch_t* b);
+void svdss_fastx_batch_free(svdss_fastx_batch_t* b);
+/* bytes per tile of the parse kernels (tests aim at its edges) */
+int32_t svdss_fastx_tile_bytes(void);
+
 /* ---- a10: SFS placement ------------------------------------------------------
  * Replaces Clusterer::extend_alignment (clusterer.cpp:159-346) with get_aligned_pairs (bam.cpp:92-134) and
  * get_unique_kmers (clusterer.cpp:351-405) for a batch of alignments: every SFS (qs, len) of a read is mapped to the

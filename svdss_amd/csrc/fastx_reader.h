@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <functional>
 #include <thread>
 #include <string>
 #include <vector>
@@ -24,16 +25,20 @@ class FastxReader {
   explicit FastxReader(const std::string& path) : f_(gzopen(path.c_str(), "rb")), buf_((size_t)4 << 20) {
     if (f_) gzbuffer(f_, 1 << 20);
   }
+  // the same reader over memory: `source` hands over the next buffer of text (false: there is none); the buffers may be cut
+  // anywhere (the device path's fallback feeds it the text of the batches the GPU declined, csrc/fastx_device.h)
+  typedef std::function<bool(std::string&)> MemorySource;
+  explicit FastxReader(MemorySource source) : f_(nullptr), buf_((size_t)4 << 20), src_(std::move(source)) {}
   ~FastxReader() { if (f_) gzclose(f_); }
   FastxReader(const FastxReader&) = delete;
   FastxReader& operator=(const FastxReader&) = delete;
-  bool ok() const { return f_ != nullptr; }
+  bool ok() const { return f_ != nullptr || src_; }
 
   // next record; returns false at end of file
   bool next(std::string& name, std::string& seq) {
     name.clear();
     seq.clear();
-    if (!f_) return false;
+    if (!ok()) return false;
     // the header line: skip what is not one (blank lines, stray text)
     for (;;) {
       const int c = peek();
@@ -72,10 +77,23 @@ class FastxReader {
   bool fill() {
     if (eof_) return false;
     pos_ = 0;
+    if (src_) return fill_from_memory();
     const int n = gzread(f_, buf_.data(), (unsigned)buf_.size());
     end_ = n > 0 ? (size_t)n : 0;
     if (end_ == 0) eof_ = true;
     return end_ > 0;
+  }
+  bool fill_from_memory() {
+    end_ = 0;
+    while (mem_pos_ == mem_.size()) {
+      mem_.clear();
+      mem_pos_ = 0;
+      if (!src_(mem_)) { eof_ = true; return false; }
+    }
+    end_ = std::min(buf_.size(), mem_.size() - mem_pos_);
+    memcpy(buf_.data(), mem_.data() + mem_pos_, end_);
+    mem_pos_ += end_;
+    return true;
   }
   // the rest of the current line, without its end-of-line characters, appended to dst; returns the number of
   // characters appended.  A line may span any number of buffer fills (a chromosome on one line).
@@ -102,6 +120,9 @@ class FastxReader {
   size_t pos_ = 0, end_ = 0;
   bool eof_ = false;
   std::string line_, scratch_;
+  MemorySource src_;
+  std::string mem_;
+  size_t mem_pos_ = 0;
 };
 
 // A plain (not compressed) FASTA file with '\n' line ends, read by `threads` threads from a mapping: the records found by

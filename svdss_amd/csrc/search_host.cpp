@@ -29,6 +29,7 @@
 #include "cli_options.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "fastx_device.h"
 #include "sfs_units.h"
 
 namespace {
@@ -427,6 +428,203 @@ void HostPath::run() {
   }
 }
 
+// ---- `search --fastx` with the records found on the GPU (csrc/fastx_device.hip; fastx_device.h cuts the file): feeding
+// threads (batch -> upload / inflate -> records -> search) -> results in file order -> assembler -> formatting threads ->
+// writer, the back half of the BAM device path.  A batch the parser declines ends the device's part: the records it proved
+// are dealt, then the assembler reads on with FastxReader over the text the batches hand down (the feeders still inflate
+// them) and searches what it finds through the host-buffer entry point -- the same bytes as the host path for every file.
+class FastxDevicePath {
+ public:
+  FastxDevicePath(const Options& o, const SearchKnobs& knobs, const std::vector<svdss_index_t*>& replicas, FastxKind kind, const Stopwatch& clock)
+      : o_(o), knobs_(knobs), replicas_(replicas), kind_(kind), clock_(clock), flags_(o.assemble ? SVDSS_SFS_ASSEMBLE : 0) {}
+  void run();
+ private:
+  struct Out { DevOut d; bool declined = false; std::string text; };
+  void feeder(size_t replica);
+  void deliver(int64_t seq, bool last, std::unique_ptr<Out> out);
+  std::unique_ptr<Out> next_out();          // in file order; nullptr behind the last batch
+  void assemble();
+  void host_tail(std::unique_ptr<Out> first);
+
+  const Options& o_;
+  const SearchKnobs& knobs_;
+  const std::vector<svdss_index_t*>& replicas_;
+  const FastxKind kind_;
+  const Stopwatch& clock_;
+  const int32_t flags_;
+  StageSeconds t_;
+  UnitAssembler units_{o_, t_};
+  std::unique_ptr<FastxBatcher> batcher_;
+  svdss_fastx_stream_t* stream_ = nullptr;
+  std::unique_ptr<OrderedWriter> writer_;
+  std::mutex m_;
+  std::condition_variable cv_;
+  std::map<int64_t, std::unique_ptr<Out>> done_;
+  int64_t want_ = 0, last_seq_ = -1;
+  int64_t n_device_ = 0, n_host_ = 0, n_records_ = 0;   // (the assembler's)
+  double parse_ms_ = 0, text_bytes_ = 0;                // (under t_.m)
+};
+void FastxDevicePath::feeder(size_t replica) {
+  svdss_index_t* ix = replicas_[replica];
+  svdss_fastx_batch_t* batch = nullptr;
+  std::vector<uint8_t> slab;
+  FILE* f = kind_ == FastxKind::Plain ? fopen(o_.fastx.c_str(), "rb") : nullptr;
+  if (kind_ == FastxKind::Plain && !f) die("cannot open " + o_.fastx);
+  FastxJob job;
+  while (batcher_->next(job)) {
+    const auto t0 = now();
+    if (kind_ == FastxKind::Plain) {
+      slab.resize((size_t)job.plain_bytes);
+      size_t got = 0;
+      while (got < slab.size()) {
+        const ssize_t k = pread(fileno(f), slab.data() + got, slab.size() - got, (off_t)(job.plain_off + (int64_t)got));
+        if (k <= 0) die("error reading " + o_.fastx + ": short read");
+        got += (size_t)k;
+      }
+    }
+    const int rc = svdss_fastx_batch_run(stream_, job.seq, job.last ? 1 : 0, ix, (int32_t)job.comp.size(), job.comp.data(), job.comp_bytes.data(),
+                                         job.blocks.data(), job.crc.data(), job.n_blocks.data(), slab.data(), job.plain_bytes, flags_, &batch);
+    if (rc != SVDSS_OK) {
+      const std::string why = batch && *svdss_fastx_batch_error(batch) ? svdss_fastx_batch_error(batch) : svdss_fastx_stream_error(stream_);
+      if (rc == SVDSS_EIO) die("error reading " + o_.fastx + ": " + why);
+      die(std::string("svdss_fastx_batch_run: ") + svdss_strerror(rc) + " " + why + " " + svdss_last_hip_error());
+    }
+    const auto t1 = now();
+    svdss_fastx_result_t r;
+    check(svdss_fastx_batch_result(batch, &r), "svdss_fastx_batch_result");
+    std::unique_ptr<Out> out(new Out);
+    out->declined = r.declined != 0;
+    if (out->declined) out->text.assign((const char*)r.text, (size_t)r.text_bytes);
+    out->d.reads.resize((size_t)r.n_records);
+    out->d.qs.assign(r.qs, r.qs + r.total_sfs);
+    out->d.ln.assign(r.len, r.len + r.total_sfs);
+    int64_t acc = 0;
+    for (int64_t i = 0; i < r.n_records; ++i) {
+      Read& rd = out->d.reads[(size_t)i];
+      rd.name.assign(r.names + r.name_off[i], (size_t)(r.name_off[i + 1] - r.name_off[i]));
+      rd.len = r.seq_len[i];
+      rd.first = acc;
+      rd.count = r.counts[i];
+      acc += rd.count;
+    }
+    {
+      std::lock_guard<std::mutex> lk(t_.m);
+      t_.gpu += secs(t0, t1); t_.unpack += secs(t1, now()); t_.inflate_ms += r.inflate_kernel_ms; parse_ms_ += r.parse_kernel_ms;
+      if (!out->declined) text_bytes_ += (double)r.n_text_bytes;
+      for (int k = 0; k < 8; ++k) t_.device[k] += r.stage_ms[k] * 1e-3;
+    }
+    const int64_t seq = job.seq;
+    const bool last = job.last;
+    job.clear();     // (the slabs go back to the scanner)
+    deliver(seq, last, std::move(out));
+  }
+  if (!batcher_->error().empty()) die("error reading " + o_.fastx + ": " + batcher_->error());
+  if (f) fclose(f);
+  svdss_fastx_batch_free(batch);
+}
+void FastxDevicePath::deliver(int64_t seq, bool last, std::unique_ptr<Out> out) {
+  std::unique_lock<std::mutex> lk(m_);
+  cv_.wait(lk, [&] { return done_.size() < 8 || seq == want_; });
+  done_[seq] = std::move(out);
+  if (last) last_seq_ = seq;
+  lk.unlock();
+  cv_.notify_all();
+}
+std::unique_ptr<FastxDevicePath::Out> FastxDevicePath::next_out() {
+  std::unique_lock<std::mutex> lk(m_);
+  cv_.wait(lk, [&] { return done_.count(want_) || (last_seq_ >= 0 && want_ > last_seq_); });
+  auto it = done_.find(want_);
+  if (it == done_.end()) return nullptr;
+  std::unique_ptr<Out> out = std::move(it->second);
+  done_.erase(it);
+  ++want_;
+  lk.unlock();
+  cv_.notify_all();
+  return out;
+}
+void FastxDevicePath::assemble() {
+  units_.begin();
+  while (std::unique_ptr<Out> out = next_out()) {
+    n_records_ += (int64_t)out->d.reads.size();
+    units_.deal(out->d);
+    if (out->declined) { host_tail(std::move(out)); break; }
+    ++n_device_;
+  }
+  units_.end();
+}
+// from the first unparsed byte of the batch that declined to the end of the input: FastxReader over the batches' text, the
+// reads searched as HostPath searches them
+void FastxDevicePath::host_tail(std::unique_ptr<Out> first) {
+  FastxReader fx([&](std::string& buf) {
+    std::unique_ptr<Out> out = first ? std::move(first) : next_out();
+    if (!out) return false;
+    ++n_host_;
+    buf = std::move(out->text);
+    return true;
+  });
+  const int64_t super = reads_per_unit(o_);
+  svdss_sfs_batch_t* res = nullptr;
+  std::vector<uint8_t> gbuf;
+  std::vector<int64_t> goff, counts;
+  std::string seq;
+  for (bool more = true; more;) {
+    DevOut d;
+    gbuf.clear();
+    goff.assign(1, 0);
+    while ((int64_t)d.reads.size() < super) {
+      Read r;
+      if (!fx.next(r.name, seq)) { more = false; break; }
+      r.len = (int64_t)seq.size();
+      const size_t at = gbuf.size();
+      gbuf.resize(at + seq.size());
+      svdss_nt6_encode(seq.data(), (int64_t)seq.size(), gbuf.data() + at);
+      goff.push_back((int64_t)gbuf.size());
+      d.reads.push_back(std::move(r));
+    }
+    if (d.reads.empty()) break;
+    check(svdss_sfs_search_batch(replicas_[0], gbuf.data(), goff.data(), (int64_t)d.reads.size(), flags_, &res), "svdss_sfs_search_batch");
+    counts.assign(d.reads.size(), 0);
+    d.qs.resize((size_t)svdss_sfs_batch_total(res));
+    d.ln.resize(d.qs.size());
+    check(svdss_sfs_batch_fetch(res, counts.data(), d.qs.data(), d.ln.data(), nullptr), "svdss_sfs_batch_fetch");
+    int64_t acc = 0;
+    for (size_t k = 0; k < d.reads.size(); ++k) { d.reads[k].first = acc; d.reads[k].count = counts[k]; acc += counts[k]; }
+    n_records_ += (int64_t)d.reads.size();
+    units_.deal(d);
+  }
+  svdss_sfs_batch_free(res);
+}
+void FastxDevicePath::run() {
+  const size_t n_feeders = replicas_.size() * (size_t)knobs_.feeders;
+  const size_t per_batch = (size_t)knobs_.fastx_batch_bytes / knobs_.slab_bytes + 2;
+  batcher_.reset(new FastxBatcher(o_.fastx, kind_, knobs_.fastx_batch_bytes, knobs_.slab_bytes, knobs_.loaders, (size_t)knobs_.loaders + (n_feeders + 3) * per_batch));
+  if (!batcher_->ok()) die("cannot open " + o_.fastx);
+  // (a record is carried to the next batch whole: one longer than a batch declines)
+  check(svdss_fastx_stream_create(0, knobs_.fastx_batch_bytes, &stream_), "svdss_fastx_stream_create");
+  std::thread assembler([this] { assemble(); });
+  writer_.reset(new OrderedWriter(units_.pool()));
+  const int n_fmt = knobs_.format_threads ? knobs_.format_threads : (int)std::max<size_t>(5, std::min<size_t>(5 * replicas_.size(), effective_cpus()));
+  std::vector<std::thread> fmt, feeders;
+  for (int k = 0; k < n_fmt; ++k) fmt.emplace_back([this] { units_.format_units(*writer_); });
+  for (size_t d = 0; d < replicas_.size(); ++d)
+    for (int k = 0; k < knobs_.feeders; ++k) feeders.emplace_back([this, d] { feeder(d); });
+  for (std::thread& th : feeders) th.join();
+  assembler.join();
+  for (std::thread& th : fmt) th.join();
+  writer_->finish();
+  svdss_fastx_stream_free(stream_);
+  if (!o_.verbose) return;
+  logmsg("debug", std::to_string(n_records_) + " records read, " + std::to_string(writer_->lines()) + " SFS written at +" + clock_.since() + " s");
+  logmsg("debug", "FASTX device path: " + std::to_string(n_device_) + " batches on the device, " + std::to_string(n_host_) + " through the host reader, " +
+                      std::to_string(n_records_) + " records");
+  char buf[480];
+  snprintf(buf, sizeof buf, "FASTX device batches, seconds summed: upload+inflate+crc %.3f (inflate kernels %.3f), waiting for the turn %.3f, turn (lines, shape, carry) %.3f, "
+           "records+names+bases %.3f, search %.3f, results down %.3f; parse kernels %.3f ms over %.0f text bytes; re-dealing %.3f, format %.3f, write %.3f",
+           t_.device[0], t_.inflate_ms * 1e-3, t_.device[1], t_.device[2], t_.device[3], t_.device[5], t_.device[6], parse_ms_, text_bytes_, t_.assemble, t_.format,
+           writer_->busy_seconds());
+  logmsg("debug", buf);
+}
+
 // ---- the run, stage by stage
 struct SearchRun {
   SearchRun(const Options& opts, time_t process_start) : o(opts), t_process(process_start) {}
@@ -581,6 +779,14 @@ void SearchRun::run_host_path() {
     if (!bam->ok() || !bam->read_header()) die("cannot read " + o.bam + ": " + bam->error());
   } else {
     logmsg("warning", "FASTX mode is not optimized (higher running times and larger SFSs set).");
+    // an eligible file (regular; BGZF or not compressed) has its records found on the GPU; SVDSS_FASTX_DEVICE=0: the host reader
+    const FastxKind kind = knobs.fastx_device && svdss_device_count() > 0 ? fastx_device_kind(o.fastx) : FastxKind::None;
+    if (kind != FastxKind::None) {
+      if (o.bsize <= 0) die("batch size smaller than the number of threads");
+      logmsg("info", "Extracting SFS strings on the GPU (output order as with " + std::to_string(o.threads) + " threads)..");
+      FastxDevicePath(o, knobs, replicas, kind, clock).run();
+      return;
+    }
     fx.reset(new FastxReader(o.fastx));
     if (!fx->ok()) die("cannot open " + o.fastx);
   }

@@ -53,6 +53,9 @@ struct SearchKnobs {
   int lf = env_switch("SVDSS_SEARCH_LF");                                     // the rank blocks alone: 1 forces, 0 forbids
   bool lf_max_set = getenv("SVDSS_SEARCH_LF_MAX") != nullptr;                 // ... else up to this many reads to search
   double lf_max = lf_max_set ? atof(getenv("SVDSS_SEARCH_LF_MAX")) : 0;       //     (default: 2e6 per 6.18e9 BWT symbols)
+  bool fastx_device = env_switch("SVDSS_FASTX_DEVICE") != 0;                  // 0: `--fastx` through the host reader although the file is eligible
+  // text bytes per device batch of `--fastx` (192 MB; SVDSS_FASTX_BATCH_KB: the same knob for tests)
+  int64_t fastx_batch_bytes = getenv("SVDSS_FASTX_BATCH_KB") ? env_from("SVDSS_FASTX_BATCH_KB", 1, 1) << 10 : env_from("SVDSS_FASTX_BATCH_MB", 1, 192) << 20;
   bool prewarm = !getenv("SVDSS_NO_PREWARM");                                 // page-locked buffers allocated beside the restore
   bool clean_exit = getenv("SVDSS_CLEAN_EXIT") != nullptr;                    // orderly teardown instead of _exit (leak checkers)
 };
