@@ -396,6 +396,9 @@ int svdss_bam_select_store_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_la
                                svdss_bam_store_t* store, int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
                                const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
                                svdss_bam_batch_t** out);
+/* svdss_bam_store_select applies the filter as svdss_bam_select_run does: a stored record comes down if its name's hash is
+ * in the filter's set OR its alignment overlaps a region (either is enough: the caller tests the names exactly).  With a
+ * names filter a filled store serves `call`'s FIRST pass as well -- the records of the reads that have SFS, in file order. */
 int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const svdss_bam_filter_t* f, svdss_bam_batch_t** out);
 /* `SVDSS smooth` on the same front end (csrc/bam_smooth.hip): BGZF blocks in, BGZF blocks out; the inflated records never
  * leave the device.  Stands where smoother.cpp:349-571 stand (loader :498-571 with the filters of :509-537, smooth_read
@@ -485,8 +488,16 @@ int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* ou
  *   svdss_bam_smooth_search      finishes a batch of group -1 against a resident index, like svdss_bam_batch_search; the
  *                                smoothing run's stage_ms stay, the search is added to stage 7.
  *   svdss_bam_smooth_set_output  write_bam = 0 (`--nobam`): later runs take and pass on the output turn but keep no tail,
- *                                deflate nothing and bring nothing down (bgzf_bytes = 0, no index fragments); 1: the default. */
+ *                                deflate nothing and bring nothing down (bgzf_bytes = 0, no index fragments); 1: the default.
+ *   svdss_bam_smooth_set_store   `SVDSS run` (smooth, search and call in one pass over the BAM): every later svdss_bam_smooth_run
+ *                                on sm also deposits, under the batch's seq, the slim form of every record of the batch that
+ *                                passes `call`'s filters (flags 4 / 256 / 2048 clear, mapq >= min_mapq; clusterer.cpp:118-122)
+ *                                -- whether the smoothing keeps the record or not -- byte for byte what
+ *                                svdss_bam_select_store_run leaves for the same chunks (one predicate, one export kernel).  A
+ *                                store over its limit stays incomplete; the smoothing is unaffected.  store = NULL: off (the
+ *                                default).  The store is of sm's device.  svdss_bam_smooth_measure deposits nothing. */
 int svdss_bam_smooth_set_search(svdss_bam_smooth_t* sm, int32_t flags, svdss_bam_park_t* park);
+int svdss_bam_smooth_set_store(svdss_bam_smooth_t* sm, svdss_bam_store_t* store, int32_t min_mapq);
 int svdss_bam_smooth_set_output(svdss_bam_smooth_t* sm, int32_t write_bam);
 int svdss_bam_smooth_search(svdss_bam_batch_t* b, const svdss_index_t* ix);
 const char* svdss_bam_batch_error(const svdss_bam_batch_t* b);

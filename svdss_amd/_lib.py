@@ -134,6 +134,7 @@ SIGNATURES = {
     "svdss_bam_smooth_set_deflate": (C.c_int, [_p, C.c_int32]),
     "svdss_bam_smooth_set_search": (C.c_int, [_p, C.c_int32, _p]),
     "svdss_bam_smooth_set_output": (C.c_int, [_p, C.c_int32]),
+    "svdss_bam_smooth_set_store": (C.c_int, [_p, _p, C.c_int32]),
     "svdss_bam_smooth_search": (C.c_int, [_p, _p]),
     "svdss_bam_batch_index": (C.c_int, [_p, _p]),
     "svdss_bam_batch_error": (C.c_char_p, [_p]),

@@ -278,3 +278,169 @@ def select_bam_store(data, names, regions, min_mapq=0, batch_bytes=256 << 20, de
         lib.svdss_bam_filter_free(f_regions)
         lib.svdss_bam_store_free(store)
     return named, slim, stats
+
+
+# ---- the record store filled by either route, and selections from it (`SVDSS run`: csrc/run_host.cpp)
+class BamSmoothed(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("n_kept", C.c_int64), ("match_mismatch", C.POINTER(C.c_int64)), ("fits", C.POINTER(C.c_uint8)),
+                ("out_bytes", C.c_int64), ("bgzf", C.POINTER(C.c_uint8)), ("bgzf_bytes", C.c_int64), ("n_xf", C.c_int64 * 4),
+                ("inflate_kernel_ms", C.c_double), ("stage_ms", C.c_double * 8)]
+
+
+def _check(rc, what):
+    if rc:
+        raise SvdssError(rc, what)
+
+
+def _batch_groups(blocks, batch_bytes):
+    groups, cur, acc = [], [], 0
+    for b in blocks:
+        cur.append(b)
+        acc += b[2]
+        if acc >= batch_bytes:
+            groups.append(cur)
+            cur, acc = [], 0
+    groups.append(cur)
+    return groups
+
+
+def _group_tables(g):
+    rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
+    crc = np.zeros(max(1, len(g)), dtype=np.uint32)
+    for i, b in enumerate(g):
+        rec[i] = (b[0], b[1], b[2], 0)
+        crc[i] = b[3]
+    return rec, crc
+
+
+class BamFilter:
+    """svdss_bam_filter_t: read names (a list, possibly empty; None: no name test) and / or regions [(tid, beg, end)] sorted
+    by (tid, beg).  A record passes if its name's hash is in the set or its alignment overlaps a region."""
+
+    def __init__(self, n_ref, names=None, regions=None, min_mapq=0, device=0):
+        self._h = C.c_void_p()
+        names = None if names is None else [n.encode() if isinstance(n, str) else n for n in names]
+        nm = b"".join(names) if names is not None else None
+        nm_off = np.zeros(len(names or []) + 1, dtype=np.int64)
+        if names:
+            nm_off[1:] = np.cumsum([len(n) for n in names])
+        rt = np.array([r[0] for r in (regions or [])], dtype=np.int32)
+        rb = np.array([r[1] for r in (regions or [])], dtype=np.int32)
+        re_ = np.array([r[2] for r in (regions or [])], dtype=np.int32)
+        _check(lib.svdss_bam_filter_create(device, min_mapq, n_ref, nm, nm_off.ctypes.data if names is not None else None, len(names or []),
+                                           rt.ctypes.data if regions else None, rb.ctypes.data if regions else None,
+                                           re_.ctypes.data if regions else None, len(regions or []), C.byref(self._h)), "svdss_bam_filter_create")
+
+    def close(self):
+        if self._h:
+            lib.svdss_bam_filter_free(self._h)
+            self._h = C.c_void_p()
+
+
+class BamStore:
+    """svdss_bam_store_t: the slim records of every batch, in HBM.  fill_by_select: svdss_bam_select_store_run (what `SVDSS
+    call`'s first pass does); fill_by_smooth: svdss_bam_smooth_run after svdss_bam_smooth_set_store (what `SVDSS run` does).
+    Both take the bytes of a BAM file and cut it into the same batches."""
+
+    def __init__(self, max_bytes=1 << 34, initial_bytes=1 << 20, device=0):
+        self._h = C.c_void_p()
+        self.device = device
+        _check(lib.svdss_bam_store_create(device, max_bytes, min(max_bytes, initial_bytes), C.byref(self._h)), "svdss_bam_store_create")
+
+    def close(self):
+        if self._h:
+            lib.svdss_bam_store_free(self._h)
+            self._h = C.c_void_p()
+
+    def batches(self):
+        """(stored batches, complete, records, bytes)"""
+        complete, n_rec, n_bytes = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        n_b = lib.svdss_bam_store_batches(self._h, C.byref(complete), C.byref(n_rec), C.byref(n_bytes))
+        return n_b, bool(complete.value), n_rec.value, n_bytes.value
+
+    def select(self, seq, flt):
+        """svdss_bam_store_select of stored batch `seq`: (the kept slim records' bytes, their n + 1 offsets)"""
+        batch = C.c_void_p()
+        try:
+            _check(lib.svdss_bam_store_select(self._h, seq, flt._h, C.byref(batch)), "svdss_bam_store_select")
+            r = BamSelection()
+            lib.svdss_bam_batch_selection(batch, C.byref(r))
+            assert r.slim == 1
+            off = np.ctypeslib.as_array(r.rec_off, shape=(r.n_selected + 1,)).copy()
+            return (C.string_at(r.bytes, r.n_bytes) if r.n_bytes else b""), off
+        finally:
+            if batch:
+                lib.svdss_bam_batch_free(batch)
+
+    def fill_by_select(self, data, min_mapq=0, batch_bytes=256 << 20):
+        """every batch of the file through svdss_bam_select_store_run with an empty set of names; returns the batch count"""
+        blocks = bgzf.bgzf_blocks(data)
+        n_ref, skip = bam_header(data, blocks)
+        comp = np.frombuffer(bytes(data), dtype=np.uint8)
+        flt = BamFilter(n_ref, names=[], min_mapq=min_mapq, device=self.device)
+        stream, batch = C.c_void_p(), C.c_void_p()
+        _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")
+        try:
+            groups = _batch_groups(blocks, batch_bytes)
+            for seq, g in enumerate(groups):
+                rec, crc = _group_tables(g)
+                rc = lib.svdss_bam_select_store_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, flt._h, self._h, 1,
+                                                    (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
+                                                    (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+                if rc:
+                    raise SvdssError(rc, "svdss_bam_select_store_run: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
+            return len(groups)
+        finally:
+            if batch:
+                lib.svdss_bam_batch_free(batch)
+            lib.svdss_bam_stream_free(stream)
+            flt.close()
+
+
+def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20, store=None, store_min_mapq=None, device=0):
+    """svdss_bam_smooth_run over a whole BAM file (bytes) whose header names `contigs_ascii` in order; with `store` (a
+    BamStore) after svdss_bam_smooth_set_store(sm, store, store_min_mapq).  Returns (the BGZF members of the smoothed
+    stream, batch count)."""
+    blocks = bgzf.bgzf_blocks(data)
+    n_ref, skip = bam_header(data, blocks)
+    raw_head = b""
+    for coff, clen, isize, _ in blocks:
+        raw_head += zlib.decompress(bytes(data[coff:coff + clen]), -15)
+        if len(raw_head) >= skip:
+            break
+    cat = np.frombuffer("".join(contigs_ascii).encode(), dtype=np.uint8)
+    off = np.concatenate([[0], np.cumsum([len(c) for c in contigs_ascii])]).astype(np.int64)
+    tid_map = np.full(n_ref, -1, dtype=np.int32)
+    tid_map[:len(contigs_ascii)] = np.arange(len(contigs_ascii), dtype=np.int32)
+    comp = np.frombuffer(bytes(data), dtype=np.uint8)
+    ref, sm, stream, batch = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    out = bytearray()
+    try:
+        _check(lib.svdss_ref_upload(cat.ctypes.data, off.ctypes.data, len(contigs_ascii), device, C.byref(ref)), "svdss_ref_upload")
+        _check(lib.svdss_bam_smooth_create(ref, tid_map.ctypes.data, n_ref, min_mapq, C.byref(sm)), "svdss_bam_smooth_create")
+        if store is not None:
+            _check(lib.svdss_bam_smooth_set_store(sm, store._h, min_mapq if store_min_mapq is None else store_min_mapq), "svdss_bam_smooth_set_store")
+        _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")
+        head = np.frombuffer(raw_head[:skip], dtype=np.uint8)
+        _check(lib.svdss_bam_stream_set_output_prefix(stream, head.ctypes.data, len(head)), "svdss_bam_stream_set_output_prefix")
+        groups = _batch_groups(blocks, batch_bytes)
+        for seq, g in enumerate(groups):
+            rec, crc = _group_tables(g)
+            rc = lib.svdss_bam_smooth_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, C.c_double(acc), None, 0, 1,
+                                          (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
+                                          (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+            if rc:
+                raise SvdssError(rc, "svdss_bam_smooth_run: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
+            sr = BamSmoothed()
+            _check(lib.svdss_bam_batch_smoothed(batch, C.byref(sr)), "svdss_bam_batch_smoothed")
+            out += C.string_at(sr.bgzf, sr.bgzf_bytes) if sr.bgzf_bytes else b""
+        return bytes(out), len(groups)
+    finally:
+        if batch:
+            lib.svdss_bam_batch_free(batch)
+        if stream:
+            lib.svdss_bam_stream_free(stream)
+        if sm:
+            lib.svdss_bam_smooth_free(sm)
+        if ref:
+            lib.svdss_ref_free(ref)

@@ -318,12 +318,6 @@ __global__ void __launch_bounds__(256) unpack_kernel(const uint8_t* __restrict__
 }
 
 // ------------------------------------------------------------------ records selected for `call` (svdss_bam_select_run)
-__host__ __device__ inline uint64_t name_hash(const uint8_t* p, uint32_t n) {   // FNV-1a, 0 kept for "empty slot"
-  uint64_t h = 1469598103934665603ull;
-  for (uint32_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; }
-  return h ? h : 1;
-}
-
 struct SelP {
   const uint8_t* buf;
   const uint32_t* lists; int64_t list_cap;
@@ -339,7 +333,6 @@ struct SelP {
   // its slim form -- f_keep / f_kbytes (n_rec + 1 each; nullptr: no store), hpv: its HP tag (kNoHp: none)
   int64_t *f_keep, *f_kbytes, *hpv;
 };
-constexpr int64_t kNoHp = (int64_t)1 << 40;
 
 // block s < n_seg: the records of segment s; block n_seg: those that begin in the carried bytes.  A record is kept if it
 // passes the flag / mapq filters of clusterer.cpp:118-122 (= :535-540) and, when names and / or regions are given, is
@@ -362,24 +355,13 @@ __global__ void __launch_bounds__(64) select_kernel(SelP M) {
     if (M.f_keep) { M.f_keep[gi] = 0; M.f_kbytes[gi] = 0; }
     if (l_seq < 0 || head > (int64_t)bs) atomicOr((unsigned long long*)&M.hdr[H_ERR], (unsigned long long)E_CORRUPT);
     else {
-      keep = !(flag & (4u | 2048u | 256u)) && (int32_t)mapq >= M.min_mapq;
+      keep = call_keeps(flag, mapq, M.min_mapq);
       if (keep && M.f_keep) {
-        int64_t hp = 0;
-        const bool have = aux_int(M.buf + p + 4 + head, M.buf + p + 4 + bs, 'H', 'P', hp);
-        M.hpv[gi] = have ? hp : kNoHp;
         M.f_keep[gi] = 1;
-        M.f_kbytes[gi] = (4 + head - l_seq + (have ? 7 : 0) + 3) & ~(int64_t)3;    // block_size + core .. bases + "HPi" + value
+        M.f_kbytes[gi] = slim_measure(M.buf, p, bs, head, l_seq, M.hpv[gi]);
       }
       if (keep && (M.hash || M.reg_off)) {
-        bool hit = false;
-        if (M.hash) {
-          const uint64_t h = name_hash(M.buf + p + 36, l_name ? l_name - 1 : 0);
-          for (uint64_t k = h & M.hash_mask;; k = (k + 1) & M.hash_mask) {
-            const uint64_t e = M.hash[k];
-            if (e == h) { hit = true; break; }
-            if (e == 0) break;
-          }
-        }
+        bool hit = M.hash && name_in_set(M.hash, M.hash_mask, M.buf + p + 36, l_name ? l_name - 1 : 0);
         if (!hit && M.reg_off && tid >= 0 && tid < M.n_ref) {
           const int64_t lo = M.reg_off[tid], hi = M.reg_off[tid + 1];
           if (hi > lo) {
@@ -407,48 +389,12 @@ __global__ void __launch_bounds__(64) select_kernel(SelP M) {
   if (s == 0 && threadIdx.x == 0) { M.f_sel[M.n_rec] = 0; M.f_bytes[M.n_rec] = 0; if (M.f_keep) { M.f_keep[M.n_rec] = 0; M.f_kbytes[M.n_rec] = 0; } }
 }
 
-// one wavefront per stored record: block_size' | core | name | CIGAR | packed bases | HP as an int32 tag if the record had
-// an integer one -- no qualities, no other tags (`call` reads neither: clusterer.cpp:56-156, 477-610)
-__global__ void __launch_bounds__(64) slim_export_kernel(const uint8_t* __restrict__ buf, int64_t n_rec, const uint32_t* __restrict__ rpos,
-                                                         const int64_t* __restrict__ f_keep, const int64_t* __restrict__ s_keep,
-                                                         const int64_t* __restrict__ s_bytes, const int64_t* __restrict__ hpv,
-                                                         uint8_t* out, int64_t* out_off, int64_t* totals) {
-  const int64_t gi = blockIdx.x;
-  if (gi == n_rec) {
-    if (threadIdx.x == 0) { out_off[s_keep[gi]] = s_bytes[gi]; totals[0] = s_keep[gi]; totals[1] = s_bytes[gi]; }
-    return;
-  }
-  if (!f_keep[gi]) return;
-  const int64_t p = rpos[gi], o = s_bytes[gi];
-  const uint32_t w3 = ld32(buf, p + 12), w4 = ld32(buf, p + 16);
-  const int32_t l_seq = (int32_t)ld32(buf, p + 20);
-  const uint32_t l_name = w3 & 0xffu, n_cig = w4 & 0xffffu;
-  const uint32_t n1 = 36u + l_name + 4u * n_cig + ((uint32_t)l_seq + 1u) / 2u;       // bytes taken over (block_size field included)
-  const int64_t hp = hpv[gi];
-  const uint32_t total = n1 + (hp != kNoHp ? 7u : 0u);
-  if (threadIdx.x == 0) out_off[s_keep[gi]] = o;
-  uint32_t* dst = (uint32_t*)(out + o);
-  for (uint32_t k = threadIdx.x; k < n1 / 4; k += 64) {
-    uint32_t w = ld32(buf, p + 4 * (int64_t)k);
-    if (k == 0) w = total - 4u;                       // the slim record's block_size
-    dst[k] = w;
-  }
-  if (threadIdx.x == 0) {
-    uint8_t* q = out + o;
-    for (uint32_t k = n1 & ~3u; k < n1; ++k) q[k] = buf[p + k];
-    if (hp != kNoHp) {
-      const bool neg_ok = hp >= -2147483648ll && hp <= 2147483647ll;
-      q[n1] = 'H'; q[n1 + 1] = 'P'; q[n1 + 2] = neg_ok ? 'i' : 'I';
-      const uint32_t v = (uint32_t)hp;
-      q[n1 + 3] = (uint8_t)v; q[n1 + 4] = (uint8_t)(v >> 8); q[n1 + 5] = (uint8_t)(v >> 16); q[n1 + 6] = (uint8_t)(v >> 24);
-    }
-  }
-}
-
-// the second pass of `SVDSS call` over a stored batch: one lane per slim record, kept if its alignment overlaps a region
+// a pass of `SVDSS call` over a stored batch: one lane per slim record, kept if it is named in the filter's set or its
+// alignment overlaps a region (either is enough, as in select_kernel: the host looks again, exactly)
 struct StoreSelP {
   const uint8_t* recs; const int64_t* off; int64_t n;
   int32_t n_ref;
+  const uint64_t* hash; uint64_t hash_mask;              // read names wanted (hash == nullptr: no such test)
   const int64_t* reg_off; const int32_t* reg_beg; const int32_t* reg_runmax;
   int64_t *f_sel, *f_bytes;
 };
@@ -460,8 +406,8 @@ __global__ void __launch_bounds__(256) store_select_kernel(StoreSelP M) {
   const int32_t tid = (int32_t)ld32(M.recs, p + 4), pos = (int32_t)ld32(M.recs, p + 8);
   const uint32_t w3 = ld32(M.recs, p + 12), w4 = ld32(M.recs, p + 16);
   const uint32_t l_name = w3 & 0xffu, n_cig = w4 & 0xffffu;
-  bool hit = false;
-  if (M.reg_off && tid >= 0 && tid < M.n_ref) {
+  bool hit = M.hash && name_in_set(M.hash, M.hash_mask, M.recs + p + 36, l_name ? l_name - 1 : 0);
+  if (!hit && M.reg_off && tid >= 0 && tid < M.n_ref) {
     const int64_t lo = M.reg_off[tid], hi = M.reg_off[tid + 1];
     if (hi > lo) {
       int64_t ref_len = 0;
@@ -519,26 +465,6 @@ struct OffDiff {   // length of searched read k
 };
 
 }  // namespace
-
-// What `SVDSS call` keeps of its first pass over the BAM for the second one (svdss_bam_store_t): the slim records of every
-// batch, in HBM, batch by batch in arenas allocated as they are needed.
-struct StoreBatch { int arena = -1; int64_t at = 0, bytes = 0, n = 0, off_at = 0; };
-struct StoreArena { uint8_t* p = nullptr; int64_t cap = 0, used = 0; };
-struct svdss_bam_store {
-  int device = -1;
-  int64_t max_bytes = 0, arena_bytes = (int64_t)2 << 30, allocated = 0;
-  // arenas taken AHEAD of the batches by a thread of the store (see svdss_bam_store_create): next_use = the first arena no
-  // batch has been placed in yet
-  std::thread ahead;
-  std::condition_variable cv;
-  bool ahead_running = false, stop = false;
-  size_t cur = 0;                // the arena batches are being placed in
-  std::mutex m;
-  std::vector<StoreArena> arenas;
-  std::map<int64_t, StoreBatch> batches;
-  bool complete = true;          // false: a batch did not fit (the caller reads the file again)
-  int64_t n_records = 0, n_bytes = 0;
-};
 
 struct svdss_bam_filter {
   int device = -1;
@@ -1174,7 +1100,7 @@ extern "C" int64_t svdss_bam_store_batches(svdss_bam_store_t* t, int32_t* comple
   return (int64_t)t->batches.size();
 }
 // room for a batch's slim records (+ their n + 1 offsets); false: the store is over its limit (and stays incomplete)
-static bool store_reserve(svdss_bam_store* t, int64_t seq, int64_t bytes, int64_t n, StoreBatch& B, uint8_t*& base) {
+bool store_reserve(svdss_bam_store* t, int64_t seq, int64_t bytes, int64_t n, StoreBatch& B, uint8_t*& base) {
   const int64_t need = ((bytes + 255) & ~(int64_t)255) + (((n + 1) * 8 + 255) & ~(int64_t)255);
   std::unique_lock<std::mutex> lk(t->m);
   if (!t->complete) return false;
@@ -1284,7 +1210,7 @@ extern "C" int svdss_bam_select_store_run(svdss_bam_stream_t* s, int64_t seq, in
   return SVDSS_OK;
 }
 
-// The second pass over ONE stored batch: its slim records whose alignment overlaps a region of `f`, in file order, on the host
+// A pass over ONE stored batch: its slim records that `f` names or whose alignment overlaps a region of `f`, in file order, on the host
 // (svdss_bam_batch_selection, slim = 1).  Any batch object of the store's device (or none yet) may be used; calls on different
 // batch objects overlap.
 extern "C" int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const svdss_bam_filter_t* f, svdss_bam_batch_t** out) {
@@ -1312,7 +1238,7 @@ extern "C" int svdss_bam_store_select(svdss_bam_store_t* t, int64_t seq, const s
   RCHK(b->totals.ensure(64));
   StoreSelP M;
   M.recs = base + B.at; M.off = (const int64_t*)(base + B.off_at); M.n = n; M.n_ref = f->n_ref;
-  M.reg_off = f->d_reg_off; M.reg_beg = f->d_reg_beg; M.reg_runmax = f->d_reg_runmax;
+  M.hash = f->d_hash; M.hash_mask = f->hash_mask; M.reg_off = f->d_reg_off; M.reg_beg = f->d_reg_beg; M.reg_runmax = f->d_reg_runmax;
   M.f_sel = (int64_t*)b->flags.p; M.f_bytes = M.f_sel + (n + 1);
   hipLaunchKernelGGL(store_select_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, M);
   BCHK(hipGetLastError());

@@ -1,6 +1,7 @@
 // bam_device_internal.h -- what the units of the BAM device path share (bam_device.hip: front end, search, select, store;
 // bam_smooth.hip: `SVDSS smooth`): the stream and batch objects, the front end's result, the scope an entry point runs a
-// batch in (BatchRun) and the few device helpers the kernels of both units use.  Kernels stay in the unit that launches them.
+// batch in (BatchRun), the record store and the few device helpers the kernels of both units use.  Kernels stay in the unit
+// that launches them, but for the two both units launch (crc32_kernel, slim_export_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -11,9 +12,11 @@
 #include <cstring>
 #include <functional>
 #include <algorithm>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/svdss_hip.h"
@@ -73,6 +76,78 @@ __device__ bool aux_int(const uint8_t* p, const uint8_t* e, char a, char b, int6
     p += sz;
   }
   return false;
+}
+
+// ------------------------------------------------------------------ read names wanted (svdss_bam_filter_t), slim records (svdss_bam_store_t)
+__host__ __device__ inline uint64_t name_hash(const uint8_t* p, uint32_t n) {   // FNV-1a, 0 kept for "empty slot"
+  uint64_t h = 1469598103934665603ull;
+  for (uint32_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; }
+  return h ? h : 1;
+}
+// is the name's hash in the filter's open-addressed table?  (a hit may be another name with the same hash: the host looks again)
+__device__ __forceinline__ bool name_in_set(const uint64_t* __restrict__ hash, uint64_t mask, const uint8_t* name, uint32_t n) {
+  const uint64_t h = name_hash(name, n);
+  for (uint64_t k = h & mask;; k = (k + 1) & mask) {
+    const uint64_t e = hash[k];
+    if (e == h) return true;
+    if (e == 0) return false;
+  }
+}
+
+constexpr int64_t kNoHp = (int64_t)1 << 40;   // "the record has no integer HP tag"
+
+// the flag / mapq filters of `SVDSS call` (clusterer.cpp:118-122 = :535-540): what a record store keeps
+__device__ __forceinline__ bool call_keeps(uint32_t flag, uint32_t mapq, int32_t min_mapq) {
+  return !(flag & (4u | 2048u | 256u)) && (int32_t)mapq >= min_mapq;
+}
+// the size of a record's slim form, 4-aligned (block_size + core .. bases + "HPi" + value), and its HP tag (kNoHp: none);
+// the record begins at buf + p, bs = its block_size, head = core .. qualities
+__device__ __forceinline__ int64_t slim_measure(const uint8_t* buf, int64_t p, uint32_t bs, int64_t head, int32_t l_seq, int64_t& hpv) {
+  int64_t hp = 0;
+  const bool have = aux_int(buf + p + 4 + head, buf + p + 4 + bs, 'H', 'P', hp);
+  hpv = have ? hp : kNoHp;
+  return (4 + head - l_seq + (have ? 7 : 0) + 3) & ~(int64_t)3;
+}
+
+// one wavefront per stored record: block_size' | core | name | CIGAR | packed bases | HP as an int32 tag if the record had
+// an integer one -- no qualities, no other tags (`call` reads neither: clusterer.cpp:56-156, 477-610).  f_keep: which
+// records, s_keep / s_bytes: its exclusive sums (entry n_rec: the totals), hpv: what slim_measure left
+__global__ void __launch_bounds__(64) slim_export_kernel(const uint8_t* __restrict__ buf, int64_t n_rec, const uint32_t* __restrict__ rpos,
+                                                         const int64_t* __restrict__ f_keep, const int64_t* __restrict__ s_keep,
+                                                         const int64_t* __restrict__ s_bytes, const int64_t* __restrict__ hpv,
+                                                         uint8_t* out, int64_t* out_off, int64_t* totals) {
+  const int64_t gi = blockIdx.x;
+  if (gi == n_rec) {
+    if (threadIdx.x == 0) { out_off[s_keep[gi]] = s_bytes[gi]; totals[0] = s_keep[gi]; totals[1] = s_bytes[gi]; }
+    return;
+  }
+  if (!f_keep[gi]) return;
+  const int64_t p = rpos[gi], o = s_bytes[gi];
+  const uint32_t w3 = ld32(buf, p + 12), w4 = ld32(buf, p + 16);
+  const int32_t l_seq = (int32_t)ld32(buf, p + 20);
+  const uint32_t l_name = w3 & 0xffu, n_cig = w4 & 0xffffu;
+  const uint32_t n1 = 36u + l_name + 4u * n_cig + ((uint32_t)l_seq + 1u) / 2u;       // bytes taken over (block_size field included)
+  const int64_t hp = hpv[gi];
+  const uint32_t total = n1 + (hp != kNoHp ? 7u : 0u);
+  if (threadIdx.x == 0) out_off[s_keep[gi]] = o;
+  uint32_t* dst = (uint32_t*)(out + o);
+  for (uint32_t k = threadIdx.x; k < n1 / 4; k += 64) {
+    uint32_t w = ld32(buf, p + 4 * (int64_t)k);
+    if (k == 0) w = total - 4u;                       // the slim record's block_size
+    dst[k] = w;
+  }
+  if (threadIdx.x == 0) {
+    uint8_t* q = out + o;
+    for (uint32_t k = n1 & ~3u; k < n1; ++k) q[k] = buf[p + k];
+    if (hp != kNoHp) {
+      const bool neg_ok = hp >= -2147483648ll && hp <= 2147483647ll;
+      q[n1] = 'H'; q[n1 + 1] = 'P'; q[n1 + 2] = neg_ok ? 'i' : 'I';
+      const uint32_t v = (uint32_t)hp;
+      q[n1 + 3] = (uint8_t)v; q[n1 + 4] = (uint8_t)(v >> 8); q[n1 + 5] = (uint8_t)(v >> 16); q[n1 + 6] = (uint8_t)(v >> 24);
+    }
+    // the bytes up to the 4-aligned end are part of what a selection brings down: zero, not what the arena held before
+    for (uint32_t k = total; k < ((total + 3u) & ~3u); ++k) q[k] = 0;
+  }
 }
 
 // 16 ALIGNED output bytes [o0, o0 + 16) of a read's nt6 symbols (ping_pong.cpp:90-94: seq_nt16_str, then seq_nt6_table), clipped
@@ -297,6 +372,7 @@ struct svdss_bam_batch {
   struct {
     BamBuf rec, out, scratch, members, dense, len;
     BamBuf lz;   // the match finder's candidates (svdss_bam_smooth_set_deflate: lz mode only)
+    BamBuf store_flags, store_scans;   // svdss_bam_smooth_set_store: which records the store keeps, their sizes and HP; the sums
     int64_t kept = 0, out_bytes = 0, bgzf_bytes = 0, in0 = 0, xf[4] = {0, 0, 0, 0};
     const uint8_t* bgzf = nullptr;   // where the last run's BGZF members are (the caller's buffer or sel.host)
     std::vector<int64_t> nmx;
@@ -396,6 +472,32 @@ static inline void park_done(svdss_bam_park* p, int64_t g) {
   { std::lock_guard<std::mutex> lk(p->m); --p->groups[(size_t)g].pending; }
   p->cv.notify_all();
 }
+
+// ------------------------------------------------------------------ the record store (bam_device.hip owns it; bam_smooth.hip
+// deposits the batches of a smoothing run in it as well: svdss_bam_smooth_set_store)
+// What `SVDSS call` keeps of a pass over the BAM (svdss_bam_store_t): the slim records of every batch, in HBM, batch by
+// batch in arenas allocated as they are needed.
+struct StoreBatch { int arena = -1; int64_t at = 0, bytes = 0, n = 0, off_at = 0; };
+struct StoreArena { uint8_t* p = nullptr; int64_t cap = 0, used = 0; };
+struct svdss_bam_store {
+  int device = -1;
+  int64_t max_bytes = 0, arena_bytes = (int64_t)2 << 30, allocated = 0;
+  // arenas taken AHEAD of the batches by a thread of the store (see svdss_bam_store_create): next_use = the first arena no
+  // batch has been placed in yet
+  std::thread ahead;
+  std::condition_variable cv;
+  bool ahead_running = false, stop = false;
+  size_t cur = 0;                // the arena batches are being placed in
+  std::mutex m;
+  std::vector<StoreArena> arenas;
+  std::map<int64_t, StoreBatch> batches;
+  bool complete = true;          // false: a batch did not fit (the caller reads the file again)
+  int64_t n_records = 0, n_bytes = 0;
+};
+// room for batch `seq`'s slim records (+ their n + 1 offsets) at base + B.at / base + B.off_at; false: the store is over its
+// limit (and stays incomplete).  (bam_device.hip)
+__attribute__((visibility("hidden")))
+bool store_reserve(svdss_bam_store* t, int64_t seq, int64_t bytes, int64_t n, StoreBatch& B, uint8_t*& base);
 
 // ------------------------------------------------------------------ the front end's result
 // the chain of records of a batch, per segment (the argument of walk_kernel / link_kernel)

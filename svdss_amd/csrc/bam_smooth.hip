@@ -79,6 +79,25 @@ __global__ void __launch_bounds__(64) smooth_meta_kernel(SmMetaP M) {
   if (s == 0 && threadIdx.x == 0) M.f_keep[M.n_rec] = 0;
 }
 
+// svdss_bam_smooth_set_store: a thread per record of the batch, kept or dropped by the smoothing (rpos lists them all, and
+// smooth_meta_kernel has checked their sizes) -- does `SVDSS call` keep it, and how long is its slim form?  Rows of n_rec + 1.
+__global__ void __launch_bounds__(256) smooth_store_flag_kernel(const uint8_t* __restrict__ buf, const uint32_t* __restrict__ rpos, int64_t n_rec,
+                                                                int32_t min_mapq, int64_t* f_keep, int64_t* f_kbytes, int64_t* hpv) {
+  const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi > n_rec) return;
+  int64_t keep = 0, kbytes = 0, hp = kNoHp;
+  if (gi < n_rec) {
+    const int64_t p = rpos[gi];
+    const uint32_t bs = ld32(buf, p);
+    const uint32_t w3 = ld32(buf, p + 12), w4 = ld32(buf, p + 16);
+    const int32_t l_seq = (int32_t)ld32(buf, p + 20);
+    const uint32_t l_name = w3 & 0xffu, mapq = (w3 >> 8) & 0xffu, n_cig = w4 & 0xffffu, flag = w4 >> 16;
+    const int64_t head = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + l_seq;
+    if (call_keeps(flag, mapq, min_mapq)) { keep = 1; kbytes = slim_measure(buf, p, bs, head, l_seq, hp); }
+  }
+  f_keep[gi] = keep; f_kbytes[gi] = kbytes; hpv[gi] = hp;
+}
+
 struct SmWalkP {
   const uint8_t* buf;
   const uint32_t* rpos; const int64_t* f_keep; const int64_t* s_keep;
@@ -642,6 +661,8 @@ struct svdss_bam_smooth {
   int32_t search_flags = -1;            // svdss_bam_smooth_set_search (-1: the reads are not exported for a search)
   svdss_bam_park* park = nullptr;       // ... where they wait for the index (nullptr: in the batch object)
   bool write_bam = true;                // svdss_bam_smooth_set_output (false: no BGZF members)
+  svdss_bam_store* store = nullptr;     // svdss_bam_smooth_set_store (nullptr: nothing is kept for `call`)
+  int32_t store_min_mapq = 0;           // ... `call`'s own --min-mapq
   SvdssRefView ref;
   int32_t* d_tidmap = nullptr;
 };
@@ -699,6 +720,13 @@ extern "C" int svdss_bam_smooth_set_search(svdss_bam_smooth_t* sm, int32_t flags
 extern "C" int svdss_bam_smooth_set_output(svdss_bam_smooth_t* sm, int32_t write_bam) {
   if (!sm || (write_bam != 0 && write_bam != 1)) return SVDSS_EINVAL;
   sm->write_bam = write_bam != 0;
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_bam_smooth_set_store(svdss_bam_smooth_t* sm, svdss_bam_store_t* store, int32_t min_mapq) {
+  if (!sm || (store && store->device != sm->device)) return SVDSS_EINVAL;
+  sm->store = store;
+  sm->store_min_mapq = min_mapq;
   return SVDSS_OK;
 }
 
@@ -790,6 +818,25 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
     run.lap(6);
     return SVDSS_OK;
   }
+  // ---- svdss_bam_smooth_set_store: what `SVDSS call` keeps of the batch's ORIGINAL records (W.buf), whatever the smoothing
+  // thinks of them -- flags, sizes and their sums now; the totals come down with the sizes' below, the records go into the
+  // store behind that wait (the bytes svdss_bam_select_store_run leaves: its predicate, its sizes, its export kernel)
+  svdss_bam_store* store = sm->store;
+  if (store) { std::lock_guard<std::mutex> lk(store->m); if (!store->complete) store = nullptr; }
+  int64_t st_kept[2] = {0, 0};
+  int64_t *st_flags = nullptr, *st_sums = nullptr;
+  if (store) {
+    const int64_t row = n_rec + 1;
+    RCHK(b->sm.store_flags.ensure(sizeof(int64_t) * 3 * (size_t)row));
+    RCHK(b->sm.store_scans.ensure(sizeof(int64_t) * 2 * (size_t)row));
+    st_flags = (int64_t*)b->sm.store_flags.p; st_sums = (int64_t*)b->sm.store_scans.p;
+    hipLaunchKernelGGL(smooth_store_flag_kernel, dim3((unsigned)((row + 255) / 256)), dim3(256), 0, st, W.buf, (const uint32_t*)M.rpos, n_rec,
+                       sm->store_min_mapq, st_flags, st_flags + row, st_flags + 2 * row);
+    BCHK(hipGetLastError());
+    RCHK(run.scan_rows(st_flags, st_sums, row, 2));
+    BCHK(hipMemcpyAsync(&st_kept[0], st_sums + n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&st_kept[1], st_sums + row + n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  }
   // ---- sizes, places, the records
   {
     SmSizeP S;
@@ -805,6 +852,18 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
   BCHK(hipMemcpyAsync(hdr2, b->front.hdr.p, sizeof hdr2, hipMemcpyDeviceToHost, st));
   BCHK(hipStreamSynchronize(st));
   if (hdr2[H_ERR] & E_NCIG) return run.fail(SVDSS_ERANGE, "more than 65535 CIGAR operations (CG tag records are not supported)");
+  if (store) {
+    StoreBatch B;
+    uint8_t* sbase = nullptr;
+    if (store_reserve(store, seq, st_kept[1], st_kept[0], B, sbase)) {
+      const int64_t row = n_rec + 1;
+      RCHK(b->totals.ensure(64));
+      hipLaunchKernelGGL(slim_export_kernel, dim3((unsigned)row), dim3(64), 0, st, W.buf, n_rec, (const uint32_t*)M.rpos, (const int64_t*)st_flags,
+                         (const int64_t*)st_sums, (const int64_t*)(st_sums + row), (const int64_t*)(st_flags + 2 * row), sbase + B.at,
+                         (int64_t*)(sbase + B.off_at), (int64_t*)b->totals.p + 2);
+      BCHK(hipGetLastError());
+    }
+  }
   const int64_t out_bytes = tot[0];
   b->sm.out_bytes = out_bytes;
   // the output stream of the batch sits behind room for what the batch before leaves over (batch 0: the BAM header)

@@ -450,11 +450,15 @@ uint8_t enc26(char c) {   // caller.hpp:25-37
 namespace {
 
 // One pass over the BAM, record after record in file order: the records the device path keeps (sel; its filters, one per
-// region of the file, decide which) or every record of the host reader (bam).  next: 1 = record, 0 = end of the file,
-// -1 = error (err says which).
+// region of the file, decide which), every record of the host reader (bam), or -- `SVDSS run`, whose smoothing stage has
+// left every record `call` looks at in HBM -- the records filters[0] keeps of a filled record store, stored batch after
+// stored batch (store).  next: 1 = record, 0 = end of the file, -1 = error (err says which).
 struct RecordFeed {
   std::unique_ptr<ShardedBamSelect<SelectedBatch>> sel;
   std::vector<svdss_bam_filter_t*> filters;
+  svdss_bam_store_t* store = nullptr;
+  int64_t store_batches = 0, store_at = 0;
+  svdss_bam_batch_t* store_obj = nullptr;
   std::unique_ptr<BamReader> bam;
   // host reader: called with every chunk it inflates, before the first record of the chunk is handed out (the record
   // views point into it)
@@ -469,7 +473,24 @@ struct RecordFeed {
 
   ~RecordFeed() {
     sel.reset();   // (its threads use the filters)
+    if (store_obj) svdss_bam_batch_free(store_obj);
     for (svdss_bam_filter_t* f : filters) svdss_bam_filter_free(f);
+  }
+
+  // the next stored batch's selection (svdss_bam_store_select: slim records, file order); null at the end or on error
+  std::unique_ptr<SelectedBatch> next_from_store() {
+    if (store_at >= store_batches) return nullptr;
+    const int rc = svdss_bam_store_select(store, store_at++, filters[0], &store_obj);
+    if (rc != SVDSS_OK) { err = std::string("record store: ") + svdss_strerror(rc) + " " + svdss_last_hip_error(); return nullptr; }
+    svdss_bam_selection_t r;
+    (void)svdss_bam_batch_selection(store_obj, &r);
+    std::unique_ptr<SelectedBatch> out(new SelectedBatch);
+    out->bytes.assign(r.bytes, r.bytes + r.n_bytes);
+    out->off.assign(r.rec_off, r.rec_off + r.n_selected + 1);
+    out->n_records = (uint64_t)r.n_records;
+    out->slim = true;
+    for (int s = 0; s < 8; ++s) out->stage_s[s] = r.stage_ms[s] * 1e-3;
+    return out;
   }
 
   int next(BamReader::RawView& rr) {
@@ -481,10 +502,10 @@ struct RecordFeed {
     }
     while (!cur || k + 1 >= cur->off.size()) {
       const auto tw0 = std::chrono::steady_clock::now();
-      cur = sel->next();
+      cur = store ? next_from_store() : sel->next();
       wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
       k = 0;
-      if (!cur) { err = sel->error(); return err.empty() ? 0 : -1; }
+      if (!cur) { if (sel) err = sel->error(); return err.empty() ? 0 : -1; }
       n_records += cur->n_records;
       for (int s = 0; s < 8; ++s) stage_s[s] += cur->stage_s[s];
       stage_s[7] += cur->inflate_kernel_s; ++n_batches;
@@ -701,7 +722,12 @@ struct CallRun {
   std::vector<SV> svs;
   std::vector<std::vector<std::string>> sam_rows;   // per reference thread, --poa only
 
-  explicit CallRun(const CallOptions& opt) : o(opt), T(std::max(1, opt.threads)) { C.o = opt; }
+  // `SVDSS run` (run_host.cpp): the SFS text in memory, the filled record store, the chromosomes -- what the smoothing and
+  // search stages of the same process left (null: `SVDSS call`)
+  CallPreset* const preset;
+  bool from_store() const { return preset && preset->store; }
+
+  explicit CallRun(const CallOptions& opt, CallPreset* p = nullptr) : o(opt), T(std::max(1, opt.threads)), preset(p) { C.o = opt; }
 
   void stage(const char* what) {   // --verbose: seconds since the previous stage mark
     if (!o.verbose) return;
@@ -714,7 +740,10 @@ struct CallRun {
   void load_inputs() {
     // ---- load_chromosomes (chromosomes.cpp:9-27): upper-cased, FASTA order.  On a thread of its own: the SFS file is
     // parsed and pass 1 starts reading the BAM beside it; the first use of the chromosomes waits (reference_ready)
-    {
+    if (preset && preset->from_smooth) {   // (read once, by the smoothing stage)
+      C.chrom_names = std::move(preset->from_smooth->chrom_names);
+      C.chrom_seqs = std::move(preset->from_smooth->chrom_seqs);
+    } else {
       if (FILE* f = fopen(o.reference.c_str(), "rb")) fclose(f); else die("cannot open " + o.reference);
       fasta_loader = std::thread([this] {
         {   // a plain FASTA with '\n' line ends: mapped and read by several threads (fastx_reader.h)
@@ -754,7 +783,11 @@ struct CallRun {
         if (!bam_header_probe(o.bam, n_ref_hdr, bam_skip, herr, &ref_names)) die("cannot read " + o.bam + ": " + herr);
         bam_cuts = plan_bam_regions(o.bam, G, bam_skip);
       }
-      if (dev_pass && !(getenv("SVDSS_CALL_STORE") && atoi(getenv("SVDSS_CALL_STORE")) == 0)) {
+      if (from_store()) {   // (filled already: one region, no seam)
+        if (!dev_pass) die("the record store needs the device path");
+        stores.assign(1, preset->store);
+        seam_stores.assign(1, nullptr);
+      } else if (dev_pass && !(getenv("SVDSS_CALL_STORE") && atoi(getenv("SVDSS_CALL_STORE")) == 0)) {
         // (up to SVDSS_CALL_STORE_GB per GPU, default 160: a 30x human sample is ~50 GB; more than fits: the file is read again,
         // as before.  Expected size: the bases of the file, two per byte, + names and CIGARs -- at most ~2.5 x a well-compressed BAM)
         const int64_t gb = getenv("SVDSS_CALL_STORE_GB") && atoll(getenv("SVDSS_CALL_STORE_GB")) > 0 ? atoll(getenv("SVDSS_CALL_STORE_GB")) : 160;
@@ -777,7 +810,8 @@ struct CallRun {
     // ---- parse_sfsfile (sfs.cpp:5-30)
     // (csrc/sfs_file.h: the file mapped and parsed by T threads; a file that cannot be opened leaves the map empty, as
     // the reference's ifstream does)
-    (void)sfs_parse_file(o.sfs.c_str(), T, C.sfs);
+    if (preset && preset->sfs_text) (void)sfs_parse_buffer(preset->sfs_text, preset->sfs_bytes, T, C.sfs);
+    else (void)sfs_parse_file(o.sfs.c_str(), T, C.sfs);
     stage("reference + sfs file");
   }
 
@@ -808,6 +842,18 @@ struct CallRun {
     std::string names;
     std::vector<int64_t> name_off(1, 0);
     for (const auto& kv : C.sfs) { names += kv.first; name_off.push_back((int64_t)names.size()); }
+    auto names_filter = [&](int32_t dev) {
+      svdss_bam_filter_t* flt = nullptr;
+      check(svdss_bam_filter_create(dev, (int32_t)std::min<unsigned>(o.min_mapq, 256u), n_ref_hdr, names.data(), name_off.data(),
+                                    (int64_t)name_off.size() - 1, nullptr, nullptr, nullptr, 0, &flt), "svdss_bam_filter_create");
+      return flt;
+    };
+    if (from_store()) {   // the stored batches, in batch order, through the names filter: no file is opened
+      f.filters.push_back(names_filter(0));
+      f.store = preset->store;
+      f.store_batches = preset->store_batches;
+      return;
+    }
     if (store_alloc.joinable()) store_alloc.join();
     bool all_stores = !stores.empty();
     for (svdss_bam_store_t* st : stores) all_stores = all_stores && st != nullptr;
@@ -817,12 +863,7 @@ struct CallRun {
       for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
       stores.clear(); seam_stores.clear();
     }
-    open_select(f, n_ref_hdr, true, [&](int32_t dev) {
-      svdss_bam_filter_t* flt = nullptr;
-      check(svdss_bam_filter_create(dev, (int32_t)std::min<unsigned>(o.min_mapq, 256u), n_ref_hdr, names.data(), name_off.data(),
-                                    (int64_t)name_off.size() - 1, nullptr, nullptr, nullptr, 0, &flt), "svdss_bam_filter_create");
-      return flt;
-    });
+    open_select(f, n_ref_hdr, true, names_filter);
   }
 
   // Clusterer::align_and_extend (clusterer.cpp:56-156): pass 1 over the BAM, placement of every SFS
@@ -883,7 +924,12 @@ struct CallRun {
         if (ref_set_up) return;
         ref_set_up = true;
         reference_ready();
-        if (!getenv("SVDSS_PLACE_HOST") && !o.clipped) {
+        SmoothHooks* const sm = preset ? preset->from_smooth : nullptr;
+        if (sm && sm->dref) {   // (the smoothing stage's upload: the same chromosomes in the same order)
+          if (!getenv("SVDSS_PLACE_HOST") && !o.clipped) { dref = sm->dref; tid_map = sm->tid_map; }
+          else svdss_ref_free(sm->dref);
+          sm->dref = nullptr;
+        } else if (!getenv("SVDSS_PLACE_HOST") && !o.clipped) {
           std::vector<const uint8_t*> parts;
           std::vector<int64_t> lens;
           for (size_t t = 0; t < ref_names.size(); ++t) {
@@ -986,6 +1032,13 @@ struct CallRun {
       }
       if (worker.joinable()) worker.join();
       set_up_reference();   // (an input without a single batch: the later stages still want the chromosomes)
+      if (feed.store) {
+        region_batches.assign(1, feed.store_batches); region_seam.assign(1, 0);
+        char buf[240];
+        snprintf(buf, sizeof buf, "pass 1 from the records kept in HBM: %llu batches, %llu records looked at; select + records down %.3f s",
+                 (unsigned long long)feed.n_batches, (unsigned long long)feed.n_records, feed.stage_s[3]);
+        logmsg("debug", buf);
+      }
       if (const ShardedBamSelect<SelectedBatch>* sel = feed.sel.get()) {
         region_batches.clear(); region_seam.clear();
         for (size_t g = 0; g < sel->n_regions(); ++g) { region_batches.push_back(sel->region_batches(g)); region_seam.push_back(sel->region_has_seam(g) ? 1 : 0); }
@@ -1612,7 +1665,7 @@ struct CallRun {
 
 }  // namespace
 
-int main_call(const CallOptions& o) {
-  CallRun run(o);
+int main_call(const CallOptions& o, CallPreset* preset) {
+  CallRun run(o, preset);
   return run.run();
 }

@@ -2,7 +2,7 @@
 // config.cpp:26-107: the same option names, defaults and post-processing; cxxopts accepts `--opt value` and
 // `--opt=value`).  In a header of its own so that tests/test_ref_pins.py can hold it against the reference's own
 // config.cpp (oracle/_ref).  Additions of this program: --gpus N|all, --io-threads N, --write-index FILE (smooth),
-// --compress runs|lz (smooth), --nobam (smooth --index --sfs).
+// --compress runs|lz (smooth), --nobam (smooth --index --sfs), --smoothed FILE (run).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -20,6 +20,7 @@ struct Options {
   std::string write_index;                         // smooth --write-index FILE: the output's BAI (or CSI: *.csi)
   int compress = 0;                                // smooth --compress runs|lz: the GPU deflate's mode (0 runs, 1 lz)
   bool nobam = false;                              // smooth --index --sfs --nobam: the SFS text alone, no BAM on stdout
+  std::string smoothed;                            // run --smoothed FILE: also write the smoothed BAM
   bool gpus_all = false;                           // --gpus all (the caller asks the library how many there are)
   bool putative = true, assemble = true, verbose = false, version = false, help = false, clipped = false, binary = false;
 };
@@ -98,7 +99,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
       {"min-cluster-weight", INT}, {"accp", FLT}, {"clipped", FLAG}, {"noht", FLAG}, {"noassemble", FLAG},
       {"noputative", FLAG}, {"binary", FLAG}, {"version", FLAG}, {"help", FLAG}, {"h", FLAG}, {"l", FLT}, {"verbose", FLAG},
       {"gpus", STR}, {"io-threads", INT}, {"write-index", STR},
-      {"compress", STR}, {"nobam", FLAG}};   // (the last five: this program's own)
+      {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}};   // (the last six: this program's own)
   auto find = [&](const std::string& name) -> const Spec* {
     for (const Spec& sp : specs)
       if (name == sp.name) return &sp;
@@ -124,7 +125,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
     else if (n == "noht") o.useht = !b; else if (n == "noassemble") o.assemble = !b; else if (n == "noputative") o.putative = !b;
     else if (n == "binary") o.binary = b; else if (n == "version") o.version = b; else if (n == "help" || n == "h") o.help = b;
     else if (n == "verbose") o.verbose = b; else if (n == "io-threads") o.io_threads = x; else if (n == "write-index") o.write_index = v;
-    else if (n == "nobam") o.nobam = b;
+    else if (n == "nobam") o.nobam = b; else if (n == "smoothed") o.smoothed = v;
     else if (n == "compress") { if (v == "runs") o.compress = 0; else if (v == "lz") o.compress = 1; else return failed(v); }
     else if (n == "gpus") { if (v == "all") o.gpus_all = true; else if (!to_int(v, o.gpus)) return failed(v); }
     return true;

@@ -27,8 +27,7 @@ struct RawSFS { int qs, l, htag; };
 using SfsMap = std::unordered_map<std::string, std::vector<RawSFS>>;
 
 // the line-by-line reader (the reference's loop: `>> name >> qs >> l >> htag` per line)
-inline bool sfs_parse_lines(const char* path, SfsMap& out) {
-  FILE* f = fopen(path, "r");
+inline bool sfs_parse_lines(FILE* f, SfsMap& out) {
   if (!f) return false;
   char nm[4096]; int qs, l, ht; std::string cur;
   char line[8192];
@@ -40,6 +39,7 @@ inline bool sfs_parse_lines(const char* path, SfsMap& out) {
   fclose(f);
   return true;
 }
+inline bool sfs_parse_lines(const char* path, SfsMap& out) { return sfs_parse_lines(fopen(path, "r"), out); }
 
 namespace sfs_file_detail {
 
@@ -97,20 +97,12 @@ inline void parse_piece(const char* b, const char* e, Piece& P) {
 
 }  // namespace sfs_file_detail
 
-// the whole file into `out` with `threads` threads; false if it cannot be opened
-inline bool sfs_parse_file(const char* path, int threads, SfsMap& out) {
+// `size` bytes of the text at `base` into `out` with `threads` threads; false (and `out` as it was) if the text has what
+// only the line-by-line reader takes on
+inline bool sfs_parse_text(const char* base, size_t size, int threads, SfsMap& out) {
   using namespace sfs_file_detail;
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return false;
-  struct stat st;
-  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); return sfs_parse_lines(path, out); }
-  const size_t size = (size_t)st.st_size;
-  if (size == 0) { close(fd); return true; }
-  void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) return sfs_parse_lines(path, out);
-  const char* base = (const char*)m;
-  if (memchr(base, '\0', size)) { munmap(m, size); return sfs_parse_lines(path, out); }   // (fgets / sscanf stop at a NUL)
+  if (size == 0) return true;
+  if (memchr(base, '\0', size)) return false;   // (fgets / sscanf stop at a NUL)
   const size_t T = (size_t)(threads < 1 ? 1 : threads);
   const size_t n_pieces = std::max<size_t>(1, std::min<size_t>(T, size / (1 << 20) + 1));
   std::vector<const char*> cut(n_pieces + 1, base + size);
@@ -128,10 +120,8 @@ inline bool sfs_parse_file(const char* path, int threads, SfsMap& out) {
     parse_piece(cut[0], cut[1], pieces[0]);
     for (std::thread& t : pool) t.join();
   }
-  bool long_line = false;
   size_t n_groups = 0;
-  for (const Piece& P : pieces) { long_line = long_line || P.long_line; n_groups += P.groups.size(); }
-  if (long_line) { munmap(m, size); out.clear(); return sfs_parse_lines(path, out); }
+  for (const Piece& P : pieces) { if (P.long_line) return false; n_groups += P.groups.size(); }
   out.reserve(out.size() + n_groups + 1);
   std::vector<RawSFS>* cur = nullptr;       // the list of the read the last named line named
   for (const Piece& P : pieces) {
@@ -144,6 +134,27 @@ inline bool sfs_parse_file(const char* path, int threads, SfsMap& out) {
       cur->assign(P.recs.begin() + (long)g.first, P.recs.begin() + (long)(g.first + g.count));
     }
   }
-  munmap(m, size);
   return true;
+}
+
+// the text in memory (`SVDSS run`: what the search stage wrote) into `out`, with the code that parses the mapped file
+inline bool sfs_parse_buffer(const char* text, size_t size, int threads, SfsMap& out) {
+  if (sfs_parse_text(text, size, threads, out)) return true;
+  return sfs_parse_lines(fmemopen(const_cast<char*>(text), size, "r"), out);
+}
+
+// the whole file into `out` with `threads` threads; false if it cannot be opened
+inline bool sfs_parse_file(const char* path, int threads, SfsMap& out) {
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return false;
+  struct stat st;
+  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); return sfs_parse_lines(path, out); }
+  const size_t size = (size_t)st.st_size;
+  if (size == 0) { close(fd); return true; }
+  void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+  close(fd);
+  if (m == MAP_FAILED) return sfs_parse_lines(path, out);
+  const bool ok = sfs_parse_text((const char*)m, size, threads, out);
+  munmap(m, size);
+  return ok ? true : sfs_parse_lines(path, out);
 }

@@ -249,6 +249,12 @@ class SfsSide {
       logmsg("debug", buf);
     }
   }
+  // `SVDSS run`, after finish(): the index and the park leave HBM before `call` takes its workspaces
+  void free_index_and_park() {
+    svdss_index_free(early_.wait_for_offered_index());
+    svdss_bam_park_free(early_.park);
+    early_.park = nullptr;
+  }
  private:
   // the side thread: the index file, the form it becomes resident in (SVDSS_KMER, SVDSS_SEARCH_LF, SVDSS_SEARCH_LF_MAX as
   // for `search`; the estimate of the reads to search runs on the XF counts the batches bring), then to the feeders
@@ -348,13 +354,16 @@ class SfsSide {
 };
 }  // namespace
 
-int main_smooth(const CallOptions& o) {
+// hooks (`SVDSS run`, run_host.cpp): the device path also fills a record store for `call`, the SFS text goes to the hooks'
+// sink, and the function returns -- the process and the GPU context stay -- with the chromosomes handed over
+int main_smooth(const CallOptions& o, SmoothHooks* hooks) {
   std::unordered_map<std::string, std::string> chrom;
   const auto t_fasta0 = std::chrono::steady_clock::now();
   // --index FMD --sfs FILE: what it cannot run on is said before FILE or anything else is created; then the index is on its
   // way from the first moment
   std::unique_ptr<SfsSide> side;
-  if (!o.sfs.empty()) {
+  if (hooks && hooks->sfs_sink) side.reset(new SfsSide(o, hooks->sfs_sink));   // (`SVDSS run` has refused what cannot run)
+  else if (!o.sfs.empty()) {
     if (o.gpus != 1) die("smooth --index --sfs with --gpus other than 1 is out of scope: run it on one GPU");
     if (getenv("SVDSS_SMOOTH_HOST") || (getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0) ||
         (getenv("SVDSS_GPU_DEFLATE") && atoi(getenv("SVDSS_GPU_DEFLATE")) == 0))
@@ -386,13 +395,17 @@ int main_smooth(const CallOptions& o) {
     // reads); anything else -- gzip, CRLF, FASTQ-like headers -- line by line.
     std::vector<std::string> nm, sq;
     if (!getenv("SVDSS_FASTA_SERIAL") && load_fasta_mapped(o.reference, std::max(1, std::min((int)o.threads, 16)), true, nm, sq)) {
-      for (size_t i = 0; i < nm.size(); ++i) chrom[nm[i]] = std::move(sq[i]);   // (a name that occurs twice: the later record wins, as below)
+      for (size_t i = 0; i < nm.size(); ++i) {
+        if (hooks) hooks->chrom_names.push_back(nm[i]);
+        chrom[nm[i]] = std::move(sq[i]);   // (a name that occurs twice: the later record wins, as below)
+      }
     } else {
       FastxReader fx(o.reference);
       if (!fx.ok()) die("cannot open " + o.reference);
       std::string name, seq;
       while (fx.next(name, seq)) {
         for (char& c : seq) c = (char)(c - ((c >= 'a' && c <= 'z') ? 32 : 0));   // toupper (ASCII; vectorises)
+        if (hooks) hooks->chrom_names.push_back(name);
         chrom[name].swap(seq);
       }
     }
@@ -426,8 +439,9 @@ int main_smooth(const CallOptions& o) {
   // measured, smoothed, rebuilt and deflated in HBM.  SVDSS_BAM_DEVICE=0 (or SVDSS_SMOOTH_HOST=1): the host pipeline below,
   // which writes the same bytes.
   // (SVDSS_GPU_DEFLATE=0 asks for the host's deflate: that is the host pipeline's writer)
+  // (`SVDSS run` without --smoothed deflates nothing, on either side)
   if (!getenv("SVDSS_SMOOTH_HOST") && svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0) &&
-      !(getenv("SVDSS_GPU_DEFLATE") && atoi(getenv("SVDSS_GPU_DEFLATE")) == 0)) {
+      ((hooks && o.nobam) || !(getenv("SVDSS_GPU_DEFLATE") && atoi(getenv("SVDSS_GPU_DEFLATE")) == 0))) {
     if (!hp.err.empty()) die(hp.err);
     const std::string& header_text = hp.text;
     const std::vector<std::string>& names = hp.names;
@@ -581,6 +595,7 @@ int main_smooth(const CallOptions& o) {
         if (rcs[d] == SVDSS_OK) rcs[d] = svdss_bam_smooth_set_deflate(sms[d], o.compress);
         if (rcs[d] == SVDSS_OK && side) rcs[d] = svdss_bam_smooth_set_search(sms[d], side->flags(), park);
         if (rcs[d] == SVDSS_OK && o.nobam) rcs[d] = svdss_bam_smooth_set_output(sms[d], 0);
+        if (rcs[d] == SVDSS_OK && hooks && hooks->store) rcs[d] = svdss_bam_smooth_set_store(sms[d], hooks->store, (int32_t)std::min<unsigned>(o.min_mapq, 256u));
       };
       for (size_t d = 1; d < n_sm; ++d) up.emplace_back(upload, d);
       upload(0);
@@ -713,6 +728,7 @@ int main_smooth(const CallOptions& o) {
       for (uint8_t* q : pool.buf) if (q) svdss_host_free(q);
       if (!rerr.empty()) die("error reading " + o.bam + ": " + rerr);
       if (side) side->finish(n_batches);
+      if (side && hooks) side->free_index_and_park();
       if (dbg && !side)
         fprintf(stderr, "[smooth] device path: %llu records, %llu kept (XF 0/1/2/3: %llu %llu %llu %llu), %llu BGZF bytes; feeder seconds: front %.3f "
                 "turn wait %.3f turn %.3f walk %.3f rebuild %.3f output turn %.3f deflate + down %.3f (inflate kernels %.3f); writing %.3f\n",
@@ -729,6 +745,11 @@ int main_smooth(const CallOptions& o) {
     static const uint8_t eof_marker[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (!o.nobam && (fwrite(eof_marker, 1, 28, stdout) != 28 || fflush(stdout) != 0)) write_ok = false;
     for (svdss_bam_smooth_t* q : sms) svdss_bam_smooth_free(q);
+    if (hooks) {   // (the chromosomes stay where they are, for `call`'s placement kernel)
+      hooks->dref = drefs[0]; drefs[0] = nullptr;
+      hooks->tid_map = tid_map;
+      hooks->n_batches = n_batches;
+    }
     for (svdss_ref_t* q : drefs) svdss_ref_free(q);
     if (!write_ok) die("error writing the BAM to stdout");
     if (ixb) {
@@ -736,6 +757,10 @@ int main_smooth(const CallOptions& o) {
       if (!ixb->write(o.write_index, err)) die(err);
     }
     if (dbg) fprintf(stderr, "[smooth] done at +%.3f s\n", since());
+    if (hooks && hooks->keep_alive) {
+      hooks->chrom_seqs = std::move(chrom);
+      return 0;
+    }
     if (!getenv("SVDSS_CLEAN_EXIT")) {
       fprintf(stderr, "[smooth] [info] All done!\n");
       fflush(stderr);

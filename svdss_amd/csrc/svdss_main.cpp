@@ -6,11 +6,13 @@
 //   SVDSS search --index F --bam B | --fastx Q [--threads T] [--bsize N] [--noputative]
 //                [--noassemble] [--omax N] [--verbose]  (config.cpp:30-55, main.cpp:62-68; search_host.cpp)
 //   SVDSS call   --reference R --bam B --sfs S [...]    (main.cpp:55-61; call_host.cpp)
+//   SVDSS run    --reference R --bam B --index F [...]  (run_host.cpp: smooth, search and call in one pass over the BAM)
 //   SVDSS --version                                     (main.cpp:45-47)
 // This file: the usage texts, the command line, `index`; the other sub-commands have a file each.
 // Logs go to stderr (host_common.h), fatal conditions exit(1).
 // Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth),
-// --compress runs|lz (smooth), --index FMD --sfs FILE [--nobam] (smooth: the search of the smoothed reads in the same pass).
+// --compress runs|lz (smooth), --index FMD --sfs FILE [--nobam] (smooth: the search of the smoothed reads in the same pass),
+// the sub-command `run` with its --smoothed FILE.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -32,12 +34,17 @@
 
 static const char* VERSION = "v2.1.1";  // main.cpp:19
 
+// (weak: a build of the binary from a source list without run_host.cpp -- the sanitized CPU build of tests/ -- still links;
+// `run` then says so)
+__attribute__((weak)) int main_run(const CallOptions& o);
+
 static const char* MAIN_USAGE =
-    "Usage: SVDSS <index|smooth|search|call> --help\n"
+    "Usage: SVDSS <index|smooth|search|call|run> --help\n"
     "  index   build the FM-index of a reference (FASTA, gz ok):  SVDSS index -d ref.fa -o ref.fa.fmd [-t T]\n"
     "  search  extract sample-specific strings: SVDSS search --index ref.fa.fmd --bam reads.bam > specifics.txt\n"
     "  call    call SVs from the specific strings:    SVDSS call --reference ref.fa --bam reads.bam --sfs specifics.txt\n"
-    "  smooth  smooth a BAM (reads equal the reference except at long indels): SVDSS smooth --reference ref.fa --bam in.bam > out.bam\n";
+    "  smooth  smooth a BAM (reads equal the reference except at long indels): SVDSS smooth --reference ref.fa --bam in.bam > out.bam\n"
+    "  run     smooth, search and call in one pass over the BAM: SVDSS run --reference ref.fa --bam reads.bam --index ref.fa.fmd > variations.vcf\n";
 
 static const char* SMOOTH_USAGE =
     "Usage: SVDSS smooth --reference <FASTA> --bam <BAM> > smoothed.bam\n"
@@ -65,6 +72,20 @@ static const char* CALL_USAGE =
     "      -l <float>                  minimum length ratio for sub-clusters and chain merging (default: 0.97)\n"
     "      --noht                      ignore the HP tag\n"
     "      --clipped                   also call imprecise SVs from soft-clipped alignments (EXPERIMENTAL)\n";
+
+static const char* RUN_USAGE =
+    "Usage: SVDSS run --reference <FASTA> --bam <BAM> --index <FMD> > variations.vcf\n"
+    "      smooth, search and call in one process and one pass over the BAM (one GPU, the device path); stdout receives the\n"
+    "      VCF of `SVDSS smooth`, `SVDSS search` on its output and `SVDSS call` on <BAM> with the same option values\n"
+    "      --sfs <FILE>          also write the specific strings (what `SVDSS search` writes to stdout)\n"
+    "      --smoothed <FILE>     also write the smoothed BAM (what `SVDSS smooth` writes to stdout); without it nothing is deflated\n"
+    "      --write-index <FILE>  with --smoothed: its index, CSI if FILE ends in .csi, else BAI\n"
+    "      --compress <runs|lz>  with --smoothed: how the GPU deflates it (default: runs)\n"
+    "      --threads <int> --min-mapq <int> --accp <float>                      as in smooth, search and call\n"
+    "      --bsize <int> --noputative --noassemble                              as in search\n"
+    "      --min-cluster-weight <int> --min-sv-length <int> -l <float> --noht   as in call\n"
+    "      --poa <FILE> --clusters <FILE> --clipped                             as in call\n"
+    "      --verbose             stage timings and the record store's size on stderr\n";
 
 static const char* SEARCH_USAGE =
     "Usage: SVDSS search --index <FMD> --bam <BAM> | --fastx <FASTA/FASTQ>\n"
@@ -206,12 +227,14 @@ int main(int argc, char** argv) {
     const Options o = parse(argc, argv);
     if (o.help) {   // Configuration::print_help(argv[1]), config.cpp:12-24: the mode's own usage text
       fputs(!strcmp(argv[1], "search") ? SEARCH_USAGE : !strcmp(argv[1], "call") ? CALL_USAGE :
-            !strcmp(argv[1], "smooth") ? SMOOTH_USAGE : MAIN_USAGE, stderr);
+            !strcmp(argv[1], "smooth") ? SMOOTH_USAGE : !strcmp(argv[1], "run") ? RUN_USAGE : MAIN_USAGE, stderr);
       return EXIT_SUCCESS;
     }
     if (o.nobam && strcmp(argv[1], "smooth") != 0) die(std::string("--nobam is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
-    if (!o.write_index.empty() && strcmp(argv[1], "smooth") != 0)
+    if (!o.write_index.empty() && strcmp(argv[1], "smooth") != 0 && strcmp(argv[1], "run") != 0)
       die(std::string("--write-index is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
+    if (!o.smoothed.empty() && strcmp(argv[1], "run") != 0)
+      die(std::string("--smoothed is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
     if (!strcmp(argv[1], "search")) {
       if (o.index.empty() || (o.fastx.empty() && o.bam.empty())) { fputs(SEARCH_USAGE, stderr); return EXIT_FAILURE; }
       main_search(o, t0);
@@ -235,6 +258,18 @@ int main(int argc, char** argv) {
       c.index = o.index; c.sfs = o.sfs; c.bsize = o.bsize; c.putative = o.putative; c.assemble = o.assemble; c.nobam = o.nobam;
       c.verbose = o.verbose;
       main_smooth(c);
+    } else if (!strcmp(argv[1], "run")) {
+      if (o.reference.empty() || o.bam.empty() || o.index.empty()) { fputs(RUN_USAGE, stderr); return EXIT_FAILURE; }
+      if (!o.write_index.empty() && o.smoothed.empty()) die("run: --write-index needs --smoothed <FILE> (there is no BAM to index)");
+      if (o.compress != 0 && o.smoothed.empty()) die("run: --compress needs --smoothed <FILE> (nothing is deflated without it)");
+      CallOptions c;
+      c.reference = o.reference; c.bam = o.bam; c.index = o.index; c.sfs = o.sfs; c.smoothed = o.smoothed; c.threads = o.threads; c.gpus = o.gpus;
+      c.min_mapq = o.min_mapq; c.accp = o.accp; c.write_index = o.write_index; c.compress = o.compress;
+      c.bsize = o.bsize; c.putative = o.putative; c.assemble = o.assemble;
+      c.min_cluster_weight = o.min_cluster_weight; c.min_sv_length = o.min_sv_length; c.useht = o.useht; c.min_ratio = o.min_ratio;
+      c.poa = o.poa; c.clusters = o.clusters; c.clipped = o.clipped; c.verbose = o.verbose;
+      if (!main_run) die("this build of the binary has no `run` (run_host.cpp was left out)");
+      main_run(c);
     } else {
       fputs(MAIN_USAGE, stderr);
       return EXIT_FAILURE;
