@@ -234,8 +234,9 @@ class BgzfWriter {
   std::vector<uint32_t>* members_ = nullptr;
 };
 
-inline void bam_write_header(BgzfWriter& w, const std::string& text, const std::vector<std::string>& names,
-                             const std::vector<int32_t>& lens) {
+// the BAM header into anything with write(pointer, bytes): the BGZF writer above, or a plain byte sink
+template <class Writer>
+void bam_write_header(Writer& w, const std::string& text, const std::vector<std::string>& names, const std::vector<int32_t>& lens) {
   w.write("BAM\1", 4);
   const int32_t lt = (int32_t)text.size(), nr = (int32_t)names.size();
   w.write(&lt, 4);

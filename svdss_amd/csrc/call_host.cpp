@@ -1,4 +1,4 @@
-// call_host.cpp -- host side of `SVDSS call` (/root/reference/caller.cpp, clusterer.cpp, sv.cpp).
+// call_host.cpp -- host side of `SVDSS call` (the reference's caller.cpp, clusterer.cpp, sv.cpp).
 //
 // Integer/interval bookkeeping restated from the reference;
 // the three DP seams go to the GPU through the C-ABI in three batched calls:
@@ -29,6 +29,7 @@
 
 #define SVDSS_LOG_TAG "call"
 #include "host_common.h"
+#include "host_knobs.h"
 #include "bai_index.h"
 #include "bam_reader.h"
 #include "bam_device_select.h"
@@ -675,6 +676,7 @@ std::vector<std::vector<Ev>> scan_units(size_t n_units, size_t n_threads, const 
 // members are what one stage hands to the next.
 struct CallRun {
   const CallOptions& o;
+  const CallKnobs knobs{};               // every SVDSS_* variable this file reads (host_knobs.h)
   Ctx C;
   const int T;
   std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
@@ -695,19 +697,10 @@ struct CallRun {
   void reference_ready() { if (fasta_loader.joinable()) fasta_loader.join(); }
   bool dev_pass = false;                 // the BAM is read through the device path (csrc/bam_device.hip): no record cache
   int64_t bam_skip = 0;                  // the BAM header's length in the inflated stream
-  static int64_t bam_batch_bytes() {
-    const char* e = getenv("SVDSS_BAM_BATCH_MB");
-    return (e && atoll(e) > 0 ? atoll(e) : 256) << 20;
-  }
   // host threads that scan the file chunks an index names for pass 2 (SVDSS_CALL_PASS2_THREADS; 1: the single scan)
   size_t pass2_threads(size_t n_chunks) const {
-    const char* e = getenv("SVDSS_CALL_PASS2_THREADS");
-    const size_t want = e && atoi(e) > 0 ? (size_t)atoi(e) : std::min<size_t>((size_t)effective_cpus(), 32);
+    const size_t want = knobs.pass2_threads ? (size_t)knobs.pass2_threads : std::min<size_t>((size_t)effective_cpus(), 32);
     return std::max<size_t>(1, std::min(want, n_chunks / 4 + 1));
-  }
-  static int bam_feeders() {             // feeding threads (device batches in flight) per GPU of the two BAM passes
-    const char* e = getenv("SVDSS_CALL_FEEDERS");
-    return e && atoi(e) > 0 ? atoi(e) : 3;
   }
   std::vector<BamReader::RawView> cache_views;   // the record cache of the host reader (align_and_extend)
   std::vector<std::shared_ptr<BamReader::Bytes>> cache_chunks;
@@ -746,24 +739,7 @@ struct CallRun {
     } else {
       if (FILE* f = fopen(o.reference.c_str(), "rb")) fclose(f); else die("cannot open " + o.reference);
       fasta_loader = std::thread([this] {
-        {   // a plain FASTA with '\n' line ends: mapped and read by several threads (fastx_reader.h)
-          std::vector<std::string> nm, sq;
-          if (!getenv("SVDSS_FASTA_SERIAL") && load_fasta_mapped(o.reference, std::max(1, std::min(T, 16)), true, nm, sq)) {
-            for (size_t i = 0; i < nm.size(); ++i) {
-              C.chrom_names.push_back(nm[i]);
-              C.chrom_seqs[nm[i]] = std::move(sq[i]);   // (a name that occurs twice: the later record wins, as below)
-            }
-            return;
-          }
-        }
-        FastxReader fx(o.reference);
-        if (!fx.ok()) die("cannot open " + o.reference);
-        std::string name, seq;
-        while (fx.next(name, seq)) {
-          for (char& ch : seq) ch = (char)(ch - ((ch >= 'a' && ch <= 'z') ? 32 : 0));   // toupper of chromosomes.cpp:19 (ASCII; vectorises)
-          C.chrom_names.push_back(name);
-          C.chrom_seqs[name] = seq;
-        }
+        if (!load_chromosomes(o.reference, T, knobs.fasta_serial, C.chrom_names, C.chrom_seqs)) die("cannot open " + o.reference);
       });
     }
     // the record store(s) of the ONE pass over the BAM (round 6, align_and_extend / fill_clusters below): the memory is taken
@@ -777,7 +753,7 @@ struct CallRun {
       // the records clusterer.cpp:108-145 keeps -- instead of every inflated byte.  No record cache then: pass 2 takes the
       // records kept in HBM, goes through the BAI index, or reads the file again through the same path with the cluster
       // regions as the filter.  SVDSS_BAM_DEVICE=0: the host reader (chunks inflated on the GPU or the host, records sliced here).
-      dev_pass = svdss_device_count() > 0 && !(getenv("SVDSS_BAM_DEVICE") && atoi(getenv("SVDSS_BAM_DEVICE")) == 0);
+      dev_pass = svdss_device_count() > 0 && knobs.bam_device;
       if (dev_pass) {
         std::string herr;
         if (!bam_header_probe(o.bam, n_ref_hdr, bam_skip, herr, &ref_names)) die("cannot read " + o.bam + ": " + herr);
@@ -787,20 +763,16 @@ struct CallRun {
         if (!dev_pass) die("the record store needs the device path");
         stores.assign(1, preset->store);
         seam_stores.assign(1, nullptr);
-      } else if (dev_pass && !(getenv("SVDSS_CALL_STORE") && atoi(getenv("SVDSS_CALL_STORE")) == 0)) {
-        // (up to SVDSS_CALL_STORE_GB per GPU, default 160: a 30x human sample is ~50 GB; more than fits: the file is read again,
-        // as before.  Expected size: the bases of the file, two per byte, + names and CIGARs -- at most ~2.5 x a well-compressed BAM)
-        const int64_t gb = getenv("SVDSS_CALL_STORE_GB") && atoll(getenv("SVDSS_CALL_STORE_GB")) > 0 ? atoll(getenv("SVDSS_CALL_STORE_GB")) : 160;
-        const int64_t cap = getenv("SVDSS_CALL_STORE_MB") && atoll(getenv("SVDSS_CALL_STORE_MB")) > 0 ? atoll(getenv("SVDSS_CALL_STORE_MB")) << 20 : gb << 30;
+      } else if (dev_pass && knobs.store) {
+        // (sized by CallKnobs::store_sizes; more than fits: the file is read again, as before)
         const size_t n_reg = bam_cuts.size() - 1;
         stores.assign(n_reg, nullptr);
         seam_stores.assign(n_reg, nullptr);
-        store_alloc = std::thread([this, cap, n_reg] {
+        store_alloc = std::thread([this, n_reg] {
           const auto t0 = std::chrono::steady_clock::now();
           for (size_t g = 0; g < n_reg; ++g) {
-            const int64_t rsz = (int64_t)(bam_cuts[g + 1] - bam_cuts[g]);
-            const int64_t initial = getenv("SVDSS_CALL_STORE_INITIAL_MB") ? atoll(getenv("SVDSS_CALL_STORE_INITIAL_MB")) << 20 : std::min(cap, rsz * 5 / 2 + ((int64_t)256 << 20));
-            if (svdss_bam_store_create((int32_t)(g % (size_t)n_dev), cap, initial, &stores[g]) != SVDSS_OK) stores[g] = nullptr;
+            const std::pair<int64_t, int64_t> sz = knobs.store_sizes((int64_t)(bam_cuts[g + 1] - bam_cuts[g]));
+            if (svdss_bam_store_create((int32_t)(g % (size_t)n_dev), sz.first, sz.second, &stores[g]) != SVDSS_OK) stores[g] = nullptr;
             if (g > 0 && svdss_bam_store_create((int32_t)(g % (size_t)n_dev), (int64_t)64 << 20, 0, &seam_stores[g]) != SVDSS_OK) seam_stores[g] = nullptr;
           }
           store_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -823,7 +795,7 @@ struct CallRun {
       f.filters.push_back(shards[g].filter = filter((int32_t)(g % (size_t)n_dev)));
       if (with_stores && !stores.empty()) { shards[g].store = stores[g]; shards[g].seam_store = seam_stores[g]; }
     }
-    f.sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref, bam_skip, bam_feeders(), bam_batch_bytes(), bam_cuts));
+    f.sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref, bam_skip, knobs.feeders, knobs.batch_bytes, bam_cuts));
   }
 
   // the host reader, its chunks inflated on n_gpus GPUs in turn (where there are)
@@ -872,9 +844,8 @@ struct CallRun {
     // The inflated records of pass 1 are kept for pass 2 when they fit in memory (a second inflate of the whole file
     // otherwise): SVDSS_CALL_CACHE_GB, default 40 % of MemAvailable, at most 64 GiB.  Not on the device path.
     {
-      double gb = 0;
-      if (const char* e = getenv("SVDSS_CALL_CACHE_GB")) gb = atof(e);
-      else {
+      double gb = knobs.cache_gb;
+      if (!knobs.cache_gb_set) {
         if (FILE* f = fopen("/proc/meminfo", "r")) {
           char line[256];
           while (fgets(line, sizeof line, f)) {
@@ -919,28 +890,18 @@ struct CallRun {
       // was read (0.7 s of a 1.2 s pass at GRCh38 lengths).
       svdss_ref_t* dref = nullptr;
       std::vector<int32_t> tid_map(ref_names.size(), -1);
+      const bool place_on_gpu = !knobs.place_host && !o.clipped;
       bool ref_set_up = false;
-      auto set_up_reference = [this, &dref, &tid_map, &ref_set_up]() {
+      auto set_up_reference = [this, &dref, &tid_map, &ref_set_up, place_on_gpu]() {
         if (ref_set_up) return;
         ref_set_up = true;
         reference_ready();
         SmoothHooks* const sm = preset ? preset->from_smooth : nullptr;
         if (sm && sm->dref) {   // (the smoothing stage's upload: the same chromosomes in the same order)
-          if (!getenv("SVDSS_PLACE_HOST") && !o.clipped) { dref = sm->dref; tid_map = sm->tid_map; }
+          if (place_on_gpu) { dref = sm->dref; tid_map = sm->tid_map; }
           else svdss_ref_free(sm->dref);
           sm->dref = nullptr;
-        } else if (!getenv("SVDSS_PLACE_HOST") && !o.clipped) {
-          std::vector<const uint8_t*> parts;
-          std::vector<int64_t> lens;
-          for (size_t t = 0; t < ref_names.size(); ++t) {
-            auto it = C.chrom_seqs.find(ref_names[t]);
-            if (it == C.chrom_seqs.end()) continue;
-            tid_map[t] = (int32_t)parts.size();
-            parts.push_back((const uint8_t*)it->second.data());
-            lens.push_back((int64_t)it->second.size());
-          }
-          check(svdss_ref_upload_parts(parts.data(), lens.data(), (int32_t)parts.size(), 0, &dref), "svdss_ref_upload_parts");
-        }
+        } else if (place_on_gpu) check(upload_chromosomes(ref_names, C.chrom_seqs, 0, tid_map, &dref), "svdss_ref_upload_parts");
       };
       // two batches: the next one is read (inflate + slicing, this thread) while the T slices of the previous one run
       std::vector<BamRecord> batches[2];
@@ -1157,7 +1118,7 @@ struct CallRun {
     // in the same order as the full scan does among those that touch a cluster
     BaiIndex bai;
     bool have_bai = false;
-    if (!getenv("SVDSS_CALL_NO_BAI")) {
+    if (!knobs.no_bai) {
       // (x.bam.bai, x.bai, x.bam.csi, x.csi: the names htslib's sam_index_load looks for)
       const std::string stem = o.bam.size() > 4 && o.bam.compare(o.bam.size() - 4, 4, ".bam") == 0 ? o.bam.substr(0, o.bam.size() - 4) : std::string();
       have_bai = bai.load(o.bam + ".bai") || (!stem.empty() && bai.load(stem + ".bai")) || bai.load(o.bam + ".csi") ||
@@ -1176,10 +1137,9 @@ struct CallRun {
         for (const auto& ch : p.chunks) bytes += chunk_span(ch);
         struct stat st;
         const uint64_t file_bytes = stat(o.bam.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
-        const char* p2 = getenv("SVDSS_CALL_PASS2");
         const double share = std::min(0.6, 0.08 * (double)pass2_threads(p.chunks.size()));
-        if (p2 && !strcmp(p2, "device")) have_bai = false;
-        else if (!(p2 && !strcmp(p2, "bai")) && file_bytes && (double)bytes > share * (double)file_bytes) have_bai = false;
+        if (knobs.pass2 == "device") have_bai = false;
+        else if (knobs.pass2 != "bai" && file_bytes && (double)bytes > share * (double)file_bytes) have_bai = false;
       }
     }
     if (have_bai) {
@@ -1401,7 +1361,7 @@ struct CallRun {
           check(svdss_poa_batch_fetch(pb, part_lens[(size_t)g].data(), part_cons[(size_t)g].data()), "svdss_poa_batch_fetch");
           const auto tp2 = std::chrono::steady_clock::now();
           svdss_poa_batch_free(pb);
-          if (o.verbose && getenv("SVDSS_DEBUG"))
+          if (o.verbose && knobs.debug)
             fprintf(stderr, "[call] [debug] POA shard %d: batch %.3f s, fetch %.3f s, free %.3f s\n", g, std::chrono::duration<double>(tp1 - tp0).count(),
                     std::chrono::duration<double>(tp2 - tp1).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - tp2).count());
         };
@@ -1618,7 +1578,7 @@ struct CallRun {
     logmsg("info", "Writing " + std::to_string(svs.size()) + " SVs.");
     stage("vcf");
     if (cache_release.joinable()) cache_release.join();
-    if (getenv("SVDSS_CLEAN_EXIT")) {   // (otherwise the process ends with _exit)
+    if (knobs.clean_exit) {   // (otherwise the process ends with _exit)
       for (svdss_bam_store_t* st : stores) svdss_bam_store_free(st);
       for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
       stores.clear(); seam_stores.clear();

@@ -1,6 +1,6 @@
 // fastx_reader.h -- FASTA/FASTQ (optionally gzip) record reader for the host CLI.
 // Plays the role of the vendored klib kseq reader the reference uses
-// (/root/reference/fastq.hpp:17-35, chromosomes.cpp:9-27): name = first word of
+// (fastq.hpp:17-35, chromosomes.cpp:9-27): name = first word of
 // the header line, multi-line sequences concatenated, '+' section of FASTQ skipped.
 //
 // The file is read in 4 MB pieces and lines are found with memchr: a reference FASTA is 50 million lines of 60 bases,
@@ -18,6 +18,7 @@
 #include <functional>
 #include <thread>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 class FastxReader {
@@ -127,7 +128,7 @@ class FastxReader {
 
 // A plain (not compressed) FASTA file with '\n' line ends, read by `threads` threads from a mapping: the records found by
 // a parallel scan for lines that begin with '>', every record's lines joined (and upper-cased when `upper`: what
-// load_chromosomes does, /root/reference/chromosomes.cpp:19) by threads that each take a stretch of the file.  The result
+// load_chromosomes does, chromosomes.cpp:19) by threads that each take a stretch of the file.  The result
 // is what FastxReader::next gives record by record; anything this reader does not mean to handle -- a gzip header, a
 // carriage return anywhere, a line that begins with '@' (FASTQ, or FASTA with such a header), no record at all -- makes it
 // return false with the outputs untouched, and the caller reads the file with FastxReader.  (GRCh38: 3.1 GB in ~0.3 s
@@ -244,5 +245,27 @@ inline bool load_fasta_mapped(const std::string& path, int threads, bool upper, 
   munmap(mp, n);
   names.swap(nm);
   seqs.swap(sq);
+  return true;
+}
+
+// load_chromosomes (chromosomes.cpp:9-27) for `call` and `smooth`: upper-cased, `names` in FASTA order; a name that occurs
+// twice: the later record wins.  A plain FASTA goes through the mapping above (GRCh38 in ~0.3 s instead of ~2 s); anything
+// else -- gzip, CRLF, FASTQ-like headers, or `serial` -- line by line.  false: the file cannot be opened.
+inline bool load_chromosomes(const std::string& path, int threads, bool serial, std::vector<std::string>& names,
+                             std::unordered_map<std::string, std::string>& seqs) {
+  std::vector<std::string> nm, sq;
+  if (!serial && load_fasta_mapped(path, std::max(1, std::min(threads, 16)), true, nm, sq)) {
+    for (size_t i = 0; i < nm.size(); ++i) seqs[nm[i]] = std::move(sq[i]);
+    names.insert(names.end(), nm.begin(), nm.end());
+    return true;
+  }
+  FastxReader fx(path);
+  if (!fx.ok()) return false;
+  std::string name, seq;
+  while (fx.next(name, seq)) {
+    for (char& c : seq) c = (char)(c - ((c >= 'a' && c <= 'z') ? 32 : 0));   // toupper (ASCII; vectorises)
+    names.push_back(name);
+    seqs[name].swap(seq);
+  }
   return true;
 }

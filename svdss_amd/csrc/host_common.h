@@ -1,5 +1,6 @@
 // host_common.h -- what the host files of the binary (svdss_main.cpp, search_host.cpp, call_host.cpp, smooth_host.cpp) share:
-// one logmsg / die / check, and the number of GPUs a `--gpus N` comes to.
+// one logmsg / die / check, how an SVDSS_* variable is read, the number of GPUs a `--gpus N` comes to, and the chromosomes
+// in BAM header order on a GPU.
 // A file that defines SVDSS_LOG_TAG before it includes this header writes "[tag] [level] message" (`call`, `smooth`);
 // without one the lines are the reference's (spdlog's default pattern with a time stamp: main.cpp, ping_pong.cpp).
 #pragma once
@@ -8,6 +9,8 @@
 #include <cstdlib>
 #include <ctime>
 #include <string>
+#include <unordered_map>
+#include <vector>
 
 #include "../../include/svdss_hip.h"
 
@@ -35,4 +38,26 @@
 // asked, replica / shard / region d on GPU d % count -- the code path of N devices on a one-GPU box.
 inline int effective_gpus(int requested) {
   return std::max(1, getenv("SVDSS_GPUS_OVERSUBSCRIBE") ? requested : std::min(requested, std::max(1, svdss_device_count())));
+}
+
+// an SVDSS_* variable: the value if it is set and at least `least` / if it is set, raised to `least` / -1 not set, 0 off, 1 on
+inline int64_t env_from(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e && atoll(e) >= least ? atoll(e) : dflt; }
+inline int64_t env_raised(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e ? std::max<int64_t>(least, atoll(e)) : dflt; }
+inline int env_switch(const char* name) { const char* e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }
+
+// the chromosomes the BAM header names, in its order, one buffer on `device` (svdss_ref_upload_parts: no concatenation on
+// the host); tid_map[t]: the buffer's index of header reference t, -1 where the FASTA has no such name
+inline int upload_chromosomes(const std::vector<std::string>& ref_names, const std::unordered_map<std::string, std::string>& seqs, int device,
+                              std::vector<int32_t>& tid_map, svdss_ref_t** dref) {
+  std::vector<const uint8_t*> parts;
+  std::vector<int64_t> lens;
+  tid_map.assign(ref_names.size(), -1);
+  for (size_t t = 0; t < ref_names.size(); ++t) {
+    auto it = seqs.find(ref_names[t]);
+    if (it == seqs.end()) continue;
+    tid_map[t] = (int32_t)parts.size();
+    parts.push_back((const uint8_t*)it->second.data());
+    lens.push_back((int64_t)it->second.size());
+  }
+  return svdss_ref_upload_parts(parts.data(), lens.data(), (int32_t)parts.size(), device, dref);
 }

@@ -2,7 +2,7 @@
 //
 //   SVDSS smooth --reference FA --bam BAM > S;  SVDSS search --index FMD --bam S > T;  SVDSS call --reference FA --bam BAM --sfs T
 //
-// read the same alignments from disk three times.  Here the smoothing stage (main_smooth's device path with its SfsSide,
+// read the same alignments from disk three times.  Here the smoothing stage (SmoothRun's DevicePipeline with its SfsSide,
 // smooth_host.cpp) searches the smoothed reads while they are in HBM, as `smooth --index --sfs` does, and deposits what
 // `call` looks at of every ORIGINAL record in a record store (svdss_bam_smooth_set_store); the call stage (CallRun,
 // call_host.cpp) parses the SFS text from memory and takes both of its passes from that store.  The VCF on stdout is the
@@ -20,20 +20,17 @@
 
 #define SVDSS_LOG_TAG "run"
 #include "host_common.h"
+#include "host_knobs.h"
 #include "call_host.h"
 
-namespace {
-bool env_is_zero(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
-int64_t env_int(const char* name) { const char* e = getenv(name); return e && atoll(e) > 0 ? atoll(e) : 0; }
-}  // namespace
-
 int main_run(const CallOptions& o) {
-  const bool verbose = o.verbose || getenv("SVDSS_DEBUG") != nullptr;
+  const SmoothKnobs smooth_knobs;
+  const bool verbose = o.verbose || smooth_knobs.debug;
   // ---- what it cannot run on is said before anything is opened or written
   if (o.gpus != 1) die("run with --gpus other than 1 is out of scope: run it on one GPU");
-  if (getenv("SVDSS_SMOOTH_HOST")) die("run needs the device path: it does not run with SVDSS_SMOOTH_HOST=1");
-  if (env_is_zero("SVDSS_BAM_DEVICE")) die("run needs the device path: it does not run with SVDSS_BAM_DEVICE=0");
-  if (!o.smoothed.empty() && env_is_zero("SVDSS_GPU_DEFLATE")) die("run --smoothed deflates the smoothed BAM on the GPU: it does not run with SVDSS_GPU_DEFLATE=0");
+  const std::string why = smooth_knobs.no_device_path(!o.smoothed.empty());
+  if (why == "SVDSS_GPU_DEFLATE=0") die("run --smoothed deflates the smoothed BAM on the GPU: it does not run with " + why);
+  if (!why.empty()) die("run needs the device path: it does not run with " + why);
   if (svdss_device_count() <= 0) die("no GPU found: SVDSS run smooths, searches and calls on the GPU");
   if (o.bsize <= 0) die("batch size smaller than the number of threads");
   struct stat stb;
@@ -49,17 +46,12 @@ int main_run(const CallOptions& o) {
   if (!o.sfs.empty() && !(sfs_file = fopen(o.sfs.c_str(), "wb"))) die("cannot write " + o.sfs);
   int bam_fd = -1;
   if (!o.smoothed.empty() && (bam_fd = open(o.smoothed.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0) die("cannot write " + o.smoothed);
-  // ---- the record store, sized as CallRun::load_inputs sizes its own (SVDSS_CALL_STORE_GB / _MB / _INITIAL_MB; the arenas:
-  // SVDSS_STORE_ARENA_MB).  The memory is taken from now on by the store's own thread, beside the FASTA and the index.
+  // ---- the record store, sized by CallKnobs::store_sizes as `call` sizes its own (the arenas: SVDSS_STORE_ARENA_MB).  The
+  // memory is taken from now on by the store's own thread, beside the FASTA and the index.
   svdss_bam_store* store = nullptr;
-  {
-    const int64_t gb = env_int("SVDSS_CALL_STORE_GB") ? env_int("SVDSS_CALL_STORE_GB") : 160;
-    const int64_t cap = env_int("SVDSS_CALL_STORE_MB") ? env_int("SVDSS_CALL_STORE_MB") << 20 : gb << 30;
-    const int64_t initial = getenv("SVDSS_CALL_STORE_INITIAL_MB") ? atoll(getenv("SVDSS_CALL_STORE_INITIAL_MB")) << 20
-                                                                  : std::min(cap, (int64_t)stb.st_size * 5 / 2 + ((int64_t)256 << 20));
-    check(svdss_bam_store_create(0, cap, std::max<int64_t>(0, initial), &store), "svdss_bam_store_create");
-  }
-  // ---- smooth + search: main_smooth's device path; the smoothed BAM, when asked for, goes where stdout would have gone
+  const std::pair<int64_t, int64_t> store_size = CallKnobs().store_sizes((int64_t)stb.st_size);
+  check(svdss_bam_store_create(0, store_size.first, std::max<int64_t>(0, store_size.second), &store), "svdss_bam_store_create");
+  // ---- smooth + search: main_smooth's DevicePipeline; the smoothed BAM, when asked for, goes where stdout would have gone
   char* sfs_text = nullptr;
   size_t sfs_bytes = 0;
   SmoothHooks hooks;

@@ -34,10 +34,7 @@ struct Stopwatch {   // seconds since the run began, for the --verbose lines
 // ---- the knobs: every SVDSS_* variable this file reads, read once at the top of main_search (README.md has the table).
 // Not here: SVDSS_KMER / SVDSS_NO_KMER_LIMIT (the library's; choose_kmer_order SETS the first), the oversubscribe knob of
 // effective_gpus (host_common.h), and what bam_device_select.h, bam_reader.h and the library read themselves.
-// the value if it is set and at least `least` / if it is set, raised to `least` / -1 not set, 0 off, 1 on
-int64_t env_from(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e && atoll(e) >= least ? atoll(e) : dflt; }
-int64_t env_raised(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e ? std::max<int64_t>(least, atoll(e)) : dflt; }
-int env_switch(const char* name) { const char* e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }
+// (env_from / env_raised / env_switch: host_common.h)
 struct SearchKnobs {
   int64_t batch_bytes = env_from("SVDSS_BAM_BATCH_MB", 1, 192) << 20;         // inflated bytes per device batch (192 MB; `smooth` has its own default)
   size_t slab_bytes = (size_t)env_from("SVDSS_BAM_SLAB_KB", 64, 16 << 10) << 10;   // the scanners' read unit (16 MB, at least 64 KB)

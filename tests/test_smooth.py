@@ -16,7 +16,9 @@ from tests.common import BIN  # noqa: E402
 OPS = {"M": 0, "I": 1, "D": 2, "S": 4}
 
 
-def test_smooth_cli_matches_mirror(tmp_path):
+def mirror_input(tmp_path):
+    """Two contigs of 80 kb and 30 kb, 8x of 3 kb reads with a few dirty, secondary and low-mapq ones: FASTA, BAM, and what
+    the mirror needs of them (also the input of test_smooth_writer_gpu.py)."""
     ref, svs, reads = simulate(ref_lens=(80000, 30000), n_svs=5, coverage=8, read_len=3000, seed=8)
     rng = np.random.default_rng(2)
     names = ["c0", "c1"]
@@ -36,6 +38,11 @@ def test_smooth_cli_matches_mirror(tmp_path):
         alns.append(Alignment(n, flag, tid, pos, mapq, [(l, OPS[o]) for o, l in c2], s2, {}, qual))
     bam = tmp_path / "in.bam"
     bam.write_bytes(bam_writer.bam([(n, len(c)) for n, c in zip(names, ref)], recs))
+    return fa, bam, names, ref, alns
+
+
+def test_smooth_cli_matches_mirror(tmp_path):
+    fa, bam, names, ref, alns = mirror_input(tmp_path)
     out = tmp_path / "smoothed.bam"
     with open(out, "wb") as fh:
         r = subprocess.run([BIN, "smooth", "--reference", str(fa), "--bam", str(bam), "--threads", "3"], stdout=fh,
