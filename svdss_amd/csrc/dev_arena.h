@@ -31,5 +31,5 @@ struct DevArena {
     used = at + bytes;
     return (char*)p + at;
   }
-  static size_t padded(size_t bytes) { return ((bytes + 255) & ~(size_t)255) + 256; }
+  static constexpr size_t padded(size_t bytes) { return ((bytes + 255) & ~(size_t)255) + 256; }
 };

@@ -21,7 +21,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -29,6 +28,7 @@
 #include "../../include/svdss_hip.h"
 #include "dev_arena.h"
 #include "hip_check.h"
+#include "poa_plan.h"
 #include "poa_wave.h"
 #include "poa_quad.h"
 
@@ -39,20 +39,6 @@
 #define P_E2 1
 #define P_MATCH 2
 #define P_MISMATCH 4
-
-struct PoaTask {
-  int64_t seq_first, n_seqs;   // reads of this cluster: seq_off[seq_first .. seq_first+n_seqs]
-  int32_t cap_nodes, cap_edges, max_len;
-  int64_t pool_cap;            // int32 cells per DP array
-  // workspace offsets (elements of the respective typed pools)
-  int64_t node_off;            // per-node int32 arrays (stride cap_nodes): out_head,out_tail,in_head,in_tail,order,index,deg,best,row_beg,row_end,mpl,mpr + aln[5]
-  int64_t edge_off;            // per-edge int32 arrays (stride cap_edges): from,to,w,next_out,next_in
-  int64_t dp_off;              // 6 arrays of pool_cap int32
-  int64_t op_off;              // 2 arrays of (cap_nodes + max_len + 4) int32
-  int64_t row_off64;           // per-node int64: row offset into the DP arrays; then score[cap_nodes]
-  int64_t base_off;            // per-node uint8 base
-  int64_t cons_off;            // output consensus (uint8), capacity cap_nodes
-};
 
 struct PoaGraph {
   int n_nodes, n_edges, cap_nodes, cap_edges;
@@ -387,15 +373,6 @@ __global__ void __launch_bounds__(64) poa_consensus_kernel(const PoaTask* tasks,
 
 // ------------------------------------------------------------------- ABI
 
-namespace {
-struct DevMem3 {
-  void* p = nullptr;
-  ~DevMem3() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { HIPCHK(hipMalloc(&p, bytes ? bytes : 16)); return SVDSS_OK; }
-};
-
-}  // namespace
-
 struct svdss_poa_batch {
   int64_t n_clusters = 0;
   int64_t n_hbm = 0;   // clusters the LDS kernel handed to the HBM kernel
@@ -414,6 +391,238 @@ struct svdss_poa_batch {
   }
 };
 
+static_assert(poa_padded(0) == DevArena::padded(0) && poa_padded(1001) == DevArena::padded(1001), "poa_plan.h sizes what ws_arena hands out");
+
+namespace {
+struct EventPair {   // around the HBM kernel
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// One call of svdss_poa_consensus_batch: the members are what a stage hands to the next, the methods are the stages --
+// upload, rounds (per round: the plan of poa_plan.h, then per wave of launches run_wave and collect), fallback, gather.
+struct PoaBatchRun {
+  svdss_poa_batch& b;
+  const uint8_t* seqs;
+  PoaBatchIn in;                                        // the lengths, the knobs (read here, once), CUs and workspace budget
+  void *d_seqs = nullptr, *d_off = nullptr, *d_cells = nullptr;
+  hipStream_t s0 = nullptr;
+  EventPair ev;
+  std::vector<std::vector<uint8_t>> results;            // the consensus of every sub-cluster that is done
+  std::vector<int64_t> todo;                            // sub-clusters for the HBM kernel
+  std::vector<uint8_t> round0_no_wider, skip_round0;    // poa_plan_round
+  struct Mem { void *tasks, *w32, *w64, *w8, *len, *st; };   // a launch's share of ws_arena
+
+  PoaBatchRun(svdss_poa_batch& batch, const uint8_t* s, const int64_t* seq_off, const int64_t* cluster_off, int64_t n_clusters)
+      : b(batch), seqs(s), results((size_t)n_clusters), round0_no_wider((size_t)n_clusters, 0), skip_round0((size_t)n_clusters, 0) {
+    in.seq_off = seq_off; in.cluster_off = cluster_off; in.n_clusters = n_clusters;
+    in.knobs = PoaKnobs::from_env();
+  }
+
+  // ---- stage 1: the lengths checked, the reads on the device, the device sized up
+  int upload(int32_t device) {
+    const int64_t n_seqs_total = in.cluster_off[in.n_clusters];
+    const int64_t total_syms = in.seq_off[n_seqs_total];
+    for (int64_t i = 0; i < n_seqs_total; ++i) {
+      const int64_t l = in.seq_off[i + 1] - in.seq_off[i];
+      if (l < 0) return SVDSS_EINVAL;
+      if (l >= (1 << 24)) return SVDSS_ERANGE;
+    }
+    if (total_syms > 0 && !seqs) return SVDSS_EINVAL;
+    if (b.device != device) {   // (a batch object is normally used with one device)
+      for (hipStream_t st : b.streams) (void)hipStreamDestroy(st);
+      b.streams.clear();
+      b.in_arena.drop(); b.ws_arena.drop();
+      b.device = device;
+    }
+    const size_t off_bytes = sizeof(int64_t) * (size_t)(n_seqs_total + 1);
+    HIPCHK(b.in_arena.reserve(DevArena::padded((size_t)total_syms) + DevArena::padded(off_bytes) + DevArena::padded(8)));
+    d_seqs = b.in_arena.take((size_t)total_syms); d_off = b.in_arena.take(off_bytes); d_cells = b.in_arena.take(8);
+    // every copy and launch of this call goes to the batch object's own non-blocking streams and every wait is a
+    // wait for those streams: calls on different batch objects (threads) and a search running beside them overlap
+    // (few streams: the runtime multiplexes streams onto a handful of hardware queues, and streams that share one run
+    // in order)
+    while (b.streams.size() < 6) {   // (the launches of a round run side by side: one stream each while they last)
+      hipStream_t st;
+      HIPCHK(svdss_make_stream(&st, "SVDSS_CALL_CUS"));
+      b.streams.push_back(st);
+    }
+    s0 = b.streams[0];
+    if (total_syms) HIPCHK(hipMemcpyAsync(d_seqs, seqs, (size_t)total_syms, hipMemcpyHostToDevice, s0));
+    HIPCHK(hipMemcpyAsync(d_off, in.seq_off, off_bytes, hipMemcpyHostToDevice, s0));
+    HIPCHK(hipMemsetAsync(d_cells, 0, 8, s0));
+    HIPCHK(hipEventCreate(&ev.a));
+    HIPCHK(hipEventCreate(&ev.b));
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) in.n_cus = prop.multiProcessorCount;
+    size_t free_b = 0, total_b = 0;
+    const bool have = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    in.ws_budget = poa_ws_budget(in.knobs, have, free_b, b.ws_arena.cap);
+    in.set_max_work();
+    return SVDSS_OK;
+  }
+
+  bool empty(int64_t c) const { return in.cluster_off[c + 1] == in.cluster_off[c]; }
+
+  Mem take(size_t task_bytes, size_t nt, int64_t w32, int64_t w64, int64_t w8) {
+    Mem m;
+    m.tasks = b.ws_arena.take(task_bytes * nt);
+    m.w32 = b.ws_arena.take(sizeof(int32_t) * (size_t)w32);
+    m.w64 = w64 ? b.ws_arena.take(sizeof(int64_t) * (size_t)w64) : nullptr;
+    m.w8 = b.ws_arena.take((size_t)w8);
+    m.len = b.ws_arena.take(sizeof(int32_t) * nt);
+    m.st = b.ws_arena.take(sizeof(int32_t) * nt);
+    return m;
+  }
+
+  // ---- stage 2: round -1 (poa_quad.hip; whatever it hands back starts round 0), then the rounds of poa_wave.hip
+  int rounds() {
+    std::vector<int64_t> cur((size_t)in.n_clusters), next;
+    for (int64_t c = 0; c < in.n_clusters; ++c) cur[(size_t)c] = c;
+    for (int round = in.knobs.use_quad ? -1 : 0; round < kPoaRounds && !cur.empty(); ++round) {
+      const PoaRoundPlan p = poa_plan_round(in, round, cur, skip_round0, round0_no_wider);
+      next = p.next;
+      for (int64_t c : p.hbm) { todo.push_back(c); if (!empty(c)) ++b.n_hbm; }
+      for (size_t w = 0; w + 1 < p.cuts.size(); ++w)
+        if (const int rc = run_wave(round, p, p.cuts[w], p.cuts[w + 1], next)) return rc;
+      cur.swap(next);
+      if (round < 0) std::sort(cur.begin(), cur.end());
+    }
+    std::sort(todo.begin(), todo.end());
+    return SVDSS_OK;
+  }
+
+  // one wave of launches, groups [g0, g1) of the plan: the launches run concurrently on their own streams (one sub-cluster is
+  // a chain of dependent steps: the machine is filled by running many of them, whichever launch they came from)
+  int run_wave(int round, const PoaRoundPlan& p, size_t g0, size_t g1, std::vector<int64_t>& next) {
+    const bool quad = round < 0;
+    size_t tot_bytes = 0;
+    for (size_t gi = g0; gi < g1; ++gi) tot_bytes += p.groups[gi].bytes();
+    const auto ta = std::chrono::steady_clock::now();
+    HIPCHK(b.ws_arena.reserve(tot_bytes));
+    const double as = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
+    if (in.knobs.debug && as > 0.005) fprintf(stderr, "[poa] workspace of %.1f GB taken in %.3f s\n", (double)tot_bytes / 1073741824.0, as);
+    std::vector<Mem> mem;
+    for (size_t gi = g0; gi < g1; ++gi) {
+      const PoaGroup& g = p.groups[gi];
+      const size_t nt = g.tasks.size();
+      mem.push_back(take(sizeof(PoaWaveTask), nt, g.w32, 0, g.w8));
+      HIPCHK(hipMemcpyAsync(mem.back().tasks, g.tasks.data(), sizeof(PoaWaveTask) * nt, hipMemcpyHostToDevice, s0));
+      HIPCHK(hipMemsetAsync(mem.back().st, 0xff, sizeof(int32_t) * nt, s0));
+    }
+    HIPCHK(hipStreamSynchronize(s0));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t gi = g0; gi < g1; ++gi) {
+      const PoaGroup& g = p.groups[gi];
+      const Mem& m = mem[gi - g0];
+      const hipStream_t gs = b.streams[(gi - g0) % b.streams.size()];
+      const PoaWaveTask* d_tasks = (const PoaWaveTask*)m.tasks;
+      const int nt = (int)g.tasks.size();
+      if (g.gw) {
+        HIPCHK(poa_quad_launch(g.gw, g.cols, d_tasks, nt, g.max_len, (const uint8_t*)d_seqs, (const int64_t*)d_off, (int32_t*)m.w32,
+                                (int32_t*)m.len, (int32_t*)m.st, (unsigned long long*)d_cells, gs));
+        HIPCHK(poa_bundle_launch(d_tasks, nt, g.bundle_lds, (int32_t*)m.w32, (uint8_t*)m.w8, (int32_t*)m.len, (const int32_t*)m.st, gs));
+      } else
+        HIPCHK(poa_wave_launch(g.cols, d_tasks, nt, g.lds, g.bundle_lds, (const uint8_t*)d_seqs, (const int64_t*)d_off, (int32_t*)m.w32,
+                                (uint8_t*)m.w8, (int32_t*)m.len, (int32_t*)m.st, (unsigned long long*)d_cells, gs));
+    }
+    for (size_t k = 0; k < std::min(g1 - g0, b.streams.size()); ++k) HIPCHK(hipStreamSynchronize(b.streams[k]));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    b.kernel_ms += ms;   // wall time of the concurrent launches
+    int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t n_run = 0;
+    for (size_t gi = g0; gi < g1; ++gi) {
+      const PoaGroup& g = p.groups[gi];
+      n_run += (int64_t)g.tasks.size();
+      if (const int rc = collect(round, g.tasks, g.ids, mem[gi - g0], g.w8, next, why)) return rc;
+    }
+    if (in.knobs.debug) {
+      if (quad) poa_quad_debug_report(); else poa_wave_debug_report();
+      fprintf(stderr, "[poa] %s round %d: %lld clusters in %zu launches, %.3f ms, not done: first-read %d preds %d width %d band %d capacity %d other %d\n",
+              quad ? "quad" : "wave", round, (long long)n_run, g1 - g0, ms, why[1], why[2], why[3], why[4], why[5], why[0] + why[6] + why[7]);
+    }
+    return SVDSS_OK;
+  }
+
+  // Lengths, statuses and consensus bytes of one launch: what is finished goes to `results`; every other status is routed
+  // here and nowhere else.  stage: -1 the first stage, 0-2 the rounds of poa_wave.hip, 3 / 4 the passes of the HBM kernel.
+  // LDS kernels: status 3 | reason << 8 (why[reason] counts them); HBM kernel: 1 the DP pool was too small, 2 no alignment.
+  template <class Task>
+  int collect(int stage, const std::vector<Task>& tasks, const std::vector<int64_t>& ids, const Mem& m, int64_t w8, std::vector<int64_t>& next, int* why) {
+    const size_t nt = tasks.size();
+    std::vector<int32_t> lens(nt), st(nt);
+    std::vector<uint8_t> h8((size_t)w8);
+    HIPCHK(hipMemcpyAsync(lens.data(), m.len, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, s0));
+    HIPCHK(hipMemcpyAsync(st.data(), m.st, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, s0));
+    if (w8) HIPCHK(hipMemcpyAsync(h8.data(), m.w8, (size_t)w8, hipMemcpyDeviceToHost, s0));
+    HIPCHK(hipStreamSynchronize(s0));
+    for (size_t k = 0; k < nt; ++k) {
+      const int64_t id = ids[k];
+      if (st[k] == 0) {
+        const uint8_t* src = h8.data() + tasks[k].cons_off;
+        results[(size_t)id].assign(src, src + lens[k]);
+        continue;
+      }
+      const int reason = (st[k] >> 8) & 7;
+      ++why[reason];
+      if (stage < 0) {   // the first stage hands back: to round 0, or past it where round 0's rows are no wider (reason 3: width)
+        next.push_back(id);
+        ++b.n_quad_back;
+        if (reason == 3 && round0_no_wider[(size_t)id]) skip_round0[(size_t)id] = 1;
+      } else if (stage + 1 < kPoaRounds && (reason == 3 || reason == 4 || reason == 5)) next.push_back(id);   // width, band, capacity: the next round is roomier
+      else if (stage < kPoaRounds) { todo.push_back(id); ++b.n_hbm; }
+      else if (stage == kPoaRounds && st[k] == 1) next.push_back(id);   // pass 1 has the full-size DP pool
+      else return SVDSS_ERANGE;   // internal inconsistency
+    }
+    return SVDSS_OK;
+  }
+
+  // ---- stage 3: what the LDS kernels left, on the HBM kernel (pass 0, then pass 1 for what outgrew pass 0's DP pool)
+  int fallback() {
+    for (int pass = 0; pass < 2 && !todo.empty(); ++pass) {
+      std::vector<int64_t> next;
+      PoaHbmLaunch L;
+      for (size_t pos = 0; pos < todo.size();) {
+        pos = poa_plan_hbm(in.seq_off, in.cluster_off, todo, pos, pass, L);
+        const size_t nt = L.tasks.size();
+        HIPCHK(b.ws_arena.reserve(poa_padded(sizeof(PoaTask) * nt) + poa_padded(sizeof(int32_t) * (size_t)L.w32) + poa_padded(sizeof(int64_t) * (size_t)L.w64) +
+                                  poa_padded((size_t)L.w8) + 2 * poa_padded(sizeof(int32_t) * nt)));
+        const Mem m = take(sizeof(PoaTask), nt, L.w32, L.w64, L.w8);
+        HIPCHK(hipMemcpyAsync(m.tasks, L.tasks.data(), sizeof(PoaTask) * nt, hipMemcpyHostToDevice, s0));
+        HIPCHK(hipMemsetAsync(m.st, 0xff, sizeof(int32_t) * nt, s0));
+        HIPCHK(hipEventRecord(ev.a, s0));
+        hipLaunchKernelGGL(poa_consensus_kernel, dim3((unsigned)nt), dim3(64), 0, s0, (const PoaTask*)m.tasks, (const uint8_t*)d_seqs,
+                           (const int64_t*)d_off, (int32_t*)m.w32, (int64_t*)m.w64, (uint8_t*)m.w8, (int32_t*)m.len, (int32_t*)m.st,
+                           (unsigned long long*)d_cells);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.b, s0));
+        HIPCHK(hipStreamSynchronize(s0));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        b.kernel_ms += ms;
+        int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (const int rc = collect(kPoaRounds + pass, L.tasks, L.ids, m, L.w8, next, why)) return rc;
+      }
+      todo.swap(next);
+    }
+    return SVDSS_OK;
+  }
+
+  // ---- stage 4
+  int gather() {
+    unsigned long long cells = 0;
+    HIPCHK(hipMemcpyAsync(&cells, d_cells, 8, hipMemcpyDeviceToHost, s0));
+    HIPCHK(hipStreamSynchronize(s0));
+    b.cells = (int64_t)cells;
+    for (int64_t c = 0; c < in.n_clusters; ++c) {
+      b.cons_len[(size_t)c] = (int64_t)results[(size_t)c].size();
+      b.cons.insert(b.cons.end(), results[(size_t)c].begin(), results[(size_t)c].end());
+    }
+    return SVDSS_OK;
+  }
+};
+}  // namespace
+
 extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq_off, const int64_t* cluster_off,
                                          int64_t n_clusters, int32_t device, svdss_poa_batch_t** out) {
   if (!out || n_clusters < 0 || device < 0) return SVDSS_EINVAL;
@@ -430,425 +639,10 @@ extern "C" int svdss_poa_consensus_batch(const uint8_t* seqs, const int64_t* seq
   b->cons_len.assign((size_t)n_clusters, 0);
   b->cons.clear();
   if (n_clusters == 0) return SVDSS_OK;
-  const int64_t n_seqs_total = cluster_off[n_clusters];
-  const int64_t total_syms = seq_off[n_seqs_total];
-  for (int64_t i = 0; i < n_seqs_total; ++i) {
-    const int64_t l = seq_off[i + 1] - seq_off[i];
-    if (l < 0) return SVDSS_EINVAL;
-    if (l >= (1 << 24)) return SVDSS_ERANGE;
-  }
-  if (total_syms > 0 && !seqs) return SVDSS_EINVAL;
+  PoaBatchRun run(*b, seqs, seq_off, cluster_off, n_clusters);
   int rc;
-  if (b->device != device) {   // (a batch object is normally used with one device)
-    for (hipStream_t st : b->streams) (void)hipStreamDestroy(st);
-    b->streams.clear();
-    b->in_arena.drop(); b->ws_arena.drop();
-    b->device = device;
-  }
-  const size_t off_bytes = sizeof(int64_t) * (size_t)(n_seqs_total + 1);
-  HIPCHK(b->in_arena.reserve(DevArena::padded((size_t)total_syms) + DevArena::padded(off_bytes) + DevArena::padded(8)));
-  struct { void* p; } d_seqs{b->in_arena.take((size_t)total_syms)}, d_off{b->in_arena.take(off_bytes)},
-      d_cells{b->in_arena.take(8)};
-  // every copy and launch of this call goes to the batch object's own non-blocking streams and every wait is a
-  // wait for those streams: calls on different batch objects (threads) and a search running beside them overlap
-  // (few streams: the runtime multiplexes streams onto a handful of hardware queues, and streams that share one run
-  // in order)
-  while (b->streams.size() < 6) {   // (the launches of a round run side by side: one stream each while they last)
-    hipStream_t st;
-    HIPCHK(svdss_make_stream(&st, "SVDSS_CALL_CUS"));
-    b->streams.push_back(st);
-  }
-  const hipStream_t s0 = b->streams[0];
-  if (total_syms) HIPCHK(hipMemcpyAsync(d_seqs.p, seqs, (size_t)total_syms, hipMemcpyHostToDevice, s0));
-  HIPCHK(hipMemcpyAsync(d_off.p, seq_off, off_bytes, hipMemcpyHostToDevice, s0));
-  HIPCHK(hipMemsetAsync(d_cells.p, 0, 8, s0));
-  hipEvent_t ev0, ev1;
-  HIPCHK(hipEventCreate(&ev0));
-  HIPCHK(hipEventCreate(&ev1));
-  std::vector<std::vector<uint8_t>> results((size_t)n_clusters);
-  // fast path: the LDS-resident kernel in up to three rounds of growing generosity -- ring rows of 2w + 33 columns
-  // and a graph of ~1.5 x the longest read (what nearly every sub-cluster needs); then the specification's widest
-  // band (2w + 129) and 3 x; then full-matrix rows (a band that lost the sink).  What is still left (status 3)
-  // falls through to the HBM kernel: pass 0 with a banded workspace, pass 1 with a full-size DP pool
-  std::vector<int64_t> todo;
-  const bool use_lds = getenv("SVDSS_POA_HBM") == nullptr;
-  std::vector<int64_t> cur((size_t)n_clusters), retry;
-  for (int64_t c = 0; c < n_clusters; ++c) cur[(size_t)c] = c;
-  int n_cus = 256;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
-  }
-  // bytes of workspace per wave of launches (SVDSS_POA_WS_GB, default 32: a whole genome's 21,500 sub-clusters want ~64 GB and
-  // run in two waves of ~75 ms; one wave needs an allocation that large on a device other processes have just left)
-  size_t ws_budget = (size_t)(getenv("SVDSS_POA_WS_GB") && atoll(getenv("SVDSS_POA_WS_GB")) > 0 ? atoll(getenv("SVDSS_POA_WS_GB")) : 32) << 30;
-  {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) ws_budget = std::min(ws_budget, (free_b + b->ws_arena.cap) / 2);
-    if (ws_budget < ((size_t)1 << 30)) ws_budget = (size_t)1 << 30;
-  }
-  const int n_rounds = 3;
-  // round -1 (poa_quad.hip): several sub-clusters per wavefront -- the band as it is in practice, a graph of ~1.5 x the
-  // longest read, at most 7 predecessors per node; whatever it hands back starts round 0 (SVDSS_POA_QUAD=0: skip it)
-  const bool use_quad = use_lds && !(getenv("SVDSS_POA_QUAD") && atoi(getenv("SVDSS_POA_QUAD")) == 0);
-  const int64_t quad_short = getenv("SVDSS_POA_QUAD_SHORT") ? atoll(getenv("SVDSS_POA_QUAD_SHORT")) : 0;
-  const int64_t quad_minwork_pct = getenv("SVDSS_POA_QUAD_MINWORK") ? atoll(getenv("SVDSS_POA_QUAD_MINWORK")) : 0;
-  const int64_t quad_rows16 = getenv("SVDSS_POA_QUAD_ROWS16") ? atoll(getenv("SVDSS_POA_QUAD_ROWS16")) : 0;
-  const int64_t quad_rows32 = getenv("SVDSS_POA_QUAD_ROWS32") ? atoll(getenv("SVDSS_POA_QUAD_ROWS32")) : 0;
-  int64_t batch_max_work = 1;
-  for (int64_t c = 0; c < n_clusters; ++c) {
-    int64_t maxl = 0;
-    for (int64_t s = cluster_off[c]; s < cluster_off[c + 1]; ++s) maxl = std::max(maxl, seq_off[s + 1] - seq_off[s]);
-    batch_max_work = std::max(batch_max_work, (cluster_off[c + 1] - cluster_off[c]) * maxl);
-  }
-  // A sub-cluster the first stage hands back because a row got wider than its lanes hold goes straight to the round that has
-  // wider rows when round 0's rows are no wider than the first stage's were (`call` at 30x: one such sub-cluster of 21,500
-  // cost a round of 39 ms that could only fail the same way)
-  std::vector<uint8_t> round0_no_wider((size_t)n_clusters, 0), skip_round0((size_t)n_clusters, 0);
-  for (int round = use_quad ? -1 : 0; round < n_rounds && !cur.empty(); ++round) {
-    const bool quad = round < 0;
-    struct Cand { int64_t c; size_t lds; int cols; int gw; PoaWaveTask t; };
-    std::vector<Cand> cands;
-    const size_t LDS_MAX = 160 * 1024 - 512;
-    for (int64_t c : cur) {
-      PoaWaveTask t;
-      memset(&t, 0, sizeof t);
-      t.seq_first = cluster_off[c];
-      t.n_seqs = cluster_off[c + 1] - cluster_off[c];
-      int64_t tot = 0, maxl = 0;
-      for (int64_t s = t.seq_first; s < t.seq_first + t.n_seqs; ++s) {
-        const int64_t l = seq_off[s + 1] - seq_off[s];
-        tot += l;
-        if (l > maxl) maxl = l;
-      }
-      // the graph rarely grows beyond ~1.5 x the longest read (later rounds: 3 x); a cluster that outgrows its
-      // allocation is redone.  SVDSS_POA_NC scales the first estimate (percent).
-      const int nc_pct = round > 0 ? 300 : getenv("SVDSS_POA_NC") ? std::max(atoi(getenv("SVDSS_POA_NC")), 100) : 150;
-      int64_t nc = std::min<int64_t>(tot + 2, maxl * nc_pct / 100 + 8 * t.n_seqs + 64);
-      if (nc > 65000) nc = 65000;
-      const int64_t ecap = std::min<int64_t>(nc + nc / (round > 0 ? 2 : 4) + t.n_seqs + 64, 100000);
-      // widest row the ring holds: the band as it is in practice (round 0), as wide as the specification lets it
-      // get (round 1), the full matrix (round 2, after the band lost the sink)
-      const int64_t w_band = 10 + (int64_t)(0.01 * (double)maxl);
-      // (round 0: 2w + 1 columns plus slack for the spread of the predecessors' maxima -- rounded up to 64 where that
-      // leaves at least 8 of slack, so that a row is one column per lane: the C = 1 instantiation)
-      const int64_t w2 = 2 * w_band + 1;
-      const int64_t wcap0 = w2 + 8 <= 64 ? 64 : w2 + 32;
-      const int64_t wcap = std::min<int64_t>(round <= 0 ? wcap0 : round == 1 ? 2 * w_band + 129 : maxl + 1, maxl + 1);
-      if (quad) {
-        // group width x columns per lane >= 2w + 1 columns plus 8 of slack for the spread of the predecessors' maxima
-        // (SVDSS_POA_QUAD_GW: 16 -- four sub-clusters per wavefront --, 32 or 64)
-        // Group width: four short sub-clusters share a wavefront (a quarter of the wavefront slots for the latency-bound
-        // traceback / graph-update phases); a long one gets the wavefront to itself -- the longest chains of a batch
-        // decide when it ends, and a row of C = 2 columns per lane is the quickest there is.
-        // (SVDSS_POA_QUAD_ROWS16 / _ROWS32: a sub-cluster of at most that many reads x length shares its wavefront with three /
-        // one other: its chain is short enough not to become the batch's tail at the slower lock-step pace)
-        const int64_t chain = t.n_seqs * maxl;
-        const int gw = getenv("SVDSS_POA_QUAD_GW") ? atoi(getenv("SVDSS_POA_QUAD_GW"))
-                       : (maxl <= quad_short || chain <= quad_rows16) ? 16 : chain <= quad_rows32 ? 32 : 64;
-        // SVDSS_POA_QUAD_MINWORK (percent of the batch's largest reads x length): only the long chains take this stage
-        if (t.n_seqs * maxl * 100 < quad_minwork_pct * batch_max_work) { retry.push_back(c); continue; }
-        const int64_t need = std::min<int64_t>(w2 + 8, maxl + 1);
-        const int qc = (int)std::max<int64_t>((need + gw - 1) / gw, gw == 16 ? 3 : gw == 32 ? 2 : 1);
-        if ((gw != 16 && gw != 32 && gw != 64) || !poa_quad_supported(gw, qc) || t.n_seqs <= 0 || t.n_seqs > 8191 ||
-            poa_bundle_lds_bytes((int)nc) > LDS_MAX || poa_quad_lds_bytes(gw, qc, (int)maxl) > LDS_MAX) {
-          retry.push_back(c);
-          continue;
-        }
-        t.nc = (int32_t)nc; t.ec = (int32_t)ecap; t.max_len = (int32_t)maxl; t.ws = gw * qc; t.rs = 0; t.ring = 0;
-        round0_no_wider[(size_t)c] = wcap0 <= (int64_t)gw * qc ? 1 : 0;
-        cands.push_back(Cand{c, poa_quad_lds_bytes(gw, qc, (int)maxl), qc, gw, t});
-        continue;
-      }
-      if (round == 0 && skip_round0[(size_t)c] && n_rounds > 1) { retry.push_back(c); continue; }
-      int64_t ws = 64;
-      while (ws < wcap) ws <<= 1;
-      const int64_t rs = (wcap + 3) & ~(int64_t)3;
-      const int cols = wcap <= 64 ? 1 : wcap <= 128 ? 2 : wcap <= 192 ? 3 : 5;
-      const int64_t ring = 4;
-      t.nc = (int32_t)nc; t.ec = (int32_t)ecap; t.max_len = (int32_t)maxl; t.ws = (int32_t)ws; t.rs = (int32_t)rs;
-      t.ring = (int32_t)ring;
-      const size_t lds = poa_wave_lds_bytes(t.nc, t.max_len, t.rs, t.ring);
-      if (!use_lds || lds > LDS_MAX || poa_bundle_lds_bytes(t.nc) > LDS_MAX || ws > 4096 || t.n_seqs <= 0 || t.n_seqs > 8191) {
-        todo.push_back(c);
-        if (t.n_seqs > 0) ++b->n_hbm;
-        continue;
-      }
-      cands.push_back(Cand{c, lds, cols, 0, t});
-    }
-    // launches are grouped by instantiation and by LDS size class, so that small clusters are not charged the
-    // LDS of the largest one (LDS decides how many sub-clusters a CU keeps in flight); the groups run
-    // concurrently on their own streams (one sub-cluster is a chain of dependent steps: the machine is
-    // filled by running many of them, whichever launch they came from)
-    struct Group {
-      int cols = 0, gw = 0, max_len = 0;   // gw != 0: a launch of poa_quad.hip
-      int wave = 0;                        // groups of one wave of launches run together
-      size_t lds = 0, bundle_lds = 0;
-      std::vector<PoaWaveTask> tasks;
-      std::vector<int64_t> ids;
-      int64_t w32 = 0, w8 = 0;
-      void *d_tasks = nullptr, *d32 = nullptr, *d8 = nullptr, *d_len = nullptr, *d_st = nullptr;
-      size_t bytes() const {
-        const size_t nt = tasks.size();
-        return DevArena::padded(sizeof(PoaWaveTask) * nt) + DevArena::padded(sizeof(int32_t) * (size_t)w32) +
-               DevArena::padded((size_t)w8) + 2 * DevArena::padded(sizeof(int32_t) * nt);
-      }
-    };
-    std::vector<std::unique_ptr<Group>> groups;
-    const int64_t group_budget32 = (int64_t)2 << 30;    // ints of workspace per launch
-    std::sort(cands.begin(), cands.end(), [](const Cand& x, const Cand& y) { return x.lds > y.lds; });
-    // a sub-cluster is one chain of n_seqs x length dependent row steps: the longest chains of the batch decide
-    // when it ends, so they get the issue priority (s_setprio) over the short ones that fill the CUs beside them
-    if (!getenv("SVDSS_POA_NOPRIO")) {
-      int64_t wmax = 1;
-      for (const Cand& cd : cands) wmax = std::max<int64_t>(wmax, cd.t.n_seqs * (int64_t)cd.t.max_len);
-      for (Cand& cd : cands) {
-        const int64_t wk = cd.t.n_seqs * (int64_t)cd.t.max_len;
-        cd.t.prio = wk * 2 > wmax ? 3 : wk * 4 > wmax ? 2 : wk * 8 > wmax ? 1 : 0;
-      }
-    }
-    if (quad) {
-      // wavefronts of sub-clusters that are alike (the groups of a wavefront walk in lock-step: it lasts as long as its
-      // longest), the longest first; one launch per variant
-      // A batch beyond the workspace budget (a whole genome's sub-clusters at once) runs in several waves of launches, and
-      // every wave lasts at least as long as its longest chain: the sub-clusters are dealt to the waves longest first, one
-      // each in turn, so that every wave has its share of long chains and of short ones to fill the machine beside them
-      // (rounds 2-4 cut the sorted list into consecutive pieces: the first wave was all long chains, the last all short).
-      std::vector<int> wave_of(cands.size(), 0);
-      {
-        size_t total = 0;
-        for (const Cand& cd : cands) total += sizeof(int32_t) * (size_t)poa_wave_ws_ints(cd.t.nc, cd.t.ec, cd.t.max_len, cd.t.ws) + (size_t)cd.t.nc + 256;
-        const size_t n_waves = std::max<size_t>(1, (total + ws_budget - ws_budget / 8 - 1) / (ws_budget - ws_budget / 8));
-        if (n_waves > 1 && !getenv("SVDSS_POA_NO_MIX")) {
-          std::vector<size_t> by_work(cands.size());
-          for (size_t i = 0; i < by_work.size(); ++i) by_work[i] = i;
-          std::sort(by_work.begin(), by_work.end(), [&](size_t x, size_t y) {
-            const int64_t wx = cands[x].t.n_seqs * (int64_t)cands[x].t.max_len, wy = cands[y].t.n_seqs * (int64_t)cands[y].t.max_len;
-            return wx != wy ? wx > wy : cands[x].c < cands[y].c;
-          });
-          for (size_t k = 0; k < by_work.size(); ++k) wave_of[by_work[k]] = (int)(k % n_waves);
-        }
-      }
-      std::vector<size_t> order(cands.size());
-      for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-      std::sort(order.begin(), order.end(), [&](size_t xi, size_t yi) {
-        const Cand &x = cands[xi], &y = cands[yi];
-        if (wave_of[xi] != wave_of[yi]) return wave_of[xi] < wave_of[yi];
-        if (x.gw != y.gw) return x.gw > y.gw;
-        if (x.cols != y.cols) return x.cols > y.cols;
-        const int64_t wx = x.t.n_seqs * (int64_t)x.t.max_len, wy = y.t.n_seqs * (int64_t)y.t.max_len;
-        if (wx != wy) return wx > wy;
-        return x.c < y.c;
-      });
-      Group* g = nullptr;
-      for (size_t oi : order) {
-        Cand& cd = cands[oi];
-        PoaWaveTask t = cd.t;
-        const int64_t need = poa_wave_ws_ints(t.nc, t.ec, t.max_len, t.ws);
-        if (!g || g->wave != wave_of[oi] || g->gw != cd.gw || g->cols != cd.cols || g->w32 + need > group_budget32) {
-          groups.emplace_back(new Group);
-          g = groups.back().get();
-          g->cols = cd.cols; g->gw = cd.gw; g->lds = cd.lds; g->wave = wave_of[oi];
-        }
-        g->max_len = std::max(g->max_len, (int)t.max_len);
-        t.ws_off = g->w32; g->w32 += need;
-        t.cons_off = g->w8; g->w8 += t.nc;
-        g->bundle_lds = std::max(g->bundle_lds, poa_bundle_lds_bytes(t.nc));
-        g->tasks.push_back(t);
-        g->ids.push_back(cd.c);
-      }
-    }
-    for (int ci = 0; ci < kPoaWaveNCols && !quad; ++ci) {
-      Group* g = nullptr;
-      size_t fill = 0;   // sub-clusters that fill the machine at the group's LDS size
-      for (Cand& cd : cands) {
-        if (cd.cols != kPoaWaveCols[ci]) continue;
-        PoaWaveTask t = cd.t;
-        const int64_t need = poa_wave_ws_ints(t.nc, t.ec, t.max_len, t.ws);
-        // a new launch (with the smaller LDS of the clusters that follow) only once the current one fills all CUs
-        if (!g || g->w32 + need > group_budget32 || g->tasks.size() >= fill) {
-          groups.emplace_back(new Group);
-          g = groups.back().get();
-          g->cols = kPoaWaveCols[ci];
-          g->lds = cd.lds;
-          fill = (size_t)n_cus * std::min<size_t>(32, std::max<size_t>(1, LDS_MAX / cd.lds));
-        }
-        t.ws_off = g->w32; g->w32 += need;
-        t.cons_off = g->w8; g->w8 += t.nc;
-        g->bundle_lds = std::max(g->bundle_lds, poa_bundle_lds_bytes(t.nc));
-        g->tasks.push_back(t);
-        g->ids.push_back(cd.c);
-      }
-    }
-    // run the groups in waves that fit the workspace budget
-    size_t gpos = 0;
-    while (gpos < groups.size()) {
-      size_t gend = gpos, tot_bytes = 0;
-      while (gend < groups.size() && (gend == gpos || (groups[gend]->wave == groups[gpos]->wave && tot_bytes + groups[gend]->bytes() <= ws_budget)))
-        tot_bytes += groups[gend++]->bytes();
-      {
-        const auto ta = std::chrono::steady_clock::now();
-        HIPCHK(b->ws_arena.reserve(tot_bytes));
-        const double as = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
-        if (getenv("SVDSS_DEBUG") && as > 0.005) fprintf(stderr, "[poa] workspace of %.1f GB taken in %.3f s\n", (double)tot_bytes / 1073741824.0, as);
-      }
-      for (size_t gi = gpos; gi < gend; ++gi) {
-        Group& g = *groups[gi];
-        const size_t nt = g.tasks.size();
-        g.d_tasks = b->ws_arena.take(sizeof(PoaWaveTask) * nt);
-        g.d32 = b->ws_arena.take(sizeof(int32_t) * (size_t)g.w32);
-        g.d8 = b->ws_arena.take((size_t)g.w8);
-        g.d_len = b->ws_arena.take(sizeof(int32_t) * nt);
-        g.d_st = b->ws_arena.take(sizeof(int32_t) * nt);
-        HIPCHK(hipMemcpyAsync(g.d_tasks, g.tasks.data(), sizeof(PoaWaveTask) * nt, hipMemcpyHostToDevice, s0));
-        HIPCHK(hipMemsetAsync(g.d_st, 0xff, sizeof(int32_t) * nt, s0));
-      }
-      HIPCHK(hipStreamSynchronize(s0));
-      const auto t0 = std::chrono::steady_clock::now();
-      for (size_t gi = gpos; gi < gend; ++gi) {
-        Group& g = *groups[gi];
-        const hipStream_t gs = b->streams[(gi - gpos) % b->streams.size()];
-        if (g.gw) {
-          HIPCHK(poa_quad_launch(g.gw, g.cols, (const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.max_len, (const uint8_t*)d_seqs.p,
-                                  (const int64_t*)d_off.p, (int32_t*)g.d32, (int32_t*)g.d_len, (int32_t*)g.d_st,
-                                  (unsigned long long*)d_cells.p, gs));
-          HIPCHK(poa_bundle_launch((const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.bundle_lds, (int32_t*)g.d32, (uint8_t*)g.d8,
-                                    (int32_t*)g.d_len, (const int32_t*)g.d_st, gs));
-        } else
-        HIPCHK(poa_wave_launch(g.cols, (const PoaWaveTask*)g.d_tasks, (int)g.tasks.size(), g.lds, g.bundle_lds,
-                                (const uint8_t*)d_seqs.p, (const int64_t*)d_off.p, (int32_t*)g.d32, (uint8_t*)g.d8,
-                                (int32_t*)g.d_len, (int32_t*)g.d_st, (unsigned long long*)d_cells.p, gs));
-      }
-      for (size_t k = 0; k < std::min(gend - gpos, b->streams.size()); ++k) HIPCHK(hipStreamSynchronize(b->streams[k]));
-      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      b->kernel_ms += ms;   // wall time of the concurrent launches
-      int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      int64_t n_run = 0;
-      for (size_t gi = gpos; gi < gend; ++gi) {
-        Group& g = *groups[gi];
-        const int64_t nt = (int64_t)g.tasks.size();
-        n_run += nt;
-        std::vector<int32_t> lens((size_t)nt), st((size_t)nt);
-        std::vector<uint8_t> h8((size_t)g.w8);
-        HIPCHK(hipMemcpyAsync(lens.data(), g.d_len, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-        HIPCHK(hipMemcpyAsync(st.data(), g.d_st, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-        if (g.w8) HIPCHK(hipMemcpyAsync(h8.data(), g.d8, (size_t)g.w8, hipMemcpyDeviceToHost, s0));
-        HIPCHK(hipStreamSynchronize(s0));
-        for (int64_t k = 0; k < nt; ++k) {
-          if (st[(size_t)k] == 0) {
-            const uint8_t* src = h8.data() + g.tasks[(size_t)k].cons_off;
-            results[(size_t)g.ids[(size_t)k]].assign(src, src + lens[(size_t)k]);
-          } else {
-            const int reason = (st[(size_t)k] >> 8) & 7;
-            if (quad) { retry.push_back(g.ids[(size_t)k]); if (reason == 3 && round0_no_wider[(size_t)g.ids[(size_t)k]]) skip_round0[(size_t)g.ids[(size_t)k]] = 1; }
-            else if (round + 1 < n_rounds && (reason == 3 || reason == 4 || reason == 5)) retry.push_back(g.ids[(size_t)k]);
-            else { todo.push_back(g.ids[(size_t)k]); ++b->n_hbm; }
-            ++why[reason];
-            if (quad) ++b->n_quad_back;
-          }
-        }
-        groups[gi].reset();
-      }
-      if (getenv("SVDSS_DEBUG")) { if (quad) poa_quad_debug_report(); else poa_wave_debug_report(); }
-      if (getenv("SVDSS_DEBUG"))
-        fprintf(stderr, "[poa] %s round %d: %lld clusters in %zu launches, %.3f ms, not done: first-read %d preds %d width %d band %d capacity %d other %d\n",
-                quad ? "quad" : "wave", round, (long long)n_run, gend - gpos, ms, why[1], why[2], why[3], why[4], why[5], why[0] + why[6] + why[7]);
-      gpos = gend;
-    }
-    cur.swap(retry);
-    retry.clear();
-    if (quad) std::sort(cur.begin(), cur.end());
-  }
-  std::sort(todo.begin(), todo.end());
-  for (int pass = 0; pass < 2 && !todo.empty(); ++pass) {
-    std::vector<int64_t> next;
-    size_t pos = 0;
-    while (pos < todo.size()) {
-      std::vector<PoaTask> tasks;
-      std::vector<int64_t> ids;
-      int64_t w32 = 0, w64 = 0, w8 = 0;
-      const int64_t budget32 = (int64_t)3 << 30;   // 12 GiB of int32 workspace per launch
-      while (pos < todo.size()) {
-        const int64_t c = todo[pos];
-        PoaTask t;
-        memset(&t, 0, sizeof t);
-        t.seq_first = cluster_off[c];
-        t.n_seqs = cluster_off[c + 1] - cluster_off[c];
-        int64_t tot = 0, maxl = 0;
-        for (int64_t s = t.seq_first; s < t.seq_first + t.n_seqs; ++s) {
-          const int64_t l = seq_off[s + 1] - seq_off[s];
-          tot += l;
-          if (l > maxl) maxl = l;
-        }
-        t.cap_nodes = (int32_t)(tot + 2);
-        t.cap_edges = (int32_t)(tot + t.n_seqs + 2);
-        t.max_len = (int32_t)maxl;
-        const int64_t wband = 2 * (10 + (int64_t)(0.01 * (double)maxl)) + 129;
-        t.pool_cap = pass == 0 ? (int64_t)t.cap_nodes * (wband < maxl + 1 ? wband : maxl + 1)
-                               : (int64_t)t.cap_nodes * (maxl + 1);
-        const int64_t need32 = 17 * (int64_t)t.cap_nodes + 5 * (int64_t)t.cap_edges + 6 * t.pool_cap +
-                               2 * ((int64_t)t.cap_nodes + maxl + 4);
-        if (!tasks.empty() && w32 + need32 > budget32) break;
-        t.node_off = w32; w32 += 17 * (int64_t)t.cap_nodes;
-        t.edge_off = w32; w32 += 5 * (int64_t)t.cap_edges;
-        t.dp_off = w32; w32 += 6 * t.pool_cap;
-        t.op_off = w32; w32 += 2 * ((int64_t)t.cap_nodes + maxl + 4);
-        t.row_off64 = w64; w64 += 2 * (int64_t)t.cap_nodes;
-        t.base_off = w8; w8 += t.cap_nodes;
-        t.cons_off = w8; w8 += t.cap_nodes;
-        tasks.push_back(t);
-        ids.push_back(c);
-        ++pos;
-      }
-      const int64_t nt = (int64_t)tasks.size();
-      DevMem3 d_tasks, d32, d64, d8, d_len, d_st;
-      if ((rc = d_tasks.alloc(sizeof(PoaTask) * (size_t)nt)) || (rc = d32.alloc(sizeof(int32_t) * (size_t)w32)) ||
-          (rc = d64.alloc(sizeof(int64_t) * (size_t)w64)) || (rc = d8.alloc((size_t)w8)) ||
-          (rc = d_len.alloc(sizeof(int32_t) * (size_t)nt)) || (rc = d_st.alloc(sizeof(int32_t) * (size_t)nt)))
-        return rc;
-      HIPCHK(hipMemcpyAsync(d_tasks.p, tasks.data(), sizeof(PoaTask) * (size_t)nt, hipMemcpyHostToDevice, s0));
-      HIPCHK(hipMemsetAsync(d_st.p, 0xff, sizeof(int32_t) * (size_t)nt, s0));
-      HIPCHK(hipEventRecord(ev0, s0));
-      hipLaunchKernelGGL(poa_consensus_kernel, dim3((unsigned)nt), dim3(64), 0, s0, (const PoaTask*)d_tasks.p,
-                         (const uint8_t*)d_seqs.p, (const int64_t*)d_off.p, (int32_t*)d32.p, (int64_t*)d64.p,
-                         (uint8_t*)d8.p, (int32_t*)d_len.p, (int32_t*)d_st.p, (unsigned long long*)d_cells.p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev1, s0));
-      HIPCHK(hipStreamSynchronize(s0));
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-      b->kernel_ms += ms;
-      std::vector<int32_t> lens((size_t)nt), st((size_t)nt);
-      std::vector<uint8_t> h8((size_t)w8);
-      HIPCHK(hipMemcpyAsync(lens.data(), d_len.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-      HIPCHK(hipMemcpyAsync(st.data(), d_st.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s0));
-      if (w8) HIPCHK(hipMemcpyAsync(h8.data(), d8.p, (size_t)w8, hipMemcpyDeviceToHost, s0));
-      HIPCHK(hipStreamSynchronize(s0));
-      for (int64_t k = 0; k < nt; ++k) {
-        if (st[(size_t)k] == 0) {
-          const uint8_t* src = h8.data() + tasks[(size_t)k].cons_off;
-          results[(size_t)ids[(size_t)k]].assign(src, src + lens[(size_t)k]);
-        } else if (st[(size_t)k] == 1 && pass == 0) {
-          next.push_back(ids[(size_t)k]);
-        } else {
-          (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-          return SVDSS_ERANGE;   // internal inconsistency
-        }
-      }
-    }
-    todo.swap(next);
-  }
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
-  unsigned long long cells = 0;
-  HIPCHK(hipMemcpyAsync(&cells, d_cells.p, 8, hipMemcpyDeviceToHost, s0));
-  HIPCHK(hipStreamSynchronize(s0));
-  b->cells = (int64_t)cells;
-  for (int64_t c = 0; c < n_clusters; ++c) {
-    b->cons_len[(size_t)c] = (int64_t)results[(size_t)c].size();
-    b->cons.insert(b->cons.end(), results[(size_t)c].begin(), results[(size_t)c].end());
-  }
-  return SVDSS_OK;
+  if ((rc = run.upload(device)) || (rc = run.rounds()) || (rc = run.fallback())) return rc;
+  return run.gather();
 }
 
 extern "C" int64_t svdss_poa_batch_nclusters(const svdss_poa_batch_t* b) { return b ? b->n_clusters : -1; }

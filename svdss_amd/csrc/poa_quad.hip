@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "poa_plan.h"
 #include "poa_quad.h"
 #include "poa_quad_gfx950.h"
 #include "poa_quad_core.h"
@@ -33,17 +34,6 @@ static hipError_t launch_gc(const PoaWaveTask* d_tasks, int n_tasks, int max_len
   hipLaunchKernelGGL((poa_quad_kernel<GW, C>), dim3((unsigned)((n_tasks + G - 1) / G)), dim3(64), lds, stream, d_tasks, n_tasks, d_seqs,
                      d_seq_off, ws32, d_len, d_status, d_cells, pq::Geom<GW, C>::qcap(max_len));
   return hipGetLastError();
-}
-
-bool poa_quad_supported(int gw, int cols) {
-  for (int k = 0; k < kPoaQuadNVariants; ++k)
-    if (kPoaQuadVariants[k][0] == gw && kPoaQuadVariants[k][1] == cols) return true;
-  return false;
-}
-
-size_t poa_quad_lds_bytes(int gw, int cols, int max_len) {
-  const size_t rw = (size_t)(gw * cols + 2 * PQ_GD), g = (size_t)(64 / gw);
-  return sizeof(int32_t) * (g * PQ_RING * 3 * rw + 3 * rw + 16) + g * (size_t)(((max_len + gw * cols + 24 + 15) & ~15));
 }
 
 hipError_t poa_quad_launch(int gw, int cols, const PoaWaveTask* d_tasks, int n_tasks, int max_len, const uint8_t* d_seqs, const int64_t* d_seq_off,

@@ -44,6 +44,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "poa_plan.h"
 #include "poa_wave.h"
 
 #define PNEG (-0x20000000)
@@ -65,35 +66,6 @@
 #define COL_SINK 0x7FFFFFFE
 #define COL_NEW 0x7FFFFFFF
 #define RI_SLOW 3u
-
-struct WsLayout {
-  int64_t out_head, in_head, order, index, col, base;
-  int64_t row_beg, row_end, hl, prow0, prow1, row_mpl, row_mpr;
-  int64_t aln, scr, rinfo, keepf;
-  int64_t e_from, e_to, e_w, e_next_out, e_next_in;
-  int64_t op_node, op_q, path_use, path_aux;
-  int64_t gdir, gH, gE1, gE2;
-  int64_t total;
-};
-
-__host__ __device__ inline WsLayout ws_layout(int nc, int ec, int max_len, int ws) {
-  WsLayout w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t at = o; o += n; return at; };
-  w.out_head = take(nc); w.in_head = take(nc); w.order = take(nc); w.index = take(nc); w.col = take(nc); w.base = take(nc);
-  w.row_beg = take(nc); w.row_end = take(nc); w.hl = take(nc); w.prow0 = take(nc); w.prow1 = take(nc);
-  w.row_mpl = take(nc); w.row_mpr = take(nc);
-  w.aln = take(5 * (int64_t)nc);
-  w.scr = take((int64_t)nc + 64);
-  w.rinfo = take((int64_t)nc + 64); w.keepf = take((int64_t)nc + 64);
-  w.e_from = take(ec); w.e_to = take(ec); w.e_w = take(ec); w.e_next_out = take(ec); w.e_next_in = take(ec);
-  const int64_t opcap = (int64_t)nc + max_len + 4;
-  w.op_node = take(opcap); w.op_q = take(opcap); w.path_use = take(opcap); w.path_aux = take(opcap);
-  const int64_t pool = (int64_t)nc * ws;
-  w.gdir = take(pool); w.gH = take(pool); w.gE1 = take(pool); w.gE2 = take(pool);
-  w.total = o;
-  return w;
-}
 
 // (... + TGB: "no path" is 0 and everything near it, so that a lane shift can fill with zero)
 __device__ __forceinline__ int tg_up(int x, int tag) { return x <= PNEG / 2 ? 0 : (int)(((unsigned)x << 4) | (unsigned)tag) + TGB; }
@@ -1174,16 +1146,6 @@ __global__ void __launch_bounds__(64) poa_bundle_kernel(const PoaWaveTask* tasks
     cons_len[blockIdx.x] = len;
   }
 }
-
-size_t poa_wave_lds_bytes(int nc, int max_len, int rs, int ring) {
-  (void)nc;
-  const size_t ns = (size_t)ring + 2;
-  return 12 * ns * ((size_t)rs + 8) + 16 * ns + 64 + (((size_t)max_len + 15) & ~(size_t)15) + 64 + 256;
-}
-
-size_t poa_bundle_lds_bytes(int nc) { return 12 * (size_t)nc + 64; }
-
-int64_t poa_wave_ws_ints(int nc, int ec, int max_len, int ws) { return ws_layout(nc, ec, max_len, ws).total; }
 
 template <int C>
 static hipError_t launch_c(const PoaWaveTask* d_tasks, int n_tasks, size_t lds_bytes, const uint8_t* d_seqs,

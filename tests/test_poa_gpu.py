@@ -96,6 +96,57 @@ def test_lds_and_hbm_kernels_agree_with_the_oracle(monkeypatch):
     assert got == want
 
 
+def _multiwave_clusters():
+    """About 8 MB of workspace per sub-cluster at the first stage's variant (64, 2): 140 of them are beyond the 7/8 GB a wave
+    of launches may take at SVDSS_POA_WS_GB=1.  Every tenth one is short, so that every wave has short chains too."""
+    rng = np.random.default_rng(31)
+    clusters = []
+    for k in range(140):
+        length = int(rng.integers(300, 601)) if k % 10 == 9 else int(rng.integers(2400, 2601))
+        t = rng.integers(0, 4, size=length).astype(np.uint8)
+        reads = []
+        for _ in range(int(rng.integers(18, 23))):
+            r = t.copy()
+            e = rng.random(length) < 0.005
+            r[e] = (r[e] + rng.integers(1, 4, size=int(e.sum()))) % 4
+            reads.append(r)
+        clusters.append(reads)
+    return clusters
+
+
+def test_several_waves_of_launches(monkeypatch):
+    """A batch beyond the workspace budget: the sub-clusters are dealt to waves of launches, and `wave` keeps the launches of
+    different waves apart.  The oracle is run on every seventh sub-cluster (all 140 take it ~10 s on the CPU); the others are
+    compared with the run of the same batch at the default budget, which is one wave."""
+    from tests import poa_plan_lib as P
+    clusters = _multiwave_clusters()
+    lengths = [[len(r) for r in cl] for cl in clusters]
+    plan = P.Batch(lengths, budget=1 << 30).plan(-1)
+    assert len(plan["cuts"]) - 1 >= 2 and len({g["wave"] for g in plan["groups"]}) >= 2      # the shape still takes the path
+    assert len(P.Batch(lengths).plan(-1)["cuts"]) - 1 == 1
+    want, stats_want = caller.run_poa(clusters)
+    for k in range(0, len(clusters), 7):
+        assert want[k] == _to_str(O.poa_consensus(clusters[k])), k
+    monkeypatch.setenv("SVDSS_POA_WS_GB", "1")
+    got, stats = caller.run_poa(clusters)
+    assert got == want
+    assert stats["cells"] == stats_want["cells"] and stats["cells"] > 0
+    assert stats["hbm"] == stats_want["hbm"] and stats["quad_back"] == stats_want["quad_back"]
+
+
+def test_fallback_passes_through_the_arena(monkeypatch):
+    """SVDSS_POA_HBM=1: every sub-cluster on the HBM kernel, whose workspace is the batch object's arena.  Twice (run_poa
+    makes a batch object per call: two calls)."""
+    clusters = _mixed_clusters(23, 12)
+    clusters += [[], [np.array([0, 1, 2, 3], np.uint8)], [np.zeros(0, np.uint8), np.array([1, 1], np.uint8)]]
+    want = [_to_str(O.poa_consensus(reads)) for reads in clusters]
+    monkeypatch.setenv("SVDSS_POA_HBM", "1")
+    for _ in range(2):
+        got, stats = caller.run_poa(clusters)
+        assert got == want
+        assert stats["hbm"] == sum(1 for cl in clusters if len(cl) > 0)
+
+
 def test_node_with_many_predecessors_falls_back():
     rng = np.random.default_rng(22)
     t = rng.integers(0, 4, size=300).astype(np.uint8)
