@@ -276,6 +276,11 @@ void svdss_sfs_batch_free(svdss_sfs_batch_t* b);
 typedef struct svdss_bam_stream svdss_bam_stream_t;
 typedef struct svdss_bam_batch svdss_bam_batch_t;
 #define SVDSS_BAM_PUTATIVE 0x100
+/* Added to `skip` of a batch other than 0 (every entry point that runs a batch): the batch begins a RANGE of the file of its
+ * own, behind a gap -- at a known record start, skip bytes into its first member.  The bytes the batch in front carried
+ * (the record cut at its range's end) are dropped and the chain starts there.  The stream must be open at its end
+ * (svdss_bam_stream_region).  `--region` with an index reads the ranges the index names as ONE stream this way. */
+#define SVDSS_BAM_SKIP_RESTART ((int64_t)1 << 40)
 int svdss_bam_stream_create(int32_t n_ref, svdss_bam_stream_t** out);
 void svdss_bam_stream_free(svdss_bam_stream_t* s);
 const char* svdss_bam_stream_error(const svdss_bam_stream_t* s);
@@ -290,6 +295,16 @@ const char* svdss_bam_stream_error(const svdss_bam_stream_t* s);
 int svdss_bam_stream_region(svdss_bam_stream_t* s, int32_t open_start, int32_t open_end, const uint8_t* carry, int64_t n_carry);
 int64_t svdss_bam_stream_head(const svdss_bam_stream_t* s, const uint8_t** bytes);   /* after batch 0 */
 int64_t svdss_bam_stream_tail(const svdss_bam_stream_t* s, const uint8_t** bytes);   /* after the last batch */
+/* The record gate (`--region` / `--regions-file`).  Call before batch 0.  n intervals [beg, end) (0-based, half open) of
+ * references tid, sorted by (tid, beg) and merged (on one reference each begins at or behind the end of the one before);
+ * n = 0: no record is in.  From then on every entry point that runs a batch of the stream -- svdss_bam_batch_front / _run,
+ * svdss_bam_select_run / _select_store_run, svdss_bam_smooth_measure / _run -- sees the batch of a file that holds only the
+ * records with tid >= 0 whose [pos, bam_endpos) overlaps an interval of their reference (bam_endpos = pos + the reference
+ * length of the CIGAR, pos + 1 where that is 0): the others are no slot, are neither selected nor stored, are dropped by
+ * the smoothing.  n_records of a batch's result still counts them; svdss_bam_stream_gated: how many so far. */
+int svdss_bam_stream_set_regions(svdss_bam_stream_t* s, int64_t n, const int32_t* tid, const int32_t* beg, const int32_t* end);
+int64_t svdss_bam_stream_gated(const svdss_bam_stream_t* s);
+int svdss_bam_gated_total(int64_t* out);   /* ... of every stream of the process */
 /* segments whose guessed first record the chain did not arrive at (walked again, exactly), of *n_segments in all */
 int64_t svdss_bam_stream_rewalked(const svdss_bam_stream_t* s, int64_t* n_segments);
 int svdss_bam_batch_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, const svdss_index_t* ix,

@@ -105,6 +105,9 @@ SIGNATURES = {
     "svdss_bam_stream_rewalked": (_i64, [_p, _pi64]),
     "svdss_bam_stream_region": (C.c_int, [_p, _i32, _i32, _p, _i64]),
     "svdss_bam_stream_head": (_i64, [_p, C.POINTER(_p)]),
+    "svdss_bam_stream_set_regions": (C.c_int, [_p, _i64, _p, _p, _p]),
+    "svdss_bam_stream_gated": (_i64, [_p]),
+    "svdss_bam_gated_total": (C.c_int, [_pi64]),
     "svdss_bam_stream_tail": (_i64, [_p, C.POINTER(_p)]),
     "svdss_bam_batch_run": (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _p, _p, _p, _p, _p, _i32, C.POINTER(_p)]),
     "svdss_bam_store_create": (C.c_int, [_i32, _i64, _i64, C.POINTER(_p)]),

@@ -48,7 +48,21 @@ def bam_header(data, blocks):
     return n_ref, o
 
 
-def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20, n_ref=None, skip=None):
+def set_gate(stream, gate):
+    """svdss_bam_stream_set_regions: `gate` = [(tid, beg, end)] sorted by (tid, beg) and merged, 0-based half open (an
+    empty list: no record is in; None: no gate).  Before the stream's batch 0."""
+    if gate is None:
+        return
+    t = np.array([g[0] for g in gate], dtype=np.int32)
+    b = np.array([g[1] for g in gate], dtype=np.int32)
+    e = np.array([g[2] for g in gate], dtype=np.int32)
+    rc = lib.svdss_bam_stream_set_regions(stream, len(gate), t.ctypes.data if len(gate) else None, b.ctypes.data if len(gate) else None,
+                                          e.ctypes.data if len(gate) else None)
+    if rc:
+        raise SvdssError(rc, "svdss_bam_stream_set_regions")
+
+
+def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20, n_ref=None, skip=None, gate=None):
     """`data`: the bytes of a BAM file.  Runs the whole file through svdss_bam_batch_run in batches of about
     batch_bytes inflated bytes (one after the other; the binary runs several at once) and returns a list of
     (name, hp, None | [(qs, len), ...]) for every record that passed the filters, in file order, plus a dict of counters."""
@@ -62,6 +76,7 @@ def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20
         raise SvdssError(rc, "svdss_bam_stream_create")
     batch = C.c_void_p()
     out, stats = [], {"records": 0, "short": 0, "batches": 0}
+    set_gate(stream, gate)
     flags = (SVDSS_SFS_ASSEMBLE if assemble else 0) | (SVDSS_BAM_PUTATIVE if putative else 0)
     try:
         groups, cur, acc = [], [], 0
@@ -113,6 +128,7 @@ def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20
         nseg = C.c_int64(0)
         stats["rewalked"] = lib.svdss_bam_stream_rewalked(stream, C.byref(nseg))
         stats["segments"] = nseg.value
+        stats["gated"] = lib.svdss_bam_stream_gated(stream)
     finally:
         if batch:
             lib.svdss_bam_batch_free(batch)
@@ -126,7 +142,7 @@ class BamSelection(C.Structure):
                 ("slim", C.c_int32)]
 
 
-def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20, device=0):
+def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20, device=0, gate=None):
     """svdss_bam_select_run over a whole BAM file (bytes): the records `SVDSS call` keeps -- no flag 4 / 256 / 2048,
     mapq >= min_mapq, and (when given) read name in `names` or alignment overlapping one of `regions` =
     [(tid, beg, end)] sorted by (tid, beg).  Returns ([record bytes without the block_size field], counters)."""
@@ -151,6 +167,7 @@ def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20
     batch = C.c_void_p()
     out, stats = [], {"records": 0, "batches": 0}
     try:
+        set_gate(stream, gate)
         groups, cur, acc = [], [], 0
         for b in blocks:
             cur.append(b)
@@ -183,6 +200,7 @@ def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20
                     o = int(off[k])
                     bs = struct.unpack_from("<i", raw, o)[0]
                     out.append(raw[o + 4:o + 4 + bs])
+        stats["gated"] = lib.svdss_bam_stream_gated(stream)
     finally:
         if batch:
             lib.svdss_bam_batch_free(batch)
@@ -191,7 +209,55 @@ def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20
     return out, stats
 
 
-def select_bam_store(data, names, regions, min_mapq=0, batch_bytes=256 << 20, device=0, max_store_bytes=1 << 34):
+SVDSS_BAM_SKIP_RESTART = 1 << 40
+
+
+def select_bam_ranges(data, ranges, min_mapq=0, batch_blocks=16, device=0, gate=None):
+    """svdss_bam_select_run over RANGES of a BAM file as one stream, the way `--region` with an index reads it: `ranges` =
+    [(first block, end block, skip)] over bgzf.bgzf_blocks(data), ascending and disjoint, a record starting `skip` bytes into
+    each range's first block (the first range may be (0, n, header length)).  Every range is cut into batches of
+    batch_blocks blocks; the first batch of every range but the first carries SVDSS_BAM_SKIP_RESTART.  Returns the kept
+    records' bytes (without the block_size field), in order."""
+    blocks = bgzf.bgzf_blocks(data)
+    n_ref, _ = bam_header(data, blocks)
+    comp = np.frombuffer(bytes(data), dtype=np.uint8)
+    flt, stream, batch = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(lib.svdss_bam_filter_create(device, min_mapq, n_ref, None, None, 0, None, None, None, 0, C.byref(flt)), "svdss_bam_filter_create")
+    _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")
+    out = []
+    try:
+        _check(lib.svdss_bam_stream_region(stream, 0, 1, None, 0), "svdss_bam_stream_region")
+        set_gate(stream, gate)
+        jobs = []
+        for k, (b0, b1, skip) in enumerate(ranges):
+            for at in range(b0, b1, batch_blocks):
+                jobs.append((blocks[at:min(at + batch_blocks, b1)], (skip | (SVDSS_BAM_SKIP_RESTART if k else 0)) if at == b0 else 0))
+        if not jobs:
+            jobs = [([], 0)]
+        for seq, (g, skip) in enumerate(jobs):
+            rec, crc = _group_tables(g)
+            rc = lib.svdss_bam_select_run(stream, seq, 1 if seq == len(jobs) - 1 else 0, skip, flt, 1,
+                                          (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
+                                          (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+            if rc:
+                raise SvdssError(rc, "svdss_bam_select_run: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
+            r = BamSelection()
+            lib.svdss_bam_batch_selection(batch, C.byref(r))
+            if r.n_selected:
+                off = np.ctypeslib.as_array(r.rec_off, shape=(r.n_selected + 1,))
+                raw = C.string_at(r.bytes, r.n_bytes)
+                for i in range(r.n_selected):
+                    o = int(off[i])
+                    out.append(raw[o + 4:o + 4 + struct.unpack_from("<i", raw, o)[0]])
+        return out
+    finally:
+        if batch:
+            lib.svdss_bam_batch_free(batch)
+        lib.svdss_bam_stream_free(stream)
+        lib.svdss_bam_filter_free(flt)
+
+
+def select_bam_store(data, names, regions, min_mapq=0, batch_bytes=256 << 20, device=0, max_store_bytes=1 << 34, gate=None):
     """`SVDSS call`'s ONE pass: svdss_bam_select_store_run over a whole BAM file with `names` as the filter (the first pass'
     records come back whole) and every record that passes the flag / mapq filters kept, slim, in a svdss_bam_store_t; then
     svdss_bam_store_select of every stored batch with `regions` [(tid, beg, end)] sorted by (tid, beg).
@@ -230,6 +296,7 @@ def select_bam_store(data, names, regions, min_mapq=0, batch_bytes=256 << 20, de
                 bs = struct.unpack_from("<i", raw, o)[0]
                 into.append(raw[o + 4:o + 4 + bs])
     try:
+        set_gate(stream, gate)
         groups, cur, acc = [], [], 0
         for b in blocks:
             cur.append(b)
@@ -258,6 +325,7 @@ def select_bam_store(data, names, regions, min_mapq=0, batch_bytes=256 << 20, de
             stats["batches"] += 1
             stats.setdefault("named_slim", []).extend([int(r.slim)] * int(r.n_selected))
             take(r, named)
+        stats["gated"] = lib.svdss_bam_stream_gated(stream)
         complete, n_rec, n_bytes = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         n_b = lib.svdss_bam_store_batches(store, C.byref(complete), C.byref(n_rec), C.byref(n_bytes))
         stats.update({"stored_batches": n_b, "complete": complete.value, "stored_records": n_rec.value, "stored_bytes": n_bytes.value})
@@ -372,7 +440,7 @@ class BamStore:
             if batch:
                 lib.svdss_bam_batch_free(batch)
 
-    def fill_by_select(self, data, min_mapq=0, batch_bytes=256 << 20):
+    def fill_by_select(self, data, min_mapq=0, batch_bytes=256 << 20, gate=None):
         """every batch of the file through svdss_bam_select_store_run with an empty set of names; returns the batch count"""
         blocks = bgzf.bgzf_blocks(data)
         n_ref, skip = bam_header(data, blocks)
@@ -381,6 +449,7 @@ class BamStore:
         stream, batch = C.c_void_p(), C.c_void_p()
         _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")
         try:
+            set_gate(stream, gate)
             groups = _batch_groups(blocks, batch_bytes)
             for seq, g in enumerate(groups):
                 rec, crc = _group_tables(g)
@@ -397,10 +466,12 @@ class BamStore:
             flt.close()
 
 
-def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20, store=None, store_min_mapq=None, device=0):
+def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20, store=None, store_min_mapq=None, device=0, gate=None,
+               measure=False):
     """svdss_bam_smooth_run over a whole BAM file (bytes) whose header names `contigs_ascii` in order; with `store` (a
     BamStore) after svdss_bam_smooth_set_store(sm, store, store_min_mapq).  Returns (the BGZF members of the smoothed
-    stream, batch count)."""
+    stream, batch count).  gate: see set_gate.  measure=True: svdss_bam_smooth_measure instead -- returns ([(matches,
+    mismatches, fits) per kept record, in file order], [(n_records, n_kept) per batch])."""
     blocks = bgzf.bgzf_blocks(data)
     n_ref, skip = bam_header(data, blocks)
     raw_head = b""
@@ -423,9 +494,23 @@ def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20,
         _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")
         head = np.frombuffer(raw_head[:skip], dtype=np.uint8)
         _check(lib.svdss_bam_stream_set_output_prefix(stream, head.ctypes.data, len(head)), "svdss_bam_stream_set_output_prefix")
+        set_gate(stream, gate)
         groups = _batch_groups(blocks, batch_bytes)
+        measured, counts = [], []
         for seq, g in enumerate(groups):
             rec, crc = _group_tables(g)
+            if measure:
+                rc = lib.svdss_bam_smooth_measure(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, 1,
+                                                  (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
+                                                  (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+                if rc:
+                    raise SvdssError(rc, "svdss_bam_smooth_measure: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
+                sr = BamSmoothed()
+                _check(lib.svdss_bam_batch_smoothed(batch, C.byref(sr)), "svdss_bam_batch_smoothed")
+                counts.append((int(sr.n_records), int(sr.n_kept)))
+                for k in range(sr.n_kept):
+                    measured.append((int(sr.match_mismatch[2 * k]), int(sr.match_mismatch[2 * k + 1]), int(sr.fits[k])))
+                continue
             rc = lib.svdss_bam_smooth_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, C.c_double(acc), None, 0, 1,
                                           (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
                                           (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
@@ -434,6 +519,8 @@ def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20,
             sr = BamSmoothed()
             _check(lib.svdss_bam_batch_smoothed(batch, C.byref(sr)), "svdss_bam_batch_smoothed")
             out += C.string_at(sr.bgzf, sr.bgzf_bytes) if sr.bgzf_bytes else b""
+        if measure:
+            return measured, counts
         return bytes(out), len(groups)
     finally:
         if batch:

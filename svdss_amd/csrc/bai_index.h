@@ -264,7 +264,10 @@ inline std::string bam_scan_chunks(const std::string& path, const std::vector<st
       const size_t head = 32 + (size_t)v.l_name + 4u * v.n_cigar + (v.l_seq < 0 ? (size_t)0 : ((size_t)v.l_seq + 1) / 2 + (size_t)v.l_seq);
       if (v.l_seq < 0 || head > (size_t)block_size) { err = "corrupt record"; break; }
       v.l_aux = (uint32_t)((size_t)block_size - head);
-      fn(v);
+      // (--region / --regions-file: the chunks of the caller's regions, intersected with the command's)
+      if (const BamRegionSet* U = bam_regions_in_force(); U && !U->keeps(v.tid, v.pos, v.name() + v.l_name, v.n_cigar))
+        bam_region_counters().gated.fetch_add(1, std::memory_order_relaxed);
+      else fn(v);
       upos += 4 + (size_t)block_size;
       // a merged chunk can span whole chromosomes: drop the blocks the walk has left behind once they add up to 4 MB
       // (the block that holds upos stays, so voff_of keeps answering for every position still reachable)

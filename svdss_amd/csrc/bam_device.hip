@@ -32,6 +32,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <thread>
@@ -202,6 +203,104 @@ __global__ void __launch_bounds__(64) link_kernel(WalkP P, int64_t start, uint32
   hdr[H_ERR] = err;
   hdr[H_REWALK] = n_rewalk;
   hdr[H_PRE] = n_pre;
+}
+
+// ------------------------------------------------------------------ the record gate (svdss_bam_stream_set_regions)
+// `--region` / `--regions-file`: a record is IN if tid >= 0 and [pos, bam_endpos) overlaps one of the stream's intervals on
+// its reference (bam_endpos as in select_kernel: pos + the CIGAR's reference length, pos + 1 where that is 0).  The records
+// that are out leave the chain here, right behind link_kernel: the segments' lists are compacted in place, in order, and the
+// counts, bases and totals follow -- so meta_kernel, select_kernel and smooth_meta_kernel (and everything behind them) see
+// the batch of a file that holds the records that are in alone.  hdr[H_GATED] counts those that left.
+struct GateP {
+  const uint8_t* buf;
+  uint32_t* lists; int64_t list_cap;
+  int32_t* seg_cnt; int32_t* seg_base; uint32_t* pre;
+  int32_t n_seg, n_ref;
+  const int64_t* reg_off; const int32_t* reg_beg; const int32_t* reg_end;   // per tid: [reg_off[t], reg_off[t + 1]), sorted, disjoint
+  int64_t* hdr;
+};
+constexpr uint32_t kGateLaneCigar = 256;   // CIGARs up to here are summed by the record's own lane, longer ones by the wavefront
+
+__device__ __forceinline__ int64_t cigar_ref_len(uint32_t c) {
+  const uint32_t op = c & 15u;
+  return (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (int64_t)(c >> 4) : 0;
+}
+
+// block s < n_seg: the records of segment s; block n_seg: those that begin in the carried bytes.  One wavefront: 64 records
+// at a time, a lane each; a record whose CIGAR is long is summed by all 64 lanes (coalesced loads, a shuffle reduction), so
+// that a CIGAR of tens of thousands of operations does not hold 63 lanes up behind one.
+__global__ void __launch_bounds__(64) gate_kernel(GateP G) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int cnt = s < G.n_seg ? G.seg_cnt[s] : (int)(G.hdr[H_PRE] < 4 ? G.hdr[H_PRE] : 4);
+  uint32_t* list = s < G.n_seg ? G.lists + (int64_t)s * G.list_cap : G.pre;
+  int kept = 0;
+  for (int i0 = 0; i0 < cnt; i0 += 64) {
+    const bool have = i0 + lane < cnt;
+    const uint32_t p32 = have ? list[i0 + lane] : 0u;
+    const int64_t p = p32;
+    bool in = false, cand = false, longc = false;
+    int32_t tid = -1, pos = 0;
+    uint32_t n_cig = 0;
+    int64_t cg = 0, ref_len = 0;
+    if (have) {
+      const uint32_t bs = ld32(G.buf, p);
+      tid = (int32_t)ld32(G.buf, p + 4); pos = (int32_t)ld32(G.buf, p + 8);
+      const uint32_t w3 = ld32(G.buf, p + 12), w4 = ld32(G.buf, p + 16);
+      const int32_t l_seq = (int32_t)ld32(G.buf, p + 20);
+      const uint32_t l_name = w3 & 0xffu;
+      n_cig = w4 & 0xffffu;
+      cg = p + 36 + l_name;
+      const int64_t head = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)(l_seq < 0 ? 0 : l_seq) + 1) / 2 + (l_seq < 0 ? 0 : l_seq);
+      // (a record whose fields do not fit its block_size stays: the kernel behind raises "corrupt record" as it always has,
+      // and its CIGAR is not walked)
+      if (l_seq < 0 || head > (int64_t)bs) in = true;
+      else cand = tid >= 0 && tid < G.n_ref && G.reg_off[tid + 1] > G.reg_off[tid];
+      longc = cand && n_cig > kGateLaneCigar;
+      if (cand && !longc)
+        for (uint32_t k = 0; k < n_cig; ++k) ref_len += cigar_ref_len(ld32(G.buf, cg + 4 * (int64_t)k));
+    }
+    unsigned long long lm = __ballot(longc);
+    while (lm) {
+      const int src = __builtin_ctzll(lm);
+      lm &= lm - 1;
+      const int64_t cg_s = __shfl(cg, src, 64);
+      const uint32_t n_s = (uint32_t)__shfl((int)n_cig, src, 64);
+      int64_t part = 0;
+      for (uint32_t k = lane; k < n_s; k += 64) part += cigar_ref_len(ld32(G.buf, cg_s + 4 * (int64_t)k));
+      for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+      if (lane == src) ref_len = part;
+    }
+    if (cand) {
+      const int64_t a_beg = pos, a_end = (int64_t)pos + (ref_len ? ref_len : 1);
+      // the first interval that ends behind a_beg overlaps iff it begins before a_end
+      const int64_t lo = G.reg_off[tid], hi = G.reg_off[tid + 1];
+      int64_t a = lo, b = hi;
+      while (a < b) { const int64_t m = (a + b) >> 1; if ((int64_t)G.reg_end[m] > a_beg) b = m; else a = m + 1; }
+      in = a < hi && (int64_t)G.reg_beg[a] < a_end;
+    }
+    // in order, in place: the slot written is never behind the one read (and this pass has read its 64 already)
+    const unsigned long long km = __ballot(in);
+    if (in) list[kept + __popcll(km & ((1ull << lane) - 1ull))] = p32;
+    kept += __popcll(km);
+  }
+  if (lane == 0) {
+    if (s < G.n_seg) G.seg_cnt[s] = kept; else G.hdr[H_PRE] = kept;
+    if (cnt > kept) atomicAdd((unsigned long long*)&G.hdr[H_GATED], (unsigned long long)(cnt - kept));
+  }
+}
+// the segments' bases and the batch's total, from the counts gate_kernel left (one wavefront, 64 segments per step)
+__global__ void __launch_bounds__(64) gate_base_kernel(GateP G) {
+  const int lane = threadIdx.x;
+  int run = (int)G.hdr[H_PRE];
+  for (int s0 = 0; s0 < G.n_seg; s0 += 64) {
+    const int s = s0 + lane;
+    const int c = s < G.n_seg ? G.seg_cnt[s] : 0;
+    int inc = c;
+    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+    if (s < G.n_seg) G.seg_base[s] = run + inc - c;
+    run += __shfl(inc, 63, 64);
+  }
+  if (lane == 0) G.hdr[H_NREC] = run;
 }
 
 // ------------------------------------------------------------------ per record: fields, filters, tags
@@ -466,6 +565,8 @@ struct OffDiff {   // length of searched read k
 
 }  // namespace
 
+static std::atomic<int64_t> g_gated_total{0};   // records the gate took out, every stream of the process (svdss_bam_gated_total)
+
 struct svdss_bam_filter {
   int device = -1;
   int32_t min_mapq = 0, n_ref = 0;
@@ -494,6 +595,40 @@ extern "C" int svdss_bam_stream_region(svdss_bam_stream_t* s, int32_t open_start
   s->open_end = open_end != 0;
   try { s->carry.assign(carry, carry + n_carry); } catch (...) { return SVDSS_ENOMEM; }
   return SVDSS_OK;
+}
+extern "C" int svdss_bam_stream_set_regions(svdss_bam_stream_t* s, int64_t n, const int32_t* tid, const int32_t* beg, const int32_t* end) {
+  if (!s || n < 0 || (n > 0 && (!tid || !beg || !end))) return SVDSS_EINVAL;
+  std::lock_guard<std::mutex> lk(s->m);
+  if (s->next_seq != 0) return SVDSS_EINVAL;   // (before the first batch)
+  try {
+    std::vector<int64_t> off((size_t)s->n_ref + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+      if (tid[i] < 0 || tid[i] >= s->n_ref || beg[i] < 0 || end[i] <= beg[i]) return SVDSS_EINVAL;
+      // sorted and merged: by reference, then ascending and apart
+      if (i > 0 && (tid[i] < tid[i - 1] || (tid[i] == tid[i - 1] && beg[i] < end[i - 1]))) return SVDSS_EINVAL;
+      ++off[(size_t)tid[i] + 1];
+    }
+    for (int32_t t = 0; t < s->n_ref; ++t) off[(size_t)t + 1] += off[(size_t)t];
+    s->gate_tab.resize(off.size() * 8 + (size_t)n * 8);
+    memcpy(s->gate_tab.data(), off.data(), off.size() * 8);
+    if (n > 0) {
+      memcpy(s->gate_tab.data() + off.size() * 8, beg, (size_t)n * 4);
+      memcpy(s->gate_tab.data() + off.size() * 8 + (size_t)n * 4, end, (size_t)n * 4);
+    }
+  } catch (...) { return SVDSS_ENOMEM; }
+  s->gate_n = n;
+  s->gate_on = true;
+  return SVDSS_OK;
+}
+extern "C" int svdss_bam_gated_total(int64_t* out) {
+  if (!out) return SVDSS_EINVAL;
+  *out = g_gated_total.load();
+  return SVDSS_OK;
+}
+extern "C" int64_t svdss_bam_stream_gated(const svdss_bam_stream_t* s) {
+  if (!s) return -1;
+  std::lock_guard<std::mutex> lk(const_cast<svdss_bam_stream*>(s)->m);
+  return s->n_gated;
 }
 extern "C" int64_t svdss_bam_stream_head(const svdss_bam_stream_t* s, const uint8_t** bytes) {
   if (!s) return -1;
@@ -530,6 +665,10 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
                 svdss_bam_batch_t** out, Front& F) {
   BatchRun run(*out);
   run.release = [&](int code, const std::string& msg) { pass_turn(s, &svdss_bam_stream::next_seq, seq, code, msg); };
+  // SVDSS_BAM_SKIP_RESTART: this batch begins a range of the file of its own -- at a known record start, `skip` bytes into
+  // its first member -- behind a gap: what the batch in front carried (the cut record at its range's end) is dropped
+  const bool restart = (skip & SVDSS_BAM_SKIP_RESTART) != 0;
+  skip &= ~SVDSS_BAM_SKIP_RESTART;
   if (n_chunks > 0 && (!comp || !comp_bytes || !blocks || !crc || !n_blocks)) return run.fail(SVDSS_EINVAL, "bad argument");
   BCHK(hipSetDevice(device));
   RCHK(run.batch_object(out, device));
@@ -584,6 +723,12 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   }
   BCHK(hipMemsetAsync(b->front.status.p, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
   BCHK(hipMemsetAsync(b->front.hdr.p, 0, sizeof(int64_t) * H_N, st));
+  // (the gate's intervals: set before batch 0 and not changed after it, so read without the stream's lock)
+  const bool gate_on = s->gate_on;
+  if (gate_on) {
+    RCHK(b->front.gate.ensure(s->gate_tab.size() + 64));
+    BCHK(hipMemcpyAsync(b->front.gate.p, s->gate_tab.data(), s->gate_tab.size(), hipMemcpyHostToDevice, st));
+  }
   int32_t* d_status = (int32_t*)b->front.status.p;
   int32_t* d_crcbad = d_status + total_blocks;
   if (total_blocks > 0) {
@@ -599,7 +744,7 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   // ---- the chain of records, guessed per segment (does not need the carry)
   SegWalk W;
   W.buf = (const uint8_t*)b->front.buf.p;
-  W.lo = HEAD + (seq == 0 ? skip : 0);
+  W.lo = HEAD + (seq == 0 || restart ? skip : 0);
   W.hi = HEAD + total_inf;
   W.n_ref = s->n_ref;
   {
@@ -642,7 +787,7 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   std::string turn_msg;
   int64_t hdr[H_N] = {0};
   {
-    const int64_t carry_len = (int64_t)s->carry.size();
+    const int64_t carry_len = restart && seq > 0 ? 0 : (int64_t)s->carry.size();
     auto turn_fail = [&](int code, const std::string& msg) { turn_code = code; turn_msg = msg; };
     hipError_t e = hipSuccess;
     if (carry_len > HEAD) turn_fail(SVDSS_ERANGE, "a record larger than the head room (SVDSS_BAM_HEADROOM_MB)");
@@ -651,7 +796,7 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
     if (!turn_code && e == hipSuccess) {
       // (SVDSS_REGION_TEST, for the tests of the caller's second run: 1 = start at a guess that is no record, 2 = a head one byte short)
       static const int region_test = getenv("SVDSS_REGION_TEST") ? atoi(getenv("SVDSS_REGION_TEST")) : 0;
-      const int64_t start = seq == 0 && s->open_start ? (region_test == 1 ? -2 : -1) : seq == 0 && carry_len == 0 ? W.lo : HEAD - carry_len;
+      const int64_t start = seq == 0 && s->open_start ? (region_test == 1 ? -2 : -1) : (seq == 0 || restart) && carry_len == 0 ? W.lo : HEAD - carry_len;
       hipLaunchKernelGGL(link_kernel, dim3(1), dim3(64), 0, st, WalkP{W}, start, (uint32_t*)b->front.pre.p, seg_base, (int64_t*)b->front.hdr.p);
       e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(hdr, b->front.hdr.p, sizeof hdr, hipMemcpyDeviceToHost, st);
@@ -687,7 +832,26 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   }
   done_turn(s, &svdss_bam_stream::next_seq, turn_code, turn_msg);
   if (turn_code) { b->err = turn_msg; return turn_code; }
-  run.lap(2);   // the turn: carry in, link, carry out
+  // ---- the record gate, outside the turn (it needs nothing of the batches in front): the chain loses the records outside
+  // the stream's regions before any front end looks at it
+  if (gate_on && hdr[H_NREC] > 0) {
+    GateP G;
+    G.buf = W.buf; G.lists = W.lists; G.list_cap = W.list_cap; G.seg_cnt = W.seg_cnt; G.seg_base = seg_base; G.pre = (uint32_t*)b->front.pre.p;
+    G.n_seg = W.n_seg; G.n_ref = s->n_ref;
+    G.reg_off = (const int64_t*)b->front.gate.p;
+    G.reg_beg = (const int32_t*)(G.reg_off + (s->n_ref + 1)); G.reg_end = G.reg_beg + s->gate_n;
+    G.hdr = (int64_t*)b->front.hdr.p;
+    hipLaunchKernelGGL(gate_kernel, dim3((unsigned)W.n_seg + 1), dim3(64), 0, st, G);
+    BCHK(hipGetLastError());
+    hipLaunchKernelGGL(gate_base_kernel, dim3(1), dim3(64), 0, st, G);
+    BCHK(hipGetLastError());
+    BCHK(hipMemcpyAsync(hdr, b->front.hdr.p, sizeof hdr, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
+    std::lock_guard<std::mutex> lk(s->m);
+    s->n_gated += hdr[H_GATED];
+    g_gated_total.fetch_add(hdr[H_GATED], std::memory_order_relaxed);
+  }
+  run.lap(2);   // the turn: carry in, link, carry out (and the gate)
   F.W = W; F.seg_base = seg_base; F.total_inf = total_inf; F.HEAD = HEAD;
   memcpy(F.hdr, hdr, sizeof hdr);
   return SVDSS_OK;
@@ -813,7 +977,7 @@ extern "C" int svdss_bam_batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t
 
   // ---- fields, filters, tags; where everything goes
   const int64_t n_rec = hdr[H_NREC];
-  b->n_records = n_rec;
+  b->n_records = n_rec + hdr[H_GATED];   // (the records the gate took out of the chain are records of the batch)
   RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));
   RCHK(b->flags.ensure(sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
   RCHK(b->scans.ensure(sizeof(int64_t) * 4 * (size_t)(n_rec + 1)));
@@ -1149,7 +1313,7 @@ extern "C" int svdss_bam_select_store_run(svdss_bam_stream_t* s, int64_t seq, in
   const hipStream_t st = run.st;
   const SegWalk& W = F.W;
   const int64_t n_rec = F.hdr[H_NREC];
-  b->n_records = n_rec;
+  b->n_records = n_rec + F.hdr[H_GATED];
   b->sel.n = 0; b->sel.bytes = 0; b->sel.slim = false;
   RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));
   RCHK(b->flags.ensure(sizeof(int64_t) * 5 * (size_t)(n_rec + 1)));

@@ -25,7 +25,7 @@
 
 // error bits a batch's kernels raise (hdr[H_ERR]; bam_smooth.hip adds one of its own)
 enum { E_CORRUPT = 1, E_TID = 2 };
-enum { H_NREC = 0, H_TAIL = 1, H_ERR = 2, H_REWALK = 3, H_PRE = 4, H_SHORT = 5, H_START = 6, H_N = 8 };
+enum { H_NREC = 0, H_TAIL = 1, H_ERR = 2, H_REWALK = 3, H_PRE = 4, H_SHORT = 5, H_START = 6, H_GATED = 7, H_N = 8 };
 
 // what the host says about them: the words of the host path (BamReader::next_view, ping_pong.cpp:76-79)
 static inline const char* record_error(int64_t bits) {
@@ -302,6 +302,11 @@ struct svdss_bam_stream {
   // BAM header of the output)
   int64_t next_out = 0;
   std::vector<uint8_t> out_tail;
+  // the record gate (svdss_bam_stream_set_regions): the intervals as gate_kernel reads them -- n_ref + 1 offsets (int64), the
+  // begins, the ends (int32 each) -- and the records of the batches so far that were outside them
+  bool gate_on = false;
+  std::vector<uint8_t> gate_tab;
+  int64_t gate_n = 0, n_gated = 0;
 };
 
 // Batches take turns in file order: at the carry (`turn` = &svdss_bam_stream::next_seq) and, when smoothing, at the output
@@ -341,7 +346,7 @@ struct svdss_bam_batch {
   BamBuf rpos, flags, scans, tmp, totals;
   // batch_front: the blocks, the inflated bytes, the record chain (pre and hdr are read by the job that follows)
   struct {
-    BamBuf comp, blks, crcb, status, buf, seg, lists, pre, hdr;
+    BamBuf comp, blks, crcb, status, buf, seg, lists, pre, hdr, gate;
     PinBuf<2, 4096> pin;             // page-locked staging of the block tables (grows to n + n / 4 + 4096)
     std::vector<int32_t> h_status;
   } front;

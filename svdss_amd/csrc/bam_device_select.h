@@ -105,6 +105,36 @@ inline bool bam_header_probe(const std::string& path, int32_t& n_ref, int64_t& s
 }
 
 
+// --region / --regions-file (bam_regions.h): the command's regions given to a record stream of the device path before its
+// batch 0 (svdss_bam_stream_set_regions); none in force: nothing to do
+inline int bam_stream_apply_regions(svdss_bam_stream_t* s) {
+  const BamRegionSet* U = bam_regions_in_force();
+  return U ? svdss_bam_stream_set_regions(s, (int64_t)U->size(), U->tid.data(), U->beg.data(), U->end.data()) : SVDSS_OK;
+}
+
+// --verbose with regions in force: one line when the command is done (main, and the commands that end the process themselves).
+// Every pass over the file counts: `smooth` measures before it runs, `call` may read a file twice.
+inline void bam_regions_report() {
+  const BamRegionSet* U = bam_regions_in_force();
+  if (!U || !bam_region_counters().verbose) return;
+  bam_region_counters().verbose = false;   // (once)
+  int64_t on_device = 0;
+  (void)svdss_bam_gated_total(&on_device);
+  const BamRegionPlan& plan = bam_region_plan();
+  // (the host readers -- SVDSS_BAM_DEVICE=0, SVDSS_SMOOTH_HOST=1, pass 1 of a `call` without the device path -- take no
+  // ranges: they read the whole file, and the bytes figure counts the device path's alone)
+  if (const long long h = (long long)bam_region_counters().host_readers.load())
+    fprintf(stderr, "[regions] %lld host reader(s) read the WHOLE file through the gate, with or without an index; their bytes are not in the figure below\n", h);
+  if (plan.active)
+    fprintf(stderr, "[regions] %zu interval(s); %zu range(s) of %zu bytes named by %s, %lld compressed bytes read, %lld records gated out\n", U->size(),
+            plan.ranges.size(), plan.bytes(), plan.index_path.c_str(), (long long)bam_region_counters().comp_bytes.load(),
+            (long long)(bam_region_counters().gated.load() + on_device));
+  else
+    fprintf(stderr, "[regions] %zu interval(s); no usable index: the whole file goes through the record gate, 1 range, %lld compressed bytes read, "
+                    "%lld records gated out\n", U->size(), (long long)bam_region_counters().comp_bytes.load(),
+            (long long)(bam_region_counters().gated.load() + on_device));
+}
+
 // the kept records of one device batch, in file order: record k = bytes[off[k] + 4 ..), block_size at bytes[off[k]]
 struct SelectedBatch {
   std::vector<uint8_t> bytes;   // (smoothing: the batch's BGZF members)
@@ -201,9 +231,14 @@ class DeviceBamSelect {
       sc_ = own_sc_.get();
     }
     if (!sc_->ok()) { err_ = BamRunError{SVDSS_EIO, "cannot open file", ""}; return; }
+    // --region with an index (bam_region_plan): the scanner reads the index's ranges; the first record is where the first
+    // range says, and the stream may end inside the record its last range cuts
+    const bool ranged = sc_->ranged();
+    if (ranged) skip_ = sc_->first_skip();
     if (!stream_ && svdss_bam_stream_create(n_ref, &stream_) != SVDSS_OK) { err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return; }
-    if (region.open_start || region.open_end || !region.carry.empty())
-      if (svdss_bam_stream_region(stream_, region.open_start ? 1 : 0, region.open_end ? 1 : 0, region.carry.data(), (int64_t)region.carry.size()) != SVDSS_OK) {
+    if (const int rc = bam_stream_apply_regions(stream_)) { err_ = BamRunError{rc, "the regions do not fit the BAM header", ""}; return; }
+    if (region.open_start || region.open_end || ranged || !region.carry.empty())
+      if (svdss_bam_stream_region(stream_, region.open_start ? 1 : 0, region.open_end || ranged ? 1 : 0, region.carry.data(), (int64_t)region.carry.size()) != SVDSS_OK) {
         err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return;
       }
     n_feeders_ = n_devices * (size_t)feeders;
@@ -264,7 +299,7 @@ class DeviceBamSelect {
   int64_t segments_walked_again(int64_t* n_segments) const { return stream_ ? svdss_bam_stream_rewalked(stream_, n_segments) : 0; }
 
  private:
-  struct Job { uint64_t seq = 0; bool last = false; std::vector<std::unique_ptr<CompChunk>> chunks; };
+  struct Job { uint64_t seq = 0; bool last = false; bool restart = false; int64_t skip = 0; std::vector<std::unique_ptr<CompChunk>> chunks; };
   bool fed() const { return feeders_done_ == n_feeders_; }
   void fail(const BamRunError& e) {
     { std::lock_guard<std::mutex> lk(m_); if (!err_.failed()) err_ = e; }
@@ -294,6 +329,19 @@ class DeviceBamSelect {
       std::unique_ptr<CompChunk> c = sc_->next();
       w_file += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
       if (!c) break;
+      if (bam_regions_in_force()) {   // (--verbose: the BGZF members read, header and footer of 26 bytes each included)
+        int64_t cb = 0;
+        for (const svdss_bgzf_block_t& k : c->blocks) cb += (int64_t)k.clen + 26;
+        bam_region_counters().comp_bytes.fetch_add(cb, std::memory_order_relaxed);
+      }
+      // a range of its own begins with this slab: the batch in hand ends here, the next one starts the chain again
+      if (c->range_start && !cur->chunks.empty()) {
+        cur->seq = seq++;
+        if (!push(std::move(cur))) return;
+        cur.reset(new Job);
+        acc = 0;
+      }
+      if (c->range_start) { cur->restart = true; cur->skip = c->skip; }
       acc += c->inflated;
       const bool last = c->last;
       cur->chunks.push_back(std::move(c));
@@ -332,7 +380,8 @@ class DeviceBamSelect {
         comp.push_back(c->data); comp_bytes.push_back((int64_t)c->n_bytes); n_blocks.push_back((int64_t)c->blocks.size());
         blocks.push_back(c->blocks.data()); crcs.push_back(c->crc.data());
       }
-      const int rc = run_(stream_, (int64_t)job->seq, job->last ? 1 : 0, job->seq == 0 ? skip_ : 0, d, (int32_t)comp.size(), comp.data(), comp_bytes.data(),
+      const int64_t skip = job->restart && job->seq > 0 ? (job->skip | SVDSS_BAM_SKIP_RESTART) : job->seq == 0 ? skip_ : 0;
+      const int rc = run_(stream_, (int64_t)job->seq, job->last ? 1 : 0, skip, d, (int32_t)comp.size(), comp.data(), comp_bytes.data(),
                           blocks.data(), crcs.data(), n_blocks.data(), &batch);
       for (std::unique_ptr<CompChunk>& c : job->chunks) sc_->recycle(std::move(c));
       if (rc != SVDSS_OK) {
@@ -388,6 +437,8 @@ inline std::vector<size_t> plan_bam_regions(const std::string& path, int n, int6
   std::vector<size_t> cuts{0};
   if (stat(path.c_str(), &st) != 0 || st.st_size <= 0) return {0, 0};
   const size_t fsize = (size_t)st.st_size;
+  // (--region with an index: the ranges the index names are read as one stream, on one GPU)
+  if (bam_region_plan().active && bam_region_plan().path == path) return {0, fsize};
   const size_t min_bytes = getenv("SVDSS_REGION_MIN_KB") && atoll(getenv("SVDSS_REGION_MIN_KB")) > 0 ? (size_t)atoll(getenv("SVDSS_REGION_MIN_KB")) << 10
                                                                                                          : (size_t)64 << 20;
   // (the first region holds the whole BAM header)
@@ -591,6 +642,7 @@ class ShardedBamSelect {
     comp.resize(comp.size() + 64);
     svdss_bam_stream_t* st = nullptr;
     if (svdss_bam_stream_create(n_ref_, &st) != SVDSS_OK) { err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return false; }
+    if (const int rc = bam_stream_apply_regions(st)) { err_ = BamRunError{rc, "the regions do not fit the BAM header", ""}; svdss_bam_stream_free(st); return false; }
     svdss_bam_batch_t* batch = nullptr;
     const uint8_t* cp = comp.data();
     const int64_t cb = (int64_t)comp.size(), nb = (int64_t)blk.size();

@@ -4,8 +4,11 @@
 // /root/reference/ping_pong.cpp:58,247-249,196-201.  Only what `search` consumes is
 // decoded: flag, refID, l_seq, read name, 4-bit SEQ, integer aux tags (XF, HP).
 // (The block inflaters are in bgzf_inflater.h.)
+// With --region / --regions-file in force (bam_regions.h) next / next_raw / next_view pass over the records outside the
+// regions: the reader then reads the file that holds the others alone.
 #pragma once
 #include "bgzf_inflater.h"
+#include "bam_regions.h"
 
 struct BamRecord {
   int32_t tid = -1, pos = 0, l_seq = 0;
@@ -173,6 +176,14 @@ class BamReader {
   // 1 = record read, 0 = clean end of file, -1 = error
   // (want_qual = false leaves r.qual empty: `search` never looks at qualities)
   int next(BamRecord& r, bool want_qual = true) {
+    for (;;) {
+      count_reader();
+      const int rc = next_any(r, want_qual);
+      if (rc <= 0 || !gate_ || gate_->keeps(r.tid, r.pos, (const uint8_t*)r.cigar.data(), (uint32_t)r.cigar.size())) return rc;
+      bam_region_counters().gated.fetch_add(1, std::memory_order_relaxed);
+    }
+  }
+  int next_any(BamRecord& r, bool want_qual) {
     int32_t block_size;
     size_t got = read_some(&block_size, 4);
     if (got == 0) return err_.empty() ? 0 : -1;
@@ -330,6 +341,15 @@ class BamReader {
 
   // 1 = record appended to arena, 0 = clean end of file, -1 = error
   int next_raw(Arena& arena, RawRec& rr) {
+    for (;;) {
+      count_reader();
+      const int rc = next_raw_any(arena, rr);
+      if (rc <= 0 || !gate_ || gate_->keeps(rr.tid, rr.pos, arena.data() + rr.off + rr.l_name, rr.n_cigar)) return rc;
+      arena.resize(rr.off);
+      bam_region_counters().gated.fetch_add(1, std::memory_order_relaxed);
+    }
+  }
+  int next_raw_any(Arena& arena, RawRec& rr) {
     int32_t block_size;
     const size_t got = read_some(&block_size, 4);
     if (got == 0) return err_.empty() ? 0 : -1;
@@ -377,6 +397,14 @@ class BamReader {
 
   // 1 = record, 0 = clean end of file, -1 = error
   int next_view(RawView& v) {
+    for (;;) {
+      count_reader();
+      const int rc = next_view_any(v);
+      if (rc <= 0 || !gate_ || gate_->keeps(v.tid, v.pos, v.name() + v.l_name, v.n_cigar)) return rc;
+      bam_region_counters().gated.fetch_add(1, std::memory_order_relaxed);
+    }
+  }
+  int next_view_any(RawView& v) {
     int32_t block_size;
     const size_t got = read_some(&block_size, 4);
     if (got == 0) return err_.empty() ? 0 : -1;
@@ -479,6 +507,14 @@ class BamReader {
   }
 
  private:
+  const BamRegionSet* gate_ = bam_regions_in_force();   // the command's regions (nullptr: every record is in)
+  bool counted_ = false;
+  // a reader that reads RECORDS with regions in force reads the whole file (one that only reads the header does not count)
+  void count_reader() {
+    if (!gate_ || counted_) return;
+    counted_ = true;
+    bam_region_counters().host_readers.fetch_add(1, std::memory_order_relaxed);
+  }
   bool fail(const char* m) { err_ = m; return false; }
   bool read(void* dst, size_t n) { return read_some(dst, n) == n; }
   // n bytes into a string that grows as they arrive (a damaged length field costs a failed read, not an allocation)

@@ -759,7 +759,7 @@ static int smooth_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64
   const hipStream_t st = run.st;
   const SegWalk& W = F.W;
   const int64_t n_rec = F.hdr[H_NREC];
-  b->n_records = n_rec;
+  b->n_records = n_rec + F.hdr[H_GATED];
   b->sm.kept = 0; b->sm.out_bytes = 0; b->sm.bgzf_bytes = 0; b->sm.bgzf = nullptr;
   for (int k = 0; k < 4; ++k) b->sm.xf[k] = 0;
   RCHK(b->rpos.ensure(sizeof(uint32_t) * (size_t)(n_rec + 1)));

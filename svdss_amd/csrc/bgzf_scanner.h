@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "bam_regions.h"
 
 struct CompChunk {
   uint8_t* data = nullptr;       // the slab (+ overlap): page-locked when the hooks gave such memory
@@ -31,6 +32,10 @@ struct CompChunk {
   std::vector<uint32_t> crc;
   int64_t inflated = 0;          // sum of the blocks' isize
   bool last = false;             // the file ends with this chunk
+  // (a slab may come out with NO blocks: the last member of the slab before it ran past the slab's end and to the end of
+  // the scanner's range -- the trailing slab(s) planned for a range that is not the last one; the batcher adds nothing for it)
+  bool range_start = false;      // (a scanner of ranges) the first slab of a range: the chain of records starts again,
+  int64_t skip = 0;              // skip bytes into the slab's first member
 };
 
 class BgzfScanner {
@@ -51,7 +56,20 @@ class BgzfScanner {
     size_ = end && end < fsize_ ? end : fsize_;
     begin_ = begin < size_ ? begin : size_;
     next_off_ = begin_;
-    n_tickets_ = size_ > begin_ ? (size_ - begin_ + slab_ - 1) / slab_ : 0;
+    // --region with an index: a scanner of the whole file reads the ranges the index names, one after the other
+    const BamRegionPlan& plan = bam_region_plan();
+    if (plan.active && path == plan.path && begin_ == 0 && size_ == fsize_) {
+      ranged_ = true;
+      for (const BamFileRange& r : plan.ranges)
+        if (r.begin < r.end && r.end <= fsize_) ranges_.push_back(r);
+    } else {
+      BamFileRange whole;
+      whole.begin = begin_; whole.end = size_;
+      if (size_ > begin_) ranges_.push_back(whole);
+    }
+    for (size_t r = 0; r < ranges_.size(); ++r)
+      for (size_t b = ranges_[r].begin; b < ranges_[r].end; b += slab_) tickets_.push_back(Ticket{b, r, b == ranges_[r].begin});
+    n_tickets_ = tickets_.size();
     if (f_) for (int i = 0; i < (loaders < 1 ? 1 : loaders); ++i) th_.emplace_back([this] { loader(); });
   }
   ~BgzfScanner() {
@@ -66,7 +84,10 @@ class BgzfScanner {
   BgzfScanner& operator=(const BgzfScanner&) = delete;
   bool ok() const { return f_ != nullptr; }
   size_t file_size() const { return fsize_; }
-  size_t range_bytes() const { return size_ - begin_; }
+  size_t range_bytes() const { size_t b = 0; for (const BamFileRange& r : ranges_) b += r.end - r.begin; return b; }
+  // a scanner of the ranges of bam_region_plan(): its slabs say where a range starts (CompChunk::range_start)
+  bool ranged() const { return ranged_; }
+  int64_t first_skip() const { return ranges_.empty() ? 0 : ranges_[0].skip; }
 
   // One BGZF member header at h (avail bytes visible): its length in the file, where its deflate stream is and how long.
   // 0 = not a member header, -1 = more bytes needed.
@@ -169,7 +190,7 @@ class BgzfScanner {
   void recycle(std::unique_ptr<CompChunk> c) {
     {
       std::lock_guard<std::mutex> lk(m_);
-      c->blocks.clear(); c->crc.clear(); c->inflated = 0; c->n_bytes = 0; c->last = false;
+      c->blocks.clear(); c->crc.clear(); c->inflated = 0; c->n_bytes = 0; c->last = false; c->range_start = false; c->skip = 0;
       free_.push_back(std::move(c));
       ++recycled_;
     }
@@ -210,7 +231,8 @@ class BgzfScanner {
         if (!free_.empty()) { c = std::move(free_.back()); free_.pop_back(); }
       }
       if (!c) { c.reset(new CompChunk); if (!alloc(*c)) { fail("out of memory while loading a BAM chunk"); return; } }
-      const size_t base = begin_ + t * slab_;
+      const Ticket tk = tickets_[t];
+      const size_t base = tk.base;
       const size_t want = std::min(slab_ + kOverlap, fsize_ - base);
       size_t got = 0;
       while (got < want) {
@@ -223,11 +245,16 @@ class BgzfScanner {
       cv_.wait(lk, [&] { return stop_ || !err_.empty() || locate_turn_ == t; });
       if (stop_ || !err_.empty()) return;
       std::string e;
+      if (tk.first) {          // the members of this range: from its begin to its end
+        next_off_ = ranges_[tk.range].begin; size_ = ranges_[tk.range].end;
+        if (ranged_) { c->range_start = true; c->skip = ranges_[tk.range].skip; }
+      }
       locate(*c, base, e);     // (short: a few hundred 18-byte headers; under the lock, it is the ordered step)
       ++locate_turn_;
       if (!e.empty()) { if (err_.empty()) err_ = e; lk.unlock(); cv_.notify_all(); return; }
-      if (next_off_ >= size_ || t + 1 == n_tickets_) {
-        if (next_off_ < size_) { if (err_.empty()) err_ = "truncated BGZF block"; lk.unlock(); cv_.notify_all(); return; }
+      const bool range_over = t + 1 == tickets_.size() || tickets_[t + 1].first;   // the last slab planned for this range
+      if (range_over && next_off_ < size_) { if (err_.empty()) err_ = "truncated BGZF block"; lk.unlock(); cv_.notify_all(); return; }
+      if (tk.range + 1 == ranges_.size() && (next_off_ >= size_ || t + 1 == n_tickets_)) {
         c->last = true;
         n_tickets_ = t + 1;
       }
@@ -285,6 +312,10 @@ class BgzfScanner {
   std::vector<std::thread> th_;
   std::mutex m_;
   std::condition_variable cv_;
+  struct Ticket { size_t base; size_t range; bool first; };
+  std::vector<BamFileRange> ranges_;     // what is read: the region [begin_, size_) as one range, or the plan's ranges
+  std::vector<Ticket> tickets_;          // the slabs of the ranges, in file order
+  bool ranged_ = false;
   size_t n_tickets_ = 0, next_ticket_ = 0, locate_turn_ = 0, next_out_ = 0, recycled_ = 0;
   size_t next_off_ = 0;     // file offset of the next member to locate
   std::map<size_t, std::unique_ptr<CompChunk>> ready_;

@@ -771,7 +771,9 @@ struct CallRun {
         store_alloc = std::thread([this, n_reg] {
           const auto t0 = std::chrono::steady_clock::now();
           for (size_t g = 0; g < n_reg; ++g) {
-            const std::pair<int64_t, int64_t> sz = knobs.store_sizes((int64_t)(bam_cuts[g + 1] - bam_cuts[g]));
+            // (--region with an index: the store holds the ranges' records, and is sized by their bytes)
+            const bool ranged = bam_region_plan().active && bam_region_plan().path == o.bam;
+            const std::pair<int64_t, int64_t> sz = knobs.store_sizes(ranged ? (int64_t)bam_region_plan().bytes() : (int64_t)(bam_cuts[g + 1] - bam_cuts[g]));
             if (svdss_bam_store_create((int32_t)(g % (size_t)n_dev), sz.first, sz.second, &stores[g]) != SVDSS_OK) stores[g] = nullptr;
             if (g > 0 && svdss_bam_store_create((int32_t)(g % (size_t)n_dev), (int64_t)64 << 20, 0, &seam_stores[g]) != SVDSS_OK) seam_stores[g] = nullptr;
           }

@@ -2,12 +2,14 @@
 // config.cpp:26-107: the same option names, defaults and post-processing; cxxopts accepts `--opt value` and
 // `--opt=value`).  In a header of its own so that tests/test_ref_pins.py can hold it against the reference's own
 // config.cpp (oracle/_ref).  Additions of this program: --gpus N|all, --io-threads N, --write-index FILE (smooth),
-// --compress runs|lz (smooth), --nobam (smooth --index --sfs), --smoothed FILE (run).
+// --compress runs|lz (smooth), --nobam (smooth --index --sfs), --smoothed FILE (run), --region REG and --regions-file BED
+// (smooth, search --bam, call, run: csrc/bam_regions.h).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 struct Options {
   std::string index, bam, fastx, reference, sfs, poa, clusters, append;
@@ -21,6 +23,8 @@ struct Options {
   int compress = 0;                                // smooth --compress runs|lz: the GPU deflate's mode (0 runs, 1 lz)
   bool nobam = false;                              // smooth --index --sfs --nobam: the SFS text alone, no BAM on stdout
   std::string smoothed;                            // run --smoothed FILE: also write the smoothed BAM
+  std::vector<std::string> regions;                // --region REG, every occurrence (the one option that adds up)
+  std::string regions_file;                        // --regions-file BED
   bool gpus_all = false;                           // --gpus all (the caller asks the library how many there are)
   bool putative = true, assemble = true, verbose = false, version = false, help = false, clipped = false, binary = false;
 };
@@ -88,7 +92,8 @@ inline bool to_bool(const std::string& v, bool& out) {
 // The rules are those of the reference's parser (cxxopts as vendored beside config.cpp; tests/test_ref_pins.py holds
 // this function against it field by field): `--name value`, `--name=value`, groups of one-letter options (`-h`, `-l 0.5`),
 // flags with an implicit "true" that never take the next argument, a lone "--" ending the options, arguments that do not
-// start with '-' left alone, anything else that starts with '-' an error; numbers are checked, the last occurrence wins.
+// start with '-' left alone, anything else that starts with '-' an error; numbers are checked, the last occurrence wins
+// (but --region: every occurrence counts).
 inline bool parse_options(int argc, char** argv, int first, Options& o, std::string& err) {
   using namespace cli_detail;
   enum Kind { STR, INT, FLT, FLAG };
@@ -99,7 +104,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
       {"min-cluster-weight", INT}, {"accp", FLT}, {"clipped", FLAG}, {"noht", FLAG}, {"noassemble", FLAG},
       {"noputative", FLAG}, {"binary", FLAG}, {"version", FLAG}, {"help", FLAG}, {"h", FLAG}, {"l", FLT}, {"verbose", FLAG},
       {"gpus", STR}, {"io-threads", INT}, {"write-index", STR},
-      {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}};   // (the last six: this program's own)
+      {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}, {"region", STR}, {"regions-file", STR}};   // (the last eight: this program's own)
   auto find = [&](const std::string& name) -> const Spec* {
     for (const Spec& sp : specs)
       if (name == sp.name) return &sp;
@@ -126,6 +131,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
     else if (n == "binary") o.binary = b; else if (n == "version") o.version = b; else if (n == "help" || n == "h") o.help = b;
     else if (n == "verbose") o.verbose = b; else if (n == "io-threads") o.io_threads = x; else if (n == "write-index") o.write_index = v;
     else if (n == "nobam") o.nobam = b; else if (n == "smoothed") o.smoothed = v;
+    else if (n == "region") o.regions.push_back(v); else if (n == "regions-file") o.regions_file = v;
     else if (n == "compress") { if (v == "runs") o.compress = 0; else if (v == "lz") o.compress = 1; else return failed(v); }
     else if (n == "gpus") { if (v == "all") o.gpus_all = true; else if (!to_int(v, o.gpus)) return failed(v); }
     return true;

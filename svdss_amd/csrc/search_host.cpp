@@ -800,6 +800,7 @@ void SearchRun::run_host_path() {
 int SearchRun::finish() {
   if (!knobs.clean_exit) {
     if (bam) bam->report();
+    bam_regions_report();
     logmsg("info", "All done! Runtime: " + std::to_string((long)(time(nullptr) - t_process)) + " seconds");
     fflush(stdout);
     fflush(stderr);

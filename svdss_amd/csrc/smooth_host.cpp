@@ -462,6 +462,7 @@ struct SmoothRun {
   int finish_process() {
     if (hooks && hooks->keep_alive) { hooks->chrom_seqs = std::move(chrom); return 0; }
     if (knobs.clean_exit) return 0;
+    bam_regions_report();
     fprintf(stderr, "[smooth] [info] All done!\n");
     fflush(stdout);
     fflush(stderr);

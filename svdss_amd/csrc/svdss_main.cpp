@@ -12,7 +12,8 @@
 // Logs go to stderr (host_common.h), fatal conditions exit(1).
 // Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth),
 // --compress runs|lz (smooth), --index FMD --sfs FILE [--nobam] (smooth: the search of the smoothed reads in the same pass),
-// the sub-command `run` with its --smoothed FILE.
+// the sub-command `run` with its --smoothed FILE, --region REG / --regions-file BED (smooth, search --bam, call, run:
+// bam_regions.h).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -31,6 +32,8 @@
 #include "cli_options.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "bam_device_select.h"
+#include "bam_region_ranges.h"
 
 static const char* VERSION = "v2.1.1";  // main.cpp:19
 
@@ -46,6 +49,16 @@ static const char* MAIN_USAGE =
     "  smooth  smooth a BAM (reads equal the reference except at long indels): SVDSS smooth --reference ref.fa --bam in.bam > out.bam\n"
     "  run     smooth, search and call in one pass over the BAM: SVDSS run --reference ref.fa --bam reads.bam --index ref.fa.fmd > variations.vcf\n";
 
+// the two options of smooth, search --bam, call and run (bam_regions.h), in one place for the four usage texts
+#define REGION_HELP \
+    "      --region <REG>        only the records that overlap REG: NAME, NAME:BEG-END, NAME:BEG- or NAME:BEG (1-based,\n" \
+    "                            inclusive, commas ignored; NAME:BEG runs to the reference's end).  May be given several\n" \
+    "                            times: the regions add up.  The command then behaves as on a BAM that holds those records alone\n" \
+    "      --regions-file <BED>  the same for every line of a BED file (tab-separated, 0-based half-open); adds to --region.\n" \
+    "                            With <BAM>.bai, <BAM>.csi or <stem>.bai not older than the BAM only the parts of the file\n" \
+    "                            the index names are read, as one stream on one GPU whatever --gpus says; without one the\n" \
+    "                            whole file is read.  Either way the records are tested on the GPU\n"
+
 static const char* SMOOTH_USAGE =
     "Usage: SVDSS smooth --reference <FASTA> --bam <BAM> > smoothed.bam\n"
     "      --min-mapq <int>   minimum mapping quality (default: 20)\n"
@@ -59,7 +72,8 @@ static const char* SMOOTH_USAGE =
     "      --index <FMD> --sfs <FILE>  also search the smoothed reads while they are on the GPU: FILE receives what\n"
     "                            `SVDSS search --index FMD --bam smoothed.bam` writes to stdout, with the same --threads,\n"
     "                            --bsize, --noputative and --noassemble (one GPU, the device path)\n"
-    "      --nobam               with --index --sfs: write FILE only, nothing to stdout\n";
+    "      --nobam               with --index --sfs: write FILE only, nothing to stdout\n"
+    REGION_HELP;
 
 static const char* CALL_USAGE =
     "Usage: SVDSS call --reference <FASTA> --bam <BAM> --sfs <SFS>\n"
@@ -71,7 +85,8 @@ static const char* CALL_USAGE =
     "      --clusters <FILE>           store clusters to this file\n"
     "      -l <float>                  minimum length ratio for sub-clusters and chain merging (default: 0.97)\n"
     "      --noht                      ignore the HP tag\n"
-    "      --clipped                   also call imprecise SVs from soft-clipped alignments (EXPERIMENTAL)\n";
+    "      --clipped                   also call imprecise SVs from soft-clipped alignments (EXPERIMENTAL)\n"
+    REGION_HELP;
 
 static const char* RUN_USAGE =
     "Usage: SVDSS run --reference <FASTA> --bam <BAM> --index <FMD> > variations.vcf\n"
@@ -85,14 +100,16 @@ static const char* RUN_USAGE =
     "      --bsize <int> --noputative --noassemble                              as in search\n"
     "      --min-cluster-weight <int> --min-sv-length <int> -l <float> --noht   as in call\n"
     "      --poa <FILE> --clusters <FILE> --clipped                             as in call\n"
-    "      --verbose             stage timings and the record store's size on stderr\n";
+    "      --verbose             stage timings and the record store's size on stderr\n"
+    REGION_HELP;
 
 static const char* SEARCH_USAGE =
     "Usage: SVDSS search --index <FMD> --bam <BAM> | --fastx <FASTA/FASTQ>\n"
     "      --threads <int>   kept for output-order compatibility (default: 4)\n"
     "      --bsize <int>     batch size (default: 10000)\n"
     "      --noputative      search all reads, not only XF == 0\n"
-    "      --noassemble      do not merge overlapping specific strings\n";
+    "      --noassemble      do not merge overlapping specific strings\n"
+    REGION_HELP;
 
 static Options parse(int argc, char** argv) {
   Options o;
@@ -104,6 +121,34 @@ static Options parse(int argc, char** argv) {
 
 // ---------------------------------------------------------------- index
 
+// --region / --regions-file against the BAM header, before anything is opened for writing: the command's regions in
+// force for every reader of the process (bam_regions.h), or a message that names the offending text
+static void regions_in_force(const Options& o, const char* cmd) {
+  if (o.regions.empty() && o.regions_file.empty()) return;
+  if (o.bam.empty() && o.fastx.empty()) return;   // (the command's usage text follows)
+  if (o.bam.empty() || !o.fastx.empty())
+    die(std::string("--region / --regions-file select records of a BAM by position: not an option of `SVDSS ") + cmd + (o.fastx.empty() ? "`" : " --fastx`"));
+  int32_t n_ref = 0;
+  int64_t skip = 0;
+  std::string err;
+  std::vector<std::string> names;
+  if (!bam_header_probe(o.bam, n_ref, skip, err, &names)) die("cannot read " + o.bam + ": " + err);
+  static BamRegionSet U;
+  if (!resolve_regions(o.regions, o.regions_file, names, U, err)) die(err);
+  bam_regions_in_force() = &U;
+  // the bytes to read: what a BAI / CSI beside the BAM names for U (SVDSS_REGION_INDEX=0: the whole file, as without one)
+  std::string index_path, stale;
+  const bool want_index = !(getenv("SVDSS_REGION_INDEX") && atoi(getenv("SVDSS_REGION_INDEX")) == 0);
+  if (want_index && find_bam_index(o.bam, index_path, stale)) {
+    BaiIndex index;
+    BamRegionPlan& plan = bam_region_plan();
+    if (!index.load(index_path)) logmsg("warning", "cannot read the index " + index_path + ": the whole file is read");
+    else if (!region_file_ranges(o.bam, index, U, plan.ranges, err)) logmsg("warning", err + ": the index is not used, the whole file is read");
+    else { plan.active = true; plan.path = o.bam; plan.index_path = index_path; }
+  }
+  if (!stale.empty() && !bam_region_plan().active) logmsg("warning", "the index " + stale + " is older than " + o.bam + ": it is not used, the whole file is read");
+  bam_region_counters().verbose = o.verbose;
+}
 static int main_index(int argc, char** argv) {
   // ropebwt3 `build` flags as run_svdss:142 passes them: -t T -d <fasta> -o <out>
   std::string fasta, out;
@@ -218,6 +263,9 @@ int main(int argc, char** argv) {
     return EXIT_FAILURE;
   }
   if (!strcmp(argv[1], "index")) {
+    for (int i = 2; i < argc; ++i)
+      if (!strncmp(argv[i], "--region", 8) && (argv[i][8] == 0 || argv[i][8] == '=' || !strncmp(argv[i] + 8, "s-file", 6)))
+        die(std::string(argv[i]) + ": --region / --regions-file select records of a BAM by position: not an option of `SVDSS index`");
     logmsg("info", "FM-index construction (stands for 'ropebwt3 build')");
     const int rc = main_index(argc, argv);
     if (rc) return rc;
@@ -235,6 +283,7 @@ int main(int argc, char** argv) {
       die(std::string("--write-index is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
     if (!o.smoothed.empty() && strcmp(argv[1], "run") != 0)
       die(std::string("--smoothed is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
+    if (!strcmp(argv[1], "search") || !strcmp(argv[1], "call") || !strcmp(argv[1], "smooth") || !strcmp(argv[1], "run")) regions_in_force(o, argv[1]);
     if (!strcmp(argv[1], "search")) {
       if (o.index.empty() || (o.fastx.empty() && o.bam.empty())) { fputs(SEARCH_USAGE, stderr); return EXIT_FAILURE; }
       main_search(o, t0);
@@ -274,6 +323,7 @@ int main(int argc, char** argv) {
       fputs(MAIN_USAGE, stderr);
       return EXIT_FAILURE;
     }
+    bam_regions_report();
   }
   logmsg("info", "All done! Runtime: " + std::to_string((long)(time(nullptr) - t0)) + " seconds");
   return 0;
