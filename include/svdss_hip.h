@@ -680,6 +680,15 @@ int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, const uint8_
  * in LDS, 2 anti-diagonals in HBM, -1 none yet */
 int32_t svdss_indel_ratio_last_kernel(void);
 
+/* ---- the streams of the call side ------------------------------------------
+ * svdss_poa_consensus_batch, svdss_align_global_batch and svdss_indel_ratio_batch (the seam: Caller::run_poa, the ksw2
+ * realignment and the chain filter of caller.cpp, a14 / a15 / a17 above) each run on ONE stream, leased for the call
+ * from a process-wide pool (csrc/call_streams.h).  What the pool did so far:
+ * out[0] streams of `device` (leased or idle), out[1] streams created since load (all devices), out[2] first-stage POA
+ * launches that held both whole-wavefront variants (SVDSS_POA_MERGE=0: none), out[3] leases borrowed for launches that
+ * ran side by side.  SVDSS_EINVAL for a null `out` or a device that is negative or beyond the pool's 64. */
+int svdss_call_side_stat(int32_t device, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,7 @@ SIGNATURES = {
     "svdss_poa_batch_free": (None, [_p]),
     "svdss_indel_ratio_batch": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p]),
     "svdss_indel_ratio_last_kernel": (_i32, []),
+    "svdss_call_side_stat": (C.c_int, [_i32, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "call_streams.h"
 #include "dev_arena.h"
 #include "hip_check.h"
 
@@ -396,10 +397,6 @@ struct svdss_aln_batch {
   // device state kept between calls
   int device = -1;
   DevArena arena;
-  hipStream_t stream = nullptr;   // the batch object's own non-blocking stream: calls on different objects overlap
-  ~svdss_aln_batch() {
-    if (stream) { if (device >= 0) (void)hipSetDevice(device); (void)hipStreamDestroy(stream); }
-  }
 };
 
 namespace {
@@ -441,11 +438,12 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
   const int64_t qtot = q_off[n_pairs] - q_off[0], ttot = t_off[n_pairs] - t_off[0];
   if (b->device != device) {
     b->arena.drop();
-    if (b->stream) { (void)hipStreamDestroy(b->stream); b->stream = nullptr; }
     b->device = device;
   }
-  if (!b->stream) HIPCHK(svdss_make_stream(&b->stream, "SVDSS_CALL_CUS"));
-  const hipStream_t st = b->stream;
+  // the call's one stream, from the call side's pool (call_streams.h): calls of different threads overlap
+  CallStreamLease lease;
+  HIPCHK(lease.acquire(device));
+  const hipStream_t st = lease.get();
   const GapModel gm{gapo, gape, gapo2, gape2};
   hipEvent_t ev0, ev1;
   HIPCHK(hipEventCreate(&ev0));
@@ -639,22 +637,20 @@ extern "C" int svdss_indel_ratio_batch(const uint8_t* a, const int64_t* a_off, c
     if (lb > lb_max) lb_max = lb;
   }
   const int64_t atot = a_off[n_pairs] - a_off[0], btot = b_off[n_pairs] - b_off[0];
-  // workspace and stream of the calling thread, kept between calls (no hipMalloc / hipFree -- a device-wide
-  // synchronisation each -- and nothing on the default stream)
+  // workspace of the calling thread, kept between calls (no hipMalloc / hipFree -- a device-wide synchronisation
+  // each); the stream is the call's one lease of the call side's pool (call_streams.h): nothing on the default stream
   struct RatioState {
     int device = -1;
     DevArena arena;
-    hipStream_t stream = nullptr;
-    ~RatioState() { if (stream) { if (device >= 0) (void)hipSetDevice(device); (void)hipStreamDestroy(stream); } }
   };
   static thread_local RatioState R;
   if (R.device != device) {
     R.arena.drop();
-    if (R.stream) { (void)hipStreamDestroy(R.stream); R.stream = nullptr; }
     R.device = device;
   }
-  if (!R.stream) HIPCHK(svdss_make_stream(&R.stream, "SVDSS_CALL_CUS"));
-  const hipStream_t st = R.stream;
+  CallStreamLease lease;
+  HIPCHK(lease.acquire(device));
+  const hipStream_t st = lease.get();
   HIPCHK(R.arena.reserve(DevArena::padded((size_t)atot) + DevArena::padded((size_t)btot) +
                           DevArena::padded(sizeof(LcsPair) * (size_t)n_pairs) + DevArena::padded(sizeof(int32_t) * (size_t)ws) +
                           DevArena::padded(sizeof(int64_t) * (size_t)n_pairs) + DevArena::padded(sizeof(double) * (size_t)n_pairs) +

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "call_streams.h"
 #include "dev_arena.h"
 #include "hip_check.h"
 #include "poa_plan.h"
@@ -384,18 +385,18 @@ struct svdss_poa_batch {
   // device state kept between calls
   int device = -1;
   DevArena in_arena, ws_arena;
-  std::vector<hipStream_t> streams;
-  ~svdss_poa_batch() {
-    if (device >= 0) (void)hipSetDevice(device);
-    for (hipStream_t st : streams) (void)hipStreamDestroy(st);
-  }
 };
 
 static_assert(poa_padded(0) == DevArena::padded(0) && poa_padded(1001) == DevArena::padded(1001), "poa_plan.h sizes what ws_arena hands out");
 
 namespace {
-struct EventPair {   // around the HBM kernel
+struct EventPair {   // around the HBM kernel (created by fallback(), the only user)
   hipEvent_t a = nullptr, b = nullptr;
+  int create() {
+    if (!a) HIPCHK(hipEventCreate(&a));
+    if (!b) HIPCHK(hipEventCreate(&b));
+    return SVDSS_OK;
+  }
   ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
 
@@ -406,6 +407,7 @@ struct PoaBatchRun {
   const uint8_t* seqs;
   PoaBatchIn in;                                        // the lengths, the knobs (read here, once), CUs and workspace budget
   void *d_seqs = nullptr, *d_off = nullptr, *d_cells = nullptr;
+  CallStreamLease lease;                                // the call's one stream, s0: every copy, launch and wait goes to it
   hipStream_t s0 = nullptr;
   EventPair ev;
   std::vector<std::vector<uint8_t>> results;            // the consensus of every sub-cluster that is done
@@ -430,29 +432,21 @@ struct PoaBatchRun {
     }
     if (total_syms > 0 && !seqs) return SVDSS_EINVAL;
     if (b.device != device) {   // (a batch object is normally used with one device)
-      for (hipStream_t st : b.streams) (void)hipStreamDestroy(st);
-      b.streams.clear();
       b.in_arena.drop(); b.ws_arena.drop();
       b.device = device;
     }
     const size_t off_bytes = sizeof(int64_t) * (size_t)(n_seqs_total + 1);
     HIPCHK(b.in_arena.reserve(DevArena::padded((size_t)total_syms) + DevArena::padded(off_bytes) + DevArena::padded(8)));
     d_seqs = b.in_arena.take((size_t)total_syms); d_off = b.in_arena.take(off_bytes); d_cells = b.in_arena.take(8);
-    // every copy and launch of this call goes to the batch object's own non-blocking streams and every wait is a
-    // wait for those streams: calls on different batch objects (threads) and a search running beside them overlap
-    // (few streams: the runtime multiplexes streams onto a handful of hardware queues, and streams that share one run
-    // in order)
-    while (b.streams.size() < 6) {   // (the launches of a round run side by side: one stream each while they last)
-      hipStream_t st;
-      HIPCHK(svdss_make_stream(&st, "SVDSS_CALL_CUS"));
-      b.streams.push_back(st);
-    }
-    s0 = b.streams[0];
+    // every copy and launch of this call goes to ONE non-blocking stream of the call side's pool (call_streams.h) and
+    // every wait is a wait for that stream: calls of different threads and a search running beside them overlap, and
+    // the process has as few streams as that takes (the runtime multiplexes streams onto a handful of hardware queues,
+    // and streams that share one run in order)
+    HIPCHK(lease.acquire(device));
+    s0 = lease.get();
     if (total_syms) HIPCHK(hipMemcpyAsync(d_seqs, seqs, (size_t)total_syms, hipMemcpyHostToDevice, s0));
     HIPCHK(hipMemcpyAsync(d_off, in.seq_off, off_bytes, hipMemcpyHostToDevice, s0));
     HIPCHK(hipMemsetAsync(d_cells, 0, 8, s0));
-    HIPCHK(hipEventCreate(&ev.a));
-    HIPCHK(hipEventCreate(&ev.b));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) in.n_cus = prop.multiProcessorCount;
     size_t free_b = 0, total_b = 0;
@@ -492,8 +486,11 @@ struct PoaBatchRun {
     return SVDSS_OK;
   }
 
-  // one wave of launches, groups [g0, g1) of the plan: the launches run concurrently on their own streams (one sub-cluster is
-  // a chain of dependent steps: the machine is filled by running many of them, whichever launch they came from)
+  // one wave of launches, groups [g0, g1) of the plan.  The first stage's two whole-wavefront variants are ONE launch
+  // (poa_merge_wave), and a wave of one launch -- every wave of a batch that finishes in the first stage -- is queued behind
+  // its task upload on the call's stream with no host wait in between.  A wave that still has several launches runs them
+  // side by side (one sub-cluster is a chain of dependent steps: the machine is filled by running many of them, whichever
+  // launch they came from) on streams borrowed from the pool for as long as the wave lasts.
   int run_wave(int round, const PoaRoundPlan& p, size_t g0, size_t g1, std::vector<int64_t>& next) {
     const bool quad = round < 0;
     size_t tot_bytes = 0;
@@ -502,23 +499,47 @@ struct PoaBatchRun {
     HIPCHK(b.ws_arena.reserve(tot_bytes));
     const double as = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
     if (in.knobs.debug && as > 0.005) fprintf(stderr, "[poa] workspace of %.1f GB taken in %.3f s\n", (double)tot_bytes / 1073741824.0, as);
-    std::vector<Mem> mem;
-    for (size_t gi = g0; gi < g1; ++gi) {
-      const PoaGroup& g = p.groups[gi];
-      const size_t nt = g.tasks.size();
-      mem.push_back(take(sizeof(PoaWaveTask), nt, g.w32, 0, g.w8));
-      HIPCHK(hipMemcpyAsync(mem.back().tasks, g.tasks.data(), sizeof(PoaWaveTask) * nt, hipMemcpyHostToDevice, s0));
-      HIPCHK(hipMemsetAsync(mem.back().st, 0xff, sizeof(int32_t) * nt, s0));
+    const std::vector<PoaLaunch> launches = poa_merge_wave(in.knobs, p.groups, g0, g1);
+    struct Unit { const PoaGroup* g; PoaGroup merged; size_t n2 = 0; int max_len2 = 0, max_len1 = 0; bool pair = false; Mem m; };
+    std::vector<Unit> units(launches.size());
+    for (size_t k = 0; k < launches.size(); ++k) {
+      const PoaLaunch& L = launches[k];
+      Unit& u = units[k];
+      if (L.single >= 0) u.g = &p.groups[(size_t)L.single];
+      else {
+        const PoaGroup *c2 = L.c2 >= 0 ? &p.groups[(size_t)L.c2] : nullptr, *c1 = L.c1 >= 0 ? &p.groups[(size_t)L.c1] : nullptr;
+        u.pair = true;
+        u.merged = poa_merged_group(c2, c1, u.n2);
+        u.max_len2 = c2 ? c2->max_len : 0;
+        u.max_len1 = c1 ? c1->max_len : 0;
+      }
     }
-    HIPCHK(hipStreamSynchronize(s0));
+    for (Unit& u : units) {   // (units no longer moves: the merged groups stay where they are)
+      if (u.pair) u.g = &u.merged;
+      const size_t nt = u.g->tasks.size();
+      u.m = take(sizeof(PoaWaveTask), nt, u.g->w32, 0, u.g->w8);
+      HIPCHK(hipMemcpyAsync(u.m.tasks, u.g->tasks.data(), sizeof(PoaWaveTask) * nt, hipMemcpyHostToDevice, s0));
+      HIPCHK(hipMemsetAsync(u.m.st, 0xff, sizeof(int32_t) * nt, s0));
+    }
+    // side by side: up to five further streams, as many as there are further launches
+    std::vector<CallStreamLease> side(units.empty() ? 0 : std::min<size_t>(units.size() - 1, 5));
+    for (CallStreamLease& l : side) HIPCHK(l.acquire(b.device, true));
+    if (!side.empty()) HIPCHK(hipStreamSynchronize(s0));   // (the other streams must not start before the uploads are there)
     const auto t0 = std::chrono::steady_clock::now();
-    for (size_t gi = g0; gi < g1; ++gi) {
-      const PoaGroup& g = p.groups[gi];
-      const Mem& m = mem[gi - g0];
-      const hipStream_t gs = b.streams[(gi - g0) % b.streams.size()];
+    for (size_t k = 0; k < units.size(); ++k) {
+      const Unit& u = units[k];
+      const PoaGroup& g = *u.g;
+      const Mem& m = u.m;
+      const size_t si = k % (side.size() + 1);
+      const hipStream_t gs = si ? side[si - 1].get() : s0;
       const PoaWaveTask* d_tasks = (const PoaWaveTask*)m.tasks;
       const int nt = (int)g.tasks.size();
-      if (g.gw) {
+      if (u.pair) {
+        HIPCHK(poa_quad_pair_launch(d_tasks, (int)u.n2, nt - (int)u.n2, u.max_len2, u.max_len1, (const uint8_t*)d_seqs, (const int64_t*)d_off,
+                                     (int32_t*)m.w32, (int32_t*)m.len, (int32_t*)m.st, (unsigned long long*)d_cells, gs));
+        HIPCHK(poa_bundle_launch(d_tasks, nt, g.bundle_lds, (int32_t*)m.w32, (uint8_t*)m.w8, (int32_t*)m.len, (const int32_t*)m.st, gs));
+        if (u.n2 && (size_t)nt > u.n2) { std::lock_guard<std::mutex> lock(call_stream_pool().mu); ++call_stream_pool().merged; }
+      } else if (g.gw) {
         HIPCHK(poa_quad_launch(g.gw, g.cols, d_tasks, nt, g.max_len, (const uint8_t*)d_seqs, (const int64_t*)d_off, (int32_t*)m.w32,
                                 (int32_t*)m.len, (int32_t*)m.st, (unsigned long long*)d_cells, gs));
         HIPCHK(poa_bundle_launch(d_tasks, nt, g.bundle_lds, (int32_t*)m.w32, (uint8_t*)m.w8, (int32_t*)m.len, (const int32_t*)m.st, gs));
@@ -526,20 +547,21 @@ struct PoaBatchRun {
         HIPCHK(poa_wave_launch(g.cols, d_tasks, nt, g.lds, g.bundle_lds, (const uint8_t*)d_seqs, (const int64_t*)d_off, (int32_t*)m.w32,
                                 (uint8_t*)m.w8, (int32_t*)m.len, (int32_t*)m.st, (unsigned long long*)d_cells, gs));
     }
-    for (size_t k = 0; k < std::min(g1 - g0, b.streams.size()); ++k) HIPCHK(hipStreamSynchronize(b.streams[k]));
+    for (CallStreamLease& l : side) HIPCHK(hipStreamSynchronize(l.get()));
+    HIPCHK(hipStreamSynchronize(s0));   // (for kernel_ms: collect's copies would wait for the kernels all the same)
+    side.clear();                       // the borrowed streams are back before collect
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    b.kernel_ms += ms;   // wall time of the concurrent launches
+    b.kernel_ms += ms;   // wall time of the launches
     int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t n_run = 0;
-    for (size_t gi = g0; gi < g1; ++gi) {
-      const PoaGroup& g = p.groups[gi];
-      n_run += (int64_t)g.tasks.size();
-      if (const int rc = collect(round, g.tasks, g.ids, mem[gi - g0], g.w8, next, why)) return rc;
+    for (const Unit& u : units) {
+      n_run += (int64_t)u.g->tasks.size();
+      if (const int rc = collect(round, u.g->tasks, u.g->ids, u.m, u.g->w8, next, why)) return rc;
     }
     if (in.knobs.debug) {
       if (quad) poa_quad_debug_report(); else poa_wave_debug_report();
       fprintf(stderr, "[poa] %s round %d: %lld clusters in %zu launches, %.3f ms, not done: first-read %d preds %d width %d band %d capacity %d other %d\n",
-              quad ? "quad" : "wave", round, (long long)n_run, g1 - g0, ms, why[1], why[2], why[3], why[4], why[5], why[0] + why[6] + why[7]);
+              quad ? "quad" : "wave", round, (long long)n_run, units.size(), ms, why[1], why[2], why[3], why[4], why[5], why[0] + why[6] + why[7]);
     }
     return SVDSS_OK;
   }
@@ -590,6 +612,7 @@ struct PoaBatchRun {
         const Mem m = take(sizeof(PoaTask), nt, L.w32, L.w64, L.w8);
         HIPCHK(hipMemcpyAsync(m.tasks, L.tasks.data(), sizeof(PoaTask) * nt, hipMemcpyHostToDevice, s0));
         HIPCHK(hipMemsetAsync(m.st, 0xff, sizeof(int32_t) * nt, s0));
+        if (const int rc = ev.create()) return rc;
         HIPCHK(hipEventRecord(ev.a, s0));
         hipLaunchKernelGGL(poa_consensus_kernel, dim3((unsigned)nt), dim3(64), 0, s0, (const PoaTask*)m.tasks, (const uint8_t*)d_seqs,
                            (const int64_t*)d_off, (int32_t*)m.w32, (int64_t*)m.w64, (uint8_t*)m.w8, (int32_t*)m.len, (int32_t*)m.st,
@@ -658,3 +681,14 @@ extern "C" int svdss_poa_batch_fetch(const svdss_poa_batch_t* b, int64_t* cons_l
   return SVDSS_OK;
 }
 extern "C" void svdss_poa_batch_free(svdss_poa_batch_t* b) { delete b; }
+
+extern "C" int svdss_call_side_stat(int32_t device, int64_t out[4]) {
+  if (!out || device < 0 || device >= kCallStreamDevices) return SVDSS_EINVAL;
+  CallStreamPool& p = call_stream_pool();
+  std::lock_guard<std::mutex> lock(p.mu);
+  out[0] = p.live[device];
+  out[1] = p.created;
+  out[2] = p.merged;
+  out[3] = p.borrowed;
+  return SVDSS_OK;
+}

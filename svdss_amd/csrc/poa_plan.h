@@ -40,6 +40,7 @@ struct PoaKnobs {
   bool noprio = false;           // SVDSS_POA_NOPRIO: no issue priority for the long chains
   bool no_mix = false;           // SVDSS_POA_NO_MIX: waves of launches are consecutive pieces of the sorted list
   int64_t ws_gb = 32;            // SVDSS_POA_WS_GB: workspace per wave of launches
+  bool merge = true;             // SVDSS_POA_MERGE does not parse to 0 (0: every group of the first stage is a launch of its own, as before the merge)
   bool debug = false;            // SVDSS_DEBUG
 
   static PoaKnobs from_env() {
@@ -57,6 +58,7 @@ struct PoaKnobs {
     k.noprio = getenv("SVDSS_POA_NOPRIO") != nullptr;
     k.no_mix = getenv("SVDSS_POA_NO_MIX") != nullptr;
     k.ws_gb = ll("SVDSS_POA_WS_GB", 0) > 0 ? ll("SVDSS_POA_WS_GB", 0) : 32;
+    k.merge = !(getenv("SVDSS_POA_MERGE") && atoi(getenv("SVDSS_POA_MERGE")) == 0);
     k.debug = getenv("SVDSS_DEBUG") != nullptr;
     return k;
   }
@@ -365,6 +367,71 @@ inline PoaRoundPlan poa_plan_round(const PoaBatchIn& in, int round, const std::v
   }
   p.cuts.push_back(p.groups.size());
   return p;
+}
+
+// ------------------------------------------------------------------------------------------ the launches of a wave
+// The plan stays one group per variant; what is merged is merged at launch time.  The two variants that give a long
+// sub-cluster the wavefront to itself, (64, 2) and (64, 1), are one kernel with two bodies (poa_quad_pair_kernel): a launch
+// costs a place in the stream's hardware queue, where it may wait behind another stream's kernel, and the second launch of a
+// pair waited behind the first one's bundle kernel or beside it on another stream for nothing -- both fill the same CUs.
+// c2 / c1: the wave's group of (64, 2) / (64, 1) sub-clusters, -1: none (a merged launch may have an empty half);
+// single: any other group, a launch of its own.
+struct PoaLaunch { int c2 = -1, c1 = -1, single = -1; };
+
+inline bool poa_group_pairs(const PoaGroup& g) { return g.gw == 64 && (g.cols == 1 || g.cols == 2); }
+
+// The launches of groups [g0, g1) of a plan, in the order of the groups (a merged launch where its first group stands).
+// The k-th (64, 2) group of a wave pairs with the k-th (64, 1) group of the same wave.
+inline std::vector<PoaLaunch> poa_merge_wave(const PoaKnobs& k, const std::vector<PoaGroup>& groups, size_t g0, size_t g1) {
+  std::vector<PoaLaunch> out;
+  std::vector<uint8_t> used(g1 > g0 ? g1 - g0 : 0, 0);
+  for (size_t gi = g0; gi < g1; ++gi) {
+    if (used[gi - g0]) continue;
+    const PoaGroup& g = groups[gi];
+    PoaLaunch L;
+    if (!k.merge || !poa_group_pairs(g)) { L.single = (int)gi; out.push_back(L); continue; }
+    (g.cols == 2 ? L.c2 : L.c1) = (int)gi;
+    for (size_t gj = gi + 1; gj < g1; ++gj) {   // the first unused group of the other variant in the same wave
+      const PoaGroup& h = groups[gj];
+      if (used[gj - g0] || !poa_group_pairs(h) || h.cols == g.cols || h.wave != g.wave) continue;
+      (h.cols == 2 ? L.c2 : L.c1) = (int)gj;
+      used[gj - g0] = 1;
+      break;
+    }
+    out.push_back(L);
+  }
+  return out;
+}
+
+// The tasks of a merged launch as ONE group: the C = 2 tasks first (blocks are dispatched in index order, and the long
+// chains, which decide when the launch ends, are the C = 2 ones), then the C = 1 tasks with their workspace offsets moved
+// behind the C = 2 group's.  n2: how many tasks are the first half's.  The int32 workspace of the two stays below 2^32
+// ints (kPoaGroupBudget32 each), which the 32-bit offsets of the first stage need.
+inline PoaGroup poa_merged_group(const PoaGroup* c2, const PoaGroup* c1, size_t& n2) {
+  PoaGroup m;
+  m.gw = 64; m.cols = 0;
+  n2 = 0;
+  if (c2) {
+    m = *c2;
+    m.cols = 0;
+    n2 = c2->tasks.size();
+  }
+  if (c1) {
+    if (!c2) m.wave = c1->wave;
+    m.max_len = std::max(m.max_len, c1->max_len);
+    m.lds = std::max(m.lds, c1->lds);
+    m.bundle_lds = std::max(m.bundle_lds, c1->bundle_lds);
+    for (size_t i = 0; i < c1->tasks.size(); ++i) {
+      PoaWaveTask t = c1->tasks[i];
+      t.ws_off += m.w32;
+      t.cons_off += m.w8;
+      m.tasks.push_back(t);
+      m.ids.push_back(c1->ids[i]);
+    }
+    m.w32 += c1->w32;
+    m.w8 += c1->w8;
+  }
+  return m;
 }
 
 // -------------------------------------------------------------------------------------------------- the HBM fallback

@@ -3,6 +3,7 @@
 // goes to poa_wave.hip's rounds.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -33,6 +34,33 @@ static hipError_t launch_gc(const PoaWaveTask* d_tasks, int n_tasks, int max_len
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((poa_quad_kernel<GW, C>), dim3((unsigned)((n_tasks + G - 1) / G)), dim3(64), lds, stream, d_tasks, n_tasks, d_seqs,
                      d_seq_off, ws32, d_len, d_status, d_cells, pq::Geom<GW, C>::qcap(max_len));
+  return hipGetLastError();
+}
+
+// The two variants that give a sub-cluster the wavefront to itself as ONE launch: tasks [0, n2) are C = 2 sub-clusters,
+// tasks [n2, n2 + n1) C = 1 ones; a block runs the body of its task's variant (uniform per block).  Lengths and statuses
+// are indexed like the tasks; the tasks' workspace offsets are into the one ws32.  Either half may be empty.
+__global__ void __launch_bounds__(64, PQ_MIN_WAVES) poa_quad_pair_kernel(const PoaWaveTask* tasks, int n2, int n1, const uint8_t* seqs,
+                                                                         const int64_t* seq_off, int32_t* ws32, int32_t* cons_len, int32_t* status,
+                                                                         unsigned long long* cells, int qcap2, int qcap1) {
+  extern __shared__ __align__(16) int32_t poaq_lds[];
+  const int block = (int)blockIdx.x;
+  if (block < n2) pq::poaq_run<64, 2>(tasks, n2, seqs, seq_off, ws32, cons_len, status, cells, poaq_lds, block, qcap2);
+  else pq::poaq_run<64, 1>(tasks + n2, n1, seqs, seq_off, ws32, cons_len + n2, status + n2, cells, poaq_lds, block - n2, qcap1);
+}
+
+hipError_t poa_quad_pair_launch(const PoaWaveTask* d_tasks, int n2, int n1, int max_len2, int max_len1, const uint8_t* d_seqs,
+                                const int64_t* d_seq_off, int32_t* ws32, int32_t* d_len, int32_t* d_status, unsigned long long* d_cells,
+                                hipStream_t stream) {
+  if (n2 < 0 || n1 < 0 || n2 + n1 <= 0) return hipErrorInvalidValue;
+  size_t lds = 0;
+  if (n2) lds = std::max(lds, pq::Geom<64, 2>::lds_bytes(max_len2));
+  if (n1) lds = std::max(lds, pq::Geom<64, 1>::lds_bytes(max_len1));
+  if (lds > 160 * 1024 - 512) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute((const void*)poa_quad_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(poa_quad_pair_kernel, dim3((unsigned)(n2 + n1)), dim3(64), lds, stream, d_tasks, n2, n1, d_seqs, d_seq_off, ws32, d_len,
+                     d_status, d_cells, pq::Geom<64, 2>::qcap(max_len2), pq::Geom<64, 1>::qcap(max_len1));
   return hipGetLastError();
 }
 
