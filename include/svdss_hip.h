@@ -125,6 +125,9 @@ int svdss_index_verify_device(const svdss_index_t* ix, int64_t stride, int64_t o
 
 /* GPUs this process sees (0: none). */
 int svdss_device_count(void);
+/* Free and total memory of `device` as the runtime reports them now (hipMemGetInfo): what `SVDSS run --samples` prints at
+ * the start of every sample with --verbose, and what it decides on whether the index stays resident through the call stage. */
+int svdss_device_memory(int32_t device, int64_t* free_bytes, int64_t* total_bytes);
 /* A stream of the kind the library makes for its own searches, for callers that pass their stream to
  * svdss_sfs_search_batch_device (bench.py): non-blocking, and restricted to the compute units SVDSS_SEARCH_CUS names
  * ("first,count": bits of hipExtStreamCreateWithCUMask's mask; csrc/hip_check.h) when that is set.  The call-side

@@ -120,6 +120,7 @@ inline void bam_regions_report() {
   bam_region_counters().verbose = false;   // (once)
   int64_t on_device = 0;
   (void)svdss_bam_gated_total(&on_device);
+  on_device -= bam_region_counters().device_base;
   const BamRegionPlan& plan = bam_region_plan();
   // (the host readers -- SVDSS_BAM_DEVICE=0, SVDSS_SMOOTH_HOST=1, pass 1 of a `call` without the device path -- take no
   // ranges: they read the whole file, and the bytes figure counts the device path's alone)

@@ -162,7 +162,8 @@ inline const BamRegionSet*& bam_regions_in_force() { static const BamRegionSet* 
 // what the host readers counted for --verbose (bam_regions_report, bam_device_select.h): records gated out by BamReader /
 // bam_scan_chunks (the device path counts its own: svdss_bam_gated_total), compressed bytes the device path read
 // host_readers: BamReader objects that read the file with the regions in force (they read the whole file: no ranges)
-struct BamRegionCounters { std::atomic<int64_t> gated{0}, comp_bytes{0}, host_readers{0}; bool verbose = false; };
+// device_base: what the device path had counted when the regions came into force (`run --samples`: one report per sample)
+struct BamRegionCounters { std::atomic<int64_t> gated{0}, comp_bytes{0}, host_readers{0}; bool verbose = false; int64_t device_base = 0; };
 inline BamRegionCounters& bam_region_counters() { static BamRegionCounters c; return c; }
 
 // The byte ranges of the BAM that a BAI / CSI names for the regions in force (bam_region_ranges.h computes them, main puts

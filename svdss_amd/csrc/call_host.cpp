@@ -719,6 +719,9 @@ struct CallRun {
   // search stages of the same process left (null: `SVDSS call`)
   CallPreset* const preset;
   bool from_store() const { return preset && preset->store; }
+  // `SVDSS run --samples`: the process goes on to the next sample -- chromosomes and their copy in HBM go back to the hooks,
+  // the record stores are freed
+  SmoothHooks* session() const { return preset && preset->from_smooth && preset->from_smooth->session ? preset->from_smooth : nullptr; }
 
   explicit CallRun(const CallOptions& opt, CallPreset* p = nullptr) : o(opt), T(std::max(1, opt.threads)), preset(p) { C.o = opt; }
 
@@ -892,16 +895,18 @@ struct CallRun {
       // was read (0.7 s of a 1.2 s pass at GRCh38 lengths).
       svdss_ref_t* dref = nullptr;
       std::vector<int32_t> tid_map(ref_names.size(), -1);
+      svdss_ref_t* session_dref = nullptr;   // (`run --samples`: the smoothing stage's upload, handed back below)
       const bool place_on_gpu = !knobs.place_host && !o.clipped;
       bool ref_set_up = false;
-      auto set_up_reference = [this, &dref, &tid_map, &ref_set_up, place_on_gpu]() {
+      auto set_up_reference = [this, &dref, &tid_map, &ref_set_up, &session_dref, place_on_gpu]() {
         if (ref_set_up) return;
         ref_set_up = true;
         reference_ready();
         SmoothHooks* const sm = preset ? preset->from_smooth : nullptr;
         if (sm && sm->dref) {   // (the smoothing stage's upload: the same chromosomes in the same order)
           if (place_on_gpu) { dref = sm->dref; tid_map = sm->tid_map; }
-          else svdss_ref_free(sm->dref);
+          if (sm->session) session_dref = sm->dref;
+          else if (!place_on_gpu) svdss_ref_free(sm->dref);
           sm->dref = nullptr;
         } else if (place_on_gpu) check(upload_chromosomes(ref_names, C.chrom_seqs, 0, tid_map, &dref), "svdss_ref_upload_parts");
       };
@@ -938,7 +943,7 @@ struct CallRun {
         // the same order per slice
         worker = std::thread([this, &per_thread, &per_thread_clips, &batch, &dref, &tid_map, &set_up_reference]() {
           set_up_reference();
-          if (dref) {
+          if (dref && !batch.empty()) {   // (the batch behind the last record may be empty: nothing to place, nothing to hand the kernel)
             // placement on the GPU (csrc/place.hip: one lane per alignment); the results go to the T per-thread lists in
             // the order the reference's slices would have produced them (record n belongs to slice n % T)
             std::vector<int32_t> tid, pos, sq, sl, cnt;
@@ -1021,7 +1026,8 @@ struct CallRun {
           logmsg("debug", buf);
         }
       }
-      svdss_ref_free(dref);
+      if (session_dref) session()->dref = session_dref;
+      else svdss_ref_free(dref);
       for (int t = 0; t < T; ++t) extended.insert(extended.end(), per_thread[(size_t)t].begin(), per_thread[(size_t)t].end());
       for (int t = T; t-- > 0;)   // each thread's list goes in front of the others' (clusterer.cpp:24)
         clips.insert(clips.end(), per_thread_clips[(size_t)t].begin(), per_thread_clips[(size_t)t].end());
@@ -1580,7 +1586,7 @@ struct CallRun {
     logmsg("info", "Writing " + std::to_string(svs.size()) + " SVs.");
     stage("vcf");
     if (cache_release.joinable()) cache_release.join();
-    if (knobs.clean_exit) {   // (otherwise the process ends with _exit)
+    if (knobs.clean_exit || session()) {   // (otherwise the process ends with _exit)
       for (svdss_bam_store_t* st : stores) svdss_bam_store_free(st);
       for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
       stores.clear(); seam_stores.clear();
@@ -1621,6 +1627,10 @@ struct CallRun {
     realign_and_extract();
     dedup_and_filter();
     write_outputs();
+    if (SmoothHooks* sm = session()) {
+      sm->chrom_names = std::move(C.chrom_names);
+      sm->chrom_seqs = std::move(C.chrom_seqs);
+    }
     return 0;
   }
 };

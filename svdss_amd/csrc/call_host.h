@@ -35,6 +35,7 @@ struct CallOptions {
 // `SVDSS run` (run_host.cpp) drives the two units below; what passes between them:
 struct svdss_bam_store;
 struct svdss_ref;
+struct svdss_index;
 // ... into main_smooth's device path: the store every batch's records for `call` go into, where the SFS text goes instead
 // of the file --sfs names, and what is handed over instead of freed when the stream is through
 struct SmoothHooks {
@@ -47,6 +48,21 @@ struct SmoothHooks {
   std::unordered_map<std::string, std::string> chrom_seqs;
   svdss_ref* dref = nullptr;
   std::vector<int32_t> tid_map;
+  // `SVDSS run --samples` (the session of run_host.cpp): the hooks live through every sample, and what does not depend on
+  // the BAM stays in them.  in: chrom_names / chrom_seqs of the sample before (non-empty: the FASTA is not read), dref with
+  // tid_map as uploaded for a header of dref_names / dref_lens (the same header: not uploaded again), the index.  out: the
+  // same, as this sample leaves them; `call` hands chromosomes and dref back instead of freeing them.
+  bool session = false;
+  std::vector<std::string> dref_names;
+  std::vector<int32_t> dref_lens;
+  // the index: index_host holds the records as svdss_index_load read them (once); `index` is what is resident -- a handle of
+  // the rank blocks alone (index_rank_only) or index_host itself after the full restore.  The policy: a later
+  // sample reuses what is resident, but the rank blocks alone give way to the full restore when its own estimate asks for
+  // that; never the other way round.
+  svdss_index* index_host = nullptr;
+  svdss_index* index = nullptr;
+  bool index_rank_only = false;
+  int n_fasta_reads = 0, n_index_reads = 0, n_ref_uploads = 0;   // counted for the session's --verbose lines
 };
 // ... into CallRun: the SFS text in memory instead of the file, the filled store instead of the first pass over the file
 // (nullptr: the file is read, exactly as `SVDSS call` does), the chromosomes main_smooth loaded
@@ -64,3 +80,10 @@ int main_search(const Options& o, time_t process_start);   // search_host.cpp
 int main_call(const CallOptions& o, CallPreset* preset = nullptr);
 int main_smooth(const CallOptions& o, SmoothHooks* hooks = nullptr);
 int main_run(const CallOptions& o);                        // run_host.cpp
+// `SVDSS run --samples LIST` (run_host.cpp): o.bam is empty; regions / regions_file are resolved against every sample's header
+int main_run_samples(const CallOptions& o, const std::string& list, const std::vector<std::string>& regions, const std::string& regions_file);
+// --region / --regions-file against the header of `bam`, in force for every reader of the process from here on
+// (svdss_main.cpp; `run --samples` calls it per sample, after regions_reset)
+void regions_in_force(const std::vector<std::string>& regions, const std::string& regions_file, const std::string& bam, bool verbose);
+void regions_reset();
+void regions_report();   // bam_regions_report of bam_device_select.h, for the sample that has just ended

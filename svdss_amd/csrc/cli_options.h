@@ -3,7 +3,7 @@
 // `--opt=value`).  In a header of its own so that tests/test_ref_pins.py can hold it against the reference's own
 // config.cpp (oracle/_ref).  Additions of this program: --gpus N|all, --io-threads N, --write-index FILE (smooth),
 // --compress runs|lz (smooth), --nobam (smooth --index --sfs), --smoothed FILE (run), --region REG and --regions-file BED
-// (smooth, search --bam, call, run: csrc/bam_regions.h).
+// (smooth, search --bam, call, run: csrc/bam_regions.h), --samples LIST (run: csrc/run_samples.h).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -21,10 +21,12 @@ struct Options {
   int gpus = 1;                                    // --gpus N: index replicated, batches / sub-clusters shard
   std::string write_index;                         // smooth --write-index FILE: the output's BAI (or CSI: *.csi)
   int compress = 0;                                // smooth --compress runs|lz: the GPU deflate's mode (0 runs, 1 lz)
+  bool compress_given = false;                     // ... named at all (`run --samples` refuses it whatever its value)
   bool nobam = false;                              // smooth --index --sfs --nobam: the SFS text alone, no BAM on stdout
   std::string smoothed;                            // run --smoothed FILE: also write the smoothed BAM
   std::vector<std::string> regions;                // --region REG, every occurrence (the one option that adds up)
   std::string regions_file;                        // --regions-file BED
+  std::string samples;                             // run --samples LIST: many BAMs in one process (run_samples.h)
   bool gpus_all = false;                           // --gpus all (the caller asks the library how many there are)
   bool putative = true, assemble = true, verbose = false, version = false, help = false, clipped = false, binary = false;
 };
@@ -104,7 +106,8 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
       {"min-cluster-weight", INT}, {"accp", FLT}, {"clipped", FLAG}, {"noht", FLAG}, {"noassemble", FLAG},
       {"noputative", FLAG}, {"binary", FLAG}, {"version", FLAG}, {"help", FLAG}, {"h", FLAG}, {"l", FLT}, {"verbose", FLAG},
       {"gpus", STR}, {"io-threads", INT}, {"write-index", STR},
-      {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}, {"region", STR}, {"regions-file", STR}};   // (the last eight: this program's own)
+      {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}, {"region", STR}, {"regions-file", STR},
+      {"samples", STR}};   // (the last nine: this program's own)
   auto find = [&](const std::string& name) -> const Spec* {
     for (const Spec& sp : specs)
       if (name == sp.name) return &sp;
@@ -132,7 +135,8 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
     else if (n == "verbose") o.verbose = b; else if (n == "io-threads") o.io_threads = x; else if (n == "write-index") o.write_index = v;
     else if (n == "nobam") o.nobam = b; else if (n == "smoothed") o.smoothed = v;
     else if (n == "region") o.regions.push_back(v); else if (n == "regions-file") o.regions_file = v;
-    else if (n == "compress") { if (v == "runs") o.compress = 0; else if (v == "lz") o.compress = 1; else return failed(v); }
+    else if (n == "samples") o.samples = v;
+    else if (n == "compress") { o.compress_given = true; if (v == "runs") o.compress = 0; else if (v == "lz") o.compress = 1; else return failed(v); }
     else if (n == "gpus") { if (v == "all") o.gpus_all = true; else if (!to_int(v, o.gpus)) return failed(v); }
     return true;
   };

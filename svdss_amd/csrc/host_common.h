@@ -25,8 +25,15 @@
 #endif
 }
 
+// `SVDSS run --samples` (run_host.cpp): while a sample runs, a fatal message is prefixed by the sample's number and BAM, and
+// the outputs it has begun (<path>.tmp) go with the process.  Empty for every other command: the messages are as they were.
+struct DieContext { std::string prefix; std::vector<std::string> unlink; };
+inline DieContext& die_context() { static DieContext c; return c; }
+
 [[noreturn]] [[maybe_unused]] static void die(const std::string& m) {
-  logmsg("critical", m);
+  const DieContext& c = die_context();
+  logmsg("critical", c.prefix + m);
+  for (const std::string& p : c.unlink) (void)remove(p.c_str());
   exit(EXIT_FAILURE);
 }
 

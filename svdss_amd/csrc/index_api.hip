@@ -566,6 +566,16 @@ extern "C" int svdss_device_count(void) {
   return n;
 }
 
+extern "C" int svdss_device_memory(int32_t device, int64_t* free_bytes, int64_t* total_bytes) {
+  if (device < 0 || !free_bytes || !total_bytes) return SVDSS_EINVAL;
+  HIPCHK(hipSetDevice(device));
+  size_t f = 0, t = 0;
+  HIPCHK(hipMemGetInfo(&f, &t));
+  *free_bytes = (int64_t)f;
+  *total_bytes = (int64_t)t;
+  return SVDSS_OK;
+}
+
 extern "C" int svdss_search_stream_create(int32_t device, void** stream) {
   if (!stream) return SVDSS_EINVAL;
   HIPCHK(hipSetDevice(device));

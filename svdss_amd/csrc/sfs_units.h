@@ -494,20 +494,28 @@ inline bool choose_kmer_order(const std::string& input, bool bam_mode, svdss_ind
 // suffixes sorted for a text, a suffix array and a k-mer table; ~1 M reads/s instead of 8 - 24 M, results identical
 // (svdss_index_attach_blocks).  SVDSS_SEARCH_LF=0|1 forces the choice, SVDSS_SEARCH_LF_MAX moves the threshold (reads).
 // True: the blocks are attached.
-inline bool choose_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, svdss_index_t* ix, const std::string& index_path, bool user_kmer,
-                                     bool verbose, const Stopwatch& clock) {
+// The decision alone (`run --samples` takes it for every sample while the rank blocks alone are resident, and attaches
+// nothing): est / t_est: the estimate it rests on and when it was known.
+inline bool wants_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, int64_t index_n, bool user_kmer, const Stopwatch& clock, double& est,
+                                    std::string& t_est) {
   if (user_kmer || knobs.lf == 0) return false;
   const bool forced = knobs.lf == 1;
   const auto w0 = now();
   while (!forced && !early.front_is_finished() && early.records.load() < 50000 && secs(w0, now()) <= 1.5)
     std::this_thread::sleep_for(std::chrono::milliseconds(5));
-  const double est = early.estimate_reads_to_search();
-  const std::string t_est = clock.since();
+  est = early.estimate_reads_to_search();
+  t_est = clock.since();
   // (what the rank structure alone saves is the rest of the restore -- ~4.5 s at GRCh38 lengths, in proportion for a
   // smaller reference --, what it costs is the search at ~1 M reads/s instead of 8 - 24 M: worth it below ~2 M reads
   // per 6.2e9 BWT symbols; profiles/r06q_*)
-  const double lf_max = knobs.lf_max_set ? knobs.lf_max : 2e6 * (double)svdss_index_size(ix) / 6.18e9;
-  if (!forced && !(est >= 0 && est <= lf_max)) return false;
+  const double lf_max = knobs.lf_max_set ? knobs.lf_max : 2e6 * (double)index_n / 6.18e9;
+  return forced || (est >= 0 && est <= lf_max);
+}
+inline bool choose_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, svdss_index_t* ix, const std::string& index_path, bool user_kmer,
+                                     bool verbose, const Stopwatch& clock) {
+  double est = -1;
+  std::string t_est;
+  if (!wants_rank_blocks_alone(knobs, early, svdss_index_size(ix), user_kmer, clock, est, t_est)) return false;
   const int rc = svdss_index_attach_blocks(ix, index_path.c_str());
   if (rc == SVDSS_OK) {
     if (verbose) logmsg("debug", "~" + std::to_string((long long)std::max(0.0, est)) + " reads to search (known at +" + t_est + " s): the index as a rank structure alone (blocks read at +" + clock.since() + " s)");

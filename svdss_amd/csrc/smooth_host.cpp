@@ -199,12 +199,13 @@ void write_record(ByteSink& w, const BamRecord& r, const std::vector<uint32_t>& 
 // -- and from there through search's own units, format_batch and ordered writer into FILE.
 class SfsSide {
  public:
-  SfsSide(const CallOptions& c, FILE* sink, bool debug) : sink_(sink) {
+  SfsSide(const CallOptions& c, FILE* sink, bool debug, SmoothHooks* hooks = nullptr) : hooks_(hooks && hooks->session ? hooks : nullptr), sink_(sink) {
     o_.index = c.index; o_.bam = c.bam; o_.threads = std::max(1, c.threads); o_.bsize = c.bsize; o_.putative = c.putative; o_.assemble = c.assemble;
     o_.verbose = c.verbose || debug;
     flags_ = (o_.assemble ? SVDSS_SFS_ASSEMBLE : 0) | (o_.putative ? SVDSS_BAM_PUTATIVE : 0);
     struct stat stb;
     early_.file_bytes = stat(c.bam.c_str(), &stb) == 0 ? (int64_t)stb.st_size : 0;
+    if (hooks_) svdss_index_kmer_limit(0);   // (process-wide, for tables built from now on: what the sample before learnt is not this one's)
     index_thread_ = std::thread([this] { make_index_resident(); });
   }
   int32_t flags() const { return flags_; }
@@ -264,8 +265,10 @@ class SfsSide {
     }
   }
   // `SVDSS run`, after finish(): the index and the park leave HBM before `call` takes its workspaces
+  // (`run --samples`: the index stays, through the call stage and for the next sample)
   void free_index_and_park() {
-    svdss_index_free(early_.wait_for_offered_index());
+    svdss_index_t* const ix = early_.wait_for_offered_index();
+    if (!hooks_) svdss_index_free(ix);
     svdss_bam_park_free(early_.park);
     early_.park = nullptr;
   }
@@ -273,6 +276,7 @@ class SfsSide {
   // the side thread: the index file, the form it becomes resident in (SVDSS_KMER, SVDSS_SEARCH_LF, SVDSS_SEARCH_LF_MAX as
   // for `search`; the estimate of the reads to search runs on the XF counts the batches bring), then to the feeders
   void make_index_resident() {
+    if (hooks_) { make_session_index_resident(); return; }
     svdss_index_t* ix = nullptr;
     check(svdss_index_load(o_.index.c_str(), &ix), "svdss_index_load");
     early_.index_n.store(svdss_index_size(ix));
@@ -285,6 +289,58 @@ class SfsSide {
     if (lf_only_) early_.offer_index_held_back(ix);
     if (knobs_.early_hold_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(knobs_.early_hold_ms));
     early_.release_index(ix);
+  }
+  // ... of `run --samples`: the index file is read by the first sample; what is resident is reused -- the rank blocks alone
+  // only while this sample's own estimate still asks for them, else the full restore is made from the records kept on the
+  // host and stays.  Reused, the index is there from the start: it is held back from the feeders as the rank blocks are, so
+  // that the reads are parked and searched one launch per group, not one small segmented launch per device batch.
+  void session_note(const std::string& m) const { if (o_.verbose) fprintf(stderr, "[run] index: %s\n", m.c_str()); }
+  void make_session_index_resident() {
+    SmoothHooks& h = *hooks_;
+    if (!h.index_host) {
+      check(svdss_index_load(o_.index.c_str(), &h.index_host), "svdss_index_load");
+      ++h.n_index_reads;
+      session_note("file read, " + std::to_string((long long)svdss_index_size(h.index_host)) + " symbols");
+    }
+    const int64_t n = svdss_index_size(h.index_host);
+    early_.index_n.store(n);
+    const bool reused_full = h.index && !h.index_rank_only;
+    if (!reused_full) {
+      const bool kmer_was_set = getenv("SVDSS_KMER") != nullptr;
+      const bool user_kmer = choose_kmer_order(o_.bam, true, h.index_host, o_.verbose);
+      double est = -1;
+      std::string t_est;
+      bool lf = wants_rank_blocks_alone(knobs_, early_, n, user_kmer, clock_, est, t_est);
+      const std::string what = "~" + std::to_string((long long)std::max(0.0, est)) + " reads to search (known at +" + t_est + " s)";
+      if (lf && !h.index) {
+        const int rc = svdss_index_load_blocks(o_.index.c_str(), &h.index);
+        if (rc == SVDSS_OK && svdss_index_size(h.index) != n) { svdss_index_free(h.index); h.index = nullptr; }
+        else if (rc != SVDSS_OK && rc != SVDSS_EINVAL) check(rc, "svdss_index_load_blocks");
+        if (h.index) {
+          check(svdss_index_to_device(h.index, 0), "svdss_index_to_device");
+          h.index_rank_only = true;
+          session_note(what + ": rank blocks alone made resident");
+        } else lf = false;    // (no such section in the file: restore as before)
+      } else if (lf) session_note(what + ": resident index reused (rank blocks alone)");
+      if (!lf) {
+        if (h.index) {
+          session_note(what + ": full restore replaces the rank blocks alone");
+          svdss_index_free(h.index);
+        }
+        h.index = nullptr;
+        check(svdss_index_to_device(h.index_host, 0), "svdss_index_to_device");
+        h.index = h.index_host;
+        h.index_rank_only = false;
+        session_note("full restore made resident");
+      }
+      // (the order choose_kmer_order asked for was this sample's: the next full restore, if there is one, asks again)
+      if (!kmer_was_set) unsetenv("SVDSS_KMER");
+    } else session_note("resident index reused (full restore)");
+    lf_only_ = h.index_rank_only;
+    t_resident_ = secs(clock_.t0, now());
+    early_.offer_index_held_back(h.index);
+    if (knobs_.early_hold_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(knobs_.early_hold_ms));
+    early_.release_index(h.index);
   }
   void deliver(uint64_t seq, std::unique_ptr<DevOut> out) {
     { std::lock_guard<std::mutex> lk(m_); ready_[seq] = std::move(out); }
@@ -345,6 +401,7 @@ class SfsSide {
     if (sfs) svdss_sfs_batch_free(sfs);
   }
 
+  SmoothHooks* const hooks_;   // `run --samples` only: where the index lives between samples
   Options o_;
   const SearchKnobs knobs_{};
   const Stopwatch clock_{};
@@ -408,7 +465,7 @@ struct SmoothRun {
   // --index FMD --sfs FILE: what it cannot run on is said before FILE or anything else is created; then the index is on its
   // way from the first moment
   void refuse_and_open_sfs() {
-    if (hooks && hooks->sfs_sink) { side.reset(new SfsSide(o, hooks->sfs_sink, knobs.debug)); return; }   // (`SVDSS run` has refused what cannot run)
+    if (hooks && hooks->sfs_sink) { side.reset(new SfsSide(o, hooks->sfs_sink, knobs.debug, hooks)); return; }   // (`SVDSS run` has refused what cannot run)
     if (o.sfs.empty()) return;
     if (o.gpus != 1) die("smooth --index --sfs with --gpus other than 1 is out of scope: run it on one GPU");
     if (!knobs.no_device_path().empty())
@@ -435,8 +492,12 @@ struct SmoothRun {
       if ((size_t)hp.n_ref != hp.names.size()) hp.err = "cannot read " + o.bam + ": inconsistent header";
     });
     std::vector<std::string> names;
-    if (!load_chromosomes(o.reference, o.threads, knobs.fasta_serial, names, chrom)) die("cannot open " + o.reference);
-    if (hooks) hooks->chrom_names = std::move(names);
+    if (hooks && hooks->session && !hooks->chrom_names.empty()) chrom = std::move(hooks->chrom_seqs);   // (read by a sample before)
+    else {
+      if (!load_chromosomes(o.reference, o.threads, knobs.fasta_serial, names, chrom)) die("cannot open " + o.reference);
+      if (hooks) { hooks->chrom_names = std::move(names); ++hooks->n_fasta_reads; }
+      if (hooks && hooks->session && (o.verbose || knobs.debug)) fprintf(stderr, "[run] reference: FASTA read, %zu sequence(s)\n", chrom.size());
+    }
     gpu_warm.join();
     header_pre.join();
   }
@@ -680,7 +741,18 @@ struct DevicePipeline {
     on_threads(n_sm, [&](size_t d, size_t) {
       std::vector<int32_t> tm;
       int& rc = rcs[d];
-      rc = upload_chromosomes(hp.names, R.chrom, (int)d, tm, &drefs[d]);
+      SmoothHooks* const h = R.hooks && R.hooks->session && d == 0 ? R.hooks : nullptr;
+      if (h && h->dref && h->dref_names == hp.names && h->dref_lens == hp.lens) {   // (the same header: the copy in HBM serves again)
+        drefs[0] = h->dref; h->dref = nullptr;
+        tm = h->tid_map;
+        rc = SVDSS_OK;
+        if (o.verbose || R.knobs.debug) fprintf(stderr, "[run] reference: copy on the GPU reused\n");
+      } else {
+        if (h && h->dref) { svdss_ref_free(h->dref); h->dref = nullptr; }
+        rc = upload_chromosomes(hp.names, R.chrom, (int)d, tm, &drefs[d]);
+        if (h) ++h->n_ref_uploads;
+        if (h && (o.verbose || R.knobs.debug)) fprintf(stderr, "[run] reference: uploaded to the GPU in the order of the BAM header\n");
+      }
       if (rc == SVDSS_OK) rc = svdss_bam_smooth_create(drefs[d], tm.data(), (int32_t)tm.size(), (int32_t)o.min_mapq, &sms[d]);
       if (rc == SVDSS_OK && R.ixb) rc = svdss_bam_smooth_set_index(sms[d], R.ix_shift, R.ix_depth);
       if (rc == SVDSS_OK) rc = svdss_bam_smooth_set_deflate(sms[d], o.compress);
@@ -771,6 +843,7 @@ struct DevicePipeline {
     if (R.hooks) {
       R.hooks->dref = drefs[0]; drefs[0] = nullptr;
       R.hooks->tid_map = tid_map;
+      R.hooks->dref_names = hp.names; R.hooks->dref_lens = hp.lens;
       R.hooks->n_batches = n_batches;
     }
     for (svdss_ref_t* q : drefs) svdss_ref_free(q);

@@ -13,7 +13,7 @@
 // Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth),
 // --compress runs|lz (smooth), --index FMD --sfs FILE [--nobam] (smooth: the search of the smoothed reads in the same pass),
 // the sub-command `run` with its --smoothed FILE, --region REG / --regions-file BED (smooth, search --bam, call, run:
-// bam_regions.h).
+// bam_regions.h), --samples LIST (run: many BAMs in one process, run_samples.h and run_host.cpp).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -23,6 +23,7 @@
 #include <ctime>
 #include <malloc.h>
 #include <string>
+#include <sys/stat.h>
 #include <thread>
 #include <unistd.h>
 #include <utime.h>
@@ -34,12 +35,14 @@
 #include "fastx_reader.h"
 #include "bam_device_select.h"
 #include "bam_region_ranges.h"
+#include "run_samples.h"
 
 static const char* VERSION = "v2.1.1";  // main.cpp:19
 
 // (weak: a build of the binary from a source list without run_host.cpp -- the sanitized CPU build of tests/ -- still links;
 // `run` then says so)
 __attribute__((weak)) int main_run(const CallOptions& o);
+__attribute__((weak)) int main_run_samples(const CallOptions& o, const std::string& list, const std::vector<std::string>& regions, const std::string& regions_file);
 
 static const char* MAIN_USAGE =
     "Usage: SVDSS <index|smooth|search|call|run> --help\n"
@@ -101,6 +104,14 @@ static const char* RUN_USAGE =
     "      --min-cluster-weight <int> --min-sv-length <int> -l <float> --noht   as in call\n"
     "      --poa <FILE> --clusters <FILE> --clipped                             as in call\n"
     "      --verbose             stage timings and the record store's size on stderr\n"
+    "      --samples <LIST>      instead of --bam: many BAMs in this one process, in the order of LIST; the reference, the index\n"
+    "                            and the pools stay between them.  LIST: one sample per line, BAM<TAB>VCF[<TAB>SFS]; empty lines\n"
+    "                            and lines that start with '#' are skipped.  VCF receives what `run --bam BAM` with the same\n"
+    "                            options writes to stdout, SFS what --sfs writes; each is written as <path>.tmp and renamed when\n"
+    "                            complete; stdout stays empty, stderr gets one line per finished sample.  Not with --sfs,\n"
+    "                            --smoothed, --write-index, --compress, --poa or --clusters.  A sample that fails ends the\n"
+    "                            process with a non-zero status: the samples before it are complete, it leaves no file, the\n"
+    "                            samples after it are not started\n"
     REGION_HELP;
 
 static const char* SEARCH_USAGE =
@@ -125,29 +136,45 @@ static Options parse(int argc, char** argv) {
 // force for every reader of the process (bam_regions.h), or a message that names the offending text
 static void regions_in_force(const Options& o, const char* cmd) {
   if (o.regions.empty() && o.regions_file.empty()) return;
+  if (!o.samples.empty() && !strcmp(cmd, "run")) return;   // (resolved per sample, against each sample's own header: run_host.cpp)
   if (o.bam.empty() && o.fastx.empty()) return;   // (the command's usage text follows)
   if (o.bam.empty() || !o.fastx.empty())
     die(std::string("--region / --regions-file select records of a BAM by position: not an option of `SVDSS ") + cmd + (o.fastx.empty() ? "`" : " --fastx`"));
+  regions_in_force(o.regions, o.regions_file, o.bam, o.verbose);
+}
+// `run --samples`, between two samples: no regions in force, no plan, the counters of the next report at zero
+void regions_reset() {
+  bam_regions_in_force() = nullptr;
+  bam_region_plan() = BamRegionPlan();
+  BamRegionCounters& c = bam_region_counters();
+  c.gated = 0; c.comp_bytes = 0; c.host_readers = 0; c.verbose = false;
+  int64_t on_device = 0;
+  (void)svdss_bam_gated_total(&on_device);
+  c.device_base = on_device;
+}
+void regions_report() { bam_regions_report(); }
+void regions_in_force(const std::vector<std::string>& regions, const std::string& regions_file, const std::string& bam, bool verbose) {
+  if (regions.empty() && regions_file.empty()) return;
   int32_t n_ref = 0;
   int64_t skip = 0;
   std::string err;
   std::vector<std::string> names;
-  if (!bam_header_probe(o.bam, n_ref, skip, err, &names)) die("cannot read " + o.bam + ": " + err);
-  static BamRegionSet U;
-  if (!resolve_regions(o.regions, o.regions_file, names, U, err)) die(err);
+  if (!bam_header_probe(bam, n_ref, skip, err, &names)) die("cannot read " + bam + ": " + err);
+  static BamRegionSet U;   // (one at a time: a sample of `run --samples` resolves its own over the one before)
+  if (!resolve_regions(regions, regions_file, names, U, err)) die(err);
   bam_regions_in_force() = &U;
   // the bytes to read: what a BAI / CSI beside the BAM names for U (SVDSS_REGION_INDEX=0: the whole file, as without one)
   std::string index_path, stale;
   const bool want_index = !(getenv("SVDSS_REGION_INDEX") && atoi(getenv("SVDSS_REGION_INDEX")) == 0);
-  if (want_index && find_bam_index(o.bam, index_path, stale)) {
+  if (want_index && find_bam_index(bam, index_path, stale)) {
     BaiIndex index;
     BamRegionPlan& plan = bam_region_plan();
     if (!index.load(index_path)) logmsg("warning", "cannot read the index " + index_path + ": the whole file is read");
-    else if (!region_file_ranges(o.bam, index, U, plan.ranges, err)) logmsg("warning", err + ": the index is not used, the whole file is read");
-    else { plan.active = true; plan.path = o.bam; plan.index_path = index_path; }
+    else if (!region_file_ranges(bam, index, U, plan.ranges, err)) logmsg("warning", err + ": the index is not used, the whole file is read");
+    else { plan.active = true; plan.path = bam; plan.index_path = index_path; }
   }
-  if (!stale.empty() && !bam_region_plan().active) logmsg("warning", "the index " + stale + " is older than " + o.bam + ": it is not used, the whole file is read");
-  bam_region_counters().verbose = o.verbose;
+  if (!stale.empty() && !bam_region_plan().active) logmsg("warning", "the index " + stale + " is older than " + bam + ": it is not used, the whole file is read");
+  bam_region_counters().verbose = verbose;
 }
 static int main_index(int argc, char** argv) {
   // ropebwt3 `build` flags as run_svdss:142 passes them: -t T -d <fasta> -o <out>
@@ -283,6 +310,8 @@ int main(int argc, char** argv) {
       die(std::string("--write-index is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
     if (!o.smoothed.empty() && strcmp(argv[1], "run") != 0)
       die(std::string("--smoothed is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
+    if (!o.samples.empty() && strcmp(argv[1], "run") != 0)
+      die(std::string("--samples is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
     if (!strcmp(argv[1], "search") || !strcmp(argv[1], "call") || !strcmp(argv[1], "smooth") || !strcmp(argv[1], "run")) regions_in_force(o, argv[1]);
     if (!strcmp(argv[1], "search")) {
       if (o.index.empty() || (o.fastx.empty() && o.bam.empty())) { fputs(SEARCH_USAGE, stderr); return EXIT_FAILURE; }
@@ -308,7 +337,15 @@ int main(int argc, char** argv) {
       c.verbose = o.verbose;
       main_smooth(c);
     } else if (!strcmp(argv[1], "run")) {
-      if (o.reference.empty() || o.bam.empty() || o.index.empty()) { fputs(RUN_USAGE, stderr); return EXIT_FAILURE; }
+      // --samples LIST: what it does not go with, before the list is looked at
+      if (!o.samples.empty()) {
+        const std::pair<const char*, bool> with[] = {{"--bam", !o.bam.empty()}, {"--sfs", !o.sfs.empty()}, {"--smoothed", !o.smoothed.empty()},
+                                                     {"--write-index", !o.write_index.empty()}, {"--compress", o.compress_given}, {"--poa", !o.poa.empty()},
+                                                     {"--clusters", !o.clusters.empty()}};
+        for (const auto& w : with)
+          if (w.second) die(std::string("run: --samples does not go with ") + w.first + " (every sample's files are named by its line of the list)");
+      }
+      if (o.reference.empty() || (o.bam.empty() && o.samples.empty()) || o.index.empty()) { fputs(RUN_USAGE, stderr); return EXIT_FAILURE; }
       if (!o.write_index.empty() && o.smoothed.empty()) die("run: --write-index needs --smoothed <FILE> (there is no BAM to index)");
       if (o.compress != 0 && o.smoothed.empty()) die("run: --compress needs --smoothed <FILE> (nothing is deflated without it)");
       CallOptions c;
@@ -317,8 +354,9 @@ int main(int argc, char** argv) {
       c.bsize = o.bsize; c.putative = o.putative; c.assemble = o.assemble;
       c.min_cluster_weight = o.min_cluster_weight; c.min_sv_length = o.min_sv_length; c.useht = o.useht; c.min_ratio = o.min_ratio;
       c.poa = o.poa; c.clusters = o.clusters; c.clipped = o.clipped; c.verbose = o.verbose;
-      if (!main_run) die("this build of the binary has no `run` (run_host.cpp was left out)");
-      main_run(c);
+      if (!main_run || !main_run_samples) die("this build of the binary has no `run` (run_host.cpp was left out)");
+      if (o.samples.empty()) main_run(c);
+      else main_run_samples(c, o.samples, o.regions, o.regions_file);
     } else {
       fputs(MAIN_USAGE, stderr);
       return EXIT_FAILURE;
