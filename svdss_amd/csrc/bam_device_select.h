@@ -202,8 +202,12 @@ struct BamRunError {
 // region begins inside a record nobody has located (svdss_bam_stream_region: the chain starts at a guess, to be proved at
 // the seam); open_end: it may end inside one; carry: the incomplete record in front of it when the region runs from a known
 // start; pending: batches that may wait for the caller while it reads this region (current: from the start; a later region
-// is not bounded until it becomes current -- its results wait until the regions in front are handed out)
-struct BamSelectRegion { size_t begin = 0, end = 0; bool open_start = false, open_end = false; std::vector<uint8_t> carry; int loaders = 8; size_t pending = 64; bool current = true; };
+// is not bounded until it becomes current -- its results wait until the regions in front are handed out); on_fed: called
+// once, by the last feeding thread as it ends (no more batches will be run; results may still be delivered); small_start:
+// the run's first batch is cut at a quarter of the batch size and the second at half of it, so that the device has work --
+// and whoever counts what the batches hold has figures, and batch 0's head is final -- after a quarter of the bytes
+struct BamSelectRegion { size_t begin = 0, end = 0; bool open_start = false, open_end = false; std::vector<uint8_t> carry; int loaders = 8; size_t pending = 64; bool current = true;
+                         std::function<void()> on_fed; bool small_start = false; };
 
 // One region of a BAM through the device path, batch results handed out in file order as `Out`: scanner (loader threads)
 // -> batcher -> feeding threads (n_devices x feeders, one batch object each; `run` is told the device slot) -> ordered
@@ -219,7 +223,7 @@ class DeviceBamSelect {
   DeviceBamSelect(const std::string& path, size_t n_devices, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes, BamRunFn run,
                   CollectFn collect, svdss_bam_stream_t* prepared_stream = nullptr, const Region& region = Region(), BgzfScanner* scanner = nullptr)
       : skip_(skip), target_(batch_bytes), run_(run), collect_(collect), sc_(scanner), stream_(prepared_stream), max_pending_(region.pending),
-        current_(region.current) {
+        current_(region.current), on_fed_(region.on_fed), small_start_(region.small_start) {
     feeders = std::max(1, feeders);
     if (!sc_) {
       BgzfScanner::Hooks hooks;
@@ -284,9 +288,10 @@ class DeviceBamSelect {
     cv_.notify_all();
   }
   // blocks until batch 0 has had its turn (svdss_bam_stream_head is final), the file has ended or the run has failed
+  // (first_run_: batch 0 has been through `run`, though its result may be one that is delivered later)
   void wait_first() {
     std::unique_lock<std::mutex> lk(m_);
-    cv_.wait(lk, [&] { return want_ > 0 || done_.count(0) || err_.failed() || fed(); });
+    cv_.wait(lk, [&] { return want_ > 0 || done_.count(0) || first_run_ || err_.failed() || fed(); });
   }
   // blocks until every feeding thread has ended (the stream's tail is final; results still to be delivered may follow)
   void wait_finished() {
@@ -309,6 +314,7 @@ class DeviceBamSelect {
   void batch_loop() {
     std::unique_ptr<Job> cur(new Job);
     int64_t acc = 0;
+    int64_t target = small_start_ ? std::max<int64_t>(1, target_ / 4) : target_;   // (of the batch in hand: doubles to target_)
     uint64_t seq = 0;
     bool any_last = false;
     double w_file = 0;
@@ -346,13 +352,14 @@ class DeviceBamSelect {
       acc += c->inflated;
       const bool last = c->last;
       cur->chunks.push_back(std::move(c));
-      if (acc >= target_ || last) {
+      if (acc >= target || last) {
         cur->seq = seq++;
         cur->last = last;
         any_last = any_last || last;
         if (!push(std::move(cur))) return;
         cur.reset(new Job);
         acc = 0;
+        target = std::min(target_, target * 2);
       }
     }
     if (!sc_->error().empty()) { fail(BamRunError{SVDSS_EIO, sc_->error(), ""}); return; }
@@ -395,6 +402,7 @@ class DeviceBamSelect {
       {
         std::unique_lock<std::mutex> lk(m_);
         const uint64_t sq = job->seq;
+        if (sq == 0) first_run_ = true;
         if (!out) ++deferred_;
         else {
           cv_.wait(lk, [&] { return stop_ || !current_ || done_.size() < max_pending_ || done_.begin()->first > sq; });
@@ -404,7 +412,9 @@ class DeviceBamSelect {
       cv_.notify_all();
     }
     if (batch) svdss_bam_batch_free(batch);
-    { std::lock_guard<std::mutex> lk(m_); ++feeders_done_; }
+    bool all = false;
+    { std::lock_guard<std::mutex> lk(m_); ++feeders_done_; all = fed(); }
+    if (all && on_fed_) on_fed_();      // (before the waiters of wait_finished hear of it)
     cv_.notify_all();
   }
 
@@ -416,7 +426,9 @@ class DeviceBamSelect {
   BgzfScanner* sc_ = nullptr;
   svdss_bam_stream_t* stream_ = nullptr;
   size_t max_pending_ = 64;
-  bool current_ = true;
+  bool current_ = true, first_run_ = false;
+  std::function<void()> on_fed_;
+  bool small_start_ = false;
   std::thread batcher_;
   std::vector<std::thread> feeders_;
   mutable std::mutex m_;
@@ -474,13 +486,18 @@ class ShardedBamSelect {
   // front of it, run on the caller's thread with is_last = 1 (its collect may not leave the result for later); stream(g): a
   // prepared record stream for region g's run (nullptr or no hook: a plain one) -- asked again if the region runs again;
   // again(g, why): the region runs again (forget what its first run left; why: its failure, empty when the seam did not
-  // fit); seam_kept(g): the seam's batch stays somewhere the caller looks for it (region_has_seam)
+  // fit); seam_kept(g): the seam's batch stays somewhere the caller looks for it (region_has_seam); fed(g): a run of region
+  // g has run its last batch (called by its last feeding thread as it ends; once per run of the region); abandon(g): the
+  // first run of region g has failed and its feeding threads have ended -- whoever delivers results of that run
+  // (deliver) stops doing so before this returns: the run's reader is dropped next, then again(g) is called
   struct Hooks {
     std::function<BamRunFn(size_t g, bool seam)> run;
     std::function<CollectFn(size_t g, bool seam)> collect;
     std::function<svdss_bam_stream_t*(size_t g)> stream;
     std::function<void(size_t g, const std::string& why)> again;
     std::function<bool(size_t g)> seam_kept;
+    std::function<void(size_t g)> fed;
+    std::function<void(size_t g)> abandon;
   };
   ShardedBamSelect(const std::string& path, const std::vector<Shard>& shards, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes,
                    const std::vector<size_t>& cuts)
@@ -516,8 +533,8 @@ class ShardedBamSelect {
   // scanners: those of the regions' first runs, opened by the caller and kept open past this object (none given: each
   // region opens its own)
   ShardedBamSelect(const std::string& path, const Hooks& hooks, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes, const std::vector<size_t>& cuts,
-                   size_t pending = 64, const std::vector<BgzfScanner*>& scanners = std::vector<BgzfScanner*>())
-      : path_(path), hooks_(hooks), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes), pending_(pending) {
+                   size_t pending = 64, const std::vector<BgzfScanner*>& scanners = std::vector<BgzfScanner*>(), bool small_start = false)
+      : path_(path), hooks_(hooks), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes), pending_(pending), small_start_(small_start) {
     start(cuts, scanners);
   }
   size_t n_regions() const { return regions_.size(); }
@@ -542,6 +559,13 @@ class ShardedBamSelect {
       if (R.sel->failure().failed()) { err_ = R.sel->failure(); return nullptr; }
       ++cur_;
     }
+  }
+  // the result of batch `seq` of region g's run, whose collect returned nullptr (any thread; not for a run that abandon(g)
+  // has been called for)
+  void deliver(size_t g, uint64_t seq, std::unique_ptr<Out> out) {
+    std::unique_lock<std::mutex> lk(sel_m_);
+    sel_cv_.wait(lk, [&] { return regions_[g].sel != nullptr; });     // (a feeding thread of a run may be through before launch() has returned)
+    regions_[g].sel->deliver(seq, std::move(out));
   }
   std::string error() const { return err_.text(); }
   const BamRunError& failure() const { return err_; }
@@ -580,8 +604,12 @@ class ShardedBamSelect {
     rg.loaders = regions_.size() > 1 ? std::max(2, 8 / (int)std::min<size_t>(regions_.size(), 4)) : 8;
     rg.pending = pending_;
     rg.current = g == cur_;
-    regions_[g].sel.reset(new DeviceBamSelect<Out>(path_, 1, n_ref_, g == 0 ? skip_ : 0, feeders_, batch_bytes_, hooks_.run(g, false), hooks_.collect(g, false),
-                                                   hooks_.stream ? hooks_.stream(g) : nullptr, rg, scanner));
+    if (hooks_.fed) rg.on_fed = [this, g] { hooks_.fed(g); };
+    rg.small_start = small_start_;
+    std::unique_ptr<DeviceBamSelect<Out>> sel(new DeviceBamSelect<Out>(path_, 1, n_ref_, g == 0 ? skip_ : 0, feeders_, batch_bytes_, hooks_.run(g, false),
+                                                                         hooks_.collect(g, false), hooks_.stream ? hooks_.stream(g) : nullptr, rg, scanner));
+    { std::lock_guard<std::mutex> lk(sel_m_); regions_[g].sel = std::move(sel); }
+    sel_cv_.notify_all();
   }
   // a region's run is over (its feeding threads have ended): what it counted goes into the sums
   void drop(Reg& R) {
@@ -590,7 +618,8 @@ class ShardedBamSelect {
     n_seg_ += n;
     wait_file_s_ += R.sel->waited_for_file();
     wait_feed_s_ += R.sel->waited_for_feeders();
-    R.sel.reset();
+    std::unique_ptr<DeviceBamSelect<Out>> gone;
+    { std::lock_guard<std::mutex> lk(sel_m_); gone = std::move(R.sel); }
   }
   // the seam in front of region g, proved; false = the run has failed (err_)
   bool enter(size_t g) {
@@ -611,6 +640,7 @@ class ShardedBamSelect {
       if (err_.failed()) return false;
       // not proved (or the region failed): once more, from the record the region in front ended in
       R.sel->wait_finished();
+      if (hooks_.abandon) hooks_.abandon(g);
       drop(R);
       R.seam.reset();
       if (hooks_.again) hooks_.again(g, why.text());
@@ -670,7 +700,10 @@ class ShardedBamSelect {
   int feeders_ = 3;
   int64_t batch_bytes_ = 0;
   size_t pending_ = 64;
+  bool small_start_ = false;         // (every run of every region: BamSelectRegion::small_start)
   std::vector<Reg> regions_;
+  std::mutex sel_m_;                 // (who may come from another thread -- deliver -- meets a region's `sel` under it)
+  std::condition_variable sel_cv_;
   size_t cur_ = 0;
   int64_t n_seams_ = 0, n_reruns_ = 0, n_seg_ = 0, n_rewalk_ = 0;
   double wait_file_s_ = 0, wait_feed_s_ = 0;

@@ -592,6 +592,10 @@ extern "C" int svdss_stream_destroy(void* stream) {
 
 // another replica of a resident (or host-side) index in the HBM of `device`: SURVEY 8(e), index replicated per GPU.
 // The new handle owns its device buffers and a copy of the small host-side parts; the source stays as it is.
+// A source that is the rank blocks alone (svdss_index_attach_blocks: no records, no text, no suffix array -- resident or
+// not, and while another thread makes it resident): the blocks are uploaded from the SOURCE's host copy and the small table
+// is built on `device`, nothing else -- the replica keeps no host copy of the blocks (gigabytes per GPU of `search --gpus
+// N`, copied for nothing), so it serves the search and nothing that reads the index on the host.
 extern "C" int svdss_index_replicate(const svdss_index_t* src, int32_t device, svdss_index_t** out) {
   if (!src || !out || device < 0) return SVDSS_EINVAL;
   if (!src->rec_lens.empty() && !getenv("SVDSS_INDEX_CPU")) {
@@ -620,15 +624,16 @@ extern "C" int svdss_index_replicate(const svdss_index_t* src, int32_t device, s
   memcpy(ix->acc, src->acc, sizeof ix->acc);
   ix->n_contigs = src->n_contigs;
   ix->sa_wide = src->sa_wide;
-  try { ix->blocks = src->blocks; ix->dollar = src->dollar; } catch (...) { delete ix; return SVDSS_ENOMEM; }
-  HIPCHK(hipSetDevice(device));
-  ix->device = device;
-  const size_t bb = ix->blocks.size() * sizeof(svdss_u4), db = (ix->dollar.size() + 1) * sizeof(int64_t);
   const bool have = (int64_t)src->text.size() == src->n &&
                     (int64_t)(src->sa_wide ? src->sa64.size() : src->sa32.size()) == src->n;
+  const bool blocks_alone = !have && src->rec_lens.empty() && src->text.empty() && !src->blocks.empty();
+  try { if (!blocks_alone) ix->blocks = src->blocks; ix->dollar = src->dollar; } catch (...) { delete ix; return SVDSS_ENOMEM; }
+  HIPCHK(hipSetDevice(device));
+  ix->device = device;
+  const size_t bb = src->blocks.size() * sizeof(svdss_u4), db = (ix->dollar.size() + 1) * sizeof(int64_t);
   auto fail = [&](int code) { free_device_side(ix); delete ix; return code; };
   if (hipMalloc(&ix->d_blocks, bb) != hipSuccess || hipMalloc(&ix->d_dollar, db) != hipSuccess) return fail(SVDSS_ENOMEM);
-  if (hipMemcpy(ix->d_blocks, ix->blocks.data(), bb, hipMemcpyHostToDevice) != hipSuccess) return fail(SVDSS_EHIP);
+  if (hipMemcpy(ix->d_blocks, src->blocks.data(), bb, hipMemcpyHostToDevice) != hipSuccess) return fail(SVDSS_EHIP);
   if (!ix->dollar.empty() &&
       hipMemcpy(ix->d_dollar, ix->dollar.data(), ix->dollar.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
     return fail(SVDSS_EHIP);

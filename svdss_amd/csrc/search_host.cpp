@@ -46,6 +46,10 @@ namespace {
 // (ShardedBamSelect: a region's first record is guessed, and proved at the seam or the region runs again).  The reads of a
 // region are dealt into units when everything before it has been (the unit a read belongs to depends on the reads in front
 // of it), so the later regions' results wait in memory (~0.6 KB per read).
+//
+// Early (the front end beside the index restore): an EarlySearch per region -- `early` is empty, or has one for every region
+// of the file --, each with a park on its region's GPU and a drain thread that searches its parked groups on that GPU's
+// replica.  A region is released when ITS replica is resident; no region waits for another's front end or index.
 // the file as the device path reads it: its regions (plan_bam_regions) and one scanner per region, opened before the index is
 // restored and kept open to the end (the process ends with _exit: their page-locked slabs are never handed back one by one)
 struct DeviceBamInput {
@@ -59,16 +63,17 @@ struct DeviceBamInput {
 class DevicePath {
  public:
   DevicePath(const Options& o, const SearchKnobs& knobs, const std::vector<svdss_index_t*>& replicas, const DeviceBamInput& in,
-             const Stopwatch& clock, EarlySearch* early = nullptr)
+             const Stopwatch& clock, const std::vector<EarlySearch*>& early = std::vector<EarlySearch*>())
       : o_(o), knobs_(knobs), replicas_(replicas), in_(in), clock_(clock), early_(early),
         flags_((o.assemble ? SVDSS_SFS_ASSEMBLE : 0) | (o.putative ? SVDSS_BAM_PUTATIVE : 0)) {}
   void run();
  private:
-  BamRunFn run_on(size_t r);
-  std::unique_ptr<DevOut> collect(const svdss_bam_batch_t* batch, uint64_t seq);
+  BamRunFn run_on(size_t r, bool seam = false);
+  std::unique_ptr<DevOut> collect(size_t r, const svdss_bam_batch_t* batch, uint64_t seq);
   std::unique_ptr<DevOut> next() { return one_ ? one_->next() : sharded_->next(); }
   void assemble();
-  void drain_park();
+  void drain_park(size_t r);
+  void run_again(size_t r);
   void report();
 
   const Options& o_;
@@ -76,7 +81,8 @@ class DevicePath {
   const std::vector<svdss_index_t*> replicas_;
   const DeviceBamInput& in_;
   const Stopwatch& clock_;
-  EarlySearch* const early_;
+  const std::vector<EarlySearch*> early_;
+  std::vector<std::thread> drains_;       // early: one per region (a region that runs again: joined and started anew by the assembler)
   const int32_t flags_;
   StageSeconds t_;
   // units of whole reference batches, formatted by a few threads, written in order
@@ -86,15 +92,17 @@ class DevicePath {
   std::unique_ptr<ShardedBamSelect<DevOut>> sharded_;
   std::unique_ptr<OrderedWriter> writer_;
 };
-// a batch through the device on replica (r + dev): the whole of it -- or, early, while the index is not resident, its front
-// half, the reads parked
-BamRunFn DevicePath::run_on(size_t r) {
-  return BamRunFn([this, r](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t dev, int32_t nc, const uint8_t* const* comp, const int64_t* cb,
-                            const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb, svdss_bam_batch_t** batch) {
+// a batch of region r through the device on replica (r + dev): the whole of it -- or, early, while the region's index is not
+// released, its front half, the reads parked.  seam: the one small batch in front of a region, on the assembler's thread:
+// a whole batch, when the region's replica is there.
+BamRunFn DevicePath::run_on(size_t r, bool seam) {
+  return BamRunFn([this, r, seam](svdss_bam_stream_t* st, int64_t seq, int32_t last, int64_t sk, size_t dev, int32_t nc, const uint8_t* const* comp, const int64_t* cb,
+                                  const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* nb, svdss_bam_batch_t** batch) {
     const auto t0 = now();
-    svdss_index_t* ix = early_ ? early_->index_for_feeders() : replicas_[(r + dev) % replicas_.size()];
+    EarlySearch* const es = early_.empty() ? nullptr : early_[r];
+    svdss_index_t* ix = !es ? replicas_[(r + dev) % replicas_.size()] : seam ? es->wait_for_released_index() : es->index_for_feeders();
     int rc = ix ? svdss_bam_batch_run(st, seq, last, sk, ix, nc, comp, cb, blocks, crc, nb, flags_, batch)
-                : svdss_bam_batch_front(st, seq, last, sk, 0, early_->park, nc, comp, cb, blocks, crc, nb, flags_, batch);
+                : svdss_bam_batch_front(st, seq, last, sk, es->device, es->park, nc, comp, cb, blocks, crc, nb, flags_, batch);
     if (rc == SVDSS_OK && !ix) {
       int64_t grp = -1;
       check(svdss_bam_batch_parked(*batch, &grp, nullptr, nullptr), "svdss_bam_batch_parked");
@@ -102,8 +110,8 @@ BamRunFn DevicePath::run_on(size_t r) {
       check(svdss_bam_batch_result(*batch, &r0), "svdss_bam_batch_result");
       int64_t job_comp = 0;
       for (int32_t k = 0; k < nc; ++k) job_comp += cb[k];
-      early_->note_batch(r0.n_records, r0.n_searched, job_comp);
-      if (grp == -1) rc = svdss_bam_batch_search(*batch, early_->wait_for_index());   // no room in the park
+      es->note_batch(r0.n_records, r0.n_searched, job_comp);
+      if (grp == -1) rc = svdss_bam_batch_search(*batch, es->wait_for_index());   // no room in the park
       // (grp == -2: nothing to search in this batch, its results are complete)
     }
     std::lock_guard<std::mutex> lk(t_.m);
@@ -112,11 +120,12 @@ BamRunFn DevicePath::run_on(size_t r) {
   });
 }
 // what a batch object holds after its run -> reads with their SFS.  A batch whose reads went into the park has names and
-// tags only: it waits in the EarlySearch, and drain_park delivers it when its group has been searched.
-std::unique_ptr<DevOut> DevicePath::collect(const svdss_bam_batch_t* batch, uint64_t seq) {
+// tags only: it waits in its region's EarlySearch, and drain_park delivers it when its group has been searched.
+std::unique_ptr<DevOut> DevicePath::collect(size_t region, const svdss_bam_batch_t* batch, uint64_t seq) {
   const auto t1 = now();
+  EarlySearch* const es = early_.empty() ? nullptr : early_[region];
   int64_t grp = -1, first = 0, n_srch = 0;
-  const bool parked = early_ && svdss_bam_batch_parked(batch, &grp, &first, &n_srch) == SVDSS_OK && grp >= 0;
+  const bool parked = es && svdss_bam_batch_parked(batch, &grp, &first, &n_srch) == SVDSS_OK && grp >= 0;
   svdss_bam_result_t r;
   check(svdss_bam_batch_result(batch, &r), "svdss_bam_batch_result");
   std::unique_ptr<DevOut> out = unpack_result(r, parked);
@@ -127,7 +136,7 @@ std::unique_ptr<DevOut> DevicePath::collect(const svdss_bam_batch_t* batch, uint
     for (int k = 0; k < 8; ++k) t_.device[k] += r.stage_ms[k] * 1e-3;
   }
   if (!parked) return out;
-  early_->add_pending(grp, EarlySearch::Pending{seq, std::move(out), first, n_srch});
+  es->add_pending(grp, EarlySearch::Pending{seq, std::move(out), first, n_srch});
   return nullptr;
 }
 void DevicePath::assemble() {
@@ -141,56 +150,74 @@ void DevicePath::assemble() {
   }
   units_.end();
 }
-// early: once the index is resident, the parked groups -- ONE launch each, one lane per read -- and their batches' results
-void DevicePath::drain_park() {
-  svdss_index_t* ix = early_->wait_for_offered_index();
+// early, region r: once its index is resident, its parked groups -- ONE launch each, one lane per read -- and their batches'
+// results.  A region whose run has failed is abandoned: the thread returns at its next look and delivers nothing more.
+void DevicePath::drain_park(size_t r) {
+  EarlySearch* const es = early_[r];
+  svdss_index_t* ix = es->wait_for_offered_index();
   svdss_sfs_batch_t* sfs = nullptr;
   std::vector<int64_t> counts, prefix;
   std::vector<int32_t> qs, ln;
   int64_t n_parked = 0, n_parked_batches = 0, n_groups = 0, n_early_groups = 0;
   double t_search = 0;
-  bool closed = false;
-  for (int64_t g = 0;; ++g) {
+  bool closed = false, abandoned = es->abandoned();
+  for (int64_t g = 0; !abandoned; ++g) {
     // the next group: one that has closed while the index is held back from the feeders, or -- once the feeders have the
     // index and the park is closed -- whatever is left
     for (;;) {
-      if (!closed && early_->released()) {
-        check(svdss_bam_park_close(early_->park), "svdss_bam_park_close");
+      if ((abandoned = es->abandoned())) break;
+      if (!closed && es->released()) {
+        check(svdss_bam_park_close(es->park), "svdss_bam_park_close");
         closed = true;
-        n_groups = svdss_bam_park_groups(early_->park);
+        n_groups = svdss_bam_park_groups(es->park);
       }
-      if (closed || svdss_bam_park_group_ready(early_->park, g)) break;
-      early_->nap();
+      if (closed || svdss_bam_park_group_ready(es->park, g)) break;
+      es->nap();
     }
-    if (closed && g >= n_groups) break;
+    if (abandoned || (closed && g >= n_groups)) break;
     if (!closed) ++n_early_groups;
     int64_t nb = 0, nr = 0, ns = 0;
-    check(svdss_bam_park_group(early_->park, g, &nb, &nr, &ns), "svdss_bam_park_group");
+    check(svdss_bam_park_group(es->park, g, &nb, &nr, &ns), "svdss_bam_park_group");
+    // (every batch of the group has handed in its names and tags -- or the region's run has failed meanwhile)
+    std::vector<EarlySearch::Pending> pending = es->take_group(g, nb);
+    if ((abandoned = es->abandoned())) break;
     const auto t0 = now();
-    check(svdss_bam_park_search(early_->park, g, ix, flags_, &sfs), "svdss_bam_park_search");
+    check(svdss_bam_park_search(es->park, g, ix, flags_, &sfs), "svdss_bam_park_search");
     const int64_t total = svdss_sfs_batch_total(sfs);
     counts.resize((size_t)nr); qs.resize((size_t)total); ln.resize((size_t)total);
     check(svdss_sfs_batch_fetch(sfs, counts.data(), qs.data(), ln.data(), nullptr), "svdss_sfs_batch_fetch");
     t_search += secs(t0, now());
     prefix.assign((size_t)nr + 1, 0);
     for (int64_t i = 0; i < nr; ++i) prefix[(size_t)i + 1] = prefix[(size_t)i] + counts[(size_t)i];
-    for (EarlySearch::Pending& P : early_->take_group(g, nb)) {
+    for (EarlySearch::Pending& P : pending) {
       fill_parked(P, counts, prefix, qs, ln);
-      one_->deliver(P.seq, std::move(P.out));
+      if (one_) one_->deliver(P.seq, std::move(P.out)); else sharded_->deliver(r, P.seq, std::move(P.out));
     }
     n_parked += nr; n_parked_batches += nb;
   }
   if (sfs) svdss_sfs_batch_free(sfs);
   { std::lock_guard<std::mutex> lk(t_.m); t_.device[5] += t_search; }
-  if (o_.verbose)
-    logmsg("debug", "front end beside the index restore: " + std::to_string(n_parked_batches) + " batches (" + std::to_string(early_->records.load()) +
-                        " records) had been read when the index was resident; their " + std::to_string(n_parked) + " reads searched in " +
-                        std::to_string(n_groups) + " launch(es), " + std::to_string(t_search) + " s" +
+  if (o_.verbose && !abandoned)
+    logmsg("debug", (sharded_ ? "region " + std::to_string(r) + ": " : std::string()) + "front end beside the index restore: " + std::to_string(n_parked_batches) +
+                        " batches (" + std::to_string(es->records.load()) + " records) had been read when the index was resident; their " + std::to_string(n_parked) +
+                        " reads searched in " + std::to_string(n_groups) + " launch(es), " + std::to_string(t_search) + " s" +
                         (n_early_groups ? " (" + std::to_string(n_early_groups) + " of them while the file was still being read)" : "") + ", done at +" + clock_.since() + " s");
+}
+// early: region r runs again (its first run's feeding threads have ended, its drain thread has been told: abandon).  What
+// the failed run parked and left pending is discarded -- a fresh park, nothing pending, nothing counted -- and a new drain
+// thread waits for the second run's groups.
+void DevicePath::run_again(size_t r) {
+  EarlySearch* const es = early_[r];
+  svdss_bam_park_free(es->park);
+  es->park = nullptr;
+  check(svdss_bam_park_create(es->device, es->park_bytes, es->park_bytes / 512 + 4096, &es->park), "svdss_bam_park_create");
+  es->reset_for_rerun();
+  drains_[r] = std::thread([this, r] { drain_park(r); });
 }
 void DevicePath::run() {
   const size_t pending = 8;       // (results of the region being dealt that may wait for the assembler)
-  auto collect_fn = [this](const svdss_bam_batch_t* batch, uint64_t seq) { return collect(batch, seq); };
+  auto collect_fn = [this](const svdss_bam_batch_t* batch, uint64_t seq) { return collect(0, batch, seq); };
+  drains_.resize(early_.size());
   if (in_.n_regions() == 1) {
     DeviceBamSelect<DevOut>::Region rg;
     rg.pending = pending;
@@ -198,13 +225,27 @@ void DevicePath::run() {
                                            in_.scanner_ptrs[0]));
   } else {
     ShardedBamSelect<DevOut>::Hooks hk;
-    hk.run = [this](size_t g, bool) { return run_on(g); };
-    hk.collect = [collect_fn](size_t, bool) { return DeviceBamSelect<DevOut>::CollectFn(collect_fn); };
+    hk.run = [this](size_t g, bool seam) { return run_on(g, seam); };
+    hk.collect = [this](size_t g, bool) {
+      return DeviceBamSelect<DevOut>::CollectFn([this, g](const svdss_bam_batch_t* batch, uint64_t seq) { return collect(g, batch, seq); });
+    };
+    if (!early_.empty()) {
+      // (a region's front is finished when the last feeding thread of its run ends; a run that failed is abandoned first)
+      hk.fed = [this](size_t g) { early_[g]->front_finished(); };
+      hk.abandon = [this](size_t g) { early_[g]->abandon(); if (drains_[g].joinable()) drains_[g].join(); };
+    }
     hk.again = [this](size_t g, const std::string& why) {
       if (o_.verbose) logmsg("debug", "region " + std::to_string(g) + " runs again from the end of region " + std::to_string(g - 1) +
                                           (why.empty() ? std::string(" (its first record was not where the chain arrives)") : " (" + why + ")"));
+      if (!early_.empty()) run_again(g);
     };
-    sharded_.reset(new ShardedBamSelect<DevOut>(o_.bam, hk, in_.n_ref, in_.skip, knobs_.feeders, knobs_.batch_bytes, in_.cuts, pending, in_.scanner_ptrs));
+    // (early: a region's first batches are small -- a quarter, then half of a batch.  Its GPU has work, its counters have
+    // figures for the sum the process decides from, and its guessed head is final after a quarter of the bytes; with the
+    // index first, as before, every batch is a whole one)
+    sharded_.reset(new ShardedBamSelect<DevOut>(o_.bam, hk, in_.n_ref, in_.skip, knobs_.feeders, knobs_.batch_bytes, in_.cuts, pending, in_.scanner_ptrs,
+                                                !early_.empty()));
+    // (from here on the assembler alone touches drains_ -- the hooks above run on its thread -- until it has ended)
+    for (size_t g = 0; g < early_.size(); ++g) drains_[g] = std::thread([this, g] { drain_park(g); });
   }
   std::thread assembler([this] { assemble(); });
   writer_.reset(new OrderedWriter(units_.pool()));
@@ -212,13 +253,15 @@ void DevicePath::run() {
   const int n_fmt = knobs_.format_threads ? knobs_.format_threads : (int)std::max<size_t>(5, std::min<size_t>(5 * replicas_.size(), effective_cpus()));
   std::vector<std::thread> fmt;
   for (int k = 0; k < n_fmt; ++k) fmt.emplace_back([this] { units_.format_units(*writer_); });
-  if (early_) {
-    std::thread drain([this] { drain_park(); });
+  if (one_ && !early_.empty()) {
+    drains_[0] = std::thread([this] { drain_park(0); });
     one_->wait_finished();
-    early_->front_finished();
-    drain.join();
+    early_[0]->front_finished();
+    drains_[0].join();
   }
+  // (regions: the assembler has dealt everything when every drain thread has delivered everything)
   assembler.join();
+  if (sharded_) for (std::thread& th : drains_) if (th.joinable()) th.join();
   for (std::thread& th : fmt) th.join();
   writer_->finish();
   if (o_.verbose) report();
@@ -635,6 +678,7 @@ struct SearchRun {
   void choose_rank_blocks_alone();
   void index_to_device();
   void release_index_to_front_end();
+  void release_replicas_to_front_ends();
   void replicate();
   void run_device_path();
   void run_host_path();
@@ -655,7 +699,9 @@ struct SearchRun {
   std::unique_ptr<BamReader> bam;      // BAM on the host path
   std::unique_ptr<FastxReader> fx;
   std::thread prewarm;
-  std::unique_ptr<EarlySearch> early;
+  // the early path: one EarlySearch (one GPU, one region) or one per region of the file, region g on GPU g % n_dev
+  std::vector<std::unique_ptr<EarlySearch>> earlies;
+  std::vector<EarlySearch*> early;     // (the same, as the decision and the device path take them; empty: the index first)
   std::thread front_end;
   svdss_index_t* ix = nullptr;
   bool user_kmer = false, lf_only = false;
@@ -695,8 +741,13 @@ void SearchRun::open_input() {
     if (bam->ok() && knobs.prewarm) prewarm = std::thread([this] { bam->prewarm(); });
   }   // (FASTX: opened when the index is resident, run_host_path)
 }
-// One GPU, one region: the BAM front end starts NOW, beside the index restore (EarlySearch; SVDSS_SEARCH_EARLY=0: the index
-// first, as PingPong::run does, ping_pong.cpp:245,329).  The park's first arena is allocated before the restore begins.
+// The BAM front end starts NOW, beside the index restore (EarlySearch; SVDSS_SEARCH_EARLY=0: the index first, as
+// PingPong::run does, ping_pong.cpp:245,329) -- on one GPU with the file as one region, and with --gpus N when the file
+// has been cut into one region per GPU: every region then has its own park, on its own GPU, allocated before the restore
+// begins.  Everything else stays index-first, as it was: SVDSS_REGION_SHARDS=0 or a file too small for N regions (one
+// region, all GPUs' feeders), --region with a BAI (one stream on one GPU), SVDSS_BAM_DEVICE=0, --fastx, and
+// SVDSS_SEARCH_EARLY=0 -- the order every test of the early path is compared with.  (`smooth`, `call` and `run` have
+// their own hosts and do not come here.)
 void SearchRun::start_front_end_early() {
   // (It pays when the restore takes seconds: an index of a chr20-length reference is resident in 0.4 s, and sharing the GPU
   // with the front end meanwhile only delays it -- 1.87 against 1.55 s per 1.03 M reads, profiles/r06t_*.  The sidecar holds
@@ -707,16 +758,36 @@ void SearchRun::start_front_end_early() {
     struct stat sti;
     if (stat((o.index + ".svdss").c_str(), &sti) == 0 || stat(o.index.c_str(), &sti) == 0) early_pays = (int64_t)sti.st_size >= (knobs.early_min_mb << 20);
   }
-  if (!(dev_bam && early_pays && in.n_regions() == 1 && n_gpus == 1 && knobs.early != 0)) return;
+  const size_t n_regions = dev_bam ? in.n_regions() : 0;
+  const bool shaped = n_gpus == 1 ? n_regions == 1 : n_regions == (size_t)n_gpus;
+  if (!(dev_bam && early_pays && shaped && knobs.early != 0)) return;
   if (o.bsize <= 0) die("batch size smaller than the number of threads");
-  early.reset(new EarlySearch);
-  struct stat stb;
-  early->file_bytes = stat(o.bam.c_str(), &stb) == 0 ? (int64_t)stb.st_size : 0;
+  for (size_t g = 0; g < n_regions; ++g) {
+    earlies.emplace_back(new EarlySearch);
+    early.push_back(earlies.back().get());
+    EarlySearch& es = *earlies.back();
+    es.device = (int32_t)(g % (size_t)n_dev);
+    // (regions that share a GPU -- more --gpus than devices, SVDSS_GPUS_OVERSUBSCRIBE -- share its park bytes)
+    es.park_bytes = park_bytes_of_region(knobs.park_bytes, n_regions, (size_t)n_dev, g);
+    if (n_regions == 1) {
+      struct stat stb;
+      es.file_bytes = stat(o.bam.c_str(), &stb) == 0 ? (int64_t)stb.st_size : 0;
+    } else {
+      es.file_bytes = (int64_t)(in.cuts[g + 1] - in.cuts[g]);
+      es.regions = &early;
+    }
+  }
   // (on a thread of its own from the first moment: this one goes straight to the index file)
   front_end = std::thread([this] {
-    check(svdss_bam_park_create(0, knobs.park_bytes, knobs.park_bytes / 512 + 4096, &early->park), "svdss_bam_park_create");
+    for (EarlySearch* es : early) check(svdss_bam_park_create(es->device, es->park_bytes, es->park_bytes / 512 + 4096, &es->park), "svdss_bam_park_create");
     if (prewarm.joinable()) prewarm.join();
-    DevicePath(o, knobs, std::vector<svdss_index_t*>(1, nullptr), in, clock, early.get()).run();
+    if (o.verbose && in.n_regions() > 1) {
+      std::string m = "file regions (bytes):";
+      for (size_t g = 0; g + 1 < in.cuts.size(); ++g) m += " " + std::to_string(in.cuts[g + 1] - in.cuts[g]);
+      logmsg("debug", m + "; every region's front end runs beside the index restore");
+    }
+    // (no replica yet: each region's EarlySearch hands its feeders theirs; one slot per GPU, for what is sized per GPU)
+    DevicePath(o, knobs, std::vector<svdss_index_t*>(early.size(), nullptr), in, clock, early).run();
   });
 }
 // (Tried: the rank blocks of the sidecar read beside the records, on a thread of their own, so that they are in memory when
@@ -724,28 +795,67 @@ void SearchRun::start_front_end_early() {
 // 0.4 s later and the blocks no sooner -- 5x `search` 2.4 -> 2.7 s.  They are read when they are wanted.)
 void SearchRun::load_index() {
   check(svdss_index_load(o.index.c_str(), &ix), "svdss_index_load");
-  if (early) early->index_n.store(svdss_index_size(ix));
+  for (EarlySearch* es : early) es->index_n.store(svdss_index_size(ix));
   if (o.verbose) logmsg("debug", "index file read at +" + clock.since() + " s");
 }
 void SearchRun::choose_kmer_order() { user_kmer = ::choose_kmer_order(bam_mode ? o.bam : o.fastx, bam_mode, ix, o.verbose); }   // (sfs_units.h)
 void SearchRun::choose_rank_blocks_alone() {
-  if (early) lf_only = ::choose_rank_blocks_alone(knobs, *early, ix, o.index, user_kmer, o.verbose, clock);   // (sfs_units.h)
+  // (one decision for the process, from the sum over the regions' front ends; the blocks are read once: sfs_units.h)
+  if (!early.empty()) lf_only = ::choose_rank_blocks_alone(knobs, early, ix, o.index, user_kmer, o.verbose, clock, n_gpus);
 }
 void SearchRun::index_to_device() {
   check(svdss_index_to_device(ix, 0), "svdss_index_to_device");
   if (o.verbose) logmsg("debug", "index and k-mer table on the device at +" + clock.since() + " s" +
                                      (lf_only ? " (rank blocks alone: few reads to search)"
-                                      : early && svdss_index_kmer(ix) < 16 ? " (table of order " + std::to_string(svdss_index_kmer(ix)) + ": few reads to search)" : ""));
+                                      : !early.empty() && svdss_index_kmer(ix) < 16 ? " (table of order " + std::to_string(svdss_index_kmer(ix)) + ": few reads to search)" : ""));
 }
 // the early path's second half: the front end gets the index, searches what it parked and goes on with whole batches
 void SearchRun::release_index_to_front_end() {
-  if (lf_only) early->offer_index_held_back(ix);
+  EarlySearch* const es = early[0];
+  if (lf_only) es->offer_index_held_back(ix);
   logmsg("info", "Extracting SFS strings on the GPU (output order as with " + std::to_string(o.threads) + " threads)..");
   // (SVDSS_EARLY_HOLD_MS, for the tests: the index is held back that long, as if its restore had taken seconds)
   if (knobs.early_hold_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(knobs.early_hold_ms));
-  early->release_index(ix);
+  es->release_index(ix);
   front_end.join();
   replicas.assign(1, ix);
+}
+// ... with --gpus N: every GPU's replica is made resident at once -- svdss_index_to_device on GPU 0, svdss_index_replicate
+// for the others (the rank blocks alone: uploads from the ONE host copy; else a build per GPU from the records) -- on a
+// thread per region, which then hands ITS region its replica: held back until that region's front end is through or its
+// park is full when the index is the rank blocks alone (offer_index_held_back blocks: hence the thread), then released.
+// Region 0 does not wait for the other replicas, and no region for another region's front end.
+void SearchRun::release_replicas_to_front_ends() {
+  logmsg("info", "Extracting SFS strings on the GPU (output order as with " + std::to_string(o.threads) + " threads)..");
+  replicas.assign((size_t)n_gpus, ix);
+  // (which form was taken is said once: choose_rank_blocks_alone says the other)
+  if (o.verbose && !lf_only) logmsg("debug", "the index as a full restore on each of " + std::to_string(n_gpus) + " GPUs, built beside the regions' front ends from +" + clock.since() + " s");
+  // (more replicas than GPUs, SVDSS_GPUS_OVERSUBSCRIBE: full builds that share a GPU go one after the other -- the
+  // buffers of two suffix sorts are not meant to fit side by side, and one GPU gains nothing from two at once)
+  std::mutex m;
+  std::condition_variable cv;
+  std::vector<char> resident((size_t)n_gpus, 0);
+  std::vector<std::thread> th;
+  for (int d = 0; d < n_gpus; ++d)
+    th.emplace_back([this, &m, &cv, &resident, d] {
+      if (!lf_only && d >= n_dev) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return resident[(size_t)(d - n_dev)] != 0; }); }
+      const int rc = d == 0 ? svdss_index_to_device(ix, 0) : svdss_index_replicate(ix, d % n_dev, &replicas[(size_t)d]);
+      if (rc != SVDSS_OK) check(rc, d == 0 ? "svdss_index_to_device" : "svdss_index_replicate");     // (the regions' feeders wait for it: the run ends here)
+      { std::lock_guard<std::mutex> lk(m); resident[(size_t)d] = 1; }
+      cv.notify_all();
+      svdss_index_t* mine = replicas[(size_t)d];
+      if (o.verbose) logmsg("debug", "GPU " + std::to_string(d % n_dev) + ": replica " + std::to_string(d) + " of the index resident at +" + clock.since() + " s" +
+                                         (lf_only ? " (rank blocks alone, uploaded from the one host copy)"
+                                          : svdss_index_kmer(mine) < 16 ? " (table of order " + std::to_string(svdss_index_kmer(mine)) + ")" : ""));
+      EarlySearch* const es = early[(size_t)d];
+      if (lf_only) es->offer_index_held_back(mine);
+      // (SVDSS_EARLY_HOLD_MS, for the tests: the index is held back that long, as if its restore had taken seconds)
+      if (knobs.early_hold_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(knobs.early_hold_ms));
+      es->release_index(mine);
+    });
+  for (std::thread& t : th) t.join();
+  logmsg("info", "Index replicated on " + std::to_string(n_gpus) + " GPUs");
+  front_end.join();
 }
 // --gpus N: one replica of the index per GPU; the batches of reads go to whichever GPU is free, the
 // text is written in input order whatever GPU searched a batch -- the same bytes as with one GPU
@@ -806,7 +916,7 @@ int SearchRun::finish() {
     fflush(stderr);
     _exit(0);
   }
-  if (early) svdss_bam_park_free(early->park);
+  for (EarlySearch* es : early) svdss_bam_park_free(es->park);
   for (svdss_index_t* r : replicas) svdss_index_free(r);
   return 0;
 }
@@ -821,10 +931,13 @@ int main_search(const Options& o, time_t process_start) {
   run.load_index();
   run.choose_kmer_order();
   run.choose_rank_blocks_alone();
-  run.index_to_device();
-  if (run.early) {
+  if (run.early.size() > 1) {
+    run.release_replicas_to_front_ends();
+  } else if (!run.early.empty()) {
+    run.index_to_device();
     run.release_index_to_front_end();
   } else {
+    run.index_to_device();
     run.replicate();
     if (run.dev_bam) run.run_device_path(); else run.run_host_path();
   }

@@ -20,6 +20,7 @@
 
 #include "host_common.h"
 #include "cli_options.h"
+#include "early_estimate.h"
 
 namespace {
 
@@ -284,31 +285,50 @@ struct DevOut { std::vector<Read> reads; std::vector<int32_t> qs, ln; int64_t n_
 // the feeders have no index they run the front half of their batches and park the unpacked reads in HBM; when the index is
 // there the parked groups are searched one large launch each (the drain thread), and the feeders go on with whole batches.
 //
-// Who touches what: `park` and `file_bytes` are set before the first feeder runs and only read then; the four counters are
-// atomics, added to by the feeders and read by anyone; everything private is under `m_`, reached through the methods alone,
-// and `cv_` is notified on every change somebody may wait for.
+// Who touches what: `park`, `device`, `park_bytes`, `file_bytes` and `regions` are set before the first feeder runs and
+// only read then; the four counters are atomics, added to by the feeders and read by anyone; everything private is under
+// `m_`, reached through the methods alone, and `cv_` is notified on every change somebody may wait for.
+//
+// --gpus N: one EarlySearch per region of the file, each with a park on its region's GPU and an index handle of its own
+// (that GPU's replica); `regions` names all of them, and what the process decides ONCE -- the order of the k-mer table,
+// the form the index becomes resident in -- comes from the sum over them (early_estimate.h).
 class EarlySearch {
  public:
   struct Pending { uint64_t seq; std::unique_ptr<DevOut> out; int64_t first, n; };
   svdss_bam_park_t* park = nullptr;
-  int64_t file_bytes = 0;
+  int32_t device = 0;                 // where the park lives and the front halves run
+  int64_t park_bytes = 0;             // what the park was created with (a region that runs again gets a fresh one)
+  int64_t file_bytes = 0;             // of the file, or of this front end's region of it
+  const std::vector<EarlySearch*>* regions = nullptr;   // every region's, this one included (null: this is the only one)
   // what the front end has seen so far (the order of the k-mer table is chosen from it: svdss_index_kmer_limit)
   std::atomic<int64_t> records{0}, searched{0}, comp_bytes{0}, index_n{0};
 
   // feeder, before a batch: the index if the feeders have it (a whole batch) -- null: the front half, the reads parked
   svdss_index_t* index_for_feeders() { std::lock_guard<std::mutex> lk(m_); return ready_ ? ix_ : nullptr; }
-  // how many reads there will be to search, from what has been seen (-1: nothing seen yet); both cost models use it
-  double estimate_reads_to_search() const {
-    const int64_t recs = records.load(), srch = searched.load(), cb = comp_bytes.load();
-    return recs > 0 && cb > 0 ? (double)srch / (double)recs * ((double)recs * (double)file_bytes / (double)cb) : -1;
+  EarlyCounters counters() {
+    EarlyCounters c;
+    c.records = records.load(); c.searched = searched.load(); c.comp_bytes = comp_bytes.load(); c.file_bytes = file_bytes;
+    c.front_done = front_is_finished();
+    return c;
   }
+  // how many reads there will be to search, from what has been seen (-1: nothing seen yet); both cost models use it
+  double estimate_reads_to_search() { return ::estimate_reads_to_search(counters()); }
   // feeder, after a front half: the counters, and from them the order of the k-mer table (its build begins when the suffix
-  // array is sorted; the limit is read then)
+  // array is sorted; the limit is read then).  The limit is the process's: with several regions it comes from their sum,
+  // once every region has seen enough to be asked.
   void note_batch(int64_t n_records, int64_t n_searched, int64_t batch_comp_bytes) {
     const int64_t recs = (records += n_records);
     searched += n_searched; comp_bytes += batch_comp_bytes;
-    if (index_n.load() < ((int64_t)1 << 31) || recs < 50000 || getenv("SVDSS_KMER") || getenv("SVDSS_NO_KMER_LIMIT")) return;
-    const double est = estimate_reads_to_search();
+    if (index_n.load() < ((int64_t)1 << 31) || recs < kEarlyEstimateRecords || getenv("SVDSS_KMER") || getenv("SVDSS_NO_KMER_LIMIT")) return;
+    double est = -1;
+    if (regions) {
+      std::vector<EarlyCounters> all;
+      for (EarlySearch* e : *regions) all.push_back(e->counters());
+      if (!estimate_wait_over(all, 0)) return;
+      est = summed_estimate(all);
+    } else {
+      est = estimate_reads_to_search();
+    }
     if (est < 0) return;
     // build: 1.6 s at K = 16, a quarter of that per step down; kernel: 16 M reads/s at K = 16, half of that per step down
     // (profiles/r05i_restore_by_table_order.txt); its seconds count double, as in choose_kmer_order
@@ -316,8 +336,10 @@ class EarlySearch {
     int best = 16;
     for (int k = 15; k >= 12; --k) if (cost(k) < cost(best)) best = k;
     if (cost(best) > 0.8 * cost(16)) best = 16;     // (a clear gain or none)
-    std::lock_guard<std::mutex> lk(m_);
-    if (best != kmer_limit_) { kmer_limit_ = best; svdss_index_kmer_limit(best == 16 ? 0 : best); }
+    static std::mutex limit_m;      // (the library's limit is one for the process: so is the last one given)
+    static int kmer_limit = 0;
+    std::lock_guard<std::mutex> lk(limit_m);
+    if (best != kmer_limit) { kmer_limit = best; svdss_index_kmer_limit(best == 16 ? 0 : best); }
   }
   // feeder whose batch found no room in the park (or it has just been closed): the batch waits here for the index
   svdss_index_t* wait_for_index() {
@@ -330,7 +352,8 @@ class EarlySearch {
   void add_pending(int64_t group, Pending p) { change([&] { by_group_[group].push_back(std::move(p)); }); }
   std::vector<Pending> take_group(int64_t group, int64_t n) {
     std::unique_lock<std::mutex> lk(m_);
-    wait_for(lk, [&] { return (int64_t)by_group_[group].size() == n; });
+    wait_for(lk, [&] { return abandoned_ || (int64_t)by_group_[group].size() == n; });
+    if (abandoned_) return std::vector<Pending>();
     return std::move(by_group_[group]);
   }
   // main thread: the index is resident but held back from the feeders (the rank blocks alone, resident long before the file
@@ -349,7 +372,19 @@ class EarlySearch {
   void front_finished() { change([&] { front_done_ = true; }); }
   bool front_is_finished() { std::lock_guard<std::mutex> lk(m_); return front_done_; }
   // drain thread: the index once it is offered or released; whether the feeders have it; a short wait for news
-  svdss_index_t* wait_for_offered_index() { std::unique_lock<std::mutex> lk(m_); return wait_for(lk, [&] { return ready_ || ix_avail_; }); }
+  svdss_index_t* wait_for_offered_index() { std::unique_lock<std::mutex> lk(m_); return wait_for(lk, [&] { return ready_ || ix_avail_ || abandoned_; }); }
+  // the seam in front of a region (one small batch, on the thread that deals the regions): the index once the feeders have it
+  svdss_index_t* wait_for_released_index() { std::unique_lock<std::mutex> lk(m_); return wait_for(lk, [&] { return ready_; }); }
+  // A region whose first run has failed runs again (ShardedBamSelect): abandon() when its feeding threads have ended --
+  // the drain thread returns at its next look, searching and delivering nothing more --, then, with the drain thread
+  // joined and the park emptied, reset_for_rerun(): nothing pending, nothing counted (the sum over the regions counts a
+  // region once), the front not finished.  What is known of the index stays.
+  void abandon() { change([&] { abandoned_ = true; }); }
+  bool abandoned() { std::lock_guard<std::mutex> lk(m_); return abandoned_; }
+  void reset_for_rerun() {
+    change([&] { by_group_.clear(); front_done_ = park_full_ = abandoned_ = false; });
+    records.store(0); searched.store(0); comp_bytes.store(0);
+  }
   bool released() { std::lock_guard<std::mutex> lk(m_); return ready_; }
   void nap() { std::unique_lock<std::mutex> lk(m_); cv_.wait_for(lk, std::chrono::milliseconds(2)); }
  private:
@@ -360,8 +395,7 @@ class EarlySearch {
   svdss_index_t* ix_ = nullptr;      // set once, with ready_ -- or before it, with ix_avail_
   bool ready_ = false, ix_avail_ = false;
   std::map<int64_t, std::vector<Pending>> by_group_;
-  bool front_done_ = false, park_full_ = false;
-  int kmer_limit_ = 0;               // the last limit given
+  bool front_done_ = false, park_full_ = false, abandoned_ = false;
 };
 
 // what a batch object holds after its run -> reads with their SFS; of a parked batch names and tags only (counts and SFS
@@ -496,33 +530,45 @@ inline bool choose_kmer_order(const std::string& input, bool bam_mode, svdss_ind
 // True: the blocks are attached.
 // The decision alone (`run --samples` takes it for every sample while the rank blocks alone are resident, and attaches
 // nothing): est / t_est: the estimate it rests on and when it was known.
-inline bool wants_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, int64_t index_n, bool user_kmer, const Stopwatch& clock, double& est,
-                                    std::string& t_est) {
+// early: one front end, or one per region of the file (--gpus N) -- ONE decision, from the sum over them, taken when
+// every one of them has seen 50,000 records or finished its front, or after 1.5 s (early_estimate.h).
+inline bool wants_rank_blocks_alone(const SearchKnobs& knobs, const std::vector<EarlySearch*>& early, int64_t index_n, bool user_kmer, const Stopwatch& clock,
+                                    double& est, std::string& t_est) {
   if (user_kmer || knobs.lf == 0) return false;
   const bool forced = knobs.lf == 1;
   const auto w0 = now();
-  while (!forced && !early.front_is_finished() && early.records.load() < 50000 && secs(w0, now()) <= 1.5)
-    std::this_thread::sleep_for(std::chrono::milliseconds(5));
-  est = early.estimate_reads_to_search();
+  std::vector<EarlyCounters> seen;
+  auto look = [&] { seen.clear(); for (EarlySearch* e : early) seen.push_back(e->counters()); };
+  for (look(); !forced && !estimate_wait_over(seen, secs(w0, now())); look()) std::this_thread::sleep_for(std::chrono::milliseconds(5));
+  est = summed_estimate(seen);
   t_est = clock.since();
   // (what the rank structure alone saves is the rest of the restore -- ~4.5 s at GRCh38 lengths, in proportion for a
   // smaller reference --, what it costs is the search at ~1 M reads/s instead of 8 - 24 M: worth it below ~2 M reads
   // per 6.2e9 BWT symbols; profiles/r06q_*)
-  const double lf_max = knobs.lf_max_set ? knobs.lf_max : 2e6 * (double)index_n / 6.18e9;
-  return forced || (est >= 0 && est <= lf_max);
+  return forced || rank_blocks_alone_pay(est, knobs.lf_max_set, knobs.lf_max, index_n);
 }
-inline bool choose_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, svdss_index_t* ix, const std::string& index_path, bool user_kmer,
-                                     bool verbose, const Stopwatch& clock) {
+inline bool wants_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, int64_t index_n, bool user_kmer, const Stopwatch& clock, double& est,
+                                    std::string& t_est) {
+  return wants_rank_blocks_alone(knobs, std::vector<EarlySearch*>(1, &early), index_n, user_kmer, clock, est, t_est);
+}
+// (n_gpus > 1: the blocks are read from the sidecar ONCE, here, and every GPU gets them from this one host copy)
+inline bool choose_rank_blocks_alone(const SearchKnobs& knobs, const std::vector<EarlySearch*>& early, svdss_index_t* ix, const std::string& index_path,
+                                     bool user_kmer, bool verbose, const Stopwatch& clock, int n_gpus = 1) {
   double est = -1;
   std::string t_est;
   if (!wants_rank_blocks_alone(knobs, early, svdss_index_size(ix), user_kmer, clock, est, t_est)) return false;
   const int rc = svdss_index_attach_blocks(ix, index_path.c_str());
   if (rc == SVDSS_OK) {
-    if (verbose) logmsg("debug", "~" + std::to_string((long long)std::max(0.0, est)) + " reads to search (known at +" + t_est + " s): the index as a rank structure alone (blocks read at +" + clock.since() + " s)");
+    if (verbose) logmsg("debug", "~" + std::to_string((long long)std::max(0.0, est)) + " reads to search (known at +" + t_est + " s): the index as a rank structure alone (blocks read" +
+                                     (n_gpus > 1 ? " once for " + std::to_string(n_gpus) + " GPUs," : "") + " at +" + clock.since() + " s)");
     return true;
   }
   if (rc != SVDSS_EINVAL) check(rc, "svdss_index_attach_blocks");
   return false;
+}
+inline bool choose_rank_blocks_alone(const SearchKnobs& knobs, EarlySearch& early, svdss_index_t* ix, const std::string& index_path, bool user_kmer,
+                                     bool verbose, const Stopwatch& clock) {
+  return choose_rank_blocks_alone(knobs, std::vector<EarlySearch*>(1, &early), ix, index_path, user_kmer, verbose, clock);
 }
 
 }  // namespace
