@@ -494,6 +494,71 @@ int svdss_bam_smooth_set_index(svdss_bam_smooth_t* sm, int32_t min_shift, int32_
  * fragments' offsets inside a block do not depend on it; the compressed offsets follow the members' lengths. */
 int svdss_bam_smooth_set_deflate(svdss_bam_smooth_t* sm, int32_t mode);
 int svdss_bam_batch_index(const svdss_bam_batch_t* b, svdss_bam_index_frag_t* out);
+/* ---- the index of the INPUT BAM (`SVDSS bamindex`, `call / run --write-bam-index`; csrc/bam_device.hip, csrc/bam_index_writer.h)
+ * Seam: what `samtools index` (htslib's bam_index_build: hts_idx_push per record read by sam_read1) does in a pass of its own
+ * in front of run_svdss; here the records are indexed where the device path has them anyway, inflated in HBM.
+ * svdss_bam_stream_set_input_index(s, min_shift, depth), before batch 0 (min_shift 0: off, the default; BAI is 14 / 5): every
+ * entry point that runs a batch of the stream -- svdss_bam_batch_front / _run, svdss_bam_select_run / _select_store_run,
+ * svdss_bam_smooth_measure / _run -- leaves the batch's input-side fragments on the batch object (svdss_bam_batch_input_index).
+ * EVERY record that starts in the batch's turn counts, whatever its flag or mapq, and in front of the record gate
+ * (svdss_bam_stream_set_regions): tid >= 0 is indexed at [pos, bam_endpos) (a span of 0 counts as 1), tid < 0 is counted.
+ * Off, nothing more is launched, allocated or copied; what the entry points return does not depend on the switch.
+ * Virtual offsets are relative to the batch's first member: (compressed offset of the member that holds the byte, from the
+ * first member's gzip header) << 16 | offset in it.  A position at a member boundary is the start of the next non-empty
+ * member; the end of the batch's last byte is comp_bytes << 16 (ends_at_boundary: to be moved to the next non-empty member
+ * of the file, or to its EOF marker, by whoever folds the batches).  A record that began in an earlier batch starts where
+ * its first byte is: the stream remembers the virtual offset of its carry; such an offset is below the batch's base and
+ * wraps as an unsigned number (adding the base << 16 modulo 2^64 gives the file's). */
+typedef struct svdss_bam_input_chunk {
+  int32_t tid;
+  uint32_t bin;
+  int64_t n_rec, n_unmapped;      /* records of the run; those of them with flag 4 set */
+  uint64_t v_beg, v_end;          /* first record's start, last record's end */
+} svdss_bam_input_chunk_t;
+typedef struct svdss_bam_input_window {
+  int32_t tid;
+  int32_t window;                 /* position >> min_shift */
+  uint64_t v_beg;                 /* start of the first record of the batch that reaches into the window */
+} svdss_bam_input_window_t;
+typedef struct svdss_bam_input_frag {
+  int32_t on;                     /* 0: the stream's switch was off (everything else is 0) */
+  int32_t unsorted;               /* a record starts before the one in front of it (tid, then position; tid < 0 behind all) */
+  int64_t n_records, n_no_coor;   /* records that start in this batch's turn; those with tid < 0 */
+  int64_t n_chunks;
+  const svdss_bam_input_chunk_t* chunks;    /* runs of consecutive indexed records with the same (tid, bin), in file order */
+  int64_t n_windows;
+  const svdss_bam_input_window_t* windows;  /* in file order */
+  int32_t first_tid, last_tid;    /* the first and last record (n_records > 0) */
+  int64_t first_beg, last_beg;
+  int64_t comp_bytes;             /* compressed length of the batch's members: the next batch's base is this batch's + comp_bytes */
+  int64_t first_data;             /* compressed offset of the batch's first non-empty member (-1: it has none) */
+  int32_t ends_at_boundary;       /* the last record ends with the batch's last byte */
+} svdss_bam_input_frag_t;
+int svdss_bam_stream_set_input_index(svdss_bam_stream_t* s, int32_t min_shift, int32_t depth);
+int svdss_bam_batch_input_index(const svdss_bam_batch_t* b, svdss_bam_input_frag_t* out);
+/* `SVDSS bamindex`: a batch through the front end alone -- blocks up, inflate, CRC, the record chain, the batch's turn and
+ * (with the switch on) the index kernels; nothing is filtered, unpacked or copied down but the fragments.  n_records of the
+ * batch: svdss_bam_input_frag_t.  Errors as svdss_bam_batch_run ("corrupt record" for fields that do not fit a block_size). */
+int svdss_bam_index_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, int32_t device,
+                        int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
+                        const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                        svdss_bam_batch_t** out);
+/* Regions of a file (svdss_bam_stream_region).  svdss_bam_stream_input_seam, after the last batch: *carry_v = the virtual
+ * offset of the first byte of the tail, relative to the member right behind the region (has_carry 0: no tail); *head_v = the
+ * virtual offset of the first record the chain of an open_start region was started at, relative to the region's first member.
+ * A record the seam completes begins at the first and ends at the second.  svdss_bam_stream_set_input_carry, before batch 0
+ * of a region that runs again from a known carry: where that carry's first byte is, relative to the region's first member. */
+int svdss_bam_stream_input_seam(const svdss_bam_stream_t* s, int32_t* has_carry, int64_t* carry_v, int64_t* head_v);
+int svdss_bam_stream_set_input_carry(svdss_bam_stream_t* s, int64_t carry_v);
+/* The fold (BamIndexBuilder, csrc/bam_index_writer.h) for callers without C++: fragments in file order, each with the file
+ * offset of its batch's first member; finish with the offset of the file's EOF marker (or the file's size where it has none)
+ * gives the BAI (csi 0) or CSI bytes, owned by the object.  create: SVDSS_ERANGE for a BAI with a reference longer than
+ * 2^29 - 1; finish: SVDSS_EIO where the records are not sorted by coordinate. */
+typedef struct svdss_bam_input_indexer svdss_bam_input_indexer_t;
+int svdss_bam_input_indexer_create(int32_t n_ref, const int32_t* ref_len, int32_t csi, int32_t* min_shift, int32_t* depth, svdss_bam_input_indexer_t** out);
+int svdss_bam_input_indexer_add(svdss_bam_input_indexer_t* ix, const svdss_bam_input_frag_t* f, int64_t base);
+int svdss_bam_input_indexer_finish(svdss_bam_input_indexer_t* ix, int64_t end_offset, const uint8_t** bytes, int64_t* n_bytes);
+void svdss_bam_input_indexer_free(svdss_bam_input_indexer_t* ix);
 /* `smooth --index --sfs` (csrc/bam_smooth.hip): one pass over the original BAM yields what `SVDSS search` would find in the
  * smoothed one.  Seam: ping_pong.cpp:53-128 read the smoothed file back (load_batch_bam :66-104: flag and l_qseq filters,
  * qname, HP, XF, seq_nt16 -> nt6); here those fields are taken from the rebuilt records while they are in HBM.

@@ -142,6 +142,15 @@ SIGNATURES = {
     "svdss_bam_smooth_search": (C.c_int, [_p, _p]),
     "svdss_bam_batch_index": (C.c_int, [_p, _p]),
     "svdss_bam_batch_error": (C.c_char_p, [_p]),
+    "svdss_bam_stream_set_input_index": (C.c_int, [_p, _i32, _i32]),
+    "svdss_bam_stream_set_input_carry": (C.c_int, [_p, _i64]),
+    "svdss_bam_stream_input_seam": (C.c_int, [_p, _p, _pi64, _pi64]),
+    "svdss_bam_batch_input_index": (C.c_int, [_p, _p]),
+    "svdss_bam_index_run": (C.c_int, [_p, _i64, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(_p)]),
+    "svdss_bam_input_indexer_create": (C.c_int, [_i32, _p, _i32, _p, _p, C.POINTER(_p)]),
+    "svdss_bam_input_indexer_add": (C.c_int, [_p, _p, _i64]),
+    "svdss_bam_input_indexer_finish": (C.c_int, [_p, _i64, C.POINTER(_p), _pi64]),
+    "svdss_bam_input_indexer_free": (None, [_p]),
     "svdss_bam_filter_create": (C.c_int, [_i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _i64, C.POINTER(_p)]),
     "svdss_bam_filter_free": (None, [_p]),
     "svdss_bam_select_run": (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _p, _p, _p, _p, _p, C.POINTER(_p)]),

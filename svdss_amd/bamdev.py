@@ -142,10 +142,76 @@ class BamSelection(C.Structure):
                 ("slim", C.c_int32)]
 
 
-def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20, device=0, gate=None):
+class BamInputFrag(C.Structure):
+    _fields_ = [("on", C.c_int32), ("unsorted", C.c_int32), ("n_records", C.c_int64), ("n_no_coor", C.c_int64), ("n_chunks", C.c_int64),
+                ("chunks", C.c_void_p), ("n_windows", C.c_int64), ("windows", C.c_void_p), ("first_tid", C.c_int32), ("last_tid", C.c_int32),
+                ("first_beg", C.c_int64), ("last_beg", C.c_int64), ("comp_bytes", C.c_int64), ("first_data", C.c_int64),
+                ("ends_at_boundary", C.c_int32)]
+
+
+def set_input_index(stream, scheme):
+    """svdss_bam_stream_set_input_index: `scheme` = (min_shift, depth), None: the switch stays off.  Before the stream's batch 0."""
+    if scheme is None:
+        return
+    rc = lib.svdss_bam_stream_set_input_index(stream, int(scheme[0]), int(scheme[1]))
+    if rc:
+        raise SvdssError(rc, "svdss_bam_stream_set_input_index")
+
+
+def bam_ref_lengths(data, blocks):
+    """the reference lengths of the BAM header, in order"""
+    n_ref, skip = bam_header(data, blocks)
+    buf = b""
+    for coff, clen, isize, _ in blocks:
+        buf += zlib.decompress(bytes(data[coff:coff + clen]), -15)
+        if len(buf) >= skip:
+            break
+    o = 12 + struct.unpack_from("<i", buf, 4)[0]
+    lens = []
+    for _ in range(n_ref):
+        l_name = struct.unpack_from("<i", buf, o)[0]
+        lens.append(struct.unpack_from("<i", buf, o + 4 + l_name)[0])
+        o += 8 + l_name
+    return lens
+
+
+def index_bam(data, csi=False, batch_bytes=256 << 20, device=0):
+    """The BAI (csi=True: CSI) index of a BAM file (bytes), built on the GPU: select_bam's loop with the stream's input index
+    switched on (svdss_bam_stream_set_input_index) and every batch's fragments folded in file order
+    (svdss_bam_input_indexer_*).  The bytes `SVDSS bamindex` writes.  SvdssError with code SVDSS_EIO for an unsorted file."""
+    blocks = bgzf.bgzf_blocks(data)
+    lens = np.array(bam_ref_lengths(data, blocks), dtype=np.int32)
+    ix, shift, depth = C.c_void_p(), C.c_int32(0), C.c_int32(0)
+    rc = lib.svdss_bam_input_indexer_create(len(lens), lens.ctypes.data if len(lens) else None, 1 if csi else 0, C.byref(shift), C.byref(depth),
+                                            C.byref(ix))
+    if rc:
+        raise SvdssError(rc, "svdss_bam_input_indexer_create")
+    try:
+        base = 0
+
+        def fold(batch):
+            nonlocal base
+            f = BamInputFrag()
+            _check(lib.svdss_bam_batch_input_index(batch, C.byref(f)), "svdss_bam_batch_input_index")
+            _check(lib.svdss_bam_input_indexer_add(ix, C.byref(f), base), "svdss_bam_input_indexer_add")
+            base += f.comp_bytes
+        select_bam(data, names=[], batch_bytes=batch_bytes, device=device, input_index=(shift.value, depth.value), on_batch=fold)
+        # the end of the stream: the EOF marker where the file ends with one, else the file's size
+        end = len(data)
+        if blocks and blocks[-1][2] == 0:
+            end = blocks[-1][0] - 18
+        out, n = C.c_void_p(), C.c_int64(0)
+        _check(lib.svdss_bam_input_indexer_finish(ix, end, C.byref(out), C.byref(n)), "svdss_bam_input_indexer_finish")
+        return C.string_at(out, n.value)
+    finally:
+        lib.svdss_bam_input_indexer_free(ix)
+
+
+def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20, device=0, gate=None, input_index=None, on_batch=None):
     """svdss_bam_select_run over a whole BAM file (bytes): the records `SVDSS call` keeps -- no flag 4 / 256 / 2048,
     mapq >= min_mapq, and (when given) read name in `names` or alignment overlapping one of `regions` =
-    [(tid, beg, end)] sorted by (tid, beg).  Returns ([record bytes without the block_size field], counters)."""
+    [(tid, beg, end)] sorted by (tid, beg).  Returns ([record bytes without the block_size field], counters).
+    input_index: see set_input_index; on_batch(batch handle): called after every batch."""
     blocks = bgzf.bgzf_blocks(data)
     n_ref, skip = bam_header(data, blocks)
     comp = np.frombuffer(bytes(data), dtype=np.uint8)
@@ -168,6 +234,7 @@ def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20
     out, stats = [], {"records": 0, "batches": 0}
     try:
         set_gate(stream, gate)
+        set_input_index(stream, input_index)
         groups, cur, acc = [], [], 0
         for b in blocks:
             cur.append(b)
@@ -193,6 +260,8 @@ def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20
             lib.svdss_bam_batch_selection(batch, C.byref(r))
             stats["records"] += r.n_records
             stats["batches"] += 1
+            if on_batch is not None:
+                on_batch(batch)
             if r.n_selected:
                 off = np.ctypeslib.as_array(r.rec_off, shape=(r.n_selected + 1,))
                 raw = C.string_at(r.bytes, r.n_bytes)
@@ -467,11 +536,11 @@ class BamStore:
 
 
 def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20, store=None, store_min_mapq=None, device=0, gate=None,
-               measure=False):
+               measure=False, input_index=None):
     """svdss_bam_smooth_run over a whole BAM file (bytes) whose header names `contigs_ascii` in order; with `store` (a
     BamStore) after svdss_bam_smooth_set_store(sm, store, store_min_mapq).  Returns (the BGZF members of the smoothed
     stream, batch count).  gate: see set_gate.  measure=True: svdss_bam_smooth_measure instead -- returns ([(matches,
-    mismatches, fits) per kept record, in file order], [(n_records, n_kept) per batch])."""
+    mismatches, fits) per kept record, in file order], [(n_records, n_kept) per batch]).  input_index: see set_input_index."""
     blocks = bgzf.bgzf_blocks(data)
     n_ref, skip = bam_header(data, blocks)
     raw_head = b""
@@ -495,6 +564,7 @@ def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20,
         head = np.frombuffer(raw_head[:skip], dtype=np.uint8)
         _check(lib.svdss_bam_stream_set_output_prefix(stream, head.ctypes.data, len(head)), "svdss_bam_stream_set_output_prefix")
         set_gate(stream, gate)
+        set_input_index(stream, input_index)
         groups = _batch_groups(blocks, batch_bytes)
         measured, counts = [], []
         for seq, g in enumerate(groups):

@@ -48,6 +48,7 @@
 
 #include "../../include/svdss_hip.h"
 #include "bam_device_internal.h"
+#include "bam_index_writer.h"
 #include "hip_check.h"
 #include "index_host.h"
 #include "inflate_dev.h"
@@ -301,6 +302,126 @@ __global__ void __launch_bounds__(64) gate_base_kernel(GateP G) {
     run += __shfl(inc, 63, 64);
   }
   if (lane == 0) G.hdr[H_NREC] = run;
+}
+
+// ------------------------------------------------------------------ the index of the input (svdss_bam_stream_set_input_index)
+// `SVDSS bamindex`, `call / run --write-bam-index`: the BAI / CSI fragments of the records AS THEY STAND IN THE FILE -- every
+// record that starts in this batch's turn, in front of the gate and of every filter -- in the style of the output side's
+// sm_ix_* kernels (bam_smooth.hip): a thread per record, hipcub scans for the placements, only chunks and windows come down.
+struct InIxP {
+  const uint8_t* buf;
+  const uint32_t* lists; int64_t list_cap;
+  const int32_t* seg_cnt; const int32_t* seg_base; const uint32_t* pre;
+  int32_t n_seg;
+  int64_t n_rec, n_pre;
+  int64_t head, hi;                   // the batch's fresh bytes are buf[head, hi)
+  const svdss_bgzf_block_t* blks;     // n_blk members, uoff = where each inflates to in buf
+  const int64_t* mstart;              // n_blk + 1: where each begins in the file, from the batch's first; [n_blk]: right behind them
+  int64_t n_blk;
+  uint64_t pre_v;                     // the virtual offset of the carried bytes' first byte (below the batch's base: wraps)
+  int32_t min_shift, depth;
+  // per record (n_rec + 1)
+  int32_t* tid; uint32_t* bin; int64_t* beg; int64_t* end; uint64_t* vb; uint64_t* ve;
+  uint64_t* key;                      // (tid << 32) | (last window + 1): a running maximum of it is the last window reached so far
+  const uint64_t* kmax;               // ... exclusive running maximum
+  int64_t *head_f, *own, *unm, *idx;  // starts a chunk; windows it reaches into first; flag 4 set; tid >= 0 -- consecutive rows
+  const int64_t *s_head, *s_own, *s_unm;
+  svdss_bam_input_chunk_t* chunks; svdss_bam_input_window_t* windows;
+  unsigned long long* err;            // bit 0: records out of coordinate order, bit 1: a record whose fields do not fit its block_size
+};
+
+// the virtual offset of buffer position q, relative to the batch's first member: the member that holds the byte (an empty
+// member holds none: it shares its place with the member behind it, which the search below arrives at); a position in the
+// carried bytes is the carry's first byte; the end of the batch's last byte is the offset right behind its members
+__device__ __forceinline__ uint64_t in_ix_voff(const InIxP& P, int64_t q) {
+  if (q < P.head) return P.pre_v;
+  if (q >= P.hi || P.n_blk == 0) return (uint64_t)P.mstart[P.n_blk] << 16;
+  int64_t a = 0, b = P.n_blk;         // the last member with uoff <= q
+  while (b - a > 1) { const int64_t m = (a + b) >> 1; if (P.blks[m].uoff <= q) a = m; else b = m; }
+  return ((uint64_t)P.mstart[a] << 16) | (uint64_t)(q - P.blks[a].uoff);
+}
+
+// block s < n_seg: the records of segment s; block n_seg: those that begin in the carried bytes.  A thread per record:
+// tid, [beg, end) (bam_endpos as gate_kernel has it; a CIGAR kept in a CG tag is read through its <l_seq>S<ref>N stand-in),
+// bin, virtual offsets of start and end
+__global__ void __launch_bounds__(64) in_ix_rec_kernel(InIxP P) {
+  const int s = blockIdx.x;
+  const int cnt = s < P.n_seg ? P.seg_cnt[s] : (int)(P.n_pre < 4 ? P.n_pre : 4);
+  const int base = s < P.n_seg ? P.seg_base[s] : 0;
+  const uint32_t* list = s < P.n_seg ? P.lists + (int64_t)s * P.list_cap : P.pre;
+  for (int i = threadIdx.x; i < cnt; i += 64) {
+    const int64_t k = base + i;
+    if (k >= P.n_rec) continue;
+    const int64_t p = list[i];
+    const uint32_t bs = ld32(P.buf, p);
+    const int32_t tid = (int32_t)ld32(P.buf, p + 4), pos = (int32_t)ld32(P.buf, p + 8);
+    const uint32_t w3 = ld32(P.buf, p + 12), w4 = ld32(P.buf, p + 16);
+    const int32_t l_seq = (int32_t)ld32(P.buf, p + 20);
+    const uint32_t l_name = w3 & 0xffu, n_cig = w4 & 0xffffu, flag = w4 >> 16;
+    const int64_t hd = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)(l_seq < 0 ? 0 : l_seq) + 1) / 2 + (l_seq < 0 ? 0 : l_seq);
+    int64_t span = 0;
+    // (a record whose fields do not fit its block_size is refused by the kernel behind, as always -- svdss_bam_index_run, which
+    // has none behind, looks at bit 1 --: its CIGAR is not walked)
+    if (l_seq < 0 || hd > (int64_t)bs) atomicOr(P.err, 2ull);
+    else {
+      const int64_t cg = p + 36 + l_name;
+      for (uint32_t j = 0; j < n_cig; ++j) span += cigar_ref_len(ld32(P.buf, cg + 4 * (int64_t)j));
+    }
+    const bool ix = tid >= 0;
+    int64_t beg = 0, end = 1;
+    if (ix) ix_extent(pos, span, P.min_shift, P.depth, beg, end);
+    P.tid[k] = tid; P.beg[k] = beg; P.end[k] = end;
+    P.bin[k] = ix ? ix_reg2bin(beg, end, P.min_shift, P.depth) : 0u;
+    P.vb[k] = in_ix_voff(P, p);
+    P.ve[k] = in_ix_voff(P, p + 4 + (int64_t)bs);
+    P.key[k] = ix ? ((uint64_t)(uint32_t)tid << 32) | (uint64_t)(((end - 1) >> P.min_shift) + 1) : 0ull;
+    P.idx[k] = ix ? 1 : 0;
+    P.unm[k] = ix && (flag & 4u) ? 1 : 0;
+  }
+}
+
+// a thread per record (+ the scans' total): its place in the order, does it start a chunk, which windows it reaches into first
+__global__ void __launch_bounds__(256) in_ix_own_kernel(InIxP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > P.n_rec) return;
+  if (k == P.n_rec) { P.head_f[k] = 0; P.own[k] = 0; P.unm[k] = 0; P.idx[k] = 0; return; }
+  const int32_t tid = P.tid[k];
+  if (k > 0) {   // by tid, then position; a record without a reference sorts behind every reference
+    const int32_t pt = P.tid[k - 1];
+    const int64_t a = tid < 0 ? 0x7fffffff : tid, b = pt < 0 ? 0x7fffffff : pt;
+    if (a < b || (a == b && P.beg[k] < P.beg[k - 1])) atomicOr(P.err, 1ull);
+  }
+  if (!P.idx[k]) { P.head_f[k] = 0; P.own[k] = 0; return; }
+  const uint64_t m = P.kmax[k];
+  const int64_t seen = (m >> 32) == (uint64_t)(uint32_t)tid ? (int64_t)(m & 0xffffffffu) - 1 : -1;   // last window reached before
+  const int64_t w0 = P.beg[k] >> P.min_shift, w1 = (P.end[k] - 1) >> P.min_shift;
+  const int64_t first = w0 > seen + 1 ? w0 : seen + 1;
+  P.own[k] = w1 >= first ? w1 - first + 1 : 0;
+  P.head_f[k] = (k == 0 || !P.idx[k - 1] || tid != P.tid[k - 1] || P.bin[k] != P.bin[k - 1]) ? 1 : 0;
+}
+
+// a thread per record: its chunk's start / end (the counts by two atomics each on zeroed fields of its own chunk) and its windows
+__global__ void __launch_bounds__(256) in_ix_emit_kernel(InIxP P) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= P.n_rec || !P.idx[k]) return;
+  const int64_t c = P.s_head[k] + P.head_f[k] - 1;
+  svdss_bam_input_chunk_t* ch = P.chunks + c;
+  if (P.head_f[k]) {
+    ch->tid = P.tid[k]; ch->bin = P.bin[k]; ch->v_beg = P.vb[k];
+    atomicAdd((unsigned long long*)&ch->n_rec, (unsigned long long)(-k));
+    atomicAdd((unsigned long long*)&ch->n_unmapped, (unsigned long long)(-P.s_unm[k]));
+  }
+  if (k + 1 == P.n_rec || P.head_f[k + 1] || !P.idx[k + 1]) {
+    ch->v_end = P.ve[k];
+    atomicAdd((unsigned long long*)&ch->n_rec, (unsigned long long)(k + 1));
+    atomicAdd((unsigned long long*)&ch->n_unmapped, (unsigned long long)P.s_unm[k + 1]);
+  }
+  const int64_t n = P.own[k];
+  if (n > 0) {
+    const int64_t w1 = (P.end[k] - 1) >> P.min_shift;
+    svdss_bam_input_window_t* w = P.windows + P.s_own[k];
+    for (int64_t j = 0; j < n; ++j) { w[j].tid = P.tid[k]; w[j].window = (int32_t)(w1 - n + 1 + j); w[j].v_beg = P.vb[k]; }
+  }
 }
 
 // ------------------------------------------------------------------ per record: fields, filters, tags
@@ -641,6 +762,91 @@ extern "C" int64_t svdss_bam_stream_tail(const svdss_bam_stream_t* s, const uint
   return (int64_t)s->carry.size();
 }
 
+extern "C" int svdss_bam_stream_set_input_index(svdss_bam_stream_t* s, int32_t min_shift, int32_t depth) {
+  if (!s || min_shift < 0 || min_shift > 30 || depth < 0 || (min_shift > 0 && (depth < 1 || min_shift + 3 * depth > 62))) return SVDSS_EINVAL;
+  std::lock_guard<std::mutex> lk(s->m);
+  if (s->next_seq != 0) return SVDSS_EINVAL;   // (before the first batch)
+  s->in_ix_shift = min_shift; s->in_ix_depth = min_shift > 0 ? depth : 0;
+  return SVDSS_OK;
+}
+extern "C" int svdss_bam_stream_set_input_carry(svdss_bam_stream_t* s, int64_t carry_v) {
+  if (!s) return SVDSS_EINVAL;
+  std::lock_guard<std::mutex> lk(s->m);
+  if (s->next_seq != 0) return SVDSS_EINVAL;   // (before the first batch)
+  s->carry_coff = carry_v >> 16;               // (below the region's first member: arithmetic shift)
+  s->carry_uoff = (int32_t)(carry_v & 0xffff);
+  return SVDSS_OK;
+}
+extern "C" int svdss_bam_stream_input_seam(const svdss_bam_stream_t* s, int32_t* has_carry, int64_t* carry_v, int64_t* head_v) {
+  if (!s || !has_carry || !carry_v || !head_v) return SVDSS_EINVAL;
+  *has_carry = s->carry.empty() ? 0 : 1;
+  *carry_v = (int64_t)(((uint64_t)s->carry_coff << 16) + (uint64_t)s->carry_uoff);
+  *head_v = s->head_v;
+  return SVDSS_OK;
+}
+extern "C" int svdss_bam_batch_input_index(const svdss_bam_batch_t* b, svdss_bam_input_frag_t* f) {
+  if (!b || !f) return SVDSS_EINVAL;
+  *f = b->in_ix.f;
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_bam_index_run(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, int32_t device,
+                                   int32_t n_chunks, const uint8_t* const* comp, const int64_t* comp_bytes,
+                                   const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc, const int64_t* n_blocks,
+                                   svdss_bam_batch_t** out) {
+  if (!s || !out || seq < 0 || skip < 0 || n_chunks < 0 || device < 0) return SVDSS_EINVAL;
+  Front F;
+  const int rc = batch_front(s, seq, is_last, skip, device, n_chunks, comp, comp_bytes, blocks, crc, n_blocks, out, F);
+  if (rc != SVDSS_OK) return rc;
+  svdss_bam_batch* b = *out;
+  b->n_records = F.hdr[H_NREC] + F.hdr[H_GATED];
+  if (b->in_ix.corrupt) { b->err = "corrupt record"; return SVDSS_EIO; }
+  return SVDSS_OK;
+}
+
+// ---- the fold of the input index for callers without C++ (BamIndexBuilder, bam_index_writer.h)
+struct svdss_bam_input_indexer {
+  std::unique_ptr<BamIndexBuilder> b;
+  std::vector<uint8_t> bytes;
+};
+extern "C" int svdss_bam_input_indexer_create(int32_t n_ref, const int32_t* ref_len, int32_t csi, int32_t* min_shift, int32_t* depth,
+                                              svdss_bam_input_indexer_t** out) {
+  if (!out || n_ref < 0 || (n_ref > 0 && !ref_len) || !min_shift || !depth) return SVDSS_EINVAL;
+  try {
+    const std::vector<int32_t> lens(ref_len, ref_len + n_ref);
+    bool is_csi = false;
+    int sh = 0, dp = 0;
+    std::string err;
+    if (!bam_index_scheme(csi ? "x.csi" : "x.bai", lens, is_csi, sh, dp, err)) { g_svdss_hip_err = err; return SVDSS_ERANGE; }
+    svdss_bam_input_indexer* ix = new svdss_bam_input_indexer();
+    ix->b.reset(new BamIndexBuilder(n_ref, is_csi, sh, dp));
+    *min_shift = sh; *depth = dp;
+    *out = ix;
+  } catch (...) { return SVDSS_ENOMEM; }
+  return SVDSS_OK;
+}
+extern "C" int svdss_bam_input_indexer_add(svdss_bam_input_indexer_t* ix, const svdss_bam_input_frag_t* f, int64_t base) {
+  if (!ix || !f || base < 0 || !f->on) return SVDSS_EINVAL;
+  try { ix->b->add_input_fragment(*f, (uint64_t)base); } catch (...) { return SVDSS_ENOMEM; }
+  return SVDSS_OK;
+}
+extern "C" int svdss_bam_input_indexer_finish(svdss_bam_input_indexer_t* ix, int64_t end_offset, const uint8_t** bytes, int64_t* n_bytes) {
+  if (!ix || !bytes || !n_bytes || end_offset < 0) return SVDSS_EINVAL;
+  ix->b->finish_input((uint64_t)end_offset);
+  if (ix->b->unsorted()) { g_svdss_hip_err = "the records are not sorted by coordinate"; return SVDSS_EIO; }
+  char* mem = nullptr;
+  size_t n = 0;
+  FILE* f = open_memstream(&mem, &n);
+  if (!f) return SVDSS_ENOMEM;
+  const bool ok = ix->b->encode(f);
+  if (fclose(f) != 0 || !ok) { free(mem); return SVDSS_EIO; }
+  try { ix->bytes.assign((const uint8_t*)mem, (const uint8_t*)mem + n); } catch (...) { free(mem); return SVDSS_ENOMEM; }
+  free(mem);
+  *bytes = ix->bytes.data(); *n_bytes = (int64_t)ix->bytes.size();
+  return SVDSS_OK;
+}
+extern "C" void svdss_bam_input_indexer_free(svdss_bam_input_indexer_t* ix) { delete ix; }
+
 extern "C" const char* svdss_bam_stream_error(const svdss_bam_stream_t* s) { return s ? s->err.c_str() : ""; }
 
 extern "C" int64_t svdss_bam_stream_rewalked(const svdss_bam_stream_t* s, int64_t* n_segments) {
@@ -657,6 +863,16 @@ extern "C" void svdss_bam_batch_free(svdss_bam_batch_t* b) {
   if (b->st) (void)hipStreamDestroy(b->st);
   if (b->search.sfs) svdss_sfs_batch_free(b->search.sfs);
   delete b;   // (its buffers: ~DevBuf / ~PinBuf, on the device made current above)
+}
+
+// the gzip header in front of a member's deflate stream at data + coff: 12 + XLEN bytes that begin with 1f 8b 08 and
+// FLG.FEXTRA, 18 in every BGZF file anybody writes (0: none found -- the stored blocks of a seam have none)
+static inline int64_t member_header_len(const uint8_t* data, int64_t coff) {
+  for (int64_t h = 18; h <= coff && h <= 12 + 0xffff; ++h) {
+    const uint8_t* q = data + coff - h;
+    if (q[0] == 31 && q[1] == 139 && q[2] == 8 && (q[3] & 4) && (int64_t)(q[10] | (q[11] << 8)) == h - 12) return h;
+  }
+  return 0;
 }
 
 int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t skip, int device,
@@ -707,8 +923,17 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   RCHK(b->front.pin.ensure(tab_bytes + 4096));
   svdss_bgzf_block_t* h_blk = (svdss_bgzf_block_t*)b->front.pin.p;
   CrcBlk* h_crc = (CrcBlk*)(h_blk + (total_blocks + 1));
+  // (the input index's scheme: set before batch 0 and not changed after it, so read without the stream's lock)
+  const bool ix_on = s->in_ix_shift > 0;
+  b->in_ix.f = svdss_bam_input_frag_t{};
+  b->in_ix.corrupt = false;
+  if (ix_on) {
+    b->in_ix.chunks.clear(); b->in_ix.windows.clear();
+    try { b->in_ix.h_mstart.assign((size_t)total_blocks + 1, 0); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
+    b->in_ix.f.on = 1; b->in_ix.f.first_data = -1;
+  }
   {
-    int64_t k = 0, coff = 0, uoff = 0;
+    int64_t k = 0, coff = 0, uoff = 0, fpos = 0;
     for (int32_t c = 0; c < n_chunks; ++c) {
       if (comp_bytes[c] > 0) BCHK(hipMemcpyAsync((uint8_t*)b->front.comp.p + coff, comp[c], (size_t)comp_bytes[c], hipMemcpyHostToDevice, st));
       for (int64_t i = 0; i < n_blocks[c]; ++i, ++k) {
@@ -717,9 +942,19 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
         h_blk[k].uoff = HEAD + uoff;
         h_crc[k] = CrcBlk{HEAD + uoff, blocks[c][i].isize, crc[c][i]};
         uoff += blocks[c][i].isize;
+        if (ix_on) {   // where the member begins in the file, from the batch's first (consecutive members: header, stream, footer)
+          b->in_ix.h_mstart[(size_t)k] = fpos;
+          if (blocks[c][i].isize > 0 && b->in_ix.f.first_data < 0) b->in_ix.f.first_data = fpos;
+          fpos += member_header_len(comp[c], blocks[c][i].coff) + blocks[c][i].clen + 8;
+        }
       }
       coff += (comp_bytes[c] + 15) & ~(int64_t)15;
     }
+    if (ix_on) { b->in_ix.h_mstart[(size_t)total_blocks] = fpos; b->in_ix.f.comp_bytes = fpos; }
+  }
+  if (ix_on) {
+    RCHK(b->in_ix.mstart.ensure(sizeof(int64_t) * (size_t)(total_blocks + 1)));
+    BCHK(hipMemcpyAsync(b->in_ix.mstart.p, b->in_ix.h_mstart.data(), sizeof(int64_t) * (size_t)(total_blocks + 1), hipMemcpyHostToDevice, st));
   }
   BCHK(hipMemsetAsync(b->front.status.p, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
   BCHK(hipMemsetAsync(b->front.hdr.p, 0, sizeof(int64_t) * H_N, st));
@@ -786,6 +1021,15 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   int turn_code = SVDSS_OK;
   std::string turn_msg;
   int64_t hdr[H_N] = {0};
+  uint64_t ix_pre_v = 0;     // (input index) where the carry that goes in begins in the file, relative to this batch's first member
+  // (input index) the virtual offset of buffer position q >= HEAD as in_ix_voff has it, in its two parts
+  auto host_voff = [&](int64_t q, int64_t& c_off, int32_t& u_off) {
+    const std::vector<int64_t>& ms = b->in_ix.h_mstart;
+    if (q >= W.hi || total_blocks == 0) { c_off = ms[(size_t)total_blocks]; u_off = 0; return; }
+    int64_t lo = 0, hi2 = total_blocks;
+    while (hi2 - lo > 1) { const int64_t m = (lo + hi2) >> 1; if (h_blk[m].uoff <= q) lo = m; else hi2 = m; }
+    c_off = ms[(size_t)lo]; u_off = (int32_t)(q - h_blk[lo].uoff);
+  };
   {
     const int64_t carry_len = restart && seq > 0 ? 0 : (int64_t)s->carry.size();
     auto turn_fail = [&](int code, const std::string& msg) { turn_code = code; turn_msg = msg; };
@@ -814,6 +1058,17 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
             }
           }
           const int64_t tail = hdr[H_TAIL], tail_len = W.hi - tail;
+          if (ix_on) {
+            // the carry that goes in began where the stream remembers; the one that goes out begins in this batch's members, or
+            // is the same record still (one longer than the batch): either way relative to the NEXT batch's first member
+            ix_pre_v = ((uint64_t)s->carry_coff << 16) + (uint64_t)s->carry_uoff;
+            const int64_t span = b->in_ix.f.comp_bytes;
+            if (tail_len > 0 && tail >= HEAD) { host_voff(tail, s->carry_coff, s->carry_uoff); s->carry_coff -= span; }
+            else if (tail_len > 0) s->carry_coff -= span;
+            else { s->carry_coff = 0; s->carry_uoff = 0; }
+            if (start < 0) { int64_t c0 = 0; int32_t u0 = 0; host_voff(hdr[H_START], c0, u0); s->head_v = (int64_t)(((uint64_t)c0 << 16) | (uint64_t)u0); }
+            b->in_ix.f.ends_at_boundary = tail_len == 0 ? 1 : 0;      // (of the last record, if there is one: below)
+          }
           try { s->carry.resize((size_t)tail_len); } catch (...) { turn_fail(SVDSS_ENOMEM, "out of memory"); }
           if (!turn_code && tail_len > 0) {
             e = hipMemcpyAsync(s->carry.data(), (const uint8_t*)b->front.buf.p + tail, (size_t)tail_len, hipMemcpyDeviceToHost, st);
@@ -832,6 +1087,84 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   }
   done_turn(s, &svdss_bam_stream::next_seq, turn_code, turn_msg);
   if (turn_code) { b->err = turn_msg; return turn_code; }
+  // ---- the index of the input, outside the turn and in front of the gate: every record of the chain as link_kernel left it
+  if (ix_on) {
+    svdss_bam_input_frag_t& f = b->in_ix.f;
+    const int64_t n = hdr[H_NREC];
+    f.n_records = n;
+    if (n == 0) f.ends_at_boundary = 0;
+    else {
+      const size_t n1 = (size_t)n + 1;
+      RCHK(b->in_ix.rec.ensure(8 + 8 * 14 * n1 + 8 * n1 + 256));
+      InIxP P;
+      P.buf = W.buf; P.lists = W.lists; P.list_cap = W.list_cap; P.seg_cnt = W.seg_cnt; P.seg_base = seg_base; P.pre = (const uint32_t*)b->front.pre.p;
+      P.n_seg = W.n_seg; P.n_rec = n; P.n_pre = hdr[H_PRE];
+      P.head = HEAD; P.hi = W.hi;
+      P.blks = (const svdss_bgzf_block_t*)b->front.blks.p; P.mstart = (const int64_t*)b->in_ix.mstart.p; P.n_blk = total_blocks;
+      P.pre_v = ix_pre_v; P.min_shift = s->in_ix_shift; P.depth = s->in_ix_depth;
+      int64_t* i64 = (int64_t*)b->in_ix.rec.p;
+      unsigned long long* d_err = (unsigned long long*)i64;    // 8 bytes, then the per-record arrays
+      P.err = d_err;
+      P.beg = i64 + 1; P.end = P.beg + n1;
+      P.head_f = P.end + n1; P.own = P.head_f + n1; P.unm = P.own + n1; P.idx = P.unm + n1;       // four rows in, four rows out
+      int64_t* s_head = P.idx + n1; int64_t* s_own = s_head + n1; int64_t* s_unm = s_own + n1; int64_t* s_idx = s_unm + n1;
+      P.s_head = s_head; P.s_own = s_own; P.s_unm = s_unm;
+      P.vb = (uint64_t*)(s_idx + n1); P.ve = P.vb + n1; P.key = P.ve + n1;
+      uint64_t* kmax = P.key + n1;
+      P.kmax = kmax;
+      P.tid = (int32_t*)(kmax + n1); P.bin = (uint32_t*)(P.tid + n1);
+      P.chunks = nullptr; P.windows = nullptr;
+      const unsigned g = (unsigned)((n + 1 + 255) / 256);
+      BCHK(hipMemsetAsync(d_err, 0, 8, st));
+      hipLaunchKernelGGL(in_ix_rec_kernel, dim3((unsigned)W.n_seg + 1), dim3(64), 0, st, P);
+      BCHK(hipGetLastError());
+      {
+        size_t t0 = 0, t1 = 0;
+        BCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, t0, P.key, kmax, hipcub::Max(), (uint64_t)0, (int)n, st));
+        BCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, P.head_f, s_head, (int)n1, st));
+        RCHK(run.scan_tmp(std::max(t0, t1)));   // (room for the sums below as well: nothing is allocated between the kernels)
+        t0 = b->tmp.cap;
+        BCHK(hipcub::DeviceScan::ExclusiveScan(b->tmp.p, t0, P.key, kmax, hipcub::Max(), (uint64_t)0, (int)n, st));
+        hipLaunchKernelGGL(in_ix_own_kernel, dim3(g), dim3(256), 0, st, P);
+        BCHK(hipGetLastError());
+        RCHK(run.scan_rows(P.head_f, s_head, (int64_t)n1, 4));
+      }
+      // counts, order flag, the first and last record's (tid, beg)
+      int64_t cnt[3] = {0, 0, 0}, be[2] = {0, 0};
+      int32_t td[2] = {0, 0};
+      unsigned long long h_err = 0;
+      BCHK(hipMemcpyAsync(&cnt[0], s_head + n, 8, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&cnt[1], s_own + n, 8, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&cnt[2], s_idx + n, 8, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&td[0], P.tid, 4, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&td[1], P.tid + (n - 1), 4, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&be[0], P.beg, 8, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(&be[1], P.beg + (n - 1), 8, hipMemcpyDeviceToHost, st));
+      BCHK(hipStreamSynchronize(st));
+      f.first_tid = td[0]; f.last_tid = td[1]; f.first_beg = be[0]; f.last_beg = be[1];
+      f.n_no_coor = n - cnt[2];
+      if (td[1] < 0) f.ends_at_boundary = 0;       // (a record without a reference has no chunk whose end could wait)
+      b->in_ix.corrupt = (h_err & 2) != 0;
+      if (h_err & 1) f.unsorted = 1;               // out of order: the builder refuses; nothing else comes down
+      else {
+        const int64_t n_ch = cnt[0], n_win = cnt[1];
+        const size_t ch_bytes = sizeof(svdss_bam_input_chunk_t) * (size_t)n_ch;
+        RCHK(b->in_ix.frag.ensure(ch_bytes + sizeof(svdss_bam_input_window_t) * (size_t)n_win + 512));
+        P.chunks = (svdss_bam_input_chunk_t*)b->in_ix.frag.p;
+        P.windows = (svdss_bam_input_window_t*)((uint8_t*)b->in_ix.frag.p + ((ch_bytes + 255) & ~(size_t)255));
+        try { b->in_ix.chunks.resize((size_t)n_ch); b->in_ix.windows.resize((size_t)n_win); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
+        if (n_ch) BCHK(hipMemsetAsync(P.chunks, 0, ch_bytes, st));
+        hipLaunchKernelGGL(in_ix_emit_kernel, dim3(g), dim3(256), 0, st, P);
+        BCHK(hipGetLastError());
+        if (n_ch) BCHK(hipMemcpyAsync(b->in_ix.chunks.data(), P.chunks, ch_bytes, hipMemcpyDeviceToHost, st));
+        if (n_win) BCHK(hipMemcpyAsync(b->in_ix.windows.data(), P.windows, sizeof(svdss_bam_input_window_t) * (size_t)n_win, hipMemcpyDeviceToHost, st));
+        BCHK(hipStreamSynchronize(st));
+        f.n_chunks = n_ch; f.chunks = b->in_ix.chunks.data();
+        f.n_windows = n_win; f.windows = b->in_ix.windows.data();
+      }
+    }
+  }
   // ---- the record gate, outside the turn (it needs nothing of the batches in front): the chain loses the records outside
   // the stream's regions before any front end looks at it
   if (gate_on && hdr[H_NREC] > 0) {

@@ -307,6 +307,13 @@ struct svdss_bam_stream {
   bool gate_on = false;
   std::vector<uint8_t> gate_tab;
   int64_t gate_n = 0, n_gated = 0;
+  // the index of the input (svdss_bam_stream_set_input_index; in_ix_shift 0: off).  Next to the carry, where its first byte
+  // is in the file: the compressed offset of the member that holds it, RELATIVE to the first member of the batch that has
+  // its turn next (so below 0), and the offset in that member.  head_v: the virtual offset of the record an open_start
+  // region's chain was started at, relative to the region's first member.
+  int32_t in_ix_shift = 0, in_ix_depth = 0;
+  int64_t carry_coff = 0, head_v = 0;
+  int32_t carry_uoff = 0;
 };
 
 // Batches take turns in file order: at the carry (`turn` = &svdss_bam_stream::next_seq) and, when smoothing, at the output
@@ -391,6 +398,16 @@ struct svdss_bam_batch {
     std::vector<svdss_bam_index_window_t> windows;
     int64_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   } sm_ix;
+  // batch_front with the stream's input index on (svdss_bam_stream_set_input_index): the fragments of the batch's records
+  // as they stand in the file (svdss_bam_batch_input_index)
+  struct {
+    BamBuf rec, frag, mstart;        // per record; the chunks and windows; where every member starts in the file
+    std::vector<int64_t> h_mstart;
+    std::vector<svdss_bam_input_chunk_t> chunks;
+    std::vector<svdss_bam_input_window_t> windows;
+    svdss_bam_input_frag_t f{};
+    bool corrupt = false;            // a record whose fields do not fit its block_size (svdss_bam_index_run refuses the batch)
+  } in_ix;
 };
 
 // ------------------------------------------------------------------ the park (bam_device.hip owns it; bam_smooth.hip parks the

@@ -136,6 +136,25 @@ inline void bam_regions_report() {
             (long long)(bam_region_counters().gated.load() + on_device));
 }
 
+// a batch's input-side index fragments (svdss_bam_batch_input_index), copied off the batch object: what travels with the
+// batch's result to whoever folds the index (bam_input_index.h); region / seam: which region of the file the batch is of,
+// and whether it is the seam in front of it (ShardedBamSelect)
+struct InputFragCopy {
+  svdss_bam_input_frag_t f{};
+  std::vector<svdss_bam_input_chunk_t> chunks;
+  std::vector<svdss_bam_input_window_t> windows;
+  size_t region = 0;
+  bool seam = false;
+  void take(const svdss_bam_batch_t* b, size_t g = 0, bool is_seam = false) {
+    region = g; seam = is_seam;
+    if (svdss_bam_batch_input_index(b, &f) != SVDSS_OK) { f = svdss_bam_input_frag_t{}; return; }
+    chunks.assign(f.chunks, f.chunks + f.n_chunks);
+    windows.assign(f.windows, f.windows + f.n_windows);
+    f.chunks = nullptr; f.windows = nullptr;
+  }
+  svdss_bam_input_frag_t frag() const { svdss_bam_input_frag_t r = f; r.chunks = chunks.data(); r.windows = windows.data(); return r; }
+};
+
 // the kept records of one device batch, in file order: record k = bytes[off[k] + 4 ..), block_size at bytes[off[k]]
 struct SelectedBatch {
   std::vector<uint8_t> bytes;   // (smoothing: the batch's BGZF members)
@@ -155,6 +174,8 @@ struct SelectedBatch {
   std::vector<svdss_bam_index_chunk_t> ix_chunks;
   std::vector<svdss_bam_index_window_t> ix_windows;
   svdss_bam_index_frag_t ix{};
+  // --write-bam-index: the batch's input-side fragments (f.on 0: not asked for)
+  InputFragCopy in_ix;
 };
 
 // a record's view (BamReader::RawView: the zero-copy form the host readers hand out) over bytes that hold it
@@ -206,8 +227,11 @@ struct BamRunError {
 // once, by the last feeding thread as it ends (no more batches will be run; results may still be delivered); small_start:
 // the run's first batch is cut at a quarter of the batch size and the second at half of it, so that the device has work --
 // and whoever counts what the batches hold has figures, and batch 0's head is final -- after a quarter of the bytes
+// ix_shift / ix_depth: the stream's input index is switched on (svdss_bam_stream_set_input_index); has_carry_v / carry_v: where
+// `carry` begins in the file, relative to the region's first member (svdss_bam_stream_set_input_carry)
 struct BamSelectRegion { size_t begin = 0, end = 0; bool open_start = false, open_end = false; std::vector<uint8_t> carry; int loaders = 8; size_t pending = 64; bool current = true;
-                         std::function<void()> on_fed; bool small_start = false; };
+                         std::function<void()> on_fed; bool small_start = false;
+                         int ix_shift = 0, ix_depth = 0; bool has_carry_v = false; int64_t carry_v = 0; };
 
 // One region of a BAM through the device path, batch results handed out in file order as `Out`: scanner (loader threads)
 // -> batcher -> feeding threads (n_devices x feeders, one batch object each; `run` is told the device slot) -> ordered
@@ -246,6 +270,10 @@ class DeviceBamSelect {
       if (svdss_bam_stream_region(stream_, region.open_start ? 1 : 0, region.open_end || ranged ? 1 : 0, region.carry.data(), (int64_t)region.carry.size()) != SVDSS_OK) {
         err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return;
       }
+    if (region.ix_shift > 0 && (svdss_bam_stream_set_input_index(stream_, region.ix_shift, region.ix_depth) != SVDSS_OK ||
+                                (region.has_carry_v && svdss_bam_stream_set_input_carry(stream_, region.carry_v) != SVDSS_OK))) {
+      err_ = BamRunError{SVDSS_EINVAL, "the input index cannot be switched on", ""}; return;
+    }
     n_feeders_ = n_devices * (size_t)feeders;
     batcher_ = std::thread([this] { batch_loop(); });
     for (size_t d = 0; d < n_devices; ++d)
@@ -499,9 +527,12 @@ class ShardedBamSelect {
     std::function<void(size_t g)> fed;
     std::function<void(size_t g)> abandon;
   };
+  // ix_shift / ix_depth (both constructors): every region's stream, and every seam's, has its input index switched on
+  // (svdss_bam_stream_set_input_index); the results then carry their fragments (SelectedBatch::in_ix), seam_voffsets says
+  // where a seam's record is in the file
   ShardedBamSelect(const std::string& path, const std::vector<Shard>& shards, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes,
-                   const std::vector<size_t>& cuts)
-      : path_(path), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes) {
+                   const std::vector<size_t>& cuts, int ix_shift = 0, int ix_depth = 0)
+      : path_(path), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes), ix_shift_(ix_shift), ix_depth_(ix_depth) {
     hooks_.run = [shards](size_t g, bool seam) {
       const Shard S = shards[g % shards.size()];
       svdss_bam_store_t* store = seam ? S.seam_store : S.store;
@@ -512,11 +543,12 @@ class ShardedBamSelect {
         return svdss_bam_select_store_run(s, seq, is_last, skip, S.filter, store, n_chunks, comp, comp_bytes, blocks, crc, n_blocks, batch);
       });
     };
-    hooks_.collect = [](size_t, bool) {
-      return CollectFn([](const svdss_bam_batch_t* batch, uint64_t) {
+    hooks_.collect = [](size_t g, bool seam) {
+      return CollectFn([g, seam](const svdss_bam_batch_t* batch, uint64_t) {
         std::unique_ptr<Out> out(new Out);
         svdss_bam_selection_t r;
         (void)svdss_bam_batch_selection(batch, &r);
+        out->in_ix.take(batch, g, seam);
         out->n_records = (uint64_t)r.n_records;
         out->slim = r.slim != 0;
         out->off.assign(r.rec_off, r.rec_off + r.n_selected + 1);
@@ -533,8 +565,10 @@ class ShardedBamSelect {
   // scanners: those of the regions' first runs, opened by the caller and kept open past this object (none given: each
   // region opens its own)
   ShardedBamSelect(const std::string& path, const Hooks& hooks, int32_t n_ref, int64_t skip, int feeders, int64_t batch_bytes, const std::vector<size_t>& cuts,
-                   size_t pending = 64, const std::vector<BgzfScanner*>& scanners = std::vector<BgzfScanner*>(), bool small_start = false)
-      : path_(path), hooks_(hooks), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes), pending_(pending), small_start_(small_start) {
+                   size_t pending = 64, const std::vector<BgzfScanner*>& scanners = std::vector<BgzfScanner*>(), bool small_start = false,
+                   int ix_shift = 0, int ix_depth = 0)
+      : path_(path), hooks_(hooks), n_ref_(n_ref), skip_(skip), feeders_(feeders), batch_bytes_(batch_bytes), pending_(pending), small_start_(small_start),
+        ix_shift_(ix_shift), ix_depth_(ix_depth) {
     start(cuts, scanners);
   }
   size_t n_regions() const { return regions_.size(); }
@@ -543,6 +577,10 @@ class ShardedBamSelect {
   // the store keys of the file's batches in file order: (shard, seam?) per region: the seam's store holds key 0
   bool region_has_seam(size_t g) const { return regions_[g].seam_stored; }
   int64_t region_batches(size_t g) const { return regions_[g].n_batches; }
+  // (input index) the record the seam in front of region g completes: it begins where the carry of the region in front
+  // begins and ends at the first record start of region g -- both as virtual offsets of the FILE
+  void seam_voffsets(size_t g, uint64_t& v_beg, uint64_t& v_end) const { v_beg = regions_[g].seam_vb; v_end = regions_[g].seam_ve; }
+  size_t region_begin(size_t g) const { return regions_[g].begin; }
 
   std::unique_ptr<Out> next() {
     for (;;) {
@@ -587,6 +625,7 @@ class ShardedBamSelect {
     std::unique_ptr<Out> seam;
     bool entered = false, seam_stored = false;
     int64_t n_batches = 0;
+    uint64_t seam_vb = 0, seam_ve = 0;
   };
   void start(const std::vector<size_t>& cuts, const std::vector<BgzfScanner*>& scanners) {
     const size_t n = cuts.size() - 1;
@@ -596,8 +635,9 @@ class ShardedBamSelect {
       launch(g, g > 0, std::vector<uint8_t>(), g < scanners.size() ? scanners[g] : nullptr);
     }
   }
-  void launch(size_t g, bool open_start, const std::vector<uint8_t>& carry, BgzfScanner* scanner = nullptr) {
+  void launch(size_t g, bool open_start, const std::vector<uint8_t>& carry, BgzfScanner* scanner = nullptr, bool has_carry_v = false, int64_t carry_v = 0) {
     typename DeviceBamSelect<Out>::Region rg;
+    rg.ix_shift = ix_shift_; rg.ix_depth = ix_depth_; rg.has_carry_v = has_carry_v; rg.carry_v = carry_v;
     rg.begin = regions_[g].begin; rg.end = regions_[g].end;
     rg.open_start = open_start; rg.open_end = g + 1 < regions_.size();
     rg.carry = carry;
@@ -629,11 +669,21 @@ class ShardedBamSelect {
     const uint8_t *tail = nullptr, *head = nullptr;
     const int64_t n_tail = svdss_bam_stream_tail(P.sel->stream(), &tail);
     const std::vector<uint8_t> carry(tail, tail + (n_tail > 0 ? n_tail : 0));
+    // (input index) where that carry begins: relative to the member right behind region g - 1, which is region g's first
+    int32_t has_carry = 0;
+    int64_t carry_v = 0, head_v = 0, unused = 0;
+    if (ix_shift_ > 0) (void)svdss_bam_stream_input_seam(P.sel->stream(), &has_carry, &carry_v, &unused);
     R.sel->wait_first();
     const BamRunError why = R.sel->failure();
     bool good = !why.failed();
     if (good) {
       const int64_t n_head = svdss_bam_stream_head(R.sel->stream(), &head);
+      if (ix_shift_ > 0) {
+        int32_t hc = 0;
+        (void)svdss_bam_stream_input_seam(R.sel->stream(), &hc, &unused, &head_v);
+        R.seam_vb = ((uint64_t)R.begin << 16) + (uint64_t)carry_v;
+        R.seam_ve = ((uint64_t)R.begin << 16) + (uint64_t)head_v;
+      }
       if ((int64_t)carry.size() + n_head > 0) { good = run_seam(g, carry, head, n_head); ++n_seams_; }
     }
     if (!good) {
@@ -645,7 +695,7 @@ class ShardedBamSelect {
       R.seam.reset();
       if (hooks_.again) hooks_.again(g, why.text());
       ++n_reruns_;
-      launch(g, false, carry);
+      launch(g, false, carry, nullptr, ix_shift_ > 0 && has_carry != 0, carry_v);
     }
     drop(P);       // (its stream's tail has been copied)
     return true;
@@ -674,17 +724,24 @@ class ShardedBamSelect {
     svdss_bam_stream_t* st = nullptr;
     if (svdss_bam_stream_create(n_ref_, &st) != SVDSS_OK) { err_ = BamRunError{SVDSS_ENOMEM, "out of memory", ""}; return false; }
     if (const int rc = bam_stream_apply_regions(st)) { err_ = BamRunError{rc, "the regions do not fit the BAM header", ""}; svdss_bam_stream_free(st); return false; }
+    if (ix_shift_ > 0) (void)svdss_bam_stream_set_input_index(st, ix_shift_, ix_depth_);
     svdss_bam_batch_t* batch = nullptr;
     const uint8_t* cp = comp.data();
     const int64_t cb = (int64_t)comp.size(), nb = (int64_t)blk.size();
     const svdss_bgzf_block_t* bp = blk.data();
     const uint32_t* rp = crc.data();
     const int rc = hooks_.run(g, true)(st, 0, 1, 0, 0, 1, &cp, &cb, &bp, &rp, &nb, &batch);
-    const bool ok = rc == SVDSS_OK;
+    bool ok = rc == SVDSS_OK;
+    if (ok && ix_shift_ > 0) {
+      // (input index) a seam's offsets are derived for the ONE record it completes (seam_voffsets): a guess that left several
+      // records in front of it counts as one that did not fit, and the region runs again from the known carry
+      svdss_bam_input_frag_t f;
+      if (svdss_bam_batch_input_index(batch, &f) != SVDSS_OK || f.n_records != 1) ok = false;
+    }
     if (ok) {
       regions_[g].seam = hooks_.collect(g, true)(batch, 0);
       regions_[g].seam_stored = hooks_.seam_kept && hooks_.seam_kept(g);
-    } else if (rc != SVDSS_EIO) {
+    } else if (rc != SVDSS_OK && rc != SVDSS_EIO) {
       err_ = BamRunError{rc, std::string("seam: ") + svdss_strerror(rc) + " " + (batch ? svdss_bam_batch_error(batch) : "") + " " + svdss_last_hip_error(),
                          svdss_last_hip_error()};
     }
@@ -701,6 +758,7 @@ class ShardedBamSelect {
   int64_t batch_bytes_ = 0;
   size_t pending_ = 64;
   bool small_start_ = false;         // (every run of every region: BamSelectRegion::small_start)
+  int ix_shift_ = 0, ix_depth_ = 0;  // the input index of every stream (0: off)
   std::vector<Reg> regions_;
   std::mutex sel_m_;                 // (who may come from another thread -- deliver -- meets a region's `sel` under it)
   std::condition_variable sel_cv_;

@@ -5,6 +5,11 @@
 // (tid, bin), the 16 kb windows the batch's records reach into first) and BamIndexBuilder folds those fragments in file
 // order; the host paths feed it one record at a time.  Both give the same bytes for the same BAM.
 //
+// The same builder indexes the BAM a command is GIVEN (`SVDSS bamindex`, `call / run --write-bam-index`; the input side:
+// add_input_fragment / add_input_seam / add_input_record / finish_input).  There every record counts: records with flag 4
+// and a position are indexed and counted as unmapped in the pseudo-bin, records without a reference are counted in the
+// trailing n_no_coor, and a record's end at the last byte of a batch waits for the next non-empty member of the file.
+//
 // Virtual offsets: a position is addressed by the member that holds its byte, so a record that starts exactly at a block
 // boundary is "start of block k + 1", and the end of the last record is the offset right after the last data member (the
 // EOF marker) -- what htslib's bgzf_tell gives while reading.  They count from the first byte `smooth` writes to stdout.
@@ -113,9 +118,73 @@ class BamIndexBuilder {
     for (int64_t w = std::max<int64_t>(w0, r.max_win + 1); w <= w1; ++w) add_window(tid, (int32_t)w, v_beg);
   }
 
+  // ---- the input side
+  // the device path: one batch's fragments (svdss_bam_batch_input_index), batches in file order; base = file offset of the
+  // batch's first member (a region of the file: the region's offset + the members of its batches so far)
+  void add_input_fragment(const svdss_bam_input_frag_t& f, uint64_t base) {
+    if (!f.on) return;
+    // an end the batch in front left at its last byte: the first member of this one that holds a byte
+    if (f.first_data >= 0) resolve_pending((base + (uint64_t)f.first_data) << 16);
+    if (f.unsorted) unsorted_ = true;
+    n_no_coor_ += (uint64_t)f.n_no_coor;
+    if (f.n_records > 0) { order_input(f.first_tid, f.first_beg); order_input(f.last_tid, f.last_beg); }
+    const uint64_t sh = base << 16;
+    for (int64_t i = 0; i < f.n_chunks; ++i) {
+      const svdss_bam_input_chunk_t& c = f.chunks[i];
+      add_chunk(c.tid, c.bin, c.n_rec - c.n_unmapped, c.v_beg + sh, c.v_end + sh, c.n_unmapped);
+    }
+    for (int64_t i = 0; i < f.n_windows; ++i) {
+      const svdss_bam_input_window_t& w = f.windows[i];
+      add_window(w.tid, w.window, w.v_beg + sh);
+    }
+    pending_ = f.ends_at_boundary != 0 && f.n_chunks > 0 && have_last_;
+  }
+  // the ONE record a seam between two regions of the file completes (f: the seam's batch, whose own offsets mean nothing
+  // in the file): it starts at v_beg, where the carry of the region in front begins, and ends at v_end, the first record
+  // start of the region behind
+  void add_input_seam(const svdss_bam_input_frag_t& f, uint64_t v_beg, uint64_t v_end) {
+    if (!f.on) return;
+    if (f.n_records != 1) { unsorted_ = true; return; }    // (the caller runs such a region again instead)
+    n_no_coor_ += (uint64_t)f.n_no_coor;
+    order_input(f.first_tid, f.first_beg);
+    for (int64_t i = 0; i < f.n_chunks; ++i) add_chunk(f.chunks[i].tid, f.chunks[i].bin, 1 - f.chunks[i].n_unmapped, v_beg, v_end, f.chunks[i].n_unmapped);
+    for (int64_t i = 0; i < f.n_windows; ++i) add_window(f.windows[i].tid, f.windows[i].window, v_beg);
+    pending_ = false;
+  }
+  // the host reader: one record of the input, in file order, with its flag, reference span and final virtual offsets
+  void add_input_record(int32_t tid, int32_t pos, uint32_t flag, int64_t span, uint64_t v_beg, uint64_t v_end) {
+    int64_t beg, end;
+    ix_extent(pos, span, min_shift_, depth_, beg, end);
+    order_input(tid, tid < 0 ? 0 : beg);
+    if (tid < 0) { ++n_no_coor_; return; }
+    if ((size_t)tid >= refs_.size()) { unsorted_ = true; return; }
+    const bool unm = (flag & 4u) != 0;
+    add_chunk(tid, ix_reg2bin(beg, end, min_shift_, depth_), unm ? 0 : 1, v_beg, v_end, unm ? 1 : 0);
+    Ref& r = refs_[(size_t)tid];
+    const int64_t w0 = beg >> min_shift_, w1 = (end - 1) >> min_shift_;
+    for (int64_t w = std::max<int64_t>(w0, r.max_win + 1); w <= w1; ++w) add_window(tid, (int32_t)w, v_beg);
+  }
+  // the input has ended: end_offset = where its EOF marker is (the file's size where it has none)
+  void finish_input(uint64_t end_offset) { resolve_pending(end_offset << 16); }
+  bool unsorted() const { return unsorted_; }
+  uint64_t n_no_coor() const { return n_no_coor_; }
+  uint64_t n_chunks() const { uint64_t n = 0; for (const Ref& r : refs_) for (const auto& kv : r.bins) n += kv.second.size(); return n; }
+  uint64_t n_windows() const { uint64_t n = 0; for (const Ref& r : refs_) n += r.lin.size(); return n; }
+
   // the index into `path` (through path + ".tmp", renamed into place when complete); false and a message otherwise
   bool write(const std::string& path, std::string& err) const {
     if (unsorted_) { err = "--write-index: the records are not sorted by coordinate; no index written"; return false; }
+    const std::string tmp = path + ".tmp";
+    FILE* f = fopen(tmp.c_str(), "wb");
+    if (!f) { err = "cannot write " + tmp; return false; }
+    bool ok = encode(f);
+    ok = fclose(f) == 0 && ok;
+    if (ok && rename(tmp.c_str(), path.c_str()) != 0) ok = false;
+    if (!ok) { unlink(tmp.c_str()); err = "cannot write " + path; }
+    return ok;
+  }
+  // the file's bytes into f (BGZF for CSI); the caller has looked at unsorted()
+  bool encode(FILE* f) const {
     std::vector<uint8_t> out;
     auto put = [&](const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
     auto p32 = [&](uint32_t v) { put(&v, 4); };
@@ -125,7 +194,7 @@ class BamIndexBuilder {
     else put("BAI\1", 4);
     p32((uint32_t)refs_.size());
     for (const Ref& r : refs_) {
-      p32((uint32_t)(r.bins.size() + (r.n_mapped ? 1 : 0)));
+      p32((uint32_t)(r.bins.size() + (r.any ? 1 : 0)));
       // CSI: per bin the start of the first record that reaches into its range = the window entry of the first window of
       // the range any record reaches (the entries grow with the window: the records are sorted)
       std::vector<int64_t> covered;
@@ -144,14 +213,15 @@ class BamIndexBuilder {
         p32((uint32_t)kv.second.size());
         for (const auto& c : kv.second) { p64(c.first); p64(c.second); }
       }
-      if (r.n_mapped) {
+      if (r.any) {
         // htslib's metadata pseudo-bin: the span of the reference's records in the file, mapped / unmapped counts
-        // (`smooth` writes mapped records only: unmapped ones are dropped with the other filters)
+        // (`smooth` writes mapped records only: unmapped ones are dropped with the other filters; an input BAM may hold
+        // records with flag 4 and a position)
         p32(meta);
         if (csi_) p64(0);
         p32(2);
         p64(r.first); p64(r.last);
-        p64(r.n_mapped); p64(0);
+        p64(r.n_mapped); p64(r.n_unmapped);
       }
       if (!csi_) {
         p32((uint32_t)r.lin.size());
@@ -159,20 +229,13 @@ class BamIndexBuilder {
         for (uint64_t v : r.lin) { if (v != kNone) last = v; p64(last); }
       }
     }
-    p64(0);   // n_no_coor
-    const std::string tmp = path + ".tmp";
-    FILE* f = fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write " + tmp; return false; }
-    bool ok;
+    p64(n_no_coor_);
     if (csi_) {
       BgzfWriter w(f, 1);
       w.write(out.data(), out.size());
-      ok = w.finish();
-    } else ok = fwrite(out.data(), 1, out.size(), f) == out.size() && fflush(f) == 0;
-    ok = fclose(f) == 0 && ok;
-    if (ok && rename(tmp.c_str(), path.c_str()) != 0) ok = false;
-    if (!ok) { unlink(tmp.c_str()); err = "cannot write " + path; }
-    return ok;
+      return w.finish();
+    }
+    return fwrite(out.data(), 1, out.size(), f) == out.size() && fflush(f) == 0;
   }
 
  private:
@@ -181,7 +244,8 @@ class BamIndexBuilder {
     std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
     std::vector<uint64_t> lin;      // per window: the first record's start (kNone: no record reaches into it)
     int64_t max_win = -1;
-    uint64_t n_mapped = 0, first = 0, last = 0;
+    uint64_t n_mapped = 0, n_unmapped = 0, first = 0, last = 0;
+    bool any = false;               // a record of the reference has been added (the pseudo-bin is written)
   };
   static int64_t first_bin(int l) { return (((int64_t)1 << (3 * l)) - 1) / 7; }
 
@@ -189,7 +253,16 @@ class BamIndexBuilder {
     if (have_prev_ && (tid < prev_tid_ || (tid == prev_tid_ && beg < prev_beg_))) unsorted_ = true;
     have_prev_ = true; prev_tid_ = tid; prev_beg_ = beg;
   }
-  void add_chunk(int32_t tid, uint32_t bin, int64_t n, uint64_t v0, uint64_t v1) {
+  // (the input side: tid < 0 sorts behind every reference)
+  void order_input(int32_t tid, int64_t beg) { order(tid < 0 ? 0x7fffffff : tid, tid < 0 ? 0 : beg); }
+  void resolve_pending(uint64_t v) {
+    if (!pending_) return;
+    pending_ = false;
+    Ref& r = refs_[(size_t)last_tid_];
+    r.bins[last_bin_].back().second = v;
+    r.last = v;
+  }
+  void add_chunk(int32_t tid, uint32_t bin, int64_t n, uint64_t v0, uint64_t v1, int64_t n_unm = 0) {
     if (tid < 0 || (size_t)tid >= refs_.size()) { unsorted_ = true; return; }
     Ref& r = refs_[(size_t)tid];
     std::vector<std::pair<uint64_t, uint64_t>>& ch = r.bins[bin];
@@ -197,9 +270,11 @@ class BamIndexBuilder {
     if (have_last_ && last_tid_ == tid && last_bin_ == bin && !ch.empty() && ch.back().second == v0) ch.back().second = v1;
     else ch.emplace_back(v0, v1);
     have_last_ = true; last_tid_ = tid; last_bin_ = bin;
-    if (!r.n_mapped) r.first = v0;
+    if (!r.any) r.first = v0;
+    r.any = true;
     r.last = v1;
     r.n_mapped += (uint64_t)n;
+    r.n_unmapped += (uint64_t)n_unm;
   }
   void add_window(int32_t tid, int32_t w, uint64_t v) {
     if (tid < 0 || (size_t)tid >= refs_.size() || w < 0) return;
@@ -213,6 +288,8 @@ class BamIndexBuilder {
   bool csi_;
   int min_shift_, depth_;
   bool unsorted_ = false, have_prev_ = false, have_last_ = false;
+  bool pending_ = false;            // the last chunk's end is the last byte of its batch: waits for the next non-empty member
+  uint64_t n_no_coor_ = 0;
   int32_t prev_tid_ = -1, last_tid_ = -1;
   int64_t prev_beg_ = 0;
   uint32_t last_bin_ = 0;

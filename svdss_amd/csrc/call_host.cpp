@@ -33,6 +33,7 @@
 #include "bai_index.h"
 #include "bam_reader.h"
 #include "bam_device_select.h"
+#include "bam_input_index.h"
 #include "gpu_inflate_hook.h"
 #include "sfs_file.h"
 #include "sv_record.h"
@@ -465,6 +466,8 @@ struct RecordFeed {
   // views point into it)
   std::function<void(const std::shared_ptr<BamReader::Bytes>&)> on_chunk;
   uint64_t seen_chunk = ~0ull;
+  // device path: called with every batch as it is taken from the reader, in file order (--write-bam-index folds its fragments)
+  std::function<void(const SelectedBatch&)> on_batch;
   // device path: the batch being handed out; what pass 1's log sums over the batches
   std::unique_ptr<SelectedBatch> cur;
   size_t k = 0;
@@ -507,6 +510,7 @@ struct RecordFeed {
       wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
       k = 0;
       if (!cur) { if (sel) err = sel->error(); return err.empty() ? 0 : -1; }
+      if (on_batch) on_batch(*cur);
       n_records += cur->n_records;
       for (int s = 0; s < 8; ++s) stage_s[s] += cur->stage_s[s];
       stage_s[7] += cur->inflate_kernel_s; ++n_batches;
@@ -794,13 +798,38 @@ struct CallRun {
 
   // the device path over the file's regions (bam_cuts): one filter per region, filter(dev) on the region's GPU; with_stores:
   // the slim form of every record that passes the flag / mapq filters also stays in the region's record store
-  void open_select(RecordFeed& f, int32_t n_ref, bool with_stores, const std::function<svdss_bam_filter_t*(int32_t)>& filter) {
+  // input_index: the streams' input index is on (pass 1 with --write-bam-index: the batches carry their fragments)
+  void open_select(RecordFeed& f, int32_t n_ref, bool with_stores, const std::function<svdss_bam_filter_t*(int32_t)>& filter, bool input_index = false) {
     std::vector<ShardedBamSelect<SelectedBatch>::Shard> shards(bam_cuts.size() - 1);
     for (size_t g = 0; g < shards.size(); ++g) {
       f.filters.push_back(shards[g].filter = filter((int32_t)(g % (size_t)n_dev)));
       if (with_stores && !stores.empty()) { shards[g].store = stores[g]; shards[g].seam_store = seam_stores[g]; }
     }
-    f.sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref, bam_skip, knobs.feeders, knobs.batch_bytes, bam_cuts));
+    f.sel.reset(new ShardedBamSelect<SelectedBatch>(o.bam, shards, n_ref, bam_skip, knobs.feeders, knobs.batch_bytes, bam_cuts,
+                                                    input_index ? bam_ix.shift() : 0, input_index ? bam_ix.depth() : 0));
+    if (input_index) f.on_batch = [this, &f](const SelectedBatch& b) { bam_ix.add(b.in_ix, *f.sel); };
+  }
+
+  // --write-bam-index FILE: the index of --bam, folded from the fragments pass 1's batches carry (the host reader: a pass of
+  // index_bam_on_host's own, one thread, beside nothing).  An unsorted BAM: a warning and no index -- the index is a by-product
+  InputIndexFold bam_ix;
+  void open_bam_index() {
+    if (o.write_bam_index.empty() || from_store()) return;
+    std::vector<int32_t> lens;
+    std::string err;
+    if (!bam_header_lengths(o.bam, lens, err)) die("cannot read " + o.bam + ": " + err);
+    if (!bam_ix.open(o.write_bam_index, lens, "--write-bam-index", err)) die(err);
+  }
+  void write_bam_index() {
+    if (!bam_ix.on()) return;
+    std::string err;
+    if (!dev_pass) {
+      uint64_t comp_bytes = 0;
+      if (!index_bam_on_host(o.bam, bam_ix, comp_bytes, err)) die("error reading " + o.bam + ": " + err);
+    }
+    if (bam_ix.finish(o.bam, err)) logmsg("info", "index of " + o.bam + " written to " + o.write_bam_index);
+    else if (bam_ix.unsorted()) logmsg("warning", "--write-bam-index: " + err);
+    else die(err);
   }
 
   // the host reader, its chunks inflated on n_gpus GPUs in turn (where there are)
@@ -840,7 +869,7 @@ struct CallRun {
       for (svdss_bam_store_t* st : seam_stores) svdss_bam_store_free(st);
       stores.clear(); seam_stores.clear();
     }
-    open_select(f, n_ref_hdr, true, names_filter);
+    open_select(f, n_ref_hdr, true, names_filter, bam_ix.on());
   }
 
   // Clusterer::align_and_extend (clusterer.cpp:56-156): pass 1 over the BAM, placement of every SFS
@@ -866,6 +895,7 @@ struct CallRun {
     }
     {
       RecordFeed feed;
+      open_bam_index();
       if (dev_pass) open_pass1_select(feed);
       else {
         // (--gpus N: the chunks of pass 1 are inflated on all N GPUs in turn, as `search` does -- on GPUs that are there,
@@ -999,6 +1029,7 @@ struct CallRun {
         cur ^= 1;
       }
       if (worker.joinable()) worker.join();
+      write_bam_index();
       set_up_reference();   // (an input without a single batch: the later stages still want the chromosomes)
       if (feed.store) {
         region_batches.assign(1, feed.store_batches); region_seam.assign(1, 0);

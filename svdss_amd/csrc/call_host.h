@@ -30,6 +30,7 @@ struct CallOptions {
   std::string clusters;        // --clusters <FILE>: the filled clusters (clusterer.cpp:613-626)
   bool clipped = false;        // --clipped: imprecise SVs from soft-clipped alignments (clipper.cpp; EXPERIMENTAL)
   std::string smoothed;        // run only: --smoothed <FILE>, the smoothed BAM (with write_index / compress above)
+  std::string write_bam_index; // call, run: --write-bam-index <FILE>, the index of --bam (bam_input_index.h); bamindex: its -o
 };
 
 // `SVDSS run` (run_host.cpp) drives the two units below; what passes between them:
@@ -38,8 +39,10 @@ struct svdss_ref;
 struct svdss_index;
 // ... into main_smooth's device path: the store every batch's records for `call` go into, where the SFS text goes instead
 // of the file --sfs names, and what is handed over instead of freed when the stream is through
+class InputIndexFold;                     // bam_input_index.h
 struct SmoothHooks {
   svdss_bam_store* store = nullptr;      // svdss_bam_smooth_set_store, with the run's --min-mapq
+  InputIndexFold* bam_index = nullptr;   // run --write-bam-index: the smoothing stage's reader folds the input's index into it
   FILE* sfs_sink = nullptr;              // the SFS text (closed when it is complete)
   bool keep_alive = false;               // return instead of ending the process: the GPU context stays up
   // out: batches of the stream; the chromosomes (FASTA order; upper-cased) and their copy on the GPU in BAM header order
@@ -80,6 +83,7 @@ int main_search(const Options& o, time_t process_start);   // search_host.cpp
 int main_call(const CallOptions& o, CallPreset* preset = nullptr);
 int main_smooth(const CallOptions& o, SmoothHooks* hooks = nullptr);
 int main_run(const CallOptions& o);                        // run_host.cpp
+int main_bamindex(const CallOptions& o);                   // bamindex_host.cpp
 // `SVDSS run --samples LIST` (run_host.cpp): o.bam is empty; regions / regions_file are resolved against every sample's header
 int main_run_samples(const CallOptions& o, const std::string& list, const std::vector<std::string>& regions, const std::string& regions_file);
 // --region / --regions-file against the header of `bam`, in force for every reader of the process from here on

@@ -3,7 +3,8 @@
 // `--opt=value`).  In a header of its own so that tests/test_ref_pins.py can hold it against the reference's own
 // config.cpp (oracle/_ref).  Additions of this program: --gpus N|all, --io-threads N, --write-index FILE (smooth),
 // --compress runs|lz (smooth), --nobam (smooth --index --sfs), --smoothed FILE (run), --region REG and --regions-file BED
-// (smooth, search --bam, call, run: csrc/bam_regions.h), --samples LIST (run: csrc/run_samples.h).
+// (smooth, search --bam, call, run: csrc/bam_regions.h), --samples LIST (run: csrc/run_samples.h), --write-bam-index FILE
+// (call, run) and -o FILE (bamindex): the index of the INPUT BAM (csrc/bam_input_index.h).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -27,6 +28,8 @@ struct Options {
   std::vector<std::string> regions;                // --region REG, every occurrence (the one option that adds up)
   std::string regions_file;                        // --regions-file BED
   std::string samples;                             // run --samples LIST: many BAMs in one process (run_samples.h)
+  std::string write_bam_index;                     // call / run --write-bam-index FILE: the index of --bam, a by-product of its pass
+  std::string out;                                 // bamindex -o FILE (default: <BAM>.bai)
   bool gpus_all = false;                           // --gpus all (the caller asks the library how many there are)
   bool putative = true, assemble = true, verbose = false, version = false, help = false, clipped = false, binary = false;
 };
@@ -107,7 +110,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
       {"noputative", FLAG}, {"binary", FLAG}, {"version", FLAG}, {"help", FLAG}, {"h", FLAG}, {"l", FLT}, {"verbose", FLAG},
       {"gpus", STR}, {"io-threads", INT}, {"write-index", STR},
       {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}, {"region", STR}, {"regions-file", STR},
-      {"samples", STR}};   // (the last nine: this program's own)
+      {"samples", STR}, {"write-bam-index", STR}, {"o", STR}};   // (the last eleven: this program's own)
   auto find = [&](const std::string& name) -> const Spec* {
     for (const Spec& sp : specs)
       if (name == sp.name) return &sp;
@@ -136,6 +139,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
     else if (n == "nobam") o.nobam = b; else if (n == "smoothed") o.smoothed = v;
     else if (n == "region") o.regions.push_back(v); else if (n == "regions-file") o.regions_file = v;
     else if (n == "samples") o.samples = v;
+    else if (n == "write-bam-index") o.write_bam_index = v; else if (n == "o") o.out = v;
     else if (n == "compress") { o.compress_given = true; if (v == "runs") o.compress = 0; else if (v == "lz") o.compress = 1; else return failed(v); }
     else if (n == "gpus") { if (v == "all") o.gpus_all = true; else if (!to_int(v, o.gpus)) return failed(v); }
     return true;

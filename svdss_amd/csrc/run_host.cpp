@@ -29,6 +29,7 @@
 #include "host_knobs.h"
 #include "call_host.h"
 #include "run_samples.h"
+#include "bam_input_index.h"
 
 namespace {
 // what `run` cannot run on: said before anything is opened or written, and before the GPU is looked for
@@ -89,6 +90,15 @@ void run_one(const CallOptions& o, SmoothHooks& hooks, bool verbose, int64_t ind
   hooks.store = store;
   hooks.keep_alive = true;
   hooks.n_batches = 0;
+  // --write-bam-index FILE: the index of o.bam, folded from what the smoothing stage's reader sees of every batch
+  InputIndexFold bam_index;
+  if (!o.write_bam_index.empty()) {
+    std::vector<int32_t> lens;
+    std::string err;
+    if (!bam_header_lengths(o.bam, lens, err)) die("cannot read " + o.bam + ": " + err);
+    if (!bam_index.open(o.write_bam_index, lens, "--write-bam-index", err)) die(err);
+    hooks.bam_index = &bam_index;
+  }
   if (!(hooks.sfs_sink = open_memstream(&sfs_text, &sfs_bytes))) die("out of memory");
   {
     CallOptions so = o;
@@ -108,6 +118,13 @@ void run_one(const CallOptions& o, SmoothHooks& hooks, bool verbose, int64_t ind
     }
   }
   hooks.sfs_sink = nullptr;
+  if (hooks.bam_index) {   // (an unsorted BAM: a warning and no index -- the index is a by-product)
+    hooks.bam_index = nullptr;
+    std::string err;
+    if (bam_index.finish(o.bam, err)) { if (verbose) fprintf(stderr, "[run] index of %s written to %s\n", o.bam.c_str(), o.write_bam_index.c_str()); }
+    else if (bam_index.unsorted()) fprintf(stderr, "[run] [warning] --write-bam-index: %s\n", err.c_str());
+    else die(err);
+  }
   if (!sfs_text) die("out of memory");
   if (sfs_file && ((sfs_bytes && fwrite(sfs_text, 1, sfs_bytes, sfs_file) != sfs_bytes) || fclose(sfs_file) != 0)) die("error writing " + o.sfs);
   stage("smooth + search");
@@ -136,7 +153,11 @@ void run_one(const CallOptions& o, SmoothHooks& hooks, bool verbose, int64_t ind
     }
   }
   // ---- call: CallRun with its SFS map from the text and, with a whole store, both passes from HBM
-  main_call(o, &preset);
+  {
+    CallOptions co = o;
+    co.write_bam_index.clear();   // (written above: a call stage that reads the file itself does not index it again)
+    main_call(co, &preset);
+  }
   free(sfs_text);
   stage("call");
   if (verbose) fprintf(stderr, "[run] [time] %-28s %.3f s\n", "total", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

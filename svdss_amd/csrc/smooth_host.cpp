@@ -28,6 +28,7 @@
 #include "host_knobs.h"
 #include "bam_reader.h"
 #include "bam_device_select.h"
+#include "bam_input_index.h"
 #include "gpu_deflate_hook.h"
 #include "gpu_inflate_hook.h"
 #include "bam_writer.h"
@@ -675,12 +676,15 @@ struct DevicePipeline {
         n_regions(cuts.size() - 1), n_sm(std::min<size_t>(n_regions, (size_t)std::max(1, svdss_device_count()))), sms(n_sm, nullptr),
         drefs(n_sm, nullptr), pool(target, per_gpu), writer(pool, o.nobam, run.knobs) {}
   void note(const char* what) const { if (R.knobs.debug) fprintf(stderr, "[smooth] %s at +%.3f s\n", what, R.since()); }
+  InputIndexFold* bam_index() const { return R.hooks ? R.hooks->bam_index : nullptr; }
   // the output's header goes in front of the first batch's records
   void set_output_prefix() {
     if (svdss_bam_stream_create(hp.n_ref, &stream) != SVDSS_OK) die("out of memory");
     ByteSink hs;
     bam_write_header(hs, hp.text, hp.names, hp.lens);
     if (svdss_bam_stream_set_output_prefix(stream, hs.v.data(), (int64_t)hs.v.size()) != SVDSS_OK) die("out of memory");
+    // (run --write-bam-index: the stream of the whole file, or of its first region, leaves the input's index fragments)
+    if (bam_index() && svdss_bam_stream_set_input_index(stream, bam_index()->shift(), bam_index()->depth()) != SVDSS_OK) die("the input index cannot be switched on");
     note("BAM header read, output prefix set");
   }
   // feeding thread: one batch smoothed, its members down into a buffer of the pool, its reads to the SfsSide
@@ -715,6 +719,7 @@ struct DevicePipeline {
     tl_slot = -1;
     for (int k = 0; k < 8; ++k) out->stage_s[k] = r.stage_ms[k] * 1e-3;
     out->inflate_kernel_s = r.inflate_kernel_ms * 1e-3;
+    if (bam_index()) out->in_ix.take(b);
     if (R.ixb) {
       (void)svdss_bam_batch_index(b, &out->ix);
       out->ix_chunks.assign(out->ix.chunks, out->ix.chunks + out->ix.n_chunks);
@@ -728,10 +733,17 @@ struct DevicePipeline {
     else {
       ShardedBamSelect<SelectedBatch>::Hooks hk;
       hk.run = [this](size_t g, bool seam) { return run_for(g, g == 0 && !seam); };
-      hk.collect = [coll](size_t, bool) { return coll; };
+      hk.collect = [coll](size_t g, bool seam) {
+        return CollectFn([coll, g, seam](const svdss_bam_batch_t* b, uint64_t seq) {
+          std::unique_ptr<SelectedBatch> out = coll(b, seq);
+          if (out) { out->in_ix.region = g; out->in_ix.seam = seam; }
+          return out;
+        });
+      };
       // (the output's header is in front of the first region's stream; the first region never runs again)
       hk.stream = [this](size_t g) { svdss_bam_stream_t* st = g == 0 ? stream : nullptr; if (g == 0) stream = nullptr; return st; };
-      rds.reset(new ShardedBamSelect<SelectedBatch>(o.bam, hk, hp.n_ref, hp.skip, per_gpu, target, cuts));
+      rds.reset(new ShardedBamSelect<SelectedBatch>(o.bam, hk, hp.n_ref, hp.skip, per_gpu, target, cuts, 64, std::vector<BgzfScanner*>(), false,
+                                                    bam_index() ? bam_index()->shift() : 0, bam_index() ? bam_index()->depth() : 0));
     }
     note("reader of the smoothing pass started");
   }
@@ -804,6 +816,7 @@ struct DevicePipeline {
         b->ix.chunks = b->ix_chunks.data(); b->ix.windows = b->ix_windows.data();
         R.ixb->add_fragment(b->ix, (uint64_t)out_bytes);
       }
+      if (bam_index()) { if (rds) bam_index()->add(b->in_ix, *rds); else bam_index()->add(b->in_ix); }
       n_rec += b->n_records; n_kept += b->n_kept; out_bytes += b->ext ? b->ext_n : b->bytes.size();
       for (int k = 0; k < 4; ++k) n_xf[k] += b->n_xf[k];
       for (int k = 0; k < 8; ++k) st_s[k] += b->stage_s[k];

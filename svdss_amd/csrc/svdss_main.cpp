@@ -7,13 +7,15 @@
 //                [--noassemble] [--omax N] [--verbose]  (config.cpp:30-55, main.cpp:62-68; search_host.cpp)
 //   SVDSS call   --reference R --bam B --sfs S [...]    (main.cpp:55-61; call_host.cpp)
 //   SVDSS run    --reference R --bam B --index F [...]  (run_host.cpp: smooth, search and call in one pass over the BAM)
+//   SVDSS bamindex --bam B [-o FILE]                    (bamindex_host.cpp: the BAI / CSI of the input, `samtools index`)
 //   SVDSS --version                                     (main.cpp:45-47)
 // This file: the usage texts, the command line, `index`; the other sub-commands have a file each.
 // Logs go to stderr (host_common.h), fatal conditions exit(1).
 // Additions of this program: --gpus N (search, call, smooth), --io-threads N, --verbose stage timings, --write-index FILE (smooth),
 // --compress runs|lz (smooth), --index FMD --sfs FILE [--nobam] (smooth: the search of the smoothed reads in the same pass),
 // the sub-command `run` with its --smoothed FILE, --region REG / --regions-file BED (smooth, search --bam, call, run:
-// bam_regions.h), --samples LIST (run: many BAMs in one process, run_samples.h and run_host.cpp).
+// bam_regions.h), --samples LIST (run: many BAMs in one process, run_samples.h and run_host.cpp), the sub-command `bamindex`
+// and --write-bam-index FILE (call, run: the index of the input BAM as a by-product, bam_input_index.h).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -36,6 +38,7 @@
 #include "bam_device_select.h"
 #include "bam_region_ranges.h"
 #include "run_samples.h"
+#include "bam_input_index.h"
 
 static const char* VERSION = "v2.1.1";  // main.cpp:19
 
@@ -43,6 +46,7 @@ static const char* VERSION = "v2.1.1";  // main.cpp:19
 // `run` then says so)
 __attribute__((weak)) int main_run(const CallOptions& o);
 __attribute__((weak)) int main_run_samples(const CallOptions& o, const std::string& list, const std::vector<std::string>& regions, const std::string& regions_file);
+__attribute__((weak)) int main_bamindex(const CallOptions& o);
 
 static const char* MAIN_USAGE =
     "Usage: SVDSS <index|smooth|search|call|run> --help\n"
@@ -61,6 +65,11 @@ static const char* MAIN_USAGE =
     "                            With <BAM>.bai, <BAM>.csi or <stem>.bai not older than the BAM only the parts of the file\n" \
     "                            the index names are read, as one stream on one GPU whatever --gpus says; without one the\n" \
     "                            whole file is read.  Either way the records are tested on the GPU\n"
+
+#define WRITE_BAM_INDEX_HELP \
+    "      --write-bam-index <FILE>    also write the index of <BAM> itself (what `SVDSS bamindex` writes: CSI if FILE ends in\n" \
+    "                                  .csi, else BAI), a by-product of the pass that reads it anyway.  Not with --region /\n" \
+    "                                  --regions-file.  An unsorted BAM: a warning, no index, the output as without the option\n"
 
 static const char* SMOOTH_USAGE =
     "Usage: SVDSS smooth --reference <FASTA> --bam <BAM> > smoothed.bam\n"
@@ -89,6 +98,7 @@ static const char* CALL_USAGE =
     "      -l <float>                  minimum length ratio for sub-clusters and chain merging (default: 0.97)\n"
     "      --noht                      ignore the HP tag\n"
     "      --clipped                   also call imprecise SVs from soft-clipped alignments (EXPERIMENTAL)\n"
+    WRITE_BAM_INDEX_HELP
     REGION_HELP;
 
 static const char* RUN_USAGE =
@@ -112,7 +122,19 @@ static const char* RUN_USAGE =
     "                            --smoothed, --write-index, --compress, --poa or --clusters.  A sample that fails ends the\n"
     "                            process with a non-zero status: the samples before it are complete, it leaves no file, the\n"
     "                            samples after it are not started\n"
+    WRITE_BAM_INDEX_HELP
     REGION_HELP;
+
+static const char* BAMINDEX_USAGE =
+    "Usage: SVDSS bamindex --bam <BAM> [-o <FILE>]\n"
+    "      the index of <BAM> (sorted by coordinate), what `samtools index` writes: one pass over the file, the records\n"
+    "      indexed on the GPU where they are inflated\n"
+    "      -o <FILE>         the index (default: <BAM>.bai): CSI if FILE ends in .csi, else BAI (no reference longer than\n"
+    "                        2^29 - 1 then).  Written as <FILE>.tmp and renamed when complete\n"
+    "      --gpus <N|all>    the file's regions, one per GPU\n"
+    "      --threads <int>   accepted as by the other sub-commands (the pass is bound by the inflate on the GPU)\n"
+    "      --verbose         records, chunks, windows, compressed bytes read and seconds on stderr\n"
+    "      SVDSS_BAM_DEVICE=0 runs the host reader instead (one thread); without a GPU and without it the command stops\n";
 
 static const char* SEARCH_USAGE =
     "Usage: SVDSS search --index <FMD> --bam <BAM> | --fastx <FASTA/FASTQ>\n"
@@ -121,6 +143,13 @@ static const char* SEARCH_USAGE =
     "      --noputative      search all reads, not only XF == 0\n"
     "      --noassemble      do not merge overlapping specific strings\n"
     REGION_HELP;
+
+// do two paths name one file?  (the same text, or the same inode where both exist)
+static bool same_file(const std::string& a, const std::string& b) {
+  if (a == b) return true;
+  struct stat sa, sb;
+  return stat(a.c_str(), &sa) == 0 && stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
 
 static Options parse(int argc, char** argv) {
   Options o;
@@ -293,6 +322,9 @@ int main(int argc, char** argv) {
     for (int i = 2; i < argc; ++i)
       if (!strncmp(argv[i], "--region", 8) && (argv[i][8] == 0 || argv[i][8] == '=' || !strncmp(argv[i] + 8, "s-file", 6)))
         die(std::string(argv[i]) + ": --region / --regions-file select records of a BAM by position: not an option of `SVDSS index`");
+    for (int i = 2; i < argc; ++i)
+      if (!strncmp(argv[i], "--write-bam-index", 17) && (argv[i][17] == 0 || argv[i][17] == '='))
+        die("--write-bam-index is an option of `SVDSS call` and `SVDSS run` only, not of `SVDSS index`");
     logmsg("info", "FM-index construction (stands for 'ropebwt3 build')");
     const int rc = main_index(argc, argv);
     if (rc) return rc;
@@ -302,7 +334,8 @@ int main(int argc, char** argv) {
     const Options o = parse(argc, argv);
     if (o.help) {   // Configuration::print_help(argv[1]), config.cpp:12-24: the mode's own usage text
       fputs(!strcmp(argv[1], "search") ? SEARCH_USAGE : !strcmp(argv[1], "call") ? CALL_USAGE :
-            !strcmp(argv[1], "smooth") ? SMOOTH_USAGE : !strcmp(argv[1], "run") ? RUN_USAGE : MAIN_USAGE, stderr);
+            !strcmp(argv[1], "smooth") ? SMOOTH_USAGE : !strcmp(argv[1], "run") ? RUN_USAGE :
+            !strcmp(argv[1], "bamindex") ? BAMINDEX_USAGE : MAIN_USAGE, stderr);
       return EXIT_SUCCESS;
     }
     if (o.nobam && strcmp(argv[1], "smooth") != 0) die(std::string("--nobam is an option of `SVDSS smooth` only, not of `SVDSS ") + argv[1] + "`");
@@ -312,6 +345,29 @@ int main(int argc, char** argv) {
       die(std::string("--smoothed is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
     if (!o.samples.empty() && strcmp(argv[1], "run") != 0)
       die(std::string("--samples is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
+    // --write-bam-index FILE / bamindex -o FILE: what they do not go with, before anything is opened for writing
+    const bool is_bamindex = !strcmp(argv[1], "bamindex");
+    if (!o.out.empty() && !is_bamindex) die(std::string("-o is an option of `SVDSS bamindex` only, not of `SVDSS ") + argv[1] + "`");
+    if (!o.write_bam_index.empty() && strcmp(argv[1], "call") != 0 && strcmp(argv[1], "run") != 0)
+      die(std::string("--write-bam-index is an option of `SVDSS call` and `SVDSS run` only, not of `SVDSS ") + argv[1] + "`" +
+          (is_bamindex ? " (its index is named by -o)" : ""));
+    if (is_bamindex && o.bam.empty()) { fputs(BAMINDEX_USAGE, stderr); return EXIT_FAILURE; }
+    const std::string bam_index_out = is_bamindex ? (o.out.empty() ? o.bam + ".bai" : o.out) : o.write_bam_index;
+    if (!bam_index_out.empty()) {
+      const char* opt = is_bamindex ? "bamindex -o" : "--write-bam-index";
+      if (!o.regions.empty() || !o.regions_file.empty())
+        die(std::string(opt) + " does not go with --region / --regions-file: a read bounded by an index sees part of the file, and the index is of the whole");
+      if (!o.samples.empty()) die(std::string("run: --samples does not go with ") + opt + " (every sample's files are named by its line of the list)");
+      for (const std::string* in : {&o.bam, &o.reference, &o.sfs, &o.index, &o.fastx})
+        if (!in->empty() && same_file(*in, bam_index_out) && !(in == &o.sfs && !strcmp(argv[1], "run")))
+          die(std::string(opt) + " " + bam_index_out + ": that is an input of the command");
+      if (!is_bamindex && !o.bam.empty()) {   // (a BAI for a reference that is too long: said now, not after the pass)
+        std::vector<int32_t> lens;
+        std::string err;
+        InputIndexFold probe;
+        if (bam_header_lengths(o.bam, lens, err) && !probe.open(bam_index_out, lens, opt, err)) die(err);
+      }
+    }
     if (!strcmp(argv[1], "search") || !strcmp(argv[1], "call") || !strcmp(argv[1], "smooth") || !strcmp(argv[1], "run")) regions_in_force(o, argv[1]);
     if (!strcmp(argv[1], "search")) {
       if (o.index.empty() || (o.fastx.empty() && o.bam.empty())) { fputs(SEARCH_USAGE, stderr); return EXIT_FAILURE; }
@@ -322,7 +378,7 @@ int main(int argc, char** argv) {
       c.reference = o.reference; c.bam = o.bam; c.sfs = o.sfs; c.threads = o.threads; c.gpus = o.gpus;
       c.min_cluster_weight = o.min_cluster_weight; c.min_sv_length = o.min_sv_length; c.min_mapq = o.min_mapq;
       c.useht = o.useht; c.min_ratio = o.min_ratio; c.poa = o.poa; c.clusters = o.clusters; c.verbose = o.verbose;
-      c.clipped = o.clipped;
+      c.clipped = o.clipped; c.write_bam_index = o.write_bam_index;
       main_call(c);
     } else if (!strcmp(argv[1], "smooth")) {
       if (o.reference.empty() || o.bam.empty()) { fputs(SMOOTH_USAGE, stderr); return EXIT_FAILURE; }   // main.cpp:73-76
@@ -353,10 +409,15 @@ int main(int argc, char** argv) {
       c.min_mapq = o.min_mapq; c.accp = o.accp; c.write_index = o.write_index; c.compress = o.compress;
       c.bsize = o.bsize; c.putative = o.putative; c.assemble = o.assemble;
       c.min_cluster_weight = o.min_cluster_weight; c.min_sv_length = o.min_sv_length; c.useht = o.useht; c.min_ratio = o.min_ratio;
-      c.poa = o.poa; c.clusters = o.clusters; c.clipped = o.clipped; c.verbose = o.verbose;
+      c.poa = o.poa; c.clusters = o.clusters; c.clipped = o.clipped; c.verbose = o.verbose; c.write_bam_index = o.write_bam_index;
       if (!main_run || !main_run_samples) die("this build of the binary has no `run` (run_host.cpp was left out)");
       if (o.samples.empty()) main_run(c);
       else main_run_samples(c, o.samples, o.regions, o.regions_file);
+    } else if (is_bamindex) {
+      CallOptions c;
+      c.bam = o.bam; c.write_bam_index = bam_index_out; c.threads = o.threads; c.gpus = o.gpus; c.verbose = o.verbose;
+      if (!main_bamindex) die("this build of the binary has no `bamindex` (bamindex_host.cpp was left out)");
+      main_bamindex(c);
     } else {
       fputs(MAIN_USAGE, stderr);
       return EXIT_FAILURE;
