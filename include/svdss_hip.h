@@ -659,6 +659,56 @@ int svdss_ref_upload(const uint8_t* seqs, const int64_t* off, int32_t n_chrom, i
  * 3 GB copy on the host to put them back to back first */
 int svdss_ref_upload_parts(const uint8_t* const* seqs, const int64_t* lens, int32_t n_chrom, int32_t device, svdss_ref_t** out);
 void svdss_ref_free(svdss_ref_t* ref);
+/* what a svdss_ref_t holds, back on the host (tests): n_chrom, and -- where given -- its n_chrom + 1 offsets and its bytes */
+int svdss_ref_read(const svdss_ref_t* ref, int32_t* n_chrom, int64_t* off, uint8_t* seqs);
+
+/* ---- the reference FASTA inflated and parsed on the device (csrc/ref_stream.hip) ---------------------------------
+ * Stands where load_chromosomes stands (chromosomes.cpp:9-27: kseq_read per record, toupper per base) and leaves the
+ * chromosomes where svdss_ref_upload would put them.  A svdss_ref_stream_t is one FASTA being read in batches numbered in
+ * file order (seq = 0, 1, 2, ...: every number exactly once, from any thread; is_last on the final one, which may be
+ * empty).  A batch is BGZF members (n_chunks pieces as for svdss_fastx_batch_run, CRC32 checked) or plain text (plain,
+ * plain_bytes; n_chunks = 0).  Upload, inflate and CRC of different batches overlap; the parse runs in the batch's turn.
+ * The shape: first byte '>', no '\r', no NUL, no line beginning with '@', no header line longer than header_cap bytes
+ * ('>' counted, '\n' not), no name twice.  Within it there is a record at every line that begins with '>', named by the
+ * bytes behind '>' up to the first blank or tab; its sequence is every other line up to the next header, joined, a-z
+ * raised, every other byte kept -- what FastxReader::next and the toupper of load_chromosomes give.  Anything else, a
+ * failed inflate and a CRC mismatch (those two also return SVDSS_EIO, from that batch and every later one) DECLINE the
+ * stream as a whole: later batches return at once, nothing is delivered, the caller reads the file with the host reader.
+ * After the last batch:
+ *   svdss_ref_stream_result    the records (or why and where the stream declined) and the counters
+ *   svdss_ref_stream_download  one record's bases, from the host copy the batches brought down while later ones ran
+ *   svdss_ref_stream_finish    records order[0 .. n) back to back as a svdss_ref_t on `device` (the stream's) -- what
+ *                              svdss_ref_upload_parts builds from the same strings -- by device-to-device copies; the
+ *                              stream's device memory is freed (once per stream; the host copy stays) */
+enum { SVDSS_REF_CR = 1, SVDSS_REF_NUL = 2, SVDSS_REF_AT = 3, SVDSS_REF_NOT_FASTA = 4, SVDSS_REF_DUPLICATE = 5,
+       SVDSS_REF_LONG_HEADER = 6, SVDSS_REF_EMPTY = 7, SVDSS_REF_IO = 8, SVDSS_REF_ERROR = 9 };
+typedef struct svdss_ref_stream svdss_ref_stream_t;
+typedef struct svdss_ref_stream_result {
+  int64_t n_records;
+  const int64_t* name_off;  /* n_records + 1: record i is called names[name_off[i] .. name_off[i + 1]) */
+  const char* names;
+  const int64_t* seq_off;   /* n_records + 1: where record i's bases stand in the whole output */
+  int32_t declined;         /* 0, or SVDSS_REF_*: nothing above is delivered */
+  int64_t declined_at;      /* the byte of the text it was decided at */
+  int64_t n_batches;        /* batches that had their turn */
+  int64_t text_bytes;
+  double inflate_kernel_ms; /* HIP events, summed over the batches */
+  double parse_kernel_ms;
+} svdss_ref_stream_result_t;
+int svdss_ref_stream_create(int32_t device, int64_t header_cap, svdss_ref_stream_t** out);
+int svdss_ref_stream_batch(svdss_ref_stream_t* s, int64_t seq, int32_t is_last, int32_t n_chunks, const uint8_t* const* comp,
+                           const int64_t* comp_bytes, const svdss_bgzf_block_t* const* blocks, const uint32_t* const* crc,
+                           const int64_t* n_blocks, const uint8_t* plain, int64_t plain_bytes);
+int svdss_ref_stream_result(const svdss_ref_stream_t* s, svdss_ref_stream_result_t* out);
+int svdss_ref_stream_download(const svdss_ref_stream_t* s, int64_t rec, uint8_t* dst);
+int svdss_ref_stream_finish(svdss_ref_stream_t* s, const int32_t* order, int32_t n, int32_t device, svdss_ref_t** out);
+/* the host copy is not needed any more (the caller has its records): its memory goes back; svdss_ref_stream_download fails from here on */
+void svdss_ref_stream_drop_host(svdss_ref_stream_t* s);
+void svdss_ref_stream_free(svdss_ref_stream_t* s);
+const char* svdss_ref_stream_error(const svdss_ref_stream_t* s);
+/* bytes per tile of its kernels (tests aim at its edges) */
+int32_t svdss_ref_stream_tile_bytes(void);
+
 int svdss_place_sfs_batch(svdss_ref_t* ref, const int32_t* tid, const int32_t* pos, const uint32_t* cigar,
                           const int64_t* cigar_off, const int32_t* sfs_qs, const int32_t* sfs_len, const int64_t* sfs_off,
                           int64_t n_aln, int32_t* out_count, int32_t* out, int64_t stats[4]);

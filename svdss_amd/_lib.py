@@ -167,6 +167,16 @@ SIGNATURES = {
     "svdss_ref_upload": (C.c_int, [_p, _p, _i32, _i32, C.POINTER(_p)]),
     "svdss_ref_upload_parts": (C.c_int, [_p, _p, _i32, _i32, C.POINTER(_p)]),
     "svdss_ref_free": (None, [_p]),
+    "svdss_ref_read": (C.c_int, [_p, _pi32, _p, _p]),
+    "svdss_ref_stream_create": (C.c_int, [_i32, _i64, C.POINTER(_p)]),
+    "svdss_ref_stream_batch": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64]),
+    "svdss_ref_stream_result": (C.c_int, [_p, _p]),
+    "svdss_ref_stream_download": (C.c_int, [_p, _i64, _p]),
+    "svdss_ref_stream_finish": (C.c_int, [_p, _p, _i32, _i32, C.POINTER(_p)]),
+    "svdss_ref_stream_drop_host": (None, [_p]),
+    "svdss_ref_stream_free": (None, [_p]),
+    "svdss_ref_stream_error": (C.c_char_p, [_p]),
+    "svdss_ref_stream_tile_bytes": (_i32, []),
     "svdss_place_sfs_batch": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
     "svdss_smooth_batch": (C.c_int, [_p] * 11 + [_i64] + [_p] * 7),
     "svdss_align_global_batch": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _i32, _i32, _i32, _i32, _i32,

@@ -548,16 +548,19 @@ def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20,
         raw_head += zlib.decompress(bytes(data[coff:coff + clen]), -15)
         if len(raw_head) >= skip:
             break
-    cat = np.frombuffer("".join(contigs_ascii).encode(), dtype=np.uint8)
-    off = np.concatenate([[0], np.cumsum([len(c) for c in contigs_ascii])]).astype(np.int64)
+    resident = contigs_ascii if hasattr(contigs_ascii, "_h") else None   # (refdev.ResidentRef: the chromosomes are in HBM already)
+    n_contigs = resident.n if resident else len(contigs_ascii)
     tid_map = np.full(n_ref, -1, dtype=np.int32)
-    tid_map[:len(contigs_ascii)] = np.arange(len(contigs_ascii), dtype=np.int32)
+    tid_map[:n_contigs] = np.arange(n_contigs, dtype=np.int32)
     comp = np.frombuffer(bytes(data), dtype=np.uint8)
     ref, sm, stream, batch = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
     out = bytearray()
     try:
-        _check(lib.svdss_ref_upload(cat.ctypes.data, off.ctypes.data, len(contigs_ascii), device, C.byref(ref)), "svdss_ref_upload")
-        _check(lib.svdss_bam_smooth_create(ref, tid_map.ctypes.data, n_ref, min_mapq, C.byref(sm)), "svdss_bam_smooth_create")
+        if resident is None:
+            cat = np.frombuffer("".join(contigs_ascii).encode(), dtype=np.uint8)
+            off = np.concatenate([[0], np.cumsum([len(c) for c in contigs_ascii])]).astype(np.int64)
+            _check(lib.svdss_ref_upload(cat.ctypes.data, off.ctypes.data, len(contigs_ascii), device, C.byref(ref)), "svdss_ref_upload")
+        _check(lib.svdss_bam_smooth_create(resident._h if resident else ref, tid_map.ctypes.data, n_ref, min_mapq, C.byref(sm)), "svdss_bam_smooth_create")
         if store is not None:
             _check(lib.svdss_bam_smooth_set_store(sm, store._h, min_mapq if store_min_mapq is None else store_min_mapq), "svdss_bam_smooth_set_store")
         _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")

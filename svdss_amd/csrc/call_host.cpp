@@ -39,6 +39,7 @@
 #include "sv_record.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "ref_loader.h"
 
 namespace {
 
@@ -688,6 +689,7 @@ struct CallRun {
   std::vector<ESFS> extended;            // pass 1: every placed SFS
   std::vector<Clip> clips;               // --clipped
   std::thread fasta_loader;              // load_chromosomes, beside the SFS file and the start of pass 1
+  RefOnDevice ref_dev;                   // where the GPU read the FASTA (ref_loader.h): its output, kept in HBM until the BAM header's order is known
   // ONE pass over the BAM (round 6): what pass 2 needs of every record stays in HBM while pass 1 runs (svdss_bam_store_t)
   // (--gpus N: the file's regions, one per GPU, each with a store of its own in that GPU's HBM -- and a small one for the
   // records of the seam in front of it; ShardedBamSelect, bam_device_select.h)
@@ -746,7 +748,7 @@ struct CallRun {
     } else {
       if (FILE* f = fopen(o.reference.c_str(), "rb")) fclose(f); else die("cannot open " + o.reference);
       fasta_loader = std::thread([this] {
-        if (!load_chromosomes(o.reference, T, knobs.fasta_serial, C.chrom_names, C.chrom_seqs)) die("cannot open " + o.reference);
+        if (!load_chromosomes(o.reference, T, knobs.fasta_serial, o.verbose, "call", C.chrom_names, C.chrom_seqs, &ref_dev)) die("cannot open " + o.reference);
       });
     }
     // the record store(s) of the ONE pass over the BAM (round 6, align_and_extend / fill_clusters below): the memory is taken
@@ -938,7 +940,8 @@ struct CallRun {
           if (sm->session) session_dref = sm->dref;
           else if (!place_on_gpu) svdss_ref_free(sm->dref);
           sm->dref = nullptr;
-        } else if (place_on_gpu) check(upload_chromosomes(ref_names, C.chrom_seqs, 0, tid_map, &dref), "svdss_ref_upload_parts");
+        } else if (place_on_gpu) check(resident_chromosomes(&ref_dev, ref_names, C.chrom_seqs, tid_map, &dref), "svdss_ref_upload_parts");
+        ref_dev.drop();
       };
       // two batches: the next one is read (inflate + slicing, this thread) while the T slices of the previous one run
       std::vector<BamRecord> batches[2];

@@ -52,19 +52,30 @@ inline int64_t env_from(const char* name, int64_t least, int64_t dflt) { const c
 inline int64_t env_raised(const char* name, int64_t least, int64_t dflt) { const char* e = getenv(name); return e ? std::max<int64_t>(least, atoll(e)) : dflt; }
 inline int env_switch(const char* name) { const char* e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }
 
+// the header references the FASTA has, in header order: `has(name)` says whether it does; tid_map[t]: the place of header
+// reference t among them, -1 where the FASTA has no such name
+template <class Has>
+inline std::vector<size_t> header_order(const std::vector<std::string>& ref_names, Has has, std::vector<int32_t>& tid_map) {
+  std::vector<size_t> order;
+  tid_map.assign(ref_names.size(), -1);
+  for (size_t t = 0; t < ref_names.size(); ++t) {
+    if (!has(ref_names[t])) continue;
+    tid_map[t] = (int32_t)order.size();
+    order.push_back(t);
+  }
+  return order;
+}
+
 // the chromosomes the BAM header names, in its order, one buffer on `device` (svdss_ref_upload_parts: no concatenation on
-// the host); tid_map[t]: the buffer's index of header reference t, -1 where the FASTA has no such name
+// the host); tid_map as header_order leaves it
 inline int upload_chromosomes(const std::vector<std::string>& ref_names, const std::unordered_map<std::string, std::string>& seqs, int device,
                               std::vector<int32_t>& tid_map, svdss_ref_t** dref) {
   std::vector<const uint8_t*> parts;
   std::vector<int64_t> lens;
-  tid_map.assign(ref_names.size(), -1);
-  for (size_t t = 0; t < ref_names.size(); ++t) {
-    auto it = seqs.find(ref_names[t]);
-    if (it == seqs.end()) continue;
-    tid_map[t] = (int32_t)parts.size();
-    parts.push_back((const uint8_t*)it->second.data());
-    lens.push_back((int64_t)it->second.size());
+  for (const size_t t : header_order(ref_names, [&](const std::string& n) { return seqs.count(n) > 0; }, tid_map)) {
+    const std::string& s = seqs.find(ref_names[t])->second;
+    parts.push_back((const uint8_t*)s.data());
+    lens.push_back((int64_t)s.size());
   }
   return svdss_ref_upload_parts(parts.data(), lens.data(), (int32_t)parts.size(), device, dref);
 }

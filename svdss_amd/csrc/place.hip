@@ -234,6 +234,30 @@ SvdssRefView svdss_ref_view(const svdss_ref_t* ref) {
   return v;
 }
 
+int svdss_ref_adopt(int device, void* d_seq, void* d_off, int32_t n_chrom, svdss_ref_t** out) {
+  if (!out || device < 0 || n_chrom < 0 || !d_seq || !d_off) return SVDSS_EINVAL;
+  HIPCHK(hipSetDevice(device));
+  svdss_ref* r = new (std::nothrow) svdss_ref();
+  if (!r) return SVDSS_ENOMEM;
+  if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) { delete r; return SVDSS_EHIP; }
+  r->device = device;
+  r->n_chrom = n_chrom;
+  r->d_ref = d_seq;
+  r->d_off = d_off;
+  *out = r;
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_ref_read(const svdss_ref_t* ref, int32_t* n_chrom, int64_t* off, uint8_t* seqs) {
+  if (!ref) return SVDSS_EINVAL;
+  if (n_chrom) *n_chrom = ref->n_chrom;
+  if (!off) return seqs ? SVDSS_EINVAL : SVDSS_OK;
+  HIPCHK(hipSetDevice(ref->device));
+  HIPCHK(hipMemcpy(off, ref->d_off, sizeof(int64_t) * (size_t)(ref->n_chrom + 1), hipMemcpyDeviceToHost));
+  if (seqs && off[ref->n_chrom] > 0) HIPCHK(hipMemcpy(seqs, ref->d_ref, (size_t)off[ref->n_chrom], hipMemcpyDeviceToHost));
+  return SVDSS_OK;
+}
+
 extern "C" int svdss_ref_upload(const uint8_t* seqs, const int64_t* off, int32_t n_chrom, int32_t device, svdss_ref_t** out) {
   if (!out || n_chrom < 0 || device < 0 || (n_chrom > 0 && (!seqs || !off))) return SVDSS_EINVAL;
   HIPCHK(hipSetDevice(device));

@@ -11,3 +11,5 @@ struct SvdssRefView {
   int32_t n_chrom = 0;
 };
 SvdssRefView svdss_ref_view(const svdss_ref_t* ref);
+// a svdss_ref_t over buffers that are on `device` already (csrc/ref_stream.hip): on SVDSS_OK they are the object's
+int svdss_ref_adopt(int device, void* d_seq, void* d_off, int32_t n_chrom, svdss_ref_t** out);

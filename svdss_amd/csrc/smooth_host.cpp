@@ -35,6 +35,7 @@
 #include "bam_index_writer.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "ref_loader.h"
 #include "sfs_units.h"
 
 namespace {
@@ -448,6 +449,7 @@ struct SmoothRun {
   std::unique_ptr<SfsSide> side;         // --index FMD --sfs FILE
   svdss_bam_park_t* park = nullptr;
   std::unordered_map<std::string, std::string> chrom;
+  RefOnDevice ref_dev;                   // where the GPU read the FASTA (ref_loader.h): its output, for GPU 0's copy of the chromosomes
   HeaderPre hp;
   bool ix_csi = false;                   // --write-index FILE: the scheme, and what collects the index
   int ix_shift = 14, ix_depth = 5;
@@ -495,7 +497,7 @@ struct SmoothRun {
     std::vector<std::string> names;
     if (hooks && hooks->session && !hooks->chrom_names.empty()) chrom = std::move(hooks->chrom_seqs);   // (read by a sample before)
     else {
-      if (!load_chromosomes(o.reference, o.threads, knobs.fasta_serial, names, chrom)) die("cannot open " + o.reference);
+      if (!load_chromosomes(o.reference, o.threads, knobs.fasta_serial, o.verbose, "smooth", names, chrom, &ref_dev)) die("cannot open " + o.reference);
       if (hooks) { hooks->chrom_names = std::move(names); ++hooks->n_fasta_reads; }
       if (hooks && hooks->session && (o.verbose || knobs.debug)) fprintf(stderr, "[run] reference: FASTA read, %zu sequence(s)\n", chrom.size());
     }
@@ -761,7 +763,7 @@ struct DevicePipeline {
         if (o.verbose || R.knobs.debug) fprintf(stderr, "[run] reference: copy on the GPU reused\n");
       } else {
         if (h && h->dref) { svdss_ref_free(h->dref); h->dref = nullptr; }
-        rc = upload_chromosomes(hp.names, R.chrom, (int)d, tm, &drefs[d]);
+        rc = d == 0 ? resident_chromosomes(&R.ref_dev, hp.names, R.chrom, tm, &drefs[d]) : upload_chromosomes(hp.names, R.chrom, (int)d, tm, &drefs[d]);
         if (h) ++h->n_ref_uploads;
         if (h && (o.verbose || R.knobs.debug)) fprintf(stderr, "[run] reference: uploaded to the GPU in the order of the BAM header\n");
       }
@@ -934,10 +936,10 @@ struct HostPipeline {
     if (R.ixb) w->record_members(&members);
     bam_write_header(*w, bam->header_text(), bam->ref_names(), bam->ref_lens());
     tid_map.assign(bam->ref_names().size(), -1);
-    if (R.knobs.smooth_host) return;   // (a developer switch: the host code below)
+    if (R.knobs.smooth_host) { R.ref_dev.drop(); return; }   // (a developer switch: the host code below)
     // (no GPU and no SVDSS_SMOOTH_HOST=1: the command fails rather than quietly running the host walk)
     if (svdss_device_count() <= 0) die("no GPU found: SVDSS smooth walks the alignments on the GPU (SVDSS_SMOOTH_HOST=1 runs the host code instead)");
-    if (upload_chromosomes(bam->ref_names(), R.chrom, 0, tid_map, &dref) != SVDSS_OK) die(std::string("svdss_ref_upload: ") + svdss_last_hip_error());
+    if (resident_chromosomes(&R.ref_dev, bam->ref_names(), R.chrom, tid_map, &dref) != SVDSS_OK) die(std::string("svdss_ref_upload: ") + svdss_last_hip_error());
   }
   // smooth_read (smoother.cpp:84-232) of one record into its serialised BAM bytes
   void smooth_one(const BamRecord& r, ByteSink& sink) const {

@@ -35,6 +35,7 @@
 #include "cli_options.h"
 #include "call_host.h"
 #include "fastx_reader.h"
+#include "ref_loader.h"
 #include "bam_device_select.h"
 #include "bam_region_ranges.h"
 #include "run_samples.h"
@@ -209,8 +210,10 @@ static int main_index(int argc, char** argv) {
   // ropebwt3 `build` flags as run_svdss:142 passes them: -t T -d <fasta> -o <out>
   std::string fasta, out;
   int threads = 4;
+  bool verbose = false;
   for (int i = 2; i < argc; ++i) {
-    if (!strcmp(argv[i], "-t") && i + 1 < argc) threads = atoi(argv[++i]);
+    if (!strcmp(argv[i], "--verbose")) verbose = true;
+    else if (!strcmp(argv[i], "-t") && i + 1 < argc) threads = atoi(argv[++i]);
     else if (!strncmp(argv[i], "-t", 2) && argv[i][2]) threads = atoi(argv[i] + 2);
     else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
     else if (!strcmp(argv[i], "-d") || !strcmp(argv[i], "-b")) continue;  // output-format switches of ropebwt3
@@ -237,7 +240,9 @@ static int main_index(int argc, char** argv) {
     // a plain FASTA is mapped and read by several threads (fastx_reader.h, as `call` and `smooth` do), the records encoded
     // side by side into one buffer sized once; gzip / CRLF / FASTQ-like files go through the line reader as before
     std::vector<std::string> nm, sq;
-    if (!getenv("SVDSS_FASTA_SERIAL") && load_fasta_mapped(fasta, std::max(1, std::min(threads < 8 ? 8 : threads, 16)), false, nm, sq)) {
+    // (a BGZF file is inflated and parsed on the GPU first, ref_loader.h: upper-cased there, which svdss_nt6_encode does not mind)
+    if (load_reference_device(fasta, threads < 8 ? 8 : threads, getenv("SVDSS_FASTA_SERIAL") != nullptr, verbose, "index", nm, sq, nullptr) ||
+        (!getenv("SVDSS_FASTA_SERIAL") && load_fasta_mapped(fasta, std::max(1, std::min(threads < 8 ? 8 : threads, 16)), false, nm, sq))) {
       std::vector<size_t> at(sq.size() + 1, 0);
       for (size_t i = 0; i < sq.size(); ++i) { at[i + 1] = at[i] + sq[i].size(); lens.push_back((int64_t)sq[i].size()); }
       cat.resize(at.back());
