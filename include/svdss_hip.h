@@ -71,6 +71,22 @@ int svdss_index_save_fmd(const svdss_index_t* ix, const char* path);
 /* The BWT an rld0 `.fmd` holds, as nt6 bytes: *n_out symbols (bwt_out may be NULL to ask for the size only;
  * SVDSS_ERANGE if cap is too small). */
 int svdss_fmd_read_bwt(const char* path, uint8_t* bwt_out, int64_t cap, int64_t* n_out);
+/* The strings of the collection a BWT stands for (nt6, '$' = 0 in `bwt`): string r is the one spelled from row r;
+ * they are written back to back into out (n - m bytes), their lengths into lens.  device >= 0: rank blocks built
+ * and walked there (csrc/bwt_invert.hip: marked LF walks, a walker per lane; the same walk on the host where HBM has
+ * no room); device < 0: the same walk on the host.  stride: the distance of the marked rows at which the walks are cut;
+ * 0 = SVDSS_INVERT_STRIDE or the default; the result never depends on it.  stride < 0 (host only): one serial walk
+ * per string without a step limit -- what a caller takes after SVDSS_ERANGE for the limit.
+ * SVDSS_EINVAL: a null pointer, n <= 0, a symbol above 5.  SVDSS_ERANGE with *n_strings = the number of strings: a
+ * capacity is too small; SVDSS_ERANGE otherwise: a walker passed SVDSS_INVERT_MAX_STEPS steps, or a symbol occurs 2^32
+ * times or more.  SVDSS_EIO: not the BWT of a string collection (a walker on no chain or on two, lengths that do not sum
+ * to n - m). */
+int svdss_bwt_strings(const uint8_t* bwt, int64_t n, int32_t device, int64_t stride,
+                      uint8_t* out, int64_t out_cap, int64_t* lens, int32_t lens_cap, int32_t* n_strings);
+/* How the calling thread's last svdss_bwt_strings ran: *route 0 = the marked walks on the host, 1 = on the device,
+ * 2 = the serial walk per string; its stride and walkers; ms[3] = milliseconds of the rank blocks' build, pass 1, pass 2
+ * (route 2: everything in ms[1]).  SVDSS_ENODEV before the first call. */
+int svdss_bwt_strings_last(int32_t* route, int64_t* stride, int64_t* walkers, double* ms);
 /* Restores an index: this library's own files (svdss_index_save, svdss_index_save_records), or an rld0 `.fmd` -- then
  * `<path>.svdss` (the file `SVDSS index` leaves beside the .fmd) is read if it is there, not older, and carries the
  * symbol counts of the .fmd's header; otherwise the BWT is
@@ -78,6 +94,15 @@ int svdss_fmd_read_bwt(const char* path, uint8_t* bwt_out, int64_t cap, int64_t*
  * inserts them) and the index is rebuilt on the GPU (no GPU: SVDSS_EHIP, unless SVDSS_INDEX_CPU=1 asks for the host
  * builder). */
 int svdss_index_load(const char* path, svdss_index_t** out);
+/* The records an index file stands for, without building the index (`SVDSS index -i OLD`): a handle that holds
+ * them, from the sidecar `path`.svdss (or `path` itself, this library's layout) where svdss_index_load would read
+ * that, else out of the .fmd's BWT: svdss_bwt_strings on `device` (< 0: on the host), one string of every
+ * reverse-complement pair.  *source: 0 records sidecar, 1 full layout, 2 device walk, 3 host walk, 4 the serial walk per
+ * string (SVDSS_FMD_IMPORT_DEVICE=0, or past the step limit).  Errors as svdss_index_load reports them. */
+int svdss_index_records_open(const char* path, int32_t device, svdss_index_t** out, int32_t* source);
+/* The records a handle holds (nt6, back to back) and their lengths: pointers into the handle, valid until it is freed
+ * or made resident.  SVDSS_ENODEV: it holds none. */
+int svdss_index_records(const svdss_index_t* ix, const uint8_t** records, const int64_t** lens, int32_t* n_records);
 void svdss_index_free(svdss_index_t* ix);
 /* number of BWT symbols, = sum_i 2*(lens[i]+1) */
 int64_t svdss_index_size(const svdss_index_t* ix);

@@ -238,8 +238,16 @@ extern "C" int svdss_fmd_read_bwt(const char* path, uint8_t* bwt_out, int64_t ca
   return SVDSS_OK;
 }
 
-// an rld0 file (ropebwt3 / upstream `SVDSS index`): decode the BWT, recover the strings, rebuild this layout
-static int import_fmd(const char* path, svdss_index_t** out) {
+static const char* NOT_CLOSED_MSG = "the .fmd is not an index of records AND their reverse complements (ropebwt3 build without -d?)";
+
+// where the records of an index came from (svdss_index_records_open)
+enum { REC_SIDECAR = 0, REC_LAYOUT = 1, REC_DEVICE_WALK = 2, REC_HOST_WALK = 3, REC_SERIAL_WALK = 4 };
+
+// The records an rld0 file (ropebwt3 / upstream `SVDSS index`) stands for: decode the BWT, recover the strings, keep one
+// of every reverse-complement pair.  device >= 0: the strings by marked LF walks on that GPU (svdss_bwt_strings,
+// bwt_invert.hip), -1: by the same walks on the host, -2: by one serial walk per string (rld0_strings_of_bwt) -- which
+// also takes over where a marked walk passed its step limit.
+static int fmd_records(const char* path, int device, std::vector<uint8_t>& cat, std::vector<int64_t>& lens, int* source) {
   std::vector<uint8_t> bwt;
   int rc = rld0_read(path, bwt);
   if (rc != SVDSS_OK) return rc;
@@ -247,27 +255,124 @@ static int import_fmd(const char* path, svdss_index_t** out) {
 #ifdef _OPENMP
   threads = omp_get_max_threads();
 #endif
+  const int64_t n = (int64_t)bwt.size();
   std::vector<std::vector<uint8_t>> strings;
-  rc = rld0_strings_of_bwt(bwt.data(), (int64_t)bwt.size(), threads, strings);
-  if (rc != SVDSS_OK) return rc;
-  std::vector<uint8_t>().swap(bwt);
+  bool walked = false;
+  if (device >= -1 && n > 0) {
+    int64_t m = 0;
+    rc = rld0_count_sentinels(bwt.data(), n, threads, &m);
+    if (rc != SVDSS_OK) return SVDSS_EIO;
+    if (m <= 0 || m >= ((int64_t)1 << 31)) return SVDSS_EIO;
+    std::vector<uint8_t, SvdssNoInitAlloc<uint8_t>> flat;
+    std::vector<int64_t> sl;
+    try { flat.resize((size_t)(n - m) + 1); sl.assign((size_t)m, 0); } catch (...) { return SVDSS_ENOMEM; }
+    int32_t k = 0;
+    rc = svdss_bwt_strings(bwt.data(), n, device, 0, flat.data(), n - m, sl.data(), (int32_t)m, &k);
+    if (rc == SVDSS_OK) {
+      std::vector<uint8_t>().swap(bwt);
+      int32_t route = 0; int64_t st = 0, wk = 0; double ms[3];
+      (void)svdss_bwt_strings_last(&route, &st, &wk, ms);
+      if (source) *source = route == 1 ? REC_DEVICE_WALK : REC_HOST_WALK;
+      try {
+        strings.resize((size_t)m);
+        int64_t at = 0;
+        for (int64_t r = 0; r < m; ++r) { strings[(size_t)r].assign(flat.begin() + at, flat.begin() + at + sl[(size_t)r]); at += sl[(size_t)r]; }
+      } catch (...) { return SVDSS_ENOMEM; }
+      walked = true;
+    } else if (rc != SVDSS_ERANGE) {
+      return rc;
+    }
+  }
+  if (!walked) {
+    rc = rld0_strings_of_bwt(bwt.data(), n, threads, strings);
+    if (rc != SVDSS_OK) return rc;
+    std::vector<uint8_t>().swap(bwt);
+    if (source) *source = REC_SERIAL_WALK;
+  }
   std::vector<int64_t> picked;
   rc = rld0_pick_strands(strings, picked);
   if (rc != SVDSS_OK) {
-    g_svdss_hip_err = "the .fmd is not an index of records AND their reverse complements (ropebwt3 build without -d?)";
+    g_svdss_hip_err = NOT_CLOSED_MSG;
     return rc;
   }
-  std::vector<int64_t> lens;
+  lens.clear();
   int64_t total = 0;
   for (int64_t i : picked) { lens.push_back((int64_t)strings[(size_t)i].size()); total += lens.back(); }
-  std::vector<uint8_t> cat;
+  cat.clear();
   try { cat.reserve((size_t)total); } catch (...) { return SVDSS_ENOMEM; }
   for (int64_t i : picked) {
     cat.insert(cat.end(), strings[(size_t)i].begin(), strings[(size_t)i].end());
     std::vector<uint8_t>().swap(strings[(size_t)i]);
   }
-  strings.clear();
+  return SVDSS_OK;
+}
+
+// how an .fmd without a sidecar gets its strings: SVDSS_FMD_IMPORT_DEVICE=1 the marked walks on the current device
+// (-1: on the host where there is none or SVDSS_INDEX_CPU is set), 0 / unset the serial walk per string.  (`dflt`: what
+// holds with the variable unset -- `SVDSS index -i` walks on the device, the import behind `search --index` has not
+// been measured at a human genome's length yet and keeps the host walk: DESIGN 4j)
+static int import_route(bool dflt) {
+  const char* e = getenv("SVDSS_FMD_IMPORT_DEVICE");
+  if (e ? atoi(e) == 0 : !dflt) return -2;
+  int dev = 0;
+  if (getenv("SVDSS_INDEX_CPU") || hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return -1; }
+  return dev;
+}
+
+// an rld0 file without a usable sidecar: its records, then this layout rebuilt from them
+static int import_fmd(const char* path, svdss_index_t** out) {
+  std::vector<uint8_t> cat;
+  std::vector<int64_t> lens;
+  int rc = fmd_records(path, import_route(false), cat, lens, nullptr);
+  if (rc != SVDSS_OK) return rc;
+  int threads = 1;
+#ifdef _OPENMP
+  threads = omp_get_max_threads();
+#endif
   return svdss_index_build(cat.data(), lens.data(), (int32_t)lens.size(), threads, out);
+}
+
+// Is `path` neither rld0 nor this library's own layout?  Then most likely ropebwt3's other format (.fmr, mrope -- what
+// `ropebwt3 build` writes without -d; rb3_fmi_restore of ping_pong.cpp:245 falls back to it when the rld0 restore fails).
+// It is not read here; say so instead of a bare I/O error.  (Its magic is not restated from memory: the file is
+// recognised by what it is not.)
+static bool foreign_index_file(const char* path) {
+  FILE* f = fopen(path, "rb");
+  char m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bool readable = f && fread(m, 1, 8, f) == 8;
+  if (f) fclose(f);
+  if (readable && memcmp(m, "SVDSSFM2", 8) != 0 && memcmp(m, "SVDSSRC1", 8) != 0) {
+    g_svdss_hip_err = "not an rld0 .fmd (magic RLD\\3) and not this library's index layout; if it is an .fmr (mrope) "
+                      "index, convert it with `ropebwt3 build -i in.fmr -do out.fmd` or rebuild with `SVDSS index -d`";
+    return true;
+  }
+  return false;
+}
+
+// `SVDSS index` leaves this library's own layout beside the .fmd it writes: restoring that is a plain read.  The
+// cache must belong to THIS .fmd: not older, and with the symbol counts of the .fmd's header (an .fmd replaced
+// under a preserved mtime, or an upstream-built one for another reference, is imported instead).
+static bool sidecar_of(const char* path, std::string& cache, uint64_t mcnt[6]) {
+  cache = std::string(path) + ".svdss";
+  struct stat a, c;
+  return !getenv("SVDSS_INDEX_NO_CACHE") && stat(path, &a) == 0 && stat(cache.c_str(), &c) == 0 &&
+         c.st_mtime >= a.st_mtime && rld0_header_counts(path, mcnt) == SVDSS_OK;
+}
+
+// this library's files: the records file `SVDSS index` leaves beside the .fmd ("SVDSSRC1": the index is rebuilt from
+// it, in HBM when it is made resident) or the full layout svdss_index_save writes ("SVDSSFM2"); a sidecar must have
+// the counts of its .fmd's header
+static int load_own_file(const std::string& file, const uint64_t* mcnt, svdss_index* ix) {
+  char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (FILE* f = fopen(file.c_str(), "rb")) { (void)!fread(magic, 1, 8, f); fclose(f); }
+  int rc = memcmp(magic, "SVDSSRC1", 8) == 0 ? svdss_index_load_records_host(file.c_str(), ix)
+                                             : svdss_index_load_host(file.c_str(), ix);
+  if (rc == SVDSS_OK && mcnt) {
+    bool same = true;
+    for (int c = 0; c < 6; ++c) same = same && (uint64_t)(ix->acc[c + 1] - ix->acc[c]) == mcnt[c];
+    if (!same) rc = SVDSS_EIO;
+  }
+  return rc;
 }
 
 extern "C" int svdss_index_load(const char* path, svdss_index_t** out) {
@@ -276,51 +381,78 @@ extern "C" int svdss_index_load(const char* path, svdss_index_t** out) {
   bool is_cache = false;
   uint64_t mcnt[6] = {0, 0, 0, 0, 0, 0};
   if (rld0_is_fmd(path)) {
-    // `SVDSS index` leaves this library's own layout beside the .fmd it writes: restoring that is a plain read.  The
-    // cache must belong to THIS .fmd: not older, and with the symbol counts of the .fmd's header (an .fmd replaced
-    // under a preserved mtime, or an upstream-built one for another reference, is imported instead).
-    const std::string cache = file + ".svdss";
-    struct stat a, c;
-    if (!getenv("SVDSS_INDEX_NO_CACHE") && stat(path, &a) == 0 && stat(cache.c_str(), &c) == 0 &&
-        c.st_mtime >= a.st_mtime && rld0_header_counts(path, mcnt) == SVDSS_OK) {
-      file = cache;
-      is_cache = true;
-    } else
-      return import_fmd(path, out);
-  } else {
-    // Neither rld0 nor this library's own layout: most likely ropebwt3's other format (.fmr, mrope -- what `ropebwt3
-    // build` writes without -d; rb3_fmi_restore of ping_pong.cpp:245 falls back to it when the rld0 restore fails).
-    // It is not read here; say so instead of a bare I/O error.  (Its magic is not restated from memory: the file is
-    // recognised by what it is not.)
-    FILE* f = fopen(path, "rb");
-    char m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const bool readable = f && fread(m, 1, 8, f) == 8;
-    if (f) fclose(f);
-    if (readable && memcmp(m, "SVDSSFM2", 8) != 0 && memcmp(m, "SVDSSRC1", 8) != 0) {
-      g_svdss_hip_err = "not an rld0 .fmd (magic RLD\\3) and not this library's index layout; if it is an .fmr (mrope) "
-                        "index, convert it with `ropebwt3 build -i in.fmr -do out.fmd` or rebuild with `SVDSS index -d`";
-      return SVDSS_EINVAL;
-    }
+    if (!sidecar_of(path, file, mcnt)) return import_fmd(path, out);
+    is_cache = true;
+  } else if (foreign_index_file(path)) {
+    return SVDSS_EINVAL;
   }
   svdss_index* ix = new (std::nothrow) svdss_index();
   if (!ix) return SVDSS_ENOMEM;
-  // this library's files: the records file `SVDSS index` leaves beside the .fmd ("SVDSSRC1": the index is rebuilt from
-  // it, in HBM when it is made resident) or the full layout svdss_index_save writes ("SVDSSFM2")
-  char magic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (FILE* f = fopen(file.c_str(), "rb")) { (void)!fread(magic, 1, 8, f); fclose(f); }
-  int rc = memcmp(magic, "SVDSSRC1", 8) == 0 ? svdss_index_load_records_host(file.c_str(), ix)
-                                             : svdss_index_load_host(file.c_str(), ix);
-  if (rc == SVDSS_OK && is_cache) {
-    bool same = true;
-    for (int c = 0; c < 6; ++c) same = same && (uint64_t)(ix->acc[c + 1] - ix->acc[c]) == mcnt[c];
-    if (!same) rc = SVDSS_EIO;
-  }
+  const int rc = load_own_file(file, is_cache ? mcnt : nullptr, ix);
   if (rc != SVDSS_OK) {
     delete ix;
     if (is_cache) return import_fmd(path, out);   // stale, truncated or foreign cache: the .fmd itself is the index
     return rc;
   }
   *out = ix;
+  return SVDSS_OK;
+}
+
+// The records an index file stands for, WITHOUT building the index (`SVDSS index -i OLD`): a handle that holds them
+// (svdss_index_records), from OLD's sidecar or OLD itself where svdss_index_load would read that, else out of the
+// .fmd's BWT (device >= 0: marked walks on that GPU, < 0: on the host; SVDSS_FMD_IMPORT_DEVICE=0: the serial walk).
+extern "C" int svdss_index_records_open(const char* path, int32_t device, svdss_index_t** out, int32_t* source) {
+  if (!path || !out || !source) return SVDSS_EINVAL;
+  std::string file = path;
+  uint64_t mcnt[6] = {0, 0, 0, 0, 0, 0};
+  const bool fmd = rld0_is_fmd(path);
+  if (!fmd && foreign_index_file(path)) return SVDSS_EINVAL;
+  svdss_index* ix = new (std::nothrow) svdss_index();
+  if (!ix) return SVDSS_ENOMEM;
+  int rc = SVDSS_EIO;
+  if (!fmd || sidecar_of(path, file, mcnt)) {
+    rc = load_own_file(file, fmd ? mcnt : nullptr, ix);
+    if (rc == SVDSS_OK && ix->rec_lens.empty()) {
+      // the full layout: the forward strands out of the text  r0 $ revcomp(r0) $ r1 $ ...
+      if ((int64_t)ix->text.size() != ix->n) rc = SVDSS_EIO;
+      int64_t pos = 0;
+      for (int32_t i = 0; rc == SVDSS_OK && i < ix->n_contigs; ++i) {
+        const void* z = pos < ix->n ? memchr(ix->text.data() + pos, 0, (size_t)(ix->n - pos)) : nullptr;
+        if (!z) { rc = SVDSS_EIO; break; }
+        const int64_t len = (const uint8_t*)z - (ix->text.data() + pos);
+        ix->records.insert(ix->records.end(), ix->text.begin() + pos, ix->text.begin() + pos + len);
+        ix->rec_lens.push_back(len);
+        pos += 2 * (len + 1);
+      }
+      *source = REC_LAYOUT;
+    } else {
+      *source = REC_SIDECAR;
+    }
+    if (rc != SVDSS_OK && !fmd) { delete ix; return rc; }
+    if (rc != SVDSS_OK) { delete ix; ix = new (std::nothrow) svdss_index(); if (!ix) return SVDSS_ENOMEM; }
+  }
+  if (rc != SVDSS_OK) {   // the .fmd itself
+    std::vector<uint8_t> cat;
+    int src = REC_SERIAL_WALK;
+    const char* e = getenv("SVDSS_FMD_IMPORT_DEVICE");
+    rc = fmd_records(path, e && atoi(e) == 0 ? -2 : device >= 0 ? device : -1, cat, ix->rec_lens, &src);
+    if (rc != SVDSS_OK) { delete ix; return rc; }
+    ix->records.assign(cat.begin(), cat.end());
+    ix->n_contigs = (int32_t)ix->rec_lens.size();
+    ix->n = 0;
+    for (int64_t l : ix->rec_lens) ix->n += 2 * (l + 1);
+    *source = src;
+  }
+  *out = ix;
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_index_records(const svdss_index_t* ix, const uint8_t** records, const int64_t** lens, int32_t* n_records) {
+  if (!ix || !records || !lens || !n_records) return SVDSS_EINVAL;
+  if (ix->rec_lens.empty()) return SVDSS_ENODEV;   // (a handle that holds no records: svdss_index_records_open makes one that does)
+  *records = ix->records.data();
+  *lens = ix->rec_lens.data();
+  *n_records = (int32_t)ix->rec_lens.size();
   return SVDSS_OK;
 }
 

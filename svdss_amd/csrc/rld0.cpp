@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "bwt_invert.h"
 #include "index_host.h"
 #include "rld0.h"
 
@@ -443,6 +444,34 @@ int rld0_strings_of_bwt(const uint8_t* bwt, int64_t n, int threads, std::vector<
     std::reverse(s.begin(), s.end());
   }
   return bad ? SVDSS_EIO : SVDSS_OK;
+}
+
+int rld0_count_sentinels(const uint8_t* bwt, int64_t n, int threads, int64_t* m) {
+  int64_t zeros = 0;
+  int wrong = 0;
+#pragma omp parallel for num_threads(threads < 1 ? 1 : threads) reduction(+ : zeros) reduction(| : wrong) schedule(static)
+  for (int64_t i = 0; i < n; ++i) {
+    zeros += bwt[(size_t)i] == 0;
+    wrong |= bwt[(size_t)i] > 5;
+  }
+  *m = zeros;
+  return wrong ? SVDSS_EINVAL : SVDSS_OK;
+}
+
+int rld0_strings_marked(const uint8_t* bwt, int64_t n, int64_t stride, int64_t max_steps, int threads, uint8_t* out, int64_t* lens, double ms[3]) {
+  const double t0 = omp_get_wtime();
+  svdss_index tmp;
+  const int rc = svdss_blocks_from_bwt(bwt, n, threads, &tmp);
+  if (rc != SVDSS_OK) return rc;
+  SvdssDevIndex v;
+  memset(&v, 0, sizeof v);
+  v.blocks = tmp.blocks.data();
+  v.dollar = tmp.dollar.data();
+  v.n = n;
+  v.n_dollar = (int32_t)tmp.dollar.size();
+  memcpy(v.acc, tmp.acc, sizeof v.acc);
+  ms[0] = 1e3 * (omp_get_wtime() - t0);
+  return bwt_invert_host(v, stride, max_steps, threads, out, lens, ms + 1);
 }
 
 // one string of every reverse-complement pair; SVDSS_EIO if the collection is not closed under reverse complement

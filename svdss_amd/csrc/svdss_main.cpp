@@ -1,7 +1,7 @@
 // svdss_main.cpp -- `SVDSS` host CLI on top of libsvdss_hip.so.
 //
 // Keeps the process boundary B1 of SURVEY.md 8(b):
-//   SVDSS index  -d ref.fa -o ref.fa.fmd [-t T]        (/root/reference/main.cpp:34-37, run_svdss:142)
+//   SVDSS index  [-i old.fmd] -d ref.fa [more.fa ...] [-o ref.fa.fmd] [-t T]   (/root/reference/main.cpp:34-37, run_svdss:142)
 //   SVDSS smooth --reference R --bam B [--threads T] [--min-mapq N] [--accp F]      (main.cpp:69-77; smooth_host.cpp)
 //   SVDSS search --index F --bam B | --fastx Q [--threads T] [--bsize N] [--noputative]
 //                [--noassemble] [--omax N] [--verbose]  (config.cpp:30-55, main.cpp:62-68; search_host.cpp)
@@ -51,7 +51,7 @@ __attribute__((weak)) int main_bamindex(const CallOptions& o);
 
 static const char* MAIN_USAGE =
     "Usage: SVDSS <index|smooth|search|call|run> --help\n"
-    "  index   build the FM-index of a reference (FASTA, gz ok):  SVDSS index -d ref.fa -o ref.fa.fmd [-t T]\n"
+    "  index   build the FM-index of a reference (FASTA, gz ok):  SVDSS index [-i old.fmd] -d ref.fa [more.fa ...] -o ref.fa.fmd [-t T]\n"
     "  search  extract sample-specific strings: SVDSS search --index ref.fa.fmd --bam reads.bam > specifics.txt\n"
     "  call    call SVs from the specific strings:    SVDSS call --reference ref.fa --bam reads.bam --sfs specifics.txt\n"
     "  smooth  smooth a BAM (reads equal the reference except at long indels): SVDSS smooth --reference ref.fa --bam in.bam > out.bam\n"
@@ -206,9 +206,23 @@ void regions_in_force(const std::vector<std::string>& regions, const std::string
   if (!stale.empty() && !bam_region_plan().active) logmsg("warning", "the index " + stale + " is older than " + bam + ": it is not used, the whole file is read");
   bam_region_counters().verbose = verbose;
 }
+static const char* INDEX_USAGE =
+    "Usage: SVDSS index [-t threads] [-i <old.fmd>] -d <in.fa[.gz]> [<in2.fa[.gz]> ...] [-o <out.fmd>]\n"
+    "      the FM-index of the records of every input and of their reverse complements, as `ropebwt3 build -d` writes it (rld0)\n"
+    "      <in.fa> ...           one input or several (FASTA, gzip and BGZF ok): the records in command-line order, then file order\n"
+    "      -i, --append <OLD>    the records of the index OLD first, then the inputs: from OLD.svdss where that is OLD's sidecar,\n"
+    "                            else recovered from OLD's BWT on the GPU (an index of upstream `SVDSS index` / ropebwt3).  OLD is\n"
+    "                            read completely before anything is written: -i x.fmd -o x.fmd works\n"
+    "      -o <out.fmd>          the index, and beside it <out.fmd>.svdss (what `search` restores).  Without -o the .fmd goes to\n"
+    "                            stdout (not a terminal) and no sidecar is written\n"
+    "      -t <int>              threads of the host side (default: 4)\n"
+    "      --verbose             where OLD's records came from, and how many\n";
+
 static int main_index(int argc, char** argv) {
-  // ropebwt3 `build` flags as run_svdss:142 passes them: -t T -d <fasta> -o <out>
-  std::string fasta, out;
+  // ropebwt3 `build` flags as run_svdss:142 passes them: -t T -d <fasta> -o <out>; -i <old> as ropebwt3 spells the index to
+  // append to [UPSTREAM-UNVERIFIED], --append as the reference's config.hpp:22
+  std::vector<std::string> inputs;
+  std::string out, old;
   int threads = 4;
   bool verbose = false;
   for (int i = 2; i < argc; ++i) {
@@ -216,12 +230,15 @@ static int main_index(int argc, char** argv) {
     else if (!strcmp(argv[i], "-t") && i + 1 < argc) threads = atoi(argv[++i]);
     else if (!strncmp(argv[i], "-t", 2) && argv[i][2]) threads = atoi(argv[i] + 2);
     else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
+    else if ((!strcmp(argv[i], "-i") || !strcmp(argv[i], "--append")) && i + 1 < argc) old = argv[++i];
+    else if (!strncmp(argv[i], "--append=", 9)) old = argv[i] + 9;
     else if (!strcmp(argv[i], "-d") || !strcmp(argv[i], "-b")) continue;  // output-format switches of ropebwt3
     else if (argv[i][0] == '-' && argv[i][1] == 'd' && argv[i][2]) continue;
-    else if (argv[i][0] != '-') fasta = argv[i];
+    else if (argv[i][0] != '-') inputs.push_back(argv[i]);
   }
-  if (fasta.empty() || out.empty()) {
-    fprintf(stderr, "Usage: SVDSS index [-t threads] -d <reference.fa[.gz]> -o <reference.fmd>\n");
+  const bool to_stdout = out.empty();
+  if (inputs.empty() || (to_stdout && isatty(STDOUT_FILENO))) {
+    fputs(INDEX_USAGE, stderr);
     return EXIT_FAILURE;
   }
   // The index is built in HBM.  Without a GPU the command fails instead of quietly taking the host builder (which
@@ -236,14 +253,51 @@ static int main_index(int argc, char** argv) {
   };
   std::vector<uint8_t> cat;
   std::vector<int64_t> lens;
-  {
+  if (!old.empty()) {
+    // OLD's records first -- read completely, and refused if it cannot be, before anything is opened for writing
+    struct stat st;
+    if (stat(old.c_str(), &st) != 0) die("cannot open " + old + " (the index to append to)");
+    svdss_index_t* h = nullptr;
+    int32_t source = -1;
+    const int device = getenv("SVDSS_INDEX_CPU") || svdss_device_count() <= 0 ? -1 : 0;
+    const int rc = svdss_index_records_open(old.c_str(), device, &h, &source);
+    if (rc != SVDSS_OK) die(old + ": " + svdss_strerror(rc) + " " + svdss_last_hip_error());
+    const uint8_t* rec = nullptr;
+    const int64_t* rl = nullptr;
+    int32_t nr = 0;
+    check(svdss_index_records(h, &rec, &rl, &nr), "svdss_index_records");
+    lens.assign(rl, rl + nr);
+    int64_t total = 0;
+    for (int64_t l : lens) total += l;
+    cat.assign(rec, rec + total);
+    svdss_index_free(h);
+    if (verbose) {
+      std::string from = source == 0 ? "its sidecar " + old + ".svdss" : source == 1 ? "this library's layout" : "";
+      if (source >= 2) {
+        int32_t route = -1;
+        int64_t stride = 0, walkers = 0;
+        double ms[3] = {0, 0, 0};
+        (void)svdss_bwt_strings_last(&route, &stride, &walkers, ms);
+        char buf[256];
+        if (source == 4) snprintf(buf, sizeof buf, "its BWT by the host walk (one serial walk per string)");
+        else snprintf(buf, sizeof buf, "its BWT by the %s walk (stride %lld, %lld walkers; pass 1 %.3f ms, pass 2 %.3f ms)", source == 2 ? "device" : "host",
+                      (long long)stride, (long long)walkers, ms[1], ms[2]);
+        from = buf;
+      }
+      logmsg("info", old + ": " + std::to_string(nr) + " record(s), " + std::to_string(total) + " bases from " + from);
+    }
+    mark("old index read");
+  }
+  for (const std::string& fasta : inputs) {
+    const size_t had = lens.size();
     // a plain FASTA is mapped and read by several threads (fastx_reader.h, as `call` and `smooth` do), the records encoded
     // side by side into one buffer sized once; gzip / CRLF / FASTQ-like files go through the line reader as before
     std::vector<std::string> nm, sq;
     // (a BGZF file is inflated and parsed on the GPU first, ref_loader.h: upper-cased there, which svdss_nt6_encode does not mind)
     if (load_reference_device(fasta, threads < 8 ? 8 : threads, getenv("SVDSS_FASTA_SERIAL") != nullptr, verbose, "index", nm, sq, nullptr) ||
         (!getenv("SVDSS_FASTA_SERIAL") && load_fasta_mapped(fasta, std::max(1, std::min(threads < 8 ? 8 : threads, 16)), false, nm, sq))) {
-      std::vector<size_t> at(sq.size() + 1, 0);
+      const size_t base = cat.size();
+      std::vector<size_t> at(sq.size() + 1, base);
       for (size_t i = 0; i < sq.size(); ++i) { at[i + 1] = at[i] + sq[i].size(); lens.push_back((int64_t)sq[i].size()); }
       cat.resize(at.back());
       std::vector<std::thread> th;
@@ -271,8 +325,8 @@ static int main_index(int argc, char** argv) {
         lens.push_back((int64_t)seq.size());
       }
     }
+    if (lens.size() == had) die("no sequence in " + fasta);
   }
-  if (lens.empty()) die("no sequence in " + fasta);
   mark("FASTA read + nt6");
   logmsg("info", "Indexing " + std::to_string(lens.size()) + " record(s), " + std::to_string(cat.size()) + " bases..");
   svdss_index_t* ix = nullptr;
@@ -285,6 +339,13 @@ static int main_index(int argc, char** argv) {
   // index -- the BWT, the records -- and the encoder is one serial pass over six billion symbols at human scale)
   int rc_side = SVDSS_OK;
   std::thread side;
+  if (to_stdout) {
+    // no -o: the .fmd to stdout (rld0_write never seeks), no sidecar -- there is no name to put it under
+    check(svdss_index_save_fmd(ix, "/dev/stdout"), "svdss_index_save_fmd");
+    mark("rld0 .fmd written");
+    svdss_index_free(ix);
+    return 0;
+  }
   const bool records_side = !getenv("SVDSS_INDEX_NO_CACHE") && !getenv("SVDSS_INDEX_FULL");
   // (an older sidecar must not outlive a failed rewrite of its .fmd: it goes first, and a failure takes the .tmp with it)
   if (!getenv("SVDSS_INDEX_NO_CACHE")) (void)unlink((out + ".svdss").c_str());

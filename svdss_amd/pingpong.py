@@ -53,6 +53,35 @@ def pack_reads(reads: Sequence) -> Tuple[np.ndarray, np.ndarray]:
     return np.ascontiguousarray(flat, dtype=np.uint8), offsets
 
 
+def bwt_strings(bwt, device: int = 0, stride: int = 0) -> List[np.ndarray]:
+    """The strings of the collection a BWT stands for (nt6 symbols, '$' = 0), string r the one spelled from row r:
+    svdss_bwt_strings -- marked LF walks on GPU `device` (csrc/bwt_invert.hip), on the host for device < 0.  The result
+    does not depend on `stride` (0: SVDSS_INVERT_STRIDE or the default).  Where a walker passes SVDSS_INVERT_MAX_STEPS
+    the strings come from the serial walk per string instead, as they do for the library's own callers."""
+    b = np.ascontiguousarray(bwt, dtype=np.uint8)
+    n = int(b.size)
+    m = int((b == 0).sum())
+    out = np.empty(max(n - m, 1), dtype=np.uint8)
+    lens = np.zeros(max(m, 1), dtype=np.int64)
+    k = C.c_int32(0)
+    rc = lib.svdss_bwt_strings(b.ctypes.data, n, device, stride, out.ctypes.data, n - m, lens.ctypes.data, m, C.byref(k))
+    if rc == 6 and k.value == m and n > 0:   # SVDSS_ERANGE with exact capacities: the step limit
+        rc = lib.svdss_bwt_strings(b.ctypes.data, n, -1, -1, out.ctypes.data, n - m, lens.ctypes.data, m, C.byref(k))
+    check(rc, "svdss_bwt_strings")
+    at = np.concatenate([[0], np.cumsum(lens[:m])])
+    return [out[at[r]:at[r + 1]].copy() for r in range(m)]
+
+
+def bwt_strings_last() -> dict:
+    """How this thread's last bwt_strings ran: route ('host', 'device' or 'serial'), stride, walkers and the milliseconds
+    of the rank blocks' build, pass 1 and pass 2."""
+    route, stride, walkers = C.c_int32(-1), C.c_int64(0), C.c_int64(0)
+    ms = (C.c_double * 3)()
+    check(lib.svdss_bwt_strings_last(C.byref(route), C.byref(stride), C.byref(walkers), ms), "svdss_bwt_strings_last")
+    return {"route": ("host", "device", "serial")[route.value], "stride": stride.value, "walkers": walkers.value,
+            "blocks_ms": ms[0], "pass1_ms": ms[1], "pass2_ms": ms[2]}
+
+
 class FMDIndex:
     """FM-index over every record and its reverse complement (rb3_fmi_t role)."""
 
