@@ -832,6 +832,59 @@ int32_t svdss_indel_ratio_last_kernel(void);
  * ran side by side.  SVDSS_EINVAL for a null `out` or a device that is negative or beyond the pool's 64. */
 int svdss_call_side_stat(int32_t device, int64_t out[4]);
 
+/* ---- plain gzip inflated on the device, chunk-parallel (csrc/gzip_stream.hip, gzip_stream.h) -------------------------
+ * ONE deflate stream (what gzip writes, not BGZF) inflated in parallel: the compressed bytes of a window are cut into
+ * chunks of chunk_bytes, a block start is searched in every chunk, every chunk is decoded from its start with references
+ * into the unknown 32 KB in front of it kept as symbols, and the symbols are resolved chunk after chunk.
+ * A svdss_gzip_stream_t is one file being read.  svdss_gzip_stream_run takes the next window: comp[0] is the byte the
+ * stream stands in (the first byte of the file at first; afterwards the byte *consumed bytes further on, every time),
+ * is_last says that comp reaches the end of the file.  It inflates as far as whole deflate blocks lie inside the window,
+ * at most to the end of the current member, whose CRC32 and ISIZE it checks.  A run that neither consumes nor delivers
+ * anything and neither ends nor declines needs more bytes in its window.
+ * The unit DECLINES what it cannot do (svdss_gzip_result_t.declined, a SVDSS_GZIP_DECLINE_* reason): the run consumes
+ * what it could and the caller reads on from the carried state (byte position, bit, the 32 KB in front of it, running
+ * CRC32 and count) with zlib: svdss_gzip_stream_host_tail does that for bytes in memory (csrc/gzip_stream.h: GzHostTail).
+ * Errors: SVDSS_EIO with svdss_gzip_stream_error() = what is wrong with the stream (a trailer that does not fit, a match
+ * that reaches in front of its member). */
+typedef struct svdss_gzip_stream svdss_gzip_stream_t;
+#define SVDSS_GZIP_DECLINE_HEADER 1      /* the first bytes are not a gzip member header */
+#define SVDSS_GZIP_DECLINE_NO_START 2    /* no chunk of the window holds a dynamic block start: nothing to do in parallel */
+#define SVDSS_GZIP_DECLINE_NO_ADVANCE 3  /* not one whole block inside the window */
+#define SVDSS_GZIP_DECLINE_DAMAGED 4     /* an invalid code at the stream's position */
+#define SVDSS_GZIP_DECLINE_TRAILING 5    /* bytes behind a member that are not a gzip member header */
+typedef struct svdss_gzip_result {
+  const uint8_t* text;        /* what the last run (or host_tail) inflated: page-locked host memory */
+  const uint8_t* d_text;      /* ... and the same bytes on the device (NULL after host_tail) */
+  int64_t text_bytes;
+  /* counters over all runs so far */
+  int64_t windows;            /* runs that inflated something */
+  int64_t n_chunks;           /* chunks the chain covered */
+  int64_t chunks_on_chain;    /* ... decoded from a start of their own */
+  int64_t chunks_merged;      /* ... without a start: decoded by the chunk before them */
+  int64_t false_starts;       /* ... with a start that no block end met */
+  int64_t members_finished;
+  int64_t device_bytes;       /* text inflated on the device */
+  int32_t ended;              /* the file's last member is finished and nothing follows */
+  int32_t declined;           /* 0, or why the host takes over */
+  /* the carried state: where the stream stands */
+  int64_t byte_pos;           /* of the file */
+  int32_t bit;                /* 0..7 in that byte */
+  int32_t in_member;          /* 1: inside a deflate stream; 0: at a member header */
+  int32_t want_trailer;       /* 1: at a member's CRC32 / ISIZE */
+  uint32_t crc;               /* of the member's text so far */
+  uint64_t count;             /* bytes of it */
+  const uint8_t* dict;        /* the dict_len bytes of text in front of the position (at most 32768) */
+  int32_t dict_len;
+  double find_ms, measure_ms, decode_ms, resolve_ms;   /* HIP-event time of the kernels, summed over all runs */
+} svdss_gzip_result_t;
+int svdss_gzip_stream_create(int32_t device, int64_t chunk_bytes, svdss_gzip_stream_t** out);
+int svdss_gzip_stream_run(svdss_gzip_stream_t* s, const uint8_t* comp, int64_t comp_bytes, int32_t is_last, int64_t* consumed);
+int svdss_gzip_stream_result(const svdss_gzip_stream_t* s, svdss_gzip_result_t* out);
+/* comp: the file from byte_pos to its end.  The text is svdss_gzip_result_t.text afterwards. */
+int svdss_gzip_stream_host_tail(svdss_gzip_stream_t* s, const uint8_t* comp, int64_t comp_bytes);
+const char* svdss_gzip_stream_error(const svdss_gzip_stream_t* s);
+void svdss_gzip_stream_free(svdss_gzip_stream_t* s);
+
 #ifdef __cplusplus
 }
 #endif

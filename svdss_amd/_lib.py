@@ -205,6 +205,12 @@ SIGNATURES = {
     "svdss_indel_ratio_batch": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p]),
     "svdss_indel_ratio_last_kernel": (_i32, []),
     "svdss_call_side_stat": (C.c_int, [_i32, _p]),
+    "svdss_gzip_stream_create": (C.c_int, [_i32, _i64, C.POINTER(_p)]),
+    "svdss_gzip_stream_run": (C.c_int, [_p, _p, _i64, _i32, _pi64]),
+    "svdss_gzip_stream_result": (C.c_int, [_p, _p]),
+    "svdss_gzip_stream_host_tail": (C.c_int, [_p, _p, _i64]),
+    "svdss_gzip_stream_error": (C.c_char_p, [_p]),
+    "svdss_gzip_stream_free": (None, [_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "crc_gf.h"
 #include "dev_buf.h"
 #include "hip_check.h"
 
@@ -182,28 +183,6 @@ __device__ __forceinline__ void nt6_chunk16(const uint8_t* __restrict__ buf, int
 
 
 // ------------------------------------------------------------------ CRC32 of BGZF blocks (crc32_kernel, bgzf_footer_kernel)
-// a(x) * b(x) mod P in the reflected representation zlib uses (bit 31 = x^0); P = 0xEDB88320
-__host__ __device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-  for (int i = 0; i < 32; ++i) {
-    p ^= (a & 0x80000000u) ? b : 0u;
-    a <<= 1;
-    b = (b >> 1) ^ ((b & 1u) ? 0xEDB88320u : 0u);
-  }
-  return p;
-}
-// x^(8 n) mod P
-__host__ __device__ inline uint32_t gf_xpow8(uint32_t n) {
-  uint32_t r = 0x80000000u;            // x^0
-  uint32_t sq = 0x00800000u;           // x^8
-  while (n) {
-    if (n & 1u) r = gf_mul(r, sq);
-    sq = gf_mul(sq, sq);
-    n >>= 1;
-  }
-  return r;
-}
-
 // Tables of the CRC kernels, computed once on the host and copied to every device that asks:
 //   [0]      the byte table of the CRC (state * x^8 for the state's low byte)
 //   [1..4]   byte k of a state times x^2048: state * x^2048 = [1][b0] ^ [2][b1] ^ [3][b2] ^ [4][b3]

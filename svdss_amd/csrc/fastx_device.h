@@ -1,13 +1,15 @@
 // fastx_device.h -- the input side of `SVDSS search --fastx` on the device (csrc/fastx_device.hip): which files are
-// eligible, and the file cut into batches -- runs of consecutive BGZF members found by BgzfScanner, or slabs of a plain
-// file.  The batches are numbered in file order; whoever takes one (the feeding threads of search_host.cpp's
+// eligible, and the file cut into batches -- runs of consecutive BGZF members found by BgzfScanner, slabs of a plain
+// file, or (plain gzip, inflated by csrc/gzip_stream.hip in a source thread of the caller's) slabs of text put().  The batches are numbered in file order; whoever takes one (the feeding threads of search_host.cpp's
 // FastxDevicePath) hands it to svdss_fastx_batch_run.  Nothing is inflated or parsed here.
 #pragma once
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -16,11 +18,12 @@
 #include "../../include/svdss_hip.h"
 #include "bgzf_scanner.h"
 
-enum class FastxKind { None, Plain, Bgzf };
+enum class FastxKind { None, Plain, Bgzf, Gzip };
 
-// A regular file that is BGZF (a gzip header with the BC extra field, what bgzip writes) or not compressed at all; plain
-// single-stream gzip, pipes and everything else stay with the host reader.
-inline FastxKind fastx_device_kind(const std::string& path) {
+// A regular file that is BGZF (a gzip header with the BC extra field, what bgzip writes) or not compressed at all; pipes and
+// everything else stay with the host reader.  Plain single-stream gzip (magic, CM = 8, not BGZF) is FastxKind::Gzip where the
+// caller asks for it (`search --fastx`), and stays with the host reader otherwise (the reference FASTA).
+inline FastxKind fastx_device_kind(const std::string& path, bool gzip_too = false) {
   struct stat st;
   if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return FastxKind::None;
   FILE* f = fopen(path.c_str(), "rb");
@@ -30,7 +33,8 @@ inline FastxKind fastx_device_kind(const std::string& path) {
   fclose(f);
   if (n >= 2 && h[0] == 0x1f && h[1] == 0x8b) {
     size_t total = 0, doff = 0, dlen = 0;
-    return BgzfScanner::parse_member(h, n, total, doff, dlen) == 1 ? FastxKind::Bgzf : FastxKind::None;
+    if (BgzfScanner::parse_member(h, n, total, doff, dlen) == 1) return FastxKind::Bgzf;
+    return gzip_too && n >= 3 && h[2] == 8 ? FastxKind::Gzip : FastxKind::None;
   }
   return FastxKind::Plain;
 }
@@ -46,9 +50,10 @@ struct FastxJob {
   std::vector<const svdss_bgzf_block_t*> blocks;
   std::vector<const uint32_t*> crc;
   int64_t plain_off = 0, plain_bytes = 0;
+  std::shared_ptr<std::vector<uint8_t>> text;              // FastxKind::Gzip: the plain_bytes of this batch, already inflated
   void clear() {
     keep.clear(); tables.clear(); comp.clear(); comp_bytes.clear(); n_blocks.clear(); blocks.clear(); crc.clear();
-    plain_off = plain_bytes = 0; last = false;
+    plain_off = plain_bytes = 0; last = false; text.reset();
   }
 };
 
@@ -62,6 +67,8 @@ class FastxBatcher {
       hooks.host_free = svdss_host_free;
       scanner_.reset(new BgzfScanner(path, hooks, slab_bytes, loaders, pool_chunks));
       ok_ = scanner_->ok();
+    } else if (kind == FastxKind::Gzip) {
+      ok_ = true;
     } else {
       struct stat st;
       ok_ = stat(path.c_str(), &st) == 0;
@@ -74,6 +81,7 @@ class FastxBatcher {
     std::lock_guard<std::mutex> lk(m_);
     job.clear();
     if (ended_) return false;
+    if (kind_ == FastxKind::Gzip) return next_text(job);
     job.seq = seq_++;
     if (kind_ == FastxKind::Plain) {
       job.plain_off = off_;
@@ -114,8 +122,50 @@ class FastxBatcher {
     return true;
   }
   const std::string& error() const { return err_; }
+  int64_t batch_bytes() const { return batch_; }
+  // FastxKind::Gzip: the source thread's side.  Text in file order, cut into batches of batch_bytes; at most `depth`
+  // batches wait (put blocks); finish() closes the stream with the last -- possibly empty -- batch.
+  void put(const uint8_t* text, size_t n, size_t depth) {
+    while (n) {
+      if (!filling_) { filling_.reset(new std::vector<uint8_t>()); filling_->reserve((size_t)batch_); }
+      const size_t k = std::min(n, (size_t)batch_ - filling_->size());
+      filling_->insert(filling_->end(), text, text + k);
+      text += k;
+      n -= k;
+      if (filling_->size() == (size_t)batch_) push(depth, false);
+    }
+  }
+  void finish() {
+    if (!filling_) filling_.reset(new std::vector<uint8_t>());
+    push(~(size_t)0, true);
+  }
 
  private:
+  void push(size_t depth, bool last) {
+    std::unique_lock<std::mutex> lk(qm_);
+    qcv_.wait(lk, [&] { return queue_.size() < depth; });
+    queue_.emplace_back(std::move(filling_), last);
+    filling_.reset();
+    lk.unlock();
+    qcv_.notify_all();
+  }
+  // (m_ is held: the batch's number follows the queue's order)
+  bool next_text(FastxJob& job) {
+    std::unique_lock<std::mutex> lk(qm_);
+    qcv_.wait(lk, [&] { return !queue_.empty(); });
+    job.text = std::move(queue_.front().first);
+    job.last = ended_ = queue_.front().second;
+    queue_.pop_front();
+    lk.unlock();
+    qcv_.notify_all();
+    job.seq = seq_++;
+    job.plain_bytes = (int64_t)job.text->size();
+    return true;
+  }
+  std::mutex qm_;
+  std::condition_variable qcv_;
+  std::deque<std::pair<std::shared_ptr<std::vector<uint8_t>>, bool>> queue_;
+  std::shared_ptr<std::vector<uint8_t>> filling_;
   const FastxKind kind_;
   const int64_t batch_;
   bool ok_ = false, ended_ = false;

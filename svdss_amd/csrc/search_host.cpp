@@ -30,6 +30,7 @@
 #include "call_host.h"
 #include "fastx_reader.h"
 #include "fastx_device.h"
+#include "gzip_stream.h"
 #include "sfs_units.h"
 
 namespace {
@@ -488,6 +489,7 @@ class FastxDevicePath {
   std::unique_ptr<Out> next_out();          // in file order; nullptr behind the last batch
   void assemble();
   void host_tail(std::unique_ptr<Out> first);
+  void gzip_source();                       // FastxKind::Gzip: the file inflated window by window, its text put() to the batcher
 
   const Options& o_;
   const SearchKnobs& knobs_;
@@ -506,7 +508,83 @@ class FastxDevicePath {
   int64_t want_ = 0, last_seq_ = -1;
   int64_t n_device_ = 0, n_host_ = 0, n_records_ = 0;   // (the assembler's)
   double parse_ms_ = 0, text_bytes_ = 0;                // (under t_.m)
+  std::string gzip_line_;                               // (the source thread's, read after it is joined)
 };
+// `search --fastx reads.fastq.gz`, plain gzip: the source thread reads the file in windows of compressed bytes, has each
+// inflated on GPU 0 (svdss_gzip_stream_run) and hands the text to the batcher, whose batches the feeders take as plain text.
+// Where the unit declines, zlib reads on from the carried state (GzHostTail) and the batches go on unchanged.
+void FastxDevicePath::gzip_source() {
+  const std::string& path = o_.fastx;
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) die("cannot open " + path);
+  svdss_gzip_stream_t* gz = nullptr;
+  check(svdss_gzip_stream_create(0, knobs_.gzip_chunk_bytes, &gz), "svdss_gzip_stream_create");
+  const size_t depth = replicas_.size() * (size_t)knobs_.feeders + 2;
+  std::vector<uint8_t> buf((size_t)knobs_.gzip_window_bytes);
+  size_t have = 0;
+  bool eof = false;
+  svdss_gzip_result_t r;
+  for (;;) {
+    while (have < buf.size() && !eof) {
+      const size_t k = fread(buf.data() + have, 1, buf.size() - have, f);
+      if (k == 0) { if (ferror(f)) die("error reading " + path + ": short read"); eof = true; }
+      have += k;
+    }
+    int64_t used = 0;
+    const int rc = svdss_gzip_stream_run(gz, buf.data(), (int64_t)have, eof ? 1 : 0, &used);
+    if (rc == SVDSS_EIO) die("error reading " + path + ": " + svdss_gzip_stream_error(gz));
+    if (rc != SVDSS_OK) die(std::string("svdss_gzip_stream_run: ") + svdss_strerror(rc) + " " + svdss_last_hip_error());
+    check(svdss_gzip_stream_result(gz, &r), "svdss_gzip_stream_result");
+    if (r.text_bytes) batcher_->put(r.text, (size_t)r.text_bytes, depth);
+    memmove(buf.data(), buf.data() + used, have - (size_t)used);
+    have -= (size_t)used;
+    if (r.declined || r.ended) break;
+    if (used == 0 && r.text_bytes == 0) {
+      if (eof) die("error reading " + path + ": truncated gzip stream");
+      buf.resize(buf.size() * 2);      // (a member header longer than the window)
+    }
+  }
+  int64_t host_bytes = 0;
+  if (r.declined) {
+    GzCarry c;
+    c.byte_pos = r.byte_pos; c.bit = r.bit; c.in_member = r.in_member; c.want_trailer = r.want_trailer;
+    c.crc = r.crc; c.count = r.count; c.dict_len = (uint32_t)r.dict_len;
+    memcpy(c.dict + 32768 - c.dict_len, r.dict, c.dict_len);
+    size_t at = 0;
+    GzHostTail tail(c, [&](uint8_t* dst, size_t cap) -> size_t {
+      if (at < have) {          // (what the last window held behind the carried position)
+        const size_t n = std::min(cap, have - at);
+        memcpy(dst, buf.data() + at, n);
+        at += n;
+        return n;
+      }
+      const size_t n = fread(dst, 1, cap, f);
+      if (n == 0 && ferror(f)) die("error reading " + path + ": short read");
+      return n;
+    });
+    std::vector<uint8_t> text((size_t)4 << 20);
+    for (;;) {
+      const int64_t n = tail.next(text.data(), text.size());
+      if (n < 0) die("error reading " + path + ": " + tail.error());
+      if (n == 0) break;
+      host_bytes += n;
+      batcher_->put(text.data(), (size_t)n, depth);
+    }
+  }
+  batcher_->finish();
+  fclose(f);
+  static const char* const why[] = {"", "not a gzip header", "no dynamic block start in a window", "no whole block in a window", "an invalid code",
+                                    "trailing bytes that are no gzip header"};
+  char line[640];
+  int n = snprintf(line, sizeof line, "fastx: gzip on the device: %lld windows, %lld chunks (%lld merged, %lld false starts), %lld bytes, "
+                   "find/measure/decode/resolve %.3f/%.3f/%.3f/%.3f ms", (long long)r.windows, (long long)r.n_chunks, (long long)r.chunks_merged,
+                   (long long)r.false_starts, (long long)r.device_bytes, r.find_ms, r.measure_ms, r.decode_ms, r.resolve_ms);
+  if (r.declined && n > 0 && (size_t)n < sizeof line)
+    snprintf(line + n, sizeof line - (size_t)n, "; the host (zlib) took over at byte %lld bit %d (%s): %lld bytes", (long long)r.byte_pos, (int)r.bit,
+             why[r.declined >= 1 && r.declined <= 5 ? r.declined : 0], (long long)host_bytes);
+  gzip_line_ = line;
+  svdss_gzip_stream_free(gz);
+}
 void FastxDevicePath::feeder(size_t replica) {
   svdss_index_t* ix = replicas_[replica];
   svdss_fastx_batch_t* batch = nullptr;
@@ -525,8 +603,9 @@ void FastxDevicePath::feeder(size_t replica) {
         got += (size_t)k;
       }
     }
+    const uint8_t* const plain = kind_ == FastxKind::Gzip ? job.text->data() : slab.data();
     const int rc = svdss_fastx_batch_run(stream_, job.seq, job.last ? 1 : 0, ix, (int32_t)job.comp.size(), job.comp.data(), job.comp_bytes.data(),
-                                         job.blocks.data(), job.crc.data(), job.n_blocks.data(), slab.data(), job.plain_bytes, flags_, &batch);
+                                         job.blocks.data(), job.crc.data(), job.n_blocks.data(), plain, job.plain_bytes, flags_, &batch);
     if (rc != SVDSS_OK) {
       const std::string why = batch && *svdss_fastx_batch_error(batch) ? svdss_fastx_batch_error(batch) : svdss_fastx_stream_error(stream_);
       if (rc == SVDSS_EIO) die("error reading " + o_.fastx + ": " + why);
@@ -651,13 +730,17 @@ void FastxDevicePath::run() {
   for (int k = 0; k < n_fmt; ++k) fmt.emplace_back([this] { units_.format_units(*writer_); });
   for (size_t d = 0; d < replicas_.size(); ++d)
     for (int k = 0; k < knobs_.feeders; ++k) feeders.emplace_back([this, d] { feeder(d); });
+  std::thread source;
+  if (kind_ == FastxKind::Gzip) source = std::thread([this] { gzip_source(); });
   for (std::thread& th : feeders) th.join();
+  if (source.joinable()) source.join();
   assembler.join();
   for (std::thread& th : fmt) th.join();
   writer_->finish();
   svdss_fastx_stream_free(stream_);
   if (!o_.verbose) return;
   logmsg("debug", std::to_string(n_records_) + " records read, " + std::to_string(writer_->lines()) + " SFS written at +" + clock_.since() + " s");
+  if (!gzip_line_.empty()) logmsg("debug", gzip_line_);
   logmsg("debug", "FASTX device path: " + std::to_string(n_device_) + " batches on the device, " + std::to_string(n_host_) + " through the host reader, " +
                       std::to_string(n_records_) + " records");
   char buf[480];
@@ -889,8 +972,9 @@ void SearchRun::run_host_path() {
     if (!bam->ok() || !bam->read_header()) die("cannot read " + o.bam + ": " + bam->error());
   } else {
     logmsg("warning", "FASTX mode is not optimized (higher running times and larger SFSs set).");
-    // an eligible file (regular; BGZF or not compressed) has its records found on the GPU; SVDSS_FASTX_DEVICE=0: the host reader
-    const FastxKind kind = knobs.fastx_device && svdss_device_count() > 0 ? fastx_device_kind(o.fastx) : FastxKind::None;
+    // an eligible file (regular; BGZF, not compressed, or -- SVDSS_FASTX_GZIP_DEVICE=1 -- plain gzip) has its records found on
+    // the GPU; SVDSS_FASTX_DEVICE=0: the host reader
+    const FastxKind kind = knobs.fastx_device && svdss_device_count() > 0 ? fastx_device_kind(o.fastx, knobs.fastx_gzip_device) : FastxKind::None;
     if (kind != FastxKind::None) {
       if (o.bsize <= 0) die("batch size smaller than the number of threads");
       logmsg("info", "Extracting SFS strings on the GPU (output order as with " + std::to_string(o.threads) + " threads)..");

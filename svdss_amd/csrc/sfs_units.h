@@ -54,6 +54,12 @@ struct SearchKnobs {
   bool fastx_device = env_switch("SVDSS_FASTX_DEVICE") != 0;                  // 0: `--fastx` through the host reader although the file is eligible
   // text bytes per device batch of `--fastx` (192 MB; SVDSS_FASTX_BATCH_KB: the same knob for tests)
   int64_t fastx_batch_bytes = getenv("SVDSS_FASTX_BATCH_KB") ? env_from("SVDSS_FASTX_BATCH_KB", 1, 1) << 10 : env_from("SVDSS_FASTX_BATCH_MB", 1, 192) << 20;
+  // plain (single-stream) gzip of `--fastx` inflated on the GPU (csrc/gzip_stream.hip): opt-in (1) until it is measured
+  // against the host reader; the chunk a wavefront decodes (256 KB) and the window of compressed bytes per run (64 MB;
+  // SVDSS_GZIP_WINDOW_KB: the same knob for tests)
+  bool fastx_gzip_device = env_switch("SVDSS_FASTX_GZIP_DEVICE") == 1;
+  int64_t gzip_chunk_bytes = std::min<int64_t>(env_from("SVDSS_GZIP_CHUNK_KB", 1, 256), 1 << 20) << 10;
+  int64_t gzip_window_bytes = getenv("SVDSS_GZIP_WINDOW_KB") ? env_from("SVDSS_GZIP_WINDOW_KB", 1, 64) << 10 : std::min<int64_t>(env_from("SVDSS_GZIP_WINDOW_MB", 1, 64), 1024) << 20;
   bool prewarm = !getenv("SVDSS_NO_PREWARM");                                 // page-locked buffers allocated beside the restore
   bool clean_exit = getenv("SVDSS_CLEAN_EXIT") != nullptr;                    // orderly teardown instead of _exit (leak checkers)
 };
