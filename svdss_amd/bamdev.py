@@ -62,10 +62,11 @@ def set_gate(stream, gate):
         raise SvdssError(rc, "svdss_bam_stream_set_regions")
 
 
-def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20, n_ref=None, skip=None, gate=None):
+def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20, n_ref=None, skip=None, gate=None, chunks_per_batch=1):
     """`data`: the bytes of a BAM file.  Runs the whole file through svdss_bam_batch_run in batches of about
     batch_bytes inflated bytes (one after the other; the binary runs several at once) and returns a list of
-    (name, hp, None | [(qs, len), ...]) for every record that passed the filters, in file order, plus a dict of counters."""
+    (name, hp, None | [(qs, len), ...]) for every record that passed the filters, in file order, plus a dict of counters.
+    chunks_per_batch: every batch's members handed over as that many chunks (bgzf.BatchArgs.split)."""
     blocks = bgzf.bgzf_blocks(data)
     if n_ref is None or skip is None:
         n_ref, skip = bam_header(data, blocks)
@@ -79,27 +80,11 @@ def search_bam(index, data, assemble=True, putative=False, batch_bytes=256 << 20
     set_gate(stream, gate)
     flags = (SVDSS_SFS_ASSEMBLE if assemble else 0) | (SVDSS_BAM_PUTATIVE if putative else 0)
     try:
-        groups, cur, acc = [], [], 0
-        for b in blocks:
-            cur.append(b)
-            acc += b[2]
-            if acc >= batch_bytes:
-                groups.append(cur)
-                cur, acc = [], 0
-        groups.append(cur)   # (possibly empty: the last batch closes the stream)
+        groups = bgzf.batches(data, batch_bytes)   # (the last one possibly empty: it closes the stream)
         for seq, g in enumerate(groups):
-            rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
-            crc = np.zeros(max(1, len(g)), dtype=np.uint32)
-            for i, b in enumerate(g):
-                rec[i] = (b[0], b[1], b[2], 0)
-                crc[i] = b[3]
-            comp_p = (C.c_void_p * 1)(comp.ctypes.data)
-            comp_n = (C.c_int64 * 1)(len(comp))
-            blk_p = (C.c_void_p * 1)(rec.ctypes.data)
-            crc_p = (C.c_void_p * 1)(crc.ctypes.data)
-            nb = (C.c_int64 * 1)(len(g))
-            rc = lib.svdss_bam_batch_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, index._h, 1,
-                                         comp_p, comp_n, blk_p, crc_p, nb, flags, C.byref(batch))
+            A = bgzf.BatchArgs.of(comp, g, chunks_per_batch)
+            rc = lib.svdss_bam_batch_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, index._h, *A.args,
+                                         flags, C.byref(batch))
             if rc:
                 e = SvdssError(rc, "svdss_bam_batch_run")
                 e.detail = (lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""
@@ -175,7 +160,7 @@ def bam_ref_lengths(data, blocks):
     return lens
 
 
-def index_bam(data, csi=False, batch_bytes=256 << 20, device=0):
+def index_bam(data, csi=False, batch_bytes=256 << 20, device=0, chunks_per_batch=1):
     """The BAI (csi=True: CSI) index of a BAM file (bytes), built on the GPU: select_bam's loop with the stream's input index
     switched on (svdss_bam_stream_set_input_index) and every batch's fragments folded in file order
     (svdss_bam_input_indexer_*).  The bytes `SVDSS bamindex` writes.  SvdssError with code SVDSS_EIO for an unsorted file."""
@@ -195,7 +180,8 @@ def index_bam(data, csi=False, batch_bytes=256 << 20, device=0):
             _check(lib.svdss_bam_batch_input_index(batch, C.byref(f)), "svdss_bam_batch_input_index")
             _check(lib.svdss_bam_input_indexer_add(ix, C.byref(f), base), "svdss_bam_input_indexer_add")
             base += f.comp_bytes
-        select_bam(data, names=[], batch_bytes=batch_bytes, device=device, input_index=(shift.value, depth.value), on_batch=fold)
+        select_bam(data, names=[], batch_bytes=batch_bytes, device=device, input_index=(shift.value, depth.value), on_batch=fold,
+                   chunks_per_batch=chunks_per_batch)
         # the end of the stream: the EOF marker where the file ends with one, else the file's size
         end = len(data)
         if blocks and blocks[-1][2] == 0:
@@ -207,11 +193,13 @@ def index_bam(data, csi=False, batch_bytes=256 << 20, device=0):
         lib.svdss_bam_input_indexer_free(ix)
 
 
-def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20, device=0, gate=None, input_index=None, on_batch=None):
+def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20, device=0, gate=None, input_index=None, on_batch=None,
+               chunks_per_batch=1):
     """svdss_bam_select_run over a whole BAM file (bytes): the records `SVDSS call` keeps -- no flag 4 / 256 / 2048,
     mapq >= min_mapq, and (when given) read name in `names` or alignment overlapping one of `regions` =
     [(tid, beg, end)] sorted by (tid, beg).  Returns ([record bytes without the block_size field], counters).
-    input_index: see set_input_index; on_batch(batch handle): called after every batch."""
+    input_index: see set_input_index; on_batch(batch handle): called after every batch; chunks_per_batch: every batch's
+    members handed over as that many chunks (bgzf.BatchArgs.split)."""
     blocks = bgzf.bgzf_blocks(data)
     n_ref, skip = bam_header(data, blocks)
     comp = np.frombuffer(bytes(data), dtype=np.uint8)
@@ -235,23 +223,10 @@ def select_bam(data, names=None, regions=None, min_mapq=0, batch_bytes=256 << 20
     try:
         set_gate(stream, gate)
         set_input_index(stream, input_index)
-        groups, cur, acc = [], [], 0
-        for b in blocks:
-            cur.append(b)
-            acc += b[2]
-            if acc >= batch_bytes:
-                groups.append(cur)
-                cur, acc = [], 0
-        groups.append(cur)
+        groups = bgzf.batches(data, batch_bytes)
         for seq, g in enumerate(groups):
-            rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
-            crc = np.zeros(max(1, len(g)), dtype=np.uint32)
-            for i, b in enumerate(g):
-                rec[i] = (b[0], b[1], b[2], 0)
-                crc[i] = b[3]
-            rc = lib.svdss_bam_select_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, flt, 1,
-                                          (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
-                                          (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+            A = bgzf.BatchArgs.of(comp, g, chunks_per_batch)
+            rc = lib.svdss_bam_select_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, flt, *A.args, C.byref(batch))
             if rc:
                 e = SvdssError(rc, "svdss_bam_select_run")
                 e.detail = (lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""
@@ -304,10 +279,8 @@ def select_bam_ranges(data, ranges, min_mapq=0, batch_blocks=16, device=0, gate=
         if not jobs:
             jobs = [([], 0)]
         for seq, (g, skip) in enumerate(jobs):
-            rec, crc = _group_tables(g)
-            rc = lib.svdss_bam_select_run(stream, seq, 1 if seq == len(jobs) - 1 else 0, skip, flt, 1,
-                                          (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
-                                          (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+            A = bgzf.BatchArgs.whole(comp, g)
+            rc = lib.svdss_bam_select_run(stream, seq, 1 if seq == len(jobs) - 1 else 0, skip, flt, *A.args, C.byref(batch))
             if rc:
                 raise SvdssError(rc, "svdss_bam_select_run: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
             r = BamSelection()
@@ -366,23 +339,11 @@ def select_bam_store(data, names, regions, min_mapq=0, batch_bytes=256 << 20, de
                 into.append(raw[o + 4:o + 4 + bs])
     try:
         set_gate(stream, gate)
-        groups, cur, acc = [], [], 0
-        for b in blocks:
-            cur.append(b)
-            acc += b[2]
-            if acc >= batch_bytes:
-                groups.append(cur)
-                cur, acc = [], 0
-        groups.append(cur)
+        groups = bgzf.batches(data, batch_bytes)
         for seq, g in enumerate(groups):
-            rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
-            crc = np.zeros(max(1, len(g)), dtype=np.uint32)
-            for i, b in enumerate(g):
-                rec[i] = (b[0], b[1], b[2], 0)
-                crc[i] = b[3]
-            rc = lib.svdss_bam_select_store_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, f_names, store, 1,
-                                                (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
-                                                (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+            A = bgzf.BatchArgs.whole(comp, g)
+            rc = lib.svdss_bam_select_store_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, f_names, store, *A.args,
+                                                C.byref(batch))
             if rc:
                 e = SvdssError(rc, "svdss_bam_select_store_run")
                 e.detail = (lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""
@@ -427,27 +388,6 @@ class BamSmoothed(C.Structure):
 def _check(rc, what):
     if rc:
         raise SvdssError(rc, what)
-
-
-def _batch_groups(blocks, batch_bytes):
-    groups, cur, acc = [], [], 0
-    for b in blocks:
-        cur.append(b)
-        acc += b[2]
-        if acc >= batch_bytes:
-            groups.append(cur)
-            cur, acc = [], 0
-    groups.append(cur)
-    return groups
-
-
-def _group_tables(g):
-    rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
-    crc = np.zeros(max(1, len(g)), dtype=np.uint32)
-    for i, b in enumerate(g):
-        rec[i] = (b[0], b[1], b[2], 0)
-        crc[i] = b[3]
-    return rec, crc
 
 
 class BamFilter:
@@ -519,12 +459,11 @@ class BamStore:
         _check(lib.svdss_bam_stream_create(n_ref, C.byref(stream)), "svdss_bam_stream_create")
         try:
             set_gate(stream, gate)
-            groups = _batch_groups(blocks, batch_bytes)
+            groups = bgzf.batches(data, batch_bytes)
             for seq, g in enumerate(groups):
-                rec, crc = _group_tables(g)
-                rc = lib.svdss_bam_select_store_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, flt._h, self._h, 1,
-                                                    (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
-                                                    (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+                A = bgzf.BatchArgs.whole(comp, g)
+                rc = lib.svdss_bam_select_store_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, flt._h, self._h, *A.args,
+                                                    C.byref(batch))
                 if rc:
                     raise SvdssError(rc, "svdss_bam_select_store_run: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
             return len(groups)
@@ -568,14 +507,12 @@ def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20,
         _check(lib.svdss_bam_stream_set_output_prefix(stream, head.ctypes.data, len(head)), "svdss_bam_stream_set_output_prefix")
         set_gate(stream, gate)
         set_input_index(stream, input_index)
-        groups = _batch_groups(blocks, batch_bytes)
+        groups = bgzf.batches(data, batch_bytes)
         measured, counts = [], []
         for seq, g in enumerate(groups):
-            rec, crc = _group_tables(g)
+            A = bgzf.BatchArgs.whole(comp, g)
             if measure:
-                rc = lib.svdss_bam_smooth_measure(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, 1,
-                                                  (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
-                                                  (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+                rc = lib.svdss_bam_smooth_measure(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, *A.args, C.byref(batch))
                 if rc:
                     raise SvdssError(rc, "svdss_bam_smooth_measure: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
                 sr = BamSmoothed()
@@ -584,9 +521,8 @@ def smooth_bam(data, contigs_ascii, min_mapq=20, acc=1.0, batch_bytes=256 << 20,
                 for k in range(sr.n_kept):
                     measured.append((int(sr.match_mismatch[2 * k]), int(sr.match_mismatch[2 * k + 1]), int(sr.fits[k])))
                 continue
-            rc = lib.svdss_bam_smooth_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, C.c_double(acc), None, 0, 1,
-                                          (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(comp)), (C.c_void_p * 1)(rec.ctypes.data),
-                                          (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), C.byref(batch))
+            rc = lib.svdss_bam_smooth_run(stream, seq, 1 if seq == len(groups) - 1 else 0, skip if seq == 0 else 0, sm, C.c_double(acc), None, 0,
+                                          *A.args, C.byref(batch))
             if rc:
                 raise SvdssError(rc, "svdss_bam_smooth_run: " + ((lib.svdss_bam_batch_error(batch) or b"").decode() if batch else ""))
             sr = BamSmoothed()

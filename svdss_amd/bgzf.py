@@ -28,6 +28,76 @@ def bgzf_blocks(data):
     return out
 
 
+def batches(data, batch_bytes):
+    """The BGZF members of `data` in groups of consecutive members that inflate to at least batch_bytes, plus the group
+    (possibly empty) that closes the stream: lists of (coff, clen, isize, crc)."""
+    groups, cur, acc = [], [], 0
+    for b in bgzf_blocks(data):
+        cur.append(b)
+        acc += b[2]
+        if acc >= batch_bytes:
+            groups.append(cur)
+            cur, acc = [], 0
+    groups.append(cur)
+    return groups
+
+
+def _member_start(data, coff):
+    """where the gzip header in front of the deflate stream at data[coff:] begins (12 + XLEN bytes, 18 in every BGZF file)"""
+    for h in range(18, min(coff, 12 + 0xffff) + 1):
+        p = coff - h
+        if data[p] == 31 and data[p + 1] == 139 and data[p + 2] == 8 and (data[p + 3] & 4) and data[p + 10] | (data[p + 11] << 8) == h - 12:
+            return p
+    raise ValueError("no gzip header in front of %d" % coff)
+
+
+class BatchArgs:
+    """The six arguments every batch entry point ends with -- n_chunks, comp, comp_bytes, blocks, crc, n_blocks -- as
+    `.args`, built from `chunks` = [(compressed bytes (numpy uint8), [(coff, clen, isize, crc)] relative to them)]; the
+    numpy arrays behind the pointers live as long as the object."""
+
+    def __init__(self, chunks):
+        import ctypes as C
+        import numpy as np
+        self._keep = []
+        n = len(chunks)
+        comp_p, comp_n, blk_p, crc_p, nb = (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)()
+        for c, (comp, g) in enumerate(chunks):
+            rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
+            crc = np.zeros(max(1, len(g)), dtype=np.uint32)
+            for i, b in enumerate(g):
+                rec[i] = (b[0], b[1], b[2], 0)
+                crc[i] = b[3]
+            self._keep += [comp, rec, crc]
+            comp_p[c], comp_n[c] = (comp.ctypes.data if len(comp) else None), len(comp)
+            blk_p[c], crc_p[c], nb[c] = rec.ctypes.data, crc.ctypes.data, len(g)
+        self.args = (n, comp_p, comp_n, blk_p, crc_p, nb)
+
+    @classmethod
+    def whole(cls, comp, group):
+        """the common case: the whole file (numpy uint8) as one chunk, `group` = some of its members"""
+        return cls([(comp, group)])
+
+    @classmethod
+    def split(cls, comp, group, k):
+        """`group` (consecutive members of the file `comp`) cut into k chunks: each a copy of its own slice of the file, from
+        the gzip header of its first member to the footer of its last, its members' coff relative to the copy (a chunk
+        that gets no member is empty)"""
+        chunks = []
+        for c in range(k):
+            g = group[c * len(group) // k:(c + 1) * len(group) // k]
+            if not g:
+                chunks.append((comp[:0].copy(), []))
+                continue
+            a, b = _member_start(comp, g[0][0]), g[-1][0] + g[-1][1] + 8
+            chunks.append((comp[a:b].copy(), [(m[0] - a,) + tuple(m[1:]) for m in g]))
+        return cls(chunks)
+
+    @classmethod
+    def of(cls, comp, group, chunks_per_batch=1):
+        return cls.whole(comp, group) if chunks_per_batch == 1 else cls.split(comp, group, chunks_per_batch)
+
+
 def gpu_inflate(data, blocks, device=0, uoff=None):
     """Inflates raw deflate streams on the GPU: blocks = [(coff, clen, isize)], block i goes to uoff[i] (default: back
     to back).  Returns the inflated bytes (numpy uint8).  Raises SvdssError (code SVDSS_EIO) with .bad_block set when a

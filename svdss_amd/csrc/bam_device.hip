@@ -885,7 +885,7 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   // its first member -- behind a gap: what the batch in front carried (the cut record at its range's end) is dropped
   const bool restart = (skip & SVDSS_BAM_SKIP_RESTART) != 0;
   skip &= ~SVDSS_BAM_SKIP_RESTART;
-  if (n_chunks > 0 && (!comp || !comp_bytes || !blocks || !crc || !n_blocks)) return run.fail(SVDSS_EINVAL, "bad argument");
+  if (const char* m = bgzf_check_args(n_chunks, comp, comp_bytes, blocks, crc, n_blocks)) return run.fail(SVDSS_EINVAL, m);
   BCHK(hipSetDevice(device));
   RCHK(run.batch_object(out, device));
   svdss_bam_batch* b = run.b;
@@ -898,65 +898,34 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   }();
 
   // ---- the batch's blocks: compressed bytes back to back, inflated bytes back to back behind the head room
-  int64_t total_blocks = 0, total_comp = 0, total_inf = 0;
-  for (int32_t c = 0; c < n_chunks; ++c) {
-    if (comp_bytes[c] < 0 || n_blocks[c] < 0 || (n_blocks[c] > 0 && (!comp[c] || !blocks[c] || !crc[c]))) return run.fail(SVDSS_EINVAL, "bad chunk");
-    total_blocks += n_blocks[c];
-    total_comp += (comp_bytes[c] + 15) & ~(int64_t)15;
-    for (int64_t i = 0; i < n_blocks[c]; ++i) {
-      const svdss_bgzf_block_t& k = blocks[c][i];
-      if (k.coff < 0 || k.clen < 0 || k.isize < 0 || k.isize > 65536 || k.coff + k.clen > comp_bytes[c]) return run.fail(SVDSS_EINVAL, "bad block");
-      total_inf += k.isize;
-    }
-  }
+  BgzfIntake& in = b->front.in;
+  RCHK(in.plan(n_chunks, comp, comp_bytes, blocks, crc, n_blocks));
+  const int64_t total_blocks = in.P.n_blocks, total_inf = in.P.inflated;
   if (HEAD + total_inf + skip >= ((int64_t)1 << 32) - 65536) return run.fail(SVDSS_ERANGE, "batch too large");
   if (skip > total_inf) return run.fail(SVDSS_EIO, "truncated header");
-  RCHK(b->front.comp.ensure((size_t)total_comp + 8192));
-  RCHK(b->front.blks.ensure(sizeof(svdss_bgzf_block_t) * (size_t)(total_blocks + 1)));
-  RCHK(b->front.crcb.ensure(sizeof(CrcBlk) * (size_t)(total_blocks + 1)));
-  RCHK(b->front.status.ensure(sizeof(int32_t) * (size_t)(total_blocks + 2)));
   RCHK(b->front.buf.ensure((size_t)(HEAD + total_inf) + 4096));
   RCHK(b->front.hdr.ensure(sizeof(int64_t) * H_N));
   RCHK(b->front.pre.ensure(64));
   RCHK(b->totals.ensure(64));
-  const size_t tab_bytes = (sizeof(svdss_bgzf_block_t) + sizeof(CrcBlk)) * (size_t)(total_blocks + 1);
-  RCHK(b->front.pin.ensure(tab_bytes + 4096));
-  svdss_bgzf_block_t* h_blk = (svdss_bgzf_block_t*)b->front.pin.p;
-  CrcBlk* h_crc = (CrcBlk*)(h_blk + (total_blocks + 1));
   // (the input index's scheme: set before batch 0 and not changed after it, so read without the stream's lock)
   const bool ix_on = s->in_ix_shift > 0;
   b->in_ix.f = svdss_bam_input_frag_t{};
   b->in_ix.corrupt = false;
-  if (ix_on) {
+  if (ix_on) {   // where every member begins in the file, from the batch's first (consecutive members: header, stream, footer)
     b->in_ix.chunks.clear(); b->in_ix.windows.clear();
     try { b->in_ix.h_mstart.assign((size_t)total_blocks + 1, 0); } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
     b->in_ix.f.on = 1; b->in_ix.f.first_data = -1;
-  }
-  {
-    int64_t k = 0, coff = 0, uoff = 0, fpos = 0;
-    for (int32_t c = 0; c < n_chunks; ++c) {
-      if (comp_bytes[c] > 0) BCHK(hipMemcpyAsync((uint8_t*)b->front.comp.p + coff, comp[c], (size_t)comp_bytes[c], hipMemcpyHostToDevice, st));
+    int64_t k = 0, fpos = 0;
+    for (int32_t c = 0; c < n_chunks; ++c)
       for (int64_t i = 0; i < n_blocks[c]; ++i, ++k) {
-        h_blk[k] = blocks[c][i];
-        h_blk[k].coff += coff;
-        h_blk[k].uoff = HEAD + uoff;
-        h_crc[k] = CrcBlk{HEAD + uoff, blocks[c][i].isize, crc[c][i]};
-        uoff += blocks[c][i].isize;
-        if (ix_on) {   // where the member begins in the file, from the batch's first (consecutive members: header, stream, footer)
-          b->in_ix.h_mstart[(size_t)k] = fpos;
-          if (blocks[c][i].isize > 0 && b->in_ix.f.first_data < 0) b->in_ix.f.first_data = fpos;
-          fpos += member_header_len(comp[c], blocks[c][i].coff) + blocks[c][i].clen + 8;
-        }
+        b->in_ix.h_mstart[(size_t)k] = fpos;
+        if (blocks[c][i].isize > 0 && b->in_ix.f.first_data < 0) b->in_ix.f.first_data = fpos;
+        fpos += member_header_len(comp[c], blocks[c][i].coff) + blocks[c][i].clen + 8;
       }
-      coff += (comp_bytes[c] + 15) & ~(int64_t)15;
-    }
-    if (ix_on) { b->in_ix.h_mstart[(size_t)total_blocks] = fpos; b->in_ix.f.comp_bytes = fpos; }
-  }
-  if (ix_on) {
+    b->in_ix.h_mstart[(size_t)total_blocks] = fpos; b->in_ix.f.comp_bytes = fpos;
     RCHK(b->in_ix.mstart.ensure(sizeof(int64_t) * (size_t)(total_blocks + 1)));
     BCHK(hipMemcpyAsync(b->in_ix.mstart.p, b->in_ix.h_mstart.data(), sizeof(int64_t) * (size_t)(total_blocks + 1), hipMemcpyHostToDevice, st));
   }
-  BCHK(hipMemsetAsync(b->front.status.p, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
   BCHK(hipMemsetAsync(b->front.hdr.p, 0, sizeof(int64_t) * H_N, st));
   // (the gate's intervals: set before batch 0 and not changed after it, so read without the stream's lock)
   const bool gate_on = s->gate_on;
@@ -964,18 +933,8 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
     RCHK(b->front.gate.ensure(s->gate_tab.size() + 64));
     BCHK(hipMemcpyAsync(b->front.gate.p, s->gate_tab.data(), s->gate_tab.size(), hipMemcpyHostToDevice, st));
   }
-  int32_t* d_status = (int32_t*)b->front.status.p;
-  int32_t* d_crcbad = d_status + total_blocks;
-  if (total_blocks > 0) {
-    BCHK(hipMemcpyAsync(b->front.blks.p, h_blk, sizeof(svdss_bgzf_block_t) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    BCHK(hipMemcpyAsync(b->front.crcb.p, h_crc, sizeof(CrcBlk) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    BCHK(hipEventRecord(b->e0, st));
-    BCHK(svdss_inflate_enqueue(st, (const uint8_t*)b->front.comp.p, (const svdss_bgzf_block_t*)b->front.blks.p, total_blocks, (uint8_t*)b->front.buf.p, d_status));
-    BCHK(hipEventRecord(b->e1, st));
-    BCHK(crc_tables_ready());
-    hipLaunchKernelGGL(crc32_kernel, dim3((unsigned)total_blocks), dim3(64), 0, st, (const uint8_t*)b->front.buf.p, (const CrcBlk*)b->front.crcb.p, d_crcbad);
-    BCHK(hipGetLastError());
-  }
+  RCHK(in.enqueue(st, b->e0, b->e1, (uint8_t*)b->front.buf.p, HEAD));
+  const svdss_bgzf_block_t* const h_blk = in.h_blk();
   // ---- the chain of records, guessed per segment (does not need the carry)
   SegWalk W;
   W.buf = (const uint8_t*)b->front.buf.p;
@@ -1001,17 +960,11 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
   W.lists = (uint32_t*)b->front.lists.p;
   hipLaunchKernelGGL(walk_kernel, dim3((unsigned)W.n_seg), dim3(64), 0, st, WalkP{W});
   BCHK(hipGetLastError());
-  b->front.h_status.resize((size_t)total_blocks + 2);
-  BCHK(hipMemcpyAsync(b->front.h_status.data(), d_status, sizeof(int32_t) * (size_t)(total_blocks + 2), hipMemcpyDeviceToHost, st));
+  RCHK(in.enqueue_status_download(st));
   BCHK(hipStreamSynchronize(st));
-  if (total_blocks > 0) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, b->e0, b->e1) == hipSuccess) b->inflate_ms = ms;
-  }
+  const int verdict = in.verdict(b->e0, b->e1, b->inflate_ms);
   run.lap(0);   // buffers, upload, inflate, CRC, segment walk
-  for (int64_t i = 0; i < total_blocks; ++i)
-    if (b->front.h_status[(size_t)i] != 0) return run.fail(SVDSS_EIO, "BGZF inflate failed");
-  if (b->front.h_status[(size_t)total_blocks] != 0) return run.fail(SVDSS_EIO, "BGZF block CRC mismatch");
+  RCHK(verdict);
 
   // ---- this batch's turn: carry in, the chain proved and completed, carry out
   const bool my_turn = wait_turn(s, &svdss_bam_stream::next_seq, seq);
@@ -1100,7 +1053,7 @@ int batch_front(svdss_bam_stream_t* s, int64_t seq, int32_t is_last, int64_t ski
       P.buf = W.buf; P.lists = W.lists; P.list_cap = W.list_cap; P.seg_cnt = W.seg_cnt; P.seg_base = seg_base; P.pre = (const uint32_t*)b->front.pre.p;
       P.n_seg = W.n_seg; P.n_rec = n; P.n_pre = hdr[H_PRE];
       P.head = HEAD; P.hi = W.hi;
-      P.blks = (const svdss_bgzf_block_t*)b->front.blks.p; P.mstart = (const int64_t*)b->in_ix.mstart.p; P.n_blk = total_blocks;
+      P.blks = (const svdss_bgzf_block_t*)in.blks.p; P.mstart = (const int64_t*)b->in_ix.mstart.p; P.n_blk = total_blocks;
       P.pre_v = ix_pre_v; P.min_shift = s->in_ix_shift; P.depth = s->in_ix_depth;
       int64_t* i64 = (int64_t*)b->in_ix.rec.p;
       unsigned long long* d_err = (unsigned long long*)i64;    // 8 bytes, then the per-record arrays

@@ -1,7 +1,8 @@
 // bam_device_internal.h -- what the units of the BAM device path share (bam_device.hip: front end, search, select, store;
 // bam_smooth.hip: `SVDSS smooth`): the stream and batch objects, the front end's result, the scope an entry point runs a
 // batch in (BatchRun), the record store and the few device helpers the kernels of both units use.  Kernels stay in the unit
-// that launches them, but for the two both units launch (crc32_kernel, slim_export_kernel).
+// that launches them, but for slim_export_kernel, which both launch.  How a batch's BGZF members get into HBM (BgzfIntake,
+// crc32_kernel), the turn in file order, BCHK / RCHK and the hipcub helper are bgzf_intake.h's: the text units share them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -20,9 +21,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
-#include "crc_gf.h"
-#include "dev_buf.h"
-#include "hip_check.h"
+#include "bgzf_intake.h"
 
 // error bits a batch's kernels raise (hdr[H_ERR]; bam_smooth.hip adds one of its own)
 enum { E_CORRUPT = 1, E_TID = 2 };
@@ -34,11 +33,6 @@ static inline const char* record_error(int64_t bits) {
 }
 
 namespace {   // (every unit its own copy: no device-side linking)
-
-__device__ __forceinline__ uint32_t ld32(const uint8_t* base, int64_t off) {
-  const uint32_t* w = (const uint32_t*)(base + (off & ~(int64_t)3));
-  return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(off & 3));
-}
 
 // bam_aux_get + bam_aux2i for one two-letter tag, as BamReader::aux_int reads it (csrc/bam_reader.h): integer types
 // only, anything unexpected ends the scan with "absent"
@@ -181,86 +175,6 @@ __device__ __forceinline__ void nt6_chunk16(const uint8_t* __restrict__ buf, int
   }
 }
 
-
-// ------------------------------------------------------------------ CRC32 of BGZF blocks (crc32_kernel, bgzf_footer_kernel)
-// Tables of the CRC kernels, computed once on the host and copied to every device that asks:
-//   [0]      the byte table of the CRC (state * x^8 for the state's low byte)
-//   [1..4]   byte k of a state times x^2048: state * x^2048 = [1][b0] ^ [2][b1] ^ [3][b2] ^ [4][b3]
-//   [5][l]   x^(32 (64 - l)), lane l's weight (entries 0..63)
-__device__ uint32_t g_crc_tab[6][256];
-
-// the tables, on the current device (once per device, unit and process)
-hipError_t crc_tables_ready() {
-  static std::mutex m;
-  static bool done[64] = {false};
-  static uint32_t h[6][256];
-  static bool built = false;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lk(m);
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  if (!built) {
-    memset(h, 0, sizeof h);
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
-      h[0][i] = c;
-    }
-    const uint32_t x2048 = gf_xpow8(256);
-    for (int k = 0; k < 4; ++k)
-      for (uint32_t i = 0; i < 256; ++i) h[1 + k][i] = gf_mul(i << (8 * k), x2048);
-    for (uint32_t l = 0; l < 64; ++l) h[5][l] = gf_xpow8(4 * (64 - l));
-    built = true;
-  }
-  e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc_tab), h, sizeof h);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
-
-// ------------------------------------------------------------------ CRC32 of the inflated blocks
-struct CrcBlk { int64_t uoff; int32_t isize; uint32_t crc; };
-
-// One wavefront per BGZF block.  The state of a CRC after words w_0 .. w_(m-1) is the sum of w_i x^(32 (m - i)) (the
-// initial value folded into w_0): lane l takes the words l, l + 64, l + 128, ... -- every load of the wave is 256
-// contiguous bytes -- with a <- a x^2048 + w (four table lookups, as many as the usual word step costs), and the lanes'
-// sums meet weighted by x^(32 (64 - l)).  The bytes behind the last whole 256 (none in blocks of 0xff00 bytes, what htslib
-// and bgzip write) go through the byte table on one lane.  (Until the second half of round 4 every lane walked its own
-// kilobyte of the block: 64 cache lines per load instruction, 205 GB/s, 8 % of the GPU's time in `search` end to end.)
-__global__ void __launch_bounds__(64) crc32_kernel(const uint8_t* __restrict__ data, const CrcBlk* __restrict__ blks, int32_t* bad) {
-  __shared__ uint32_t T[5][256];
-  const int lane = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 5; ++k)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) T[k][lane + 64 * i] = g_crc_tab[k][lane + 64 * i];
-  const uint32_t weight = g_crc_tab[5][lane];
-  __syncthreads();
-  const CrcBlk b = blks[blockIdx.x];
-  const int n = b.isize;
-  if (n <= 0) return;
-  const uint8_t* p = data + b.uoff;
-  const int J = n >> 8;
-  uint32_t state = 0xFFFFFFFFu;
-  if (J > 0) {
-    uint32_t a = 0;
-    for (int j = 0; j < J; ++j) {
-      // (the block's first byte is wherever the blocks before it end: the aligned-words-and-shift of ld32 on the offset
-      // from the buffer's -- aligned -- start, not on a pointer that is not)
-      uint32_t w = ld32(data, b.uoff + (int64_t)(j * 64 + lane) * 4);
-      if (j == 0 && lane == 0) w ^= 0xFFFFFFFFu;
-      a = T[1][a & 0xff] ^ T[2][(a >> 8) & 0xff] ^ T[3][(a >> 16) & 0xff] ^ T[4][a >> 24] ^ w;
-    }
-    uint32_t c = gf_mul(a, weight);
-    for (int d = 32; d >= 1; d >>= 1) c ^= (uint32_t)__shfl_xor((int)c, d, 64);
-    state = c;
-  }
-  if (lane == 0) {
-    for (int i = J << 8; i < n; ++i) state = T[0][(state ^ p[i]) & 0xff] ^ (state >> 8);
-    if (~state != b.crc) atomicAdd(bad, 1);
-  }
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ the stream of a file's batches
@@ -295,26 +209,8 @@ struct svdss_bam_stream {
   int32_t carry_uoff = 0;
 };
 
-// Batches take turns in file order: at the carry (`turn` = &svdss_bam_stream::next_seq) and, when smoothing, at the output
-// stream (next_out).  The turn of batch `seq` is taken by wait_turn and given up by done_turn, on every path.
-static inline bool wait_turn(svdss_bam_stream* s, int64_t svdss_bam_stream::*turn, int64_t seq) {
-  std::unique_lock<std::mutex> lk(s->m);
-  s->cv.wait(lk, [&] { return s->*turn == seq || s->failed; });
-  return !s->failed;
-}
-static inline void done_turn(svdss_bam_stream* s, int64_t svdss_bam_stream::*turn, int fail_code, const std::string& msg) {
-  {
-    std::lock_guard<std::mutex> lk(s->m);
-    if (fail_code && !s->failed) { s->failed = fail_code; s->err = msg; }
-    ++(s->*turn);
-  }
-  s->cv.notify_all();
-}
-// a batch that fails before its turn still passes the turn on: the batches behind it wait for it (a stream that already
-// failed has let everybody through)
-static inline void pass_turn(svdss_bam_stream* s, int64_t svdss_bam_stream::*turn, int64_t seq, int code, const std::string& msg) {
-  if (wait_turn(s, turn, seq)) done_turn(s, turn, code, msg);
-}
+// Batches take turns in file order (wait_turn / done_turn / pass_turn, bgzf_intake.h): at the carry (`turn` =
+// &svdss_bam_stream::next_seq) and, when smoothing, at the output stream (next_out).
 
 // ------------------------------------------------------------------ the batch object
 // One object for every job (callers reuse it across jobs); the members are grouped by the job that owns them.
@@ -332,9 +228,8 @@ struct svdss_bam_batch {
   BamBuf rpos, flags, scans, tmp, totals;
   // batch_front: the blocks, the inflated bytes, the record chain (pre and hdr are read by the job that follows)
   struct {
-    BamBuf comp, blks, crcb, status, buf, seg, lists, pre, hdr, gate;
-    PinBuf<2, 4096> pin;             // page-locked staging of the block tables (grows to n + n / 4 + 4096)
-    std::vector<int32_t> h_status;
+    BgzfIntake in;
+    BamBuf buf, seg, lists, pre, hdr, gate;
   } front;
   // svdss_bam_batch_front / _search: what the front half left for the search half, and the results on the host
   struct {
@@ -524,7 +419,7 @@ struct Front {
 // ------------------------------------------------------------------ the scope an entry point runs a batch in
 // The batch, its stream, the stage clock and the one way out on failure.  Entry points differ in a single thing: what else
 // a failure must let go of (the input turn, the park group, the output turn) -- `release`, set where it is owed and
-// cleared where it has been settled.  BCHK / RCHK return through fail() of the BatchRun named `run` of the calling function.
+// cleared where it has been settled.  BCHK / RCHK (bgzf_intake.h) return through fail() of the BatchRun named `run`.
 struct BatchRun {
   svdss_bam_batch* b = nullptr;
   hipStream_t st = nullptr;
@@ -568,26 +463,11 @@ struct BatchRun {
   int scan_tmp(size_t bytes) { return b->tmp.ensure(bytes + 256); }
   // exclusive sums of `rows` consecutive rows of n entries (the last entry of a row: its total)
   int scan_rows(int64_t* in, int64_t* out, int64_t n, int rows) {
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, st));
-    if (const int rc = scan_tmp(tb)) return rc;
-    for (int k = 0; k < rows; ++k) {
-      tb = b->tmp.cap;
-      HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, tb, in + (int64_t)k * n, out + (int64_t)k * n, (int)n, st));
-    }
-    return SVDSS_OK;
+    return cub_twice(b->tmp, st, [&](void* t, size_t& tb, hipStream_t q, int k) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, in + (int64_t)k * n, out + (int64_t)k * n, (int)n, q);
+    }, rows);
   }
 };
-
-#define BCHK(expr)                                                                                    \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
-      return run.fail(e_ == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);        \
-    }                                                                                                 \
-  } while (0)
-#define RCHK(expr) do { const int rc_ = (expr); if (rc_ != SVDSS_OK) return run.fail(rc_, g_svdss_hip_err); } while (0)
 
 // What every entry point that reads BGZF blocks does first: the batch's blocks up, inflated, checked; the record chain of
 // its segments; the batch's turn at the carry.  On success the records of the batch are listed (F.W / F.seg_base /

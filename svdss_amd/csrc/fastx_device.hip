@@ -44,10 +44,8 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
-#include "bam_device_internal.h"
-#include "hip_check.h"
+#include "bgzf_intake.h"
 #include "index_host.h"
-#include "inflate_dev.h"
 
 namespace {
 
@@ -307,9 +305,8 @@ struct svdss_fastx_batch {
   hipStream_t st = nullptr;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::string err;
-  FxBuf comp, blks, crcb, status, buf, hdr, tile_nl, tile_base, ls, hflag, slen, ridx, spos, tmp, hline, name_len, name_off, off, seq_len, names, reads;
-  PinBuf<2, 4096> pin;
-  std::vector<int32_t> h_status;
+  BgzfIntake in;
+  FxBuf buf, hdr, tile_nl, tile_base, ls, hflag, slen, ridx, spos, tmp, hline, name_len, name_off, off, seq_len, names, reads;
   svdss_sfs_batch_t* sfs = nullptr;
   // the last run's results on the host
   int64_t n_records = 0, total_sfs = 0, n_text = 0;
@@ -324,20 +321,6 @@ struct svdss_fastx_batch {
 };
 
 namespace {
-
-bool fx_wait_turn(svdss_fastx_stream* s, int64_t seq) {
-  std::unique_lock<std::mutex> lk(s->m);
-  s->cv.wait(lk, [&] { return s->next_seq == seq || s->failed; });
-  return !s->failed;
-}
-void fx_done_turn(svdss_fastx_stream* s, int code, const std::string& msg) {
-  {
-    std::lock_guard<std::mutex> lk(s->m);
-    if (code && !s->failed) { s->failed = code; s->err = msg; }
-    ++s->next_seq;
-  }
-  s->cv.notify_all();
-}
 
 // the scope of one run: the one way out on failure passes the turn on (or gives it up) with the failure
 struct FxRun {
@@ -357,29 +340,15 @@ struct FxRun {
       b->err = msg;
       if (b->st) (void)hipStreamSynchronize(b->st);   // (the caller recycles its buffers as soon as this returns)
     }
-    if (turn == 0) { if (fx_wait_turn(s, seq)) fx_done_turn(s, code, msg); }
-    else if (turn == 1) fx_done_turn(s, code, msg);
+    if (turn == 0) pass_turn(s, &svdss_fastx_stream::next_seq, seq, code, msg);
+    else if (turn == 1) done_turn(s, &svdss_fastx_stream::next_seq, code, msg);
     turn = 2;
     return code;
   }
   int scan(const int32_t* in, int32_t* out, int64_t n) {
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, b->st));
-    if (const int rc = b->tmp.ensure(tb + 256)) return rc;
-    tb = b->tmp.cap;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, tb, in, out, (int)n, b->st));
-    return SVDSS_OK;
+    return cub_twice(b->tmp, b->st, [&](void* t, size_t& tb, hipStream_t q, int) { return hipcub::DeviceScan::ExclusiveSum(t, tb, in, out, (int)n, q); });
   }
 };
-#define XCHK(expr)                                                                                    \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
-      return run.fail(e_ == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);        \
-    }                                                                                                 \
-  } while (0)
-#define XRCHK(expr) do { const int rc_ = (expr); if (rc_ != SVDSS_OK) return run.fail(rc_, g_svdss_hip_err); } while (0)
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -416,10 +385,10 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
   if (!s || !out || seq < 0 || n_chunks < 0 || plain_bytes < 0) return SVDSS_EINVAL;
   if (ix && (ix->device < 0 || !ix->d_blocks)) return SVDSS_ENODEV;   // (the caller's mistake: the stream's turn is not taken)
   FxRun run(s, seq);
-  if (n_chunks > 0 && (!comp || !comp_bytes || !blocks || !crc || !n_blocks)) return run.fail(SVDSS_EINVAL, "bad argument");
+  if (const char* m = bgzf_check_args(n_chunks, comp, comp_bytes, blocks, crc, n_blocks)) return run.fail(SVDSS_EINVAL, m);
   if (plain_bytes > 0 && (!plain || n_chunks > 0)) return run.fail(SVDSS_EINVAL, "bad argument");
   const int device = ix ? ix->device : s->device;
-  XCHK(hipSetDevice(device));
+  BCHK(hipSetDevice(device));
   if (!*out) {
     *out = new (std::nothrow) svdss_fastx_batch();
     if (!*out) return run.fail(SVDSS_ENOMEM, "out of memory");
@@ -427,8 +396,8 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
   }
   svdss_fastx_batch* b = run.b = *out;
   if (b->device != device) return run.fail(SVDSS_EINVAL, "batch object of another device");
-  if (!b->st) XCHK(svdss_make_stream(&b->st, "SVDSS_SEARCH_CUS"));
-  for (hipEvent_t& e : b->ev) if (!e) XCHK(hipEventCreate(&e));
+  if (!b->st) BCHK(svdss_make_stream(&b->st, "SVDSS_SEARCH_CUS"));
+  for (hipEvent_t& e : b->ev) if (!e) BCHK(hipEventCreate(&e));
   const hipStream_t st = b->st;
   b->err.clear();
   b->n_records = b->total_sfs = b->n_text = 0;
@@ -440,68 +409,27 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
   run.t_prev = std::chrono::steady_clock::now();
 
   // ---- this batch's bytes into HBM, behind the room for the carry: BGZF members inflated and checked, or plain bytes
-  int64_t total_blocks = 0, total_comp = 0, fresh = plain_bytes;
-  for (int32_t c = 0; c < n_chunks; ++c) {
-    if (comp_bytes[c] < 0 || n_blocks[c] < 0 || (n_blocks[c] > 0 && (!comp[c] || !blocks[c] || !crc[c]))) return run.fail(SVDSS_EINVAL, "bad chunk");
-    total_blocks += n_blocks[c];
-    total_comp += (comp_bytes[c] + 15) & ~(int64_t)15;
-    for (int64_t i = 0; i < n_blocks[c]; ++i) {
-      const svdss_bgzf_block_t& k = blocks[c][i];
-      if (k.coff < 0 || k.clen < 0 || k.isize < 0 || k.isize > 65536 || k.coff + k.clen > comp_bytes[c]) return run.fail(SVDSS_EINVAL, "bad block");
-      fresh += k.isize;
-    }
-  }
+  BgzfIntake& in = b->in;
+  RCHK(in.plan(n_chunks, comp, comp_bytes, blocks, crc, n_blocks));
+  const int64_t fresh = plain_bytes + in.P.inflated;
   const int64_t HEAD = (s->cap + FX_T - 1) / FX_T * FX_T + FX_T;
   if (HEAD + fresh >= ((int64_t)1 << 31) - 4 * FX_T) return run.fail(SVDSS_ERANGE, "batch too large");
-  XRCHK(b->buf.ensure((size_t)(HEAD + fresh) + 2 * FX_T));
-  XRCHK(b->hdr.ensure(sizeof(int64_t) * X_N));
+  RCHK(b->buf.ensure((size_t)(HEAD + fresh) + 2 * FX_T));
+  RCHK(b->hdr.ensure(sizeof(int64_t) * X_N));
   uint8_t* const buf = (uint8_t*)b->buf.p;
-  if (total_blocks > 0) {
-    XRCHK(b->comp.ensure((size_t)total_comp + 8192));
-    XRCHK(b->blks.ensure(sizeof(svdss_bgzf_block_t) * (size_t)(total_blocks + 1)));
-    XRCHK(b->crcb.ensure(sizeof(CrcBlk) * (size_t)(total_blocks + 1)));
-    XRCHK(b->status.ensure(sizeof(int32_t) * (size_t)(total_blocks + 2)));
-    XRCHK(b->pin.ensure((sizeof(svdss_bgzf_block_t) + sizeof(CrcBlk)) * (size_t)(total_blocks + 1) + 4096));
-    svdss_bgzf_block_t* h_blk = (svdss_bgzf_block_t*)b->pin.p;
-    CrcBlk* h_crc = (CrcBlk*)(h_blk + (total_blocks + 1));
-    int64_t k = 0, coff = 0, uoff = 0;
-    for (int32_t c = 0; c < n_chunks; ++c) {
-      if (comp_bytes[c] > 0) XCHK(hipMemcpyAsync((uint8_t*)b->comp.p + coff, comp[c], (size_t)comp_bytes[c], hipMemcpyHostToDevice, st));
-      for (int64_t i = 0; i < n_blocks[c]; ++i, ++k) {
-        h_blk[k] = blocks[c][i];
-        h_blk[k].coff += coff;
-        h_blk[k].uoff = HEAD + uoff;
-        h_crc[k] = CrcBlk{HEAD + uoff, blocks[c][i].isize, crc[c][i]};
-        uoff += blocks[c][i].isize;
-      }
-      coff += (comp_bytes[c] + 15) & ~(int64_t)15;
-    }
-    int32_t* d_status = (int32_t*)b->status.p;
-    XCHK(hipMemsetAsync(d_status, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
-    XCHK(hipMemcpyAsync(b->blks.p, h_blk, sizeof(svdss_bgzf_block_t) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    XCHK(hipMemcpyAsync(b->crcb.p, h_crc, sizeof(CrcBlk) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    XCHK(hipEventRecord(b->ev[0], st));
-    XCHK(svdss_inflate_enqueue(st, (const uint8_t*)b->comp.p, (const svdss_bgzf_block_t*)b->blks.p, total_blocks, buf, d_status));
-    XCHK(hipEventRecord(b->ev[1], st));
-    XCHK(crc_tables_ready());
-    hipLaunchKernelGGL(crc32_kernel, dim3((unsigned)total_blocks), dim3(64), 0, st, (const uint8_t*)buf, (const CrcBlk*)b->crcb.p, d_status + total_blocks);
-    XCHK(hipGetLastError());
-    b->h_status.resize((size_t)total_blocks + 2);
-    XCHK(hipMemcpyAsync(b->h_status.data(), d_status, sizeof(int32_t) * (size_t)(total_blocks + 2), hipMemcpyDeviceToHost, st));
-    XCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, b->ev[0], b->ev[1]) == hipSuccess) b->inflate_ms = ms;
-    for (int64_t i = 0; i < total_blocks; ++i)
-      if (b->h_status[(size_t)i] != 0) return run.fail(SVDSS_EIO, "BGZF inflate failed");
-    if (b->h_status[(size_t)total_blocks] != 0) return run.fail(SVDSS_EIO, "BGZF block CRC mismatch");
-  } else if (plain_bytes > 0) {
-    XCHK(hipMemcpyAsync(buf + HEAD, plain, (size_t)plain_bytes, hipMemcpyHostToDevice, st));
-    XCHK(hipStreamSynchronize(st));
+  if (plain_bytes > 0) {
+    BCHK(hipMemcpyAsync(buf + HEAD, plain, (size_t)plain_bytes, hipMemcpyHostToDevice, st));
+    BCHK(hipStreamSynchronize(st));
+  } else {
+    RCHK(in.enqueue(st, b->ev[0], b->ev[1], buf, HEAD));
+    RCHK(in.enqueue_status_download(st));
+    BCHK(hipStreamSynchronize(st));
+    RCHK(in.verdict(b->ev[0], b->ev[1], b->inflate_ms));
   }
   run.lap(0);   // buffers, upload, inflate, CRC
 
   // ---- this batch's turn in file order: carry in, the lines, the shape, the line the proved records end at, carry out
-  if (!fx_wait_turn(s, seq)) { run.turn = 2; return run.fail(s->failed, s->err); }
+  if (!wait_turn(s, &svdss_fastx_stream::next_seq, seq)) { run.turn = 2; return run.fail(s->failed, s->err); }
   run.turn = 1;
   run.lap(1);
   auto text_down = [&](int64_t from, int64_t to) -> hipError_t {   // buf[from, to) -> h_text
@@ -512,10 +440,10 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
   };
   const int64_t hi = HEAD + fresh;
   if (s->fallen) {
-    XCHK(text_down(HEAD, hi));
+    BCHK(text_down(HEAD, hi));
     b->declined = 1;
     b->n_text = fresh;
-    fx_done_turn(s, SVDSS_OK, "");
+    done_turn(s, &svdss_fastx_stream::next_seq, SVDSS_OK, "");
     run.turn = 2;
     run.lap(2);
     return SVDSS_OK;
@@ -524,11 +452,11 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
   const int64_t lo = HEAD - carry_len, base = lo & ~(int64_t)(FX_T - 1);
   const int64_t N = hi - lo;
   b->n_text = N;
-  if (carry_len > 0) XCHK(hipMemcpyAsync(buf + lo, s->carry.data(), (size_t)carry_len, hipMemcpyHostToDevice, st));
+  if (carry_len > 0) BCHK(hipMemcpyAsync(buf + lo, s->carry.data(), (size_t)carry_len, hipMemcpyHostToDevice, st));
   if (s->shape == 0 && N > 0) {
     uint8_t c0 = 0;
-    XCHK(hipMemcpyAsync(&c0, buf + lo, 1, hipMemcpyDeviceToHost, st));
-    XCHK(hipStreamSynchronize(st));
+    BCHK(hipMemcpyAsync(&c0, buf + lo, 1, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
     s->shape = c0 == '>' || c0 == '@' ? (int)c0 : -1;
   }
   int64_t L = 0, carry_at = 0, n_rec = 0, total_syms = 0;
@@ -536,52 +464,52 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
   bool declined = s->shape < 0;
   const bool parsed = N > 0 && !declined;
   if (parsed) {
-    XRCHK(b->tile_nl.ensure(sizeof(int32_t) * (size_t)(n_tiles + 1)));
-    XRCHK(b->tile_base.ensure(sizeof(int32_t) * (size_t)(n_tiles + 1)));
+    RCHK(b->tile_nl.ensure(sizeof(int32_t) * (size_t)(n_tiles + 1)));
+    RCHK(b->tile_base.ensure(sizeof(int32_t) * (size_t)(n_tiles + 1)));
     unsigned long long h0[X_N] = {X_NONE, 0, X_NONE, 0, 0, 0, 0, 0};
-    XCHK(hipMemcpyAsync(b->hdr.p, h0, sizeof h0, hipMemcpyHostToDevice, st));
-    XCHK(hipMemsetAsync((int32_t*)b->tile_nl.p + n_tiles, 0, sizeof(int32_t), st));
-    XCHK(hipEventRecord(b->ev[2], st));
+    BCHK(hipMemcpyAsync(b->hdr.p, h0, sizeof h0, hipMemcpyHostToDevice, st));
+    BCHK(hipMemsetAsync((int32_t*)b->tile_nl.p + n_tiles, 0, sizeof(int32_t), st));
+    BCHK(hipEventRecord(b->ev[2], st));
     hipLaunchKernelGGL(fx_tile_kernel, dim3((unsigned)n_tiles), dim3(FX_TPB), 0, st, (const uint8_t*)buf, base, lo, hi, (int32_t*)b->tile_nl.p,
                        (unsigned long long*)b->hdr.p);
-    XCHK(hipGetLastError());
-    XRCHK(run.scan((const int32_t*)b->tile_nl.p, (int32_t*)b->tile_base.p, n_tiles + 1));
+    BCHK(hipGetLastError());
+    RCHK(run.scan((const int32_t*)b->tile_nl.p, (int32_t*)b->tile_base.p, n_tiles + 1));
     int32_t n_nl = 0;
     unsigned long long h1[X_N];
-    XCHK(hipMemcpyAsync(&n_nl, (int32_t*)b->tile_base.p + n_tiles, sizeof n_nl, hipMemcpyDeviceToHost, st));
-    XCHK(hipMemcpyAsync(h1, b->hdr.p, sizeof h1, hipMemcpyDeviceToHost, st));
-    XCHK(hipStreamSynchronize(st));
+    BCHK(hipMemcpyAsync(&n_nl, (int32_t*)b->tile_base.p + n_tiles, sizeof n_nl, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(h1, b->hdr.p, sizeof h1, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
     const bool open_line = h1[X_LASTNL] == 0;     // the text ends inside a line
     L = (int64_t)n_nl + (open_line ? 1 : 0);
     const int64_t Lc = is_last ? L : n_nl;
-    for (FxBuf* q : {&b->ls, &b->hflag, &b->slen, &b->ridx, &b->spos}) XRCHK(q->ensure(sizeof(int32_t) * (size_t)(L + 2)));
+    for (FxBuf* q : {&b->ls, &b->hflag, &b->slen, &b->ridx, &b->spos}) RCHK(q->ensure(sizeof(int32_t) * (size_t)(L + 2)));
     int32_t* ls = (int32_t*)b->ls.p;
     hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)n_tiles), dim3(FX_TPB), 0, st, (const uint8_t*)buf, base, lo, hi, (const int32_t*)b->tile_base.p, ls);
-    XCHK(hipGetLastError());
+    BCHK(hipGetLastError());
     if (open_line) {   // (so that every line i is text[ls[i], ls[i + 1] - 1))
       b->sentinel = (int32_t)(N + 1);
-      XCHK(hipMemcpyAsync(ls + L, &b->sentinel, sizeof(int32_t), hipMemcpyHostToDevice, st));
+      BCHK(hipMemcpyAsync(ls + L, &b->sentinel, sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
     FxP P;
     P.text = buf + lo; P.ls = ls; P.L = (int32_t)L; P.Lc = (int32_t)Lc; P.N = (int32_t)N;
     P.fastq = s->shape == '@'; P.is_last = is_last ? 1 : 0;
     P.hflag = (int32_t*)b->hflag.p; P.slen = (int32_t*)b->slen.p; P.hdr = (unsigned long long*)b->hdr.p;
     hipLaunchKernelGGL(fx_classify_kernel, dim3(blocks_for(L + 1)), dim3(256), 0, st, P);
-    XCHK(hipGetLastError());
+    BCHK(hipGetLastError());
     if (!P.fastq) {
       hipLaunchKernelGGL(fx_limit_kernel, dim3(blocks_for(L + 1)), dim3(256), 0, st, P);
-      XCHK(hipGetLastError());
+      BCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(fx_mask_kernel, dim3(blocks_for(L + 1)), dim3(256), 0, st, P);
-    XCHK(hipGetLastError());
-    XRCHK(run.scan(P.hflag, (int32_t*)b->ridx.p, L + 1));
-    XRCHK(run.scan(P.slen, (int32_t*)b->spos.p, L + 1));
-    XCHK(hipEventRecord(b->ev[3], st));
+    BCHK(hipGetLastError());
+    RCHK(run.scan(P.hflag, (int32_t*)b->ridx.p, L + 1));
+    RCHK(run.scan(P.slen, (int32_t*)b->spos.p, L + 1));
+    BCHK(hipEventRecord(b->ev[3], st));
     int32_t tot[2] = {0, 0};
-    XCHK(hipMemcpyAsync(&tot[0], (int32_t*)b->ridx.p + L, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    XCHK(hipMemcpyAsync(&tot[1], (int32_t*)b->spos.p + L, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    XCHK(hipMemcpyAsync(h1, b->hdr.p, sizeof h1, hipMemcpyDeviceToHost, st));
-    XCHK(hipStreamSynchronize(st));
+    BCHK(hipMemcpyAsync(&tot[0], (int32_t*)b->ridx.p + L, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&tot[1], (int32_t*)b->spos.p + L, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(h1, b->hdr.p, sizeof h1, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
     n_rec = tot[0]; total_syms = tot[1];
     carry_at = (int64_t)h1[X_CARRY];
     declined = h1[X_BADLINE] != X_NONE;
@@ -603,10 +531,10 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
     } else {
       s->carry.clear();
     }
-    XCHK(e);
+    BCHK(e);
   }
   b->declined = declined ? 1 : 0;
-  fx_done_turn(s, SVDSS_OK, "");
+  done_turn(s, &svdss_fastx_stream::next_seq, SVDSS_OK, "");
   run.turn = 2;
   run.lap(2);   // the turn
 
@@ -617,43 +545,43 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
     b->h_counts.clear(); b->h_qs.clear(); b->h_len.clear(); b->h_off.clear(); b->h_reads.clear();
   } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
   if (n_rec > 0) {
-    XRCHK(b->hline.ensure(sizeof(int32_t) * (size_t)n_rec));
-    XRCHK(b->name_len.ensure(sizeof(int32_t) * (size_t)(n_rec + 1)));
-    XRCHK(b->name_off.ensure(sizeof(int32_t) * (size_t)(n_rec + 1)));
-    XRCHK(b->seq_len.ensure(sizeof(int32_t) * (size_t)n_rec));
-    XRCHK(b->off.ensure(sizeof(int64_t) * (size_t)(n_rec + 1)));
-    XRCHK(b->reads.ensure((size_t)total_syms + 4096));
+    RCHK(b->hline.ensure(sizeof(int32_t) * (size_t)n_rec));
+    RCHK(b->name_len.ensure(sizeof(int32_t) * (size_t)(n_rec + 1)));
+    RCHK(b->name_off.ensure(sizeof(int32_t) * (size_t)(n_rec + 1)));
+    RCHK(b->seq_len.ensure(sizeof(int32_t) * (size_t)n_rec));
+    RCHK(b->off.ensure(sizeof(int64_t) * (size_t)(n_rec + 1)));
+    RCHK(b->reads.ensure((size_t)total_syms + 4096));
     FxR R;
     R.text = buf + lo; R.ls = (const int32_t*)b->ls.p; R.hflag = (const int32_t*)b->hflag.p; R.ridx = (const int32_t*)b->ridx.p;
     R.spos = (const int32_t*)b->spos.p; R.L = (int32_t)L; R.n_rec = (int32_t)n_rec;
     R.hline = (int32_t*)b->hline.p; R.name_len = (int32_t*)b->name_len.p; R.off = (int64_t*)b->off.p;
-    XCHK(hipEventRecord(b->ev[4], st));
+    BCHK(hipEventRecord(b->ev[4], st));
     hipLaunchKernelGGL(fx_records_kernel, dim3(blocks_for(L + 1)), dim3(256), 0, st, R);
-    XCHK(hipGetLastError());
-    XRCHK(run.scan(R.name_len, (int32_t*)b->name_off.p, n_rec + 1));
-    XCHK(hipMemcpyAsync(b->h_name_off.data(), b->name_off.p, sizeof(int32_t) * (size_t)(n_rec + 1), hipMemcpyDeviceToHost, st));
-    XCHK(hipStreamSynchronize(st));
+    BCHK(hipGetLastError());
+    RCHK(run.scan(R.name_len, (int32_t*)b->name_off.p, n_rec + 1));
+    BCHK(hipMemcpyAsync(b->h_name_off.data(), b->name_off.p, sizeof(int32_t) * (size_t)(n_rec + 1), hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
     const int64_t name_bytes = b->h_name_off[(size_t)n_rec];
-    XRCHK(b->names.ensure((size_t)name_bytes + 16));
+    RCHK(b->names.ensure((size_t)name_bytes + 16));
     hipLaunchKernelGGL(fx_names_kernel, dim3(blocks_for(n_rec)), dim3(256), 0, st, R, (const int32_t*)b->name_off.p, (char*)b->names.p, (int32_t*)b->seq_len.p);
-    XCHK(hipGetLastError());
+    BCHK(hipGetLastError());
     if (total_syms > 0) {
       hipLaunchKernelGGL(fx_gather_kernel, dim3((unsigned)n_tiles), dim3(FX_TPB), 0, st, (const uint8_t*)buf, base, lo, hi, (const int32_t*)b->tile_base.p,
                          (const int32_t*)b->ls.p, (const int32_t*)b->slen.p, (const int32_t*)b->spos.p, (const unsigned long long*)b->hdr.p, (uint8_t*)b->reads.p);
-      XCHK(hipGetLastError());
+      BCHK(hipGetLastError());
     }
-    XCHK(hipEventRecord(b->ev[5], st));
+    BCHK(hipEventRecord(b->ev[5], st));
     try {
       b->h_names.resize((size_t)name_bytes);
       if (b->parse_only) { b->h_off.resize((size_t)n_rec + 1); b->h_reads.resize((size_t)total_syms); }
     } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
-    if (name_bytes > 0) XCHK(hipMemcpyAsync(b->h_names.data(), b->names.p, (size_t)name_bytes, hipMemcpyDeviceToHost, st));
-    XCHK(hipMemcpyAsync(b->h_seq_len.data(), b->seq_len.p, sizeof(int32_t) * (size_t)n_rec, hipMemcpyDeviceToHost, st));
+    if (name_bytes > 0) BCHK(hipMemcpyAsync(b->h_names.data(), b->names.p, (size_t)name_bytes, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(b->h_seq_len.data(), b->seq_len.p, sizeof(int32_t) * (size_t)n_rec, hipMemcpyDeviceToHost, st));
     if (b->parse_only) {
-      XCHK(hipMemcpyAsync(b->h_off.data(), b->off.p, sizeof(int64_t) * (size_t)(n_rec + 1), hipMemcpyDeviceToHost, st));
-      if (total_syms > 0) XCHK(hipMemcpyAsync(b->h_reads.data(), b->reads.p, (size_t)total_syms, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->h_off.data(), b->off.p, sizeof(int64_t) * (size_t)(n_rec + 1), hipMemcpyDeviceToHost, st));
+      if (total_syms > 0) BCHK(hipMemcpyAsync(b->h_reads.data(), b->reads.p, (size_t)total_syms, hipMemcpyDeviceToHost, st));
     }
-    XCHK(hipStreamSynchronize(st));
+    BCHK(hipStreamSynchronize(st));
   }
   if (parsed) {
     float ms = 0.f;
@@ -674,13 +602,13 @@ extern "C" int svdss_fastx_batch_run(svdss_fastx_stream_t* s, int64_t seq, int32
       b->h_counts.resize((size_t)n_rec); b->h_qs.resize((size_t)b->total_sfs); b->h_len.resize((size_t)b->total_sfs);
     } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
     void *d_counts = nullptr, *d_qs = nullptr, *d_len = nullptr;
-    XRCHK(svdss_sfs_batch_device_ptrs(b->sfs, &d_counts, &d_qs, &d_len, nullptr));
-    XCHK(hipMemcpyAsync(b->h_counts.data(), d_counts, sizeof(int64_t) * (size_t)n_rec, hipMemcpyDeviceToHost, st));
+    RCHK(svdss_sfs_batch_device_ptrs(b->sfs, &d_counts, &d_qs, &d_len, nullptr));
+    BCHK(hipMemcpyAsync(b->h_counts.data(), d_counts, sizeof(int64_t) * (size_t)n_rec, hipMemcpyDeviceToHost, st));
     if (b->total_sfs > 0) {
-      XCHK(hipMemcpyAsync(b->h_qs.data(), d_qs, sizeof(int32_t) * (size_t)b->total_sfs, hipMemcpyDeviceToHost, st));
-      XCHK(hipMemcpyAsync(b->h_len.data(), d_len, sizeof(int32_t) * (size_t)b->total_sfs, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->h_qs.data(), d_qs, sizeof(int32_t) * (size_t)b->total_sfs, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->h_len.data(), d_len, sizeof(int32_t) * (size_t)b->total_sfs, hipMemcpyDeviceToHost, st));
     }
-    XCHK(hipStreamSynchronize(st));
+    BCHK(hipStreamSynchronize(st));
     run.lap(6);   // results down
   }
   return SVDSS_OK;

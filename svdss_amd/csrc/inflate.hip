@@ -21,7 +21,7 @@
 //     by side.  (See the comment above the symbol loop; rounds of 64 bits -- rounds 2-3's engine, every lane decoding the
 //     symbol that would start at its bit offset, the chain found by pointer doubling -- remain for what a pass cannot
 //     take, the tail of a stream, and data that does not resynchronise.)
-// 15.4 KB of LDS per block.  No CRC check here (bam_device.hip's crc32_kernel, or the caller on the host, checks the BGZF
+// 15.4 KB of LDS per block.  No CRC check here (bgzf_intake.h's crc32_kernel, or the caller on the host, checks the BGZF
 // footers).  Measured on 16,384 blocks of 64 KB (tools/inflate_probe.py, GB/s of output; rounds 2-3's kernel in
 // brackets): packed bases + random qualities zlib level 1: 82 (23.7), level 6: 88 (25); binned qualities 75 (35); skewed
 // 94-value qualities 79 (27); literals only, as csrc/deflate.hip writes them: 81 (42); text 333 (335).

@@ -39,9 +39,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
-#include "bam_device_internal.h"
-#include "hip_check.h"
-#include "inflate_dev.h"
+#include "bgzf_intake.h"
 #include "ref_dev.h"
 #include "ref_pieces.h"
 
@@ -241,10 +239,10 @@ using RsBuf = DevBuf<3, 4096>;
 struct RsSlot {
   hipStream_t st = nullptr;
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  RsBuf comp, blks, crcb, status, text, hdr, tile_kind, tile_m, tile_rest, tile_seg, tile_hdrs, tile_in, tile_kept, tile_off, tile_hb, tmp;
+  BgzfIntake in;
+  RsBuf text, hdr, tile_kind, tile_m, tile_rest, tile_seg, tile_hdrs, tile_in, tile_kept, tile_off, tile_hb, tmp;
   RsBuf hdr_pos, hdr_out, ent_pos, ent_len, ent_term, ent_off, side;
-  PinBuf<2, 4096> pin;
-  std::vector<int32_t> h_status, h_ent_len, h_ent_term, h_ent_pos, h_hdr_out;
+  std::vector<int32_t> h_ent_len, h_ent_term, h_ent_pos, h_hdr_out;
   std::vector<uint8_t> h_side;
   ~RsSlot() {
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -341,31 +339,14 @@ struct RsRun {
     return code;
   }
   int scan_sum(const int32_t* in, int32_t* out, int64_t n) {
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, slot->st));
-    if (const int rc = slot->tmp.ensure(tb + 256)) return rc;
-    tb = slot->tmp.cap;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(slot->tmp.p, tb, in, out, (int)n, slot->st));
-    return SVDSS_OK;
+    return cub_twice(slot->tmp, slot->st, [&](void* t, size_t& tb, hipStream_t q, int) { return hipcub::DeviceScan::ExclusiveSum(t, tb, in, out, (int)n, q); });
   }
   int scan_max(const int32_t* in, int32_t* out, int64_t n) {
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceScan::InclusiveScan(nullptr, tb, in, out, hipcub::Max(), (int)n, slot->st));
-    if (const int rc = slot->tmp.ensure(tb + 256)) return rc;
-    tb = slot->tmp.cap;
-    HIPCHK(hipcub::DeviceScan::InclusiveScan(slot->tmp.p, tb, in, out, hipcub::Max(), (int)n, slot->st));
-    return SVDSS_OK;
+    return cub_twice(slot->tmp, slot->st, [&](void* t, size_t& tb, hipStream_t q, int) {
+      return hipcub::DeviceScan::InclusiveScan(t, tb, in, out, hipcub::Max(), (int)n, q);
+    });
   }
 };
-#define RSCHK(expr)                                                                                    \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      g_svdss_hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
-      return run.fail(e_ == hipErrorOutOfMemory ? SVDSS_ENOMEM : SVDSS_EHIP, g_svdss_hip_err);        \
-    }                                                                                                 \
-  } while (0)
-#define RSRCHK(expr) do { const int rc_ = (expr); if (rc_ != SVDSS_OK) return run.fail(rc_, g_svdss_hip_err); } while (0)
 
 // (with the stream's lock held) a complete header line: one more record whose bases begin at `out`; false: declined
 bool rs_record(svdss_ref_stream* s, const char* line, size_t len, int64_t out, int64_t at) {
@@ -414,81 +395,40 @@ extern "C" int svdss_ref_stream_batch(svdss_ref_stream_t* s, int64_t seq, int32_
     if (s->declined) return SVDSS_OK;
     if (!s->idle.empty()) { run.slot = std::move(s->idle.back()); s->idle.pop_back(); }
   }
-  if (n_chunks > 0 && (!comp || !comp_bytes || !blocks || !crc || !n_blocks)) return run.fail(SVDSS_EINVAL, "bad argument");
+  if (const char* m = bgzf_check_args(n_chunks, comp, comp_bytes, blocks, crc, n_blocks)) return run.fail(SVDSS_EINVAL, m);
   if (plain_bytes > 0 && (!plain || n_chunks > 0)) return run.fail(SVDSS_EINVAL, "bad argument");
-  RSCHK(hipSetDevice(s->device));
+  BCHK(hipSetDevice(s->device));
   if (!run.slot) {
     run.slot.reset(new (std::nothrow) RsSlot());
     if (!run.slot) return run.fail(SVDSS_ENOMEM, "out of memory");
   }
   RsSlot* b = run.slot.get();
-  if (!b->st) RSCHK(svdss_make_stream(&b->st, nullptr));
-  for (hipEvent_t& e : b->ev) if (!e) RSCHK(hipEventCreate(&e));
+  if (!b->st) BCHK(svdss_make_stream(&b->st, nullptr));
+  for (hipEvent_t& e : b->ev) if (!e) BCHK(hipEventCreate(&e));
   const hipStream_t st = b->st;
 
   // ---- this batch's bytes into HBM: BGZF members inflated and checked, or plain bytes
-  int64_t total_blocks = 0, total_comp = 0, N = plain_bytes;
-  for (int32_t c = 0; c < n_chunks; ++c) {
-    if (comp_bytes[c] < 0 || n_blocks[c] < 0 || (n_blocks[c] > 0 && (!comp[c] || !blocks[c] || !crc[c]))) return run.fail(SVDSS_EINVAL, "bad chunk");
-    total_blocks += n_blocks[c];
-    total_comp += (comp_bytes[c] + 15) & ~(int64_t)15;
-    for (int64_t i = 0; i < n_blocks[c]; ++i) {
-      const svdss_bgzf_block_t& k = blocks[c][i];
-      if (k.coff < 0 || k.clen < 0 || k.isize < 0 || k.isize > 65536 || k.coff + k.clen > comp_bytes[c]) return run.fail(SVDSS_EINVAL, "bad block");
-      N += k.isize;
-    }
-  }
+  BgzfIntake& in = b->in;
+  RCHK(in.plan(n_chunks, comp, comp_bytes, blocks, crc, n_blocks));
+  const int64_t N = plain_bytes + in.P.inflated;
   if (N >= ((int64_t)1 << 30)) return run.fail(SVDSS_ERANGE, "batch too large");
-  RSRCHK(b->text.ensure((size_t)N + 2 * RS_T));
-  RSRCHK(b->hdr.ensure(sizeof(unsigned long long) * RH_N));
+  RCHK(b->text.ensure((size_t)N + 2 * RS_T));
+  RCHK(b->hdr.ensure(sizeof(unsigned long long) * RH_N));
   uint8_t* const buf = (uint8_t*)b->text.p;
   double inflate_ms = 0, parse_ms = 0;
-  if (total_blocks > 0) {
-    RSRCHK(b->comp.ensure((size_t)total_comp + 8192));
-    RSRCHK(b->blks.ensure(sizeof(svdss_bgzf_block_t) * (size_t)(total_blocks + 1)));
-    RSRCHK(b->crcb.ensure(sizeof(CrcBlk) * (size_t)(total_blocks + 1)));
-    RSRCHK(b->status.ensure(sizeof(int32_t) * (size_t)(total_blocks + 2)));
-    RSRCHK(b->pin.ensure((sizeof(svdss_bgzf_block_t) + sizeof(CrcBlk)) * (size_t)(total_blocks + 1) + 4096));
-    svdss_bgzf_block_t* h_blk = (svdss_bgzf_block_t*)b->pin.p;
-    CrcBlk* h_crc = (CrcBlk*)(h_blk + (total_blocks + 1));
-    int64_t k = 0, coff = 0, uoff = 0;
-    for (int32_t c = 0; c < n_chunks; ++c) {
-      if (comp_bytes[c] > 0) RSCHK(hipMemcpyAsync((uint8_t*)b->comp.p + coff, comp[c], (size_t)comp_bytes[c], hipMemcpyHostToDevice, st));
-      for (int64_t i = 0; i < n_blocks[c]; ++i, ++k) {
-        h_blk[k] = blocks[c][i];
-        h_blk[k].coff += coff;
-        h_blk[k].uoff = uoff;
-        h_crc[k] = CrcBlk{uoff, blocks[c][i].isize, crc[c][i]};
-        uoff += blocks[c][i].isize;
-      }
-      coff += (comp_bytes[c] + 15) & ~(int64_t)15;
-    }
-    int32_t* d_status = (int32_t*)b->status.p;
-    RSCHK(hipMemsetAsync(d_status, 0, sizeof(int32_t) * (size_t)(total_blocks + 2), st));
-    RSCHK(hipMemcpyAsync(b->blks.p, h_blk, sizeof(svdss_bgzf_block_t) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    RSCHK(hipMemcpyAsync(b->crcb.p, h_crc, sizeof(CrcBlk) * (size_t)total_blocks, hipMemcpyHostToDevice, st));
-    RSCHK(hipEventRecord(b->ev[0], st));
-    RSCHK(svdss_inflate_enqueue(st, (const uint8_t*)b->comp.p, (const svdss_bgzf_block_t*)b->blks.p, total_blocks, buf, d_status));
-    RSCHK(hipEventRecord(b->ev[1], st));
-    RSCHK(crc_tables_ready());
-    hipLaunchKernelGGL(crc32_kernel, dim3((unsigned)total_blocks), dim3(64), 0, st, (const uint8_t*)buf, (const CrcBlk*)b->crcb.p, d_status + total_blocks);
-    RSCHK(hipGetLastError());
-    b->h_status.resize((size_t)total_blocks + 2);
-    RSCHK(hipMemcpyAsync(b->h_status.data(), d_status, sizeof(int32_t) * (size_t)(total_blocks + 2), hipMemcpyDeviceToHost, st));
-    RSCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, b->ev[0], b->ev[1]) == hipSuccess) inflate_ms = ms;
-    for (int64_t i = 0; i < total_blocks; ++i)
-      if (b->h_status[(size_t)i] != 0) return run.fail(SVDSS_EIO, "BGZF inflate failed", SVDSS_REF_IO);
-    if (b->h_status[(size_t)total_blocks] != 0) return run.fail(SVDSS_EIO, "BGZF block CRC mismatch", SVDSS_REF_IO);
-  } else if (plain_bytes > 0) {
-    RSCHK(hipMemcpyAsync(buf, plain, (size_t)plain_bytes, hipMemcpyHostToDevice, st));
-    RSCHK(hipStreamSynchronize(st));
+  if (plain_bytes > 0) {
+    BCHK(hipMemcpyAsync(buf, plain, (size_t)plain_bytes, hipMemcpyHostToDevice, st));
+    BCHK(hipStreamSynchronize(st));
+  } else {
+    RCHK(in.enqueue(st, b->ev[0], b->ev[1], buf, 0));
+    RCHK(in.enqueue_status_download(st));
+    BCHK(hipStreamSynchronize(st));
+    if (const int rc = in.verdict(b->ev[0], b->ev[1], inflate_ms)) return run.fail(rc, g_svdss_hip_err, SVDSS_REF_IO);
   }
   // the segment the batch's output goes to: never more bytes than its text
   RsSegment seg;
   if (N > 0) {
-    RSCHK(hipMalloc(&seg.d, (size_t)N + 32));
+    BCHK(hipMalloc(&seg.d, (size_t)N + 32));
     seg.h.reset(new (std::nothrow) uint8_t[(size_t)N]);
   }
   struct SegGuard { RsSegment& g; ~SegGuard() { if (g.d) (void)hipFree(g.d); } } guard{seg};
@@ -502,28 +442,28 @@ extern "C" int svdss_ref_stream_batch(svdss_ref_stream_t* s, int64_t seq, int32_
   bool in_header = s->in_header, als = s->als;
   if (N > 0) {
     for (RsBuf* q : {&b->tile_kind, &b->tile_m, &b->tile_rest, &b->tile_seg, &b->tile_hdrs, &b->tile_in, &b->tile_kept, &b->tile_off, &b->tile_hb})
-      RSRCHK(q->ensure(sizeof(int32_t) * (size_t)(n_tiles + 2)));
+      RCHK(q->ensure(sizeof(int32_t) * (size_t)(n_tiles + 2)));
     unsigned long long h0[RH_N] = {RS_NONE, 0};
-    RSCHK(hipMemcpyAsync(b->hdr.p, h0, sizeof h0, hipMemcpyHostToDevice, st));
-    RSCHK(hipMemsetAsync((int32_t*)b->tile_hdrs.p + n_tiles, 0, sizeof(int32_t), st));
-    RSCHK(hipEventRecord(b->ev[2], st));
+    BCHK(hipMemcpyAsync(b->hdr.p, h0, sizeof h0, hipMemcpyHostToDevice, st));
+    BCHK(hipMemsetAsync((int32_t*)b->tile_hdrs.p + n_tiles, 0, sizeof(int32_t), st));
+    BCHK(hipEventRecord(b->ev[2], st));
     hipLaunchKernelGGL(rs_tile_kernel, dim3((unsigned)n_tiles), dim3(RS_TPB), 0, st, (const uint8_t*)buf, N, als0, first, (int32_t*)b->tile_kind.p,
                        (int32_t*)b->tile_rest.p, (int32_t*)b->tile_seg.p, (int32_t*)b->tile_hdrs.p, (unsigned long long*)b->hdr.p);
-    RSCHK(hipGetLastError());
-    RSRCHK(run.scan_max((const int32_t*)b->tile_kind.p, (int32_t*)b->tile_m.p, n_tiles));
+    BCHK(hipGetLastError());
+    RCHK(run.scan_max((const int32_t*)b->tile_kind.p, (int32_t*)b->tile_m.p, n_tiles));
     hipLaunchKernelGGL(rs_tiles_kernel, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0, st, (const int32_t*)b->tile_m.p, (const int32_t*)b->tile_rest.p,
                        (const int32_t*)b->tile_seg.p, (int32_t)n_tiles, seed, (int32_t*)b->tile_in.p, (int32_t*)b->tile_kept.p);
-    RSCHK(hipGetLastError());
-    RSRCHK(run.scan_sum((const int32_t*)b->tile_kept.p, (int32_t*)b->tile_off.p, n_tiles + 1));
-    RSRCHK(run.scan_sum((const int32_t*)b->tile_hdrs.p, (int32_t*)b->tile_hb.p, n_tiles + 1));
-    RSCHK(hipEventRecord(b->ev[3], st));
+    BCHK(hipGetLastError());
+    RCHK(run.scan_sum((const int32_t*)b->tile_kept.p, (int32_t*)b->tile_off.p, n_tiles + 1));
+    RCHK(run.scan_sum((const int32_t*)b->tile_hdrs.p, (int32_t*)b->tile_hb.p, n_tiles + 1));
+    BCHK(hipEventRecord(b->ev[3], st));
     int32_t m_last = -1;
     unsigned long long h1[RH_N];
-    RSCHK(hipMemcpyAsync(&kept, (int32_t*)b->tile_off.p + n_tiles, sizeof kept, hipMemcpyDeviceToHost, st));
-    RSCHK(hipMemcpyAsync(&n_hdr, (int32_t*)b->tile_hb.p + n_tiles, sizeof n_hdr, hipMemcpyDeviceToHost, st));
-    RSCHK(hipMemcpyAsync(&m_last, (int32_t*)b->tile_m.p + (n_tiles - 1), sizeof m_last, hipMemcpyDeviceToHost, st));
-    RSCHK(hipMemcpyAsync(h1, b->hdr.p, sizeof h1, hipMemcpyDeviceToHost, st));
-    RSCHK(hipStreamSynchronize(st));
+    BCHK(hipMemcpyAsync(&kept, (int32_t*)b->tile_off.p + n_tiles, sizeof kept, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&n_hdr, (int32_t*)b->tile_hb.p + n_tiles, sizeof n_hdr, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(&m_last, (int32_t*)b->tile_m.p + (n_tiles - 1), sizeof m_last, hipMemcpyDeviceToHost, st));
+    BCHK(hipMemcpyAsync(h1, b->hdr.p, sizeof h1, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, b->ev[2], b->ev[3]) == hipSuccess) parse_ms += ms;
     if (h1[RH_BAD] != RS_NONE) {
@@ -539,44 +479,44 @@ extern "C" int svdss_ref_stream_batch(svdss_ref_stream_t* s, int64_t seq, int32_
     in_header = m_last < 0 ? s->in_header : (m_last & 1) != 0;
     als = h1[RH_LASTNL] != 0;
     const int32_t n_ent = seed + n_hdr;
-    RSRCHK(b->hdr_pos.ensure(sizeof(int32_t) * (size_t)(n_hdr + 1)));
-    RSRCHK(b->hdr_out.ensure(sizeof(int32_t) * (size_t)(n_hdr + 1)));
-    RSCHK(hipEventRecord(b->ev[4], st));
+    RCHK(b->hdr_pos.ensure(sizeof(int32_t) * (size_t)(n_hdr + 1)));
+    RCHK(b->hdr_out.ensure(sizeof(int32_t) * (size_t)(n_hdr + 1)));
+    BCHK(hipEventRecord(b->ev[4], st));
     hipLaunchKernelGGL(rs_gather_kernel, dim3((unsigned)n_tiles), dim3(RS_TPB), 0, st, (const uint8_t*)buf, N, als0, (const int32_t*)b->tile_in.p,
                        (const int32_t*)b->tile_off.p, (const int32_t*)b->tile_hb.p, (uint8_t*)seg.d, (int32_t*)b->hdr_pos.p, (int32_t*)b->hdr_out.p);
-    RSCHK(hipGetLastError());
+    BCHK(hipGetLastError());
     int32_t side_bytes = 0;
     if (n_ent > 0) {
-      for (RsBuf* q : {&b->ent_pos, &b->ent_len, &b->ent_term, &b->ent_off}) RSRCHK(q->ensure(sizeof(int32_t) * (size_t)(n_ent + 2)));
+      for (RsBuf* q : {&b->ent_pos, &b->ent_len, &b->ent_term, &b->ent_off}) RCHK(q->ensure(sizeof(int32_t) * (size_t)(n_ent + 2)));
       const int32_t limit = (int32_t)std::min<int64_t>(s->cap + 1, N);
       hipLaunchKernelGGL(rs_hdr_len_kernel, dim3((unsigned)(n_ent + 1)), dim3(64), 0, st, (const uint8_t*)buf, N, (const int32_t*)b->hdr_pos.p, seed, n_ent,
                          limit, (int32_t*)b->ent_pos.p, (int32_t*)b->ent_len.p, (int32_t*)b->ent_term.p);
-      RSCHK(hipGetLastError());
-      RSRCHK(run.scan_sum((const int32_t*)b->ent_len.p, (int32_t*)b->ent_off.p, (int64_t)n_ent + 1));
-      RSCHK(hipEventRecord(b->ev[5], st));
-      RSCHK(hipMemcpyAsync(&side_bytes, (int32_t*)b->ent_off.p + n_ent, sizeof side_bytes, hipMemcpyDeviceToHost, st));
-      RSCHK(hipStreamSynchronize(st));
+      BCHK(hipGetLastError());
+      RCHK(run.scan_sum((const int32_t*)b->ent_len.p, (int32_t*)b->ent_off.p, (int64_t)n_ent + 1));
+      BCHK(hipEventRecord(b->ev[5], st));
+      BCHK(hipMemcpyAsync(&side_bytes, (int32_t*)b->ent_off.p + n_ent, sizeof side_bytes, hipMemcpyDeviceToHost, st));
+      BCHK(hipStreamSynchronize(st));
       if (hipEventElapsedTime(&ms, b->ev[4], b->ev[5]) == hipSuccess) parse_ms += ms;
-      RSRCHK(b->side.ensure((size_t)side_bytes + 16));
-      RSCHK(hipEventRecord(b->ev[6], st));
+      RCHK(b->side.ensure((size_t)side_bytes + 16));
+      BCHK(hipEventRecord(b->ev[6], st));
       hipLaunchKernelGGL(rs_hdr_copy_kernel, dim3((unsigned)n_ent), dim3(64), 0, st, (const uint8_t*)buf, (const int32_t*)b->ent_pos.p,
                          (const int32_t*)b->ent_off.p, (uint8_t*)b->side.p);
-      RSCHK(hipGetLastError());
-      RSCHK(hipEventRecord(b->ev[7], st));
+      BCHK(hipGetLastError());
+      BCHK(hipEventRecord(b->ev[7], st));
       try {
         b->h_ent_len.resize((size_t)n_ent); b->h_ent_term.resize((size_t)n_ent); b->h_ent_pos.resize((size_t)n_ent);
         b->h_hdr_out.resize((size_t)n_hdr + 1); b->h_side.resize((size_t)side_bytes + 1);
       } catch (...) { return run.fail(SVDSS_ENOMEM, "out of memory"); }
-      RSCHK(hipMemcpyAsync(b->h_ent_len.data(), b->ent_len.p, sizeof(int32_t) * (size_t)n_ent, hipMemcpyDeviceToHost, st));
-      RSCHK(hipMemcpyAsync(b->h_ent_term.data(), b->ent_term.p, sizeof(int32_t) * (size_t)n_ent, hipMemcpyDeviceToHost, st));
-      RSCHK(hipMemcpyAsync(b->h_ent_pos.data(), b->ent_pos.p, sizeof(int32_t) * (size_t)n_ent, hipMemcpyDeviceToHost, st));
-      if (n_hdr > 0) RSCHK(hipMemcpyAsync(b->h_hdr_out.data(), b->hdr_out.p, sizeof(int32_t) * (size_t)n_hdr, hipMemcpyDeviceToHost, st));
-      if (side_bytes > 0) RSCHK(hipMemcpyAsync(b->h_side.data(), b->side.p, (size_t)side_bytes, hipMemcpyDeviceToHost, st));
-      RSCHK(hipStreamSynchronize(st));
+      BCHK(hipMemcpyAsync(b->h_ent_len.data(), b->ent_len.p, sizeof(int32_t) * (size_t)n_ent, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->h_ent_term.data(), b->ent_term.p, sizeof(int32_t) * (size_t)n_ent, hipMemcpyDeviceToHost, st));
+      BCHK(hipMemcpyAsync(b->h_ent_pos.data(), b->ent_pos.p, sizeof(int32_t) * (size_t)n_ent, hipMemcpyDeviceToHost, st));
+      if (n_hdr > 0) BCHK(hipMemcpyAsync(b->h_hdr_out.data(), b->hdr_out.p, sizeof(int32_t) * (size_t)n_hdr, hipMemcpyDeviceToHost, st));
+      if (side_bytes > 0) BCHK(hipMemcpyAsync(b->h_side.data(), b->side.p, (size_t)side_bytes, hipMemcpyDeviceToHost, st));
+      BCHK(hipStreamSynchronize(st));
       if (hipEventElapsedTime(&ms, b->ev[6], b->ev[7]) == hipSuccess) parse_ms += ms;
     } else {
-      RSCHK(hipEventRecord(b->ev[5], st));
-      RSCHK(hipStreamSynchronize(st));
+      BCHK(hipEventRecord(b->ev[5], st));
+      BCHK(hipStreamSynchronize(st));
       if (hipEventElapsedTime(&ms, b->ev[4], b->ev[5]) == hipSuccess) parse_ms += ms;
     }
     // the header lines, in text order: the one that goes on from the batch in front, the complete ones, the one that goes on
@@ -643,8 +583,8 @@ extern "C" int svdss_ref_stream_batch(svdss_ref_stream_t* s, int64_t seq, int32_
   const int64_t n_out = kept;
   run.end_turn();
   if (n_out > 0) {
-    RSCHK(hipMemcpyAsync(h, d, (size_t)n_out, hipMemcpyDeviceToHost, st));
-    RSCHK(hipStreamSynchronize(st));
+    BCHK(hipMemcpyAsync(h, d, (size_t)n_out, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
   }
   {
     std::lock_guard<std::mutex> lk(s->m);

@@ -23,20 +23,6 @@ def tile_bytes():
     return int(lib.svdss_fastx_tile_bytes())
 
 
-def bgzf_batches(data, batch_bytes):
-    """The BGZF members of `data` in batches of consecutive members that inflate to at least batch_bytes, plus the batch
-    (possibly empty) that closes the stream: lists of (coff, clen, isize, crc)."""
-    groups, cur, acc = [], [], 0
-    for b in _bgzf.bgzf_blocks(data):
-        cur.append(b)
-        acc += b[2]
-        if acc >= batch_bytes:
-            groups.append(cur)
-            cur, acc = [], 0
-    groups.append(cur)
-    return groups
-
-
 def plain_batches(data, batch_bytes):
     """(offset, length) of the slices of plain text; the last one closes the stream (an empty input has one empty batch)."""
     out, off = [], 0
@@ -48,9 +34,9 @@ def plain_batches(data, batch_bytes):
             return out
 
 
-def _run(data, batch_bytes, bgzf, carry_cap, index, assemble, device):
+def _run(data, batch_bytes, bgzf, carry_cap, index, assemble, device, chunks_per_batch=1):
     data = bytes(data)
-    comp = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+    comp = np.frombuffer(data, dtype=np.uint8)
     stream = C.c_void_p()
     rc = lib.svdss_fastx_stream_create(device, batch_bytes if carry_cap is None else carry_cap, C.byref(stream))
     if rc:
@@ -60,20 +46,14 @@ def _run(data, batch_bytes, bgzf, carry_cap, index, assemble, device):
     declined_at = None
     stats = {"batches": 0, "device_batches": 0, "host_batches": 0, "parse_ms": 0.0, "inflate_ms": 0.0, "text_bytes": 0}
     flags = SVDSS_SFS_ASSEMBLE if assemble else 0
-    jobs = bgzf_batches(data, batch_bytes) if bgzf else plain_batches(data, batch_bytes)
+    jobs = _bgzf.batches(data, batch_bytes) if bgzf else plain_batches(data, batch_bytes)
     try:
         for seq, g in enumerate(jobs):
             last = 1 if seq == len(jobs) - 1 else 0
             ix = index._h if index is not None else None
             if bgzf:
-                rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
-                crc = np.zeros(max(1, len(g)), dtype=np.uint32)
-                for i, b in enumerate(g):
-                    rec[i] = (b[0], b[1], b[2], 0)
-                    crc[i] = b[3]
-                rc = lib.svdss_fastx_batch_run(stream, seq, last, ix, 1, (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(data)),
-                                               (C.c_void_p * 1)(rec.ctypes.data), (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)),
-                                               None, 0, flags, C.byref(batch))
+                A = _bgzf.BatchArgs.of(comp, g, chunks_per_batch)
+                rc = lib.svdss_fastx_batch_run(stream, seq, last, ix, *A.args, None, 0, flags, C.byref(batch))
             else:
                 rc = lib.svdss_fastx_batch_run(stream, seq, last, ix, 0, None, None, None, None, None,
                                                comp.ctypes.data + g[0] if g[1] else None, g[1], flags, C.byref(batch))
@@ -123,12 +103,13 @@ def _run(data, batch_bytes, bgzf, carry_cap, index, assemble, device):
     return names, (np.concatenate(flat) if flat else np.zeros(0, np.uint8)), offsets, declined_at, stats, sfs
 
 
-def parse_fastx(data, batch_bytes, bgzf=False, carry_cap=None, device=0):
+def parse_fastx(data, batch_bytes, bgzf=False, carry_cap=None, device=0, chunks_per_batch=1):
     """`data`: the bytes of a FASTA / FASTQ file, plain or (bgzf=True) as BGZF members.  Parses it on the GPU in batches of
     batch_bytes and returns (names, nt6 symbols of all reads back to back, int64 offsets, the batch that declined or None,
     counters).  Records behind a declined batch are not delivered: counters["rest"] is the text from the first unparsed
-    byte on, which the caller reads with the host reader."""
-    return _run(data, batch_bytes, bgzf, carry_cap, None, True, device)[:5]
+    byte on, which the caller reads with the host reader.  chunks_per_batch: every batch's members handed over as that many
+    chunks (bgzf.BatchArgs.split)."""
+    return _run(data, batch_bytes, bgzf, carry_cap, None, True, device, chunks_per_batch)[:5]
 
 
 def search_fastx(index, data, batch_bytes=192 << 20, bgzf=False, assemble=True, carry_cap=None):

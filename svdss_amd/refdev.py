@@ -6,8 +6,9 @@ import ctypes as C
 
 import numpy as np
 
+from . import bgzf as _bgzf
 from ._lib import SvdssError, lib
-from .fastxdev import bgzf_batches, plain_batches
+from .fastxdev import plain_batches
 
 DEFAULT_HEADER_CAP = 64 << 10
 REASONS = {1: "cr", 2: "nul", 3: "at-line", 4: "not-fasta", 5: "duplicate-name", 6: "long-header", 7: "empty", 8: "io", 9: "error"}
@@ -27,27 +28,22 @@ def tile_bytes():
 class RefStream:
     """One FASTA read through svdss_ref_stream_batch: names, seq_off, declined (a key of REASONS or None), counters."""
 
-    def __init__(self, data, batch_bytes, bgzf=False, header_cap=None, device=0, jobs=None):
+    def __init__(self, data, batch_bytes, bgzf=False, header_cap=None, device=0, jobs=None, chunks_per_batch=1):
         data = bytes(data)
-        comp = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+        comp = np.frombuffer(data, dtype=np.uint8)
         self._h = C.c_void_p()
         self.device = device
         rc = lib.svdss_ref_stream_create(device, DEFAULT_HEADER_CAP if header_cap is None else header_cap, C.byref(self._h))
         if rc:
             raise SvdssError(rc, "svdss_ref_stream_create")
         if jobs is None:
-            jobs = bgzf_batches(data, batch_bytes) if bgzf else plain_batches(data, batch_bytes)
+            jobs = _bgzf.batches(data, batch_bytes) if bgzf else plain_batches(data, batch_bytes)
         try:
             for seq, g in enumerate(jobs):
                 last = 1 if seq == len(jobs) - 1 else 0
                 if bgzf:
-                    rec = np.zeros(max(1, len(g)), dtype=[("coff", "<i8"), ("clen", "<i4"), ("isize", "<i4"), ("uoff", "<i8")])
-                    crc = np.zeros(max(1, len(g)), dtype=np.uint32)
-                    for i, b in enumerate(g):
-                        rec[i] = (b[0], b[1], b[2], 0)
-                        crc[i] = b[3]
-                    rc = lib.svdss_ref_stream_batch(self._h, seq, last, 1, (C.c_void_p * 1)(comp.ctypes.data), (C.c_int64 * 1)(len(data)),
-                                                    (C.c_void_p * 1)(rec.ctypes.data), (C.c_void_p * 1)(crc.ctypes.data), (C.c_int64 * 1)(len(g)), None, 0)
+                    A = _bgzf.BatchArgs.of(comp, g, chunks_per_batch)
+                    rc = lib.svdss_ref_stream_batch(self._h, seq, last, *A.args, None, 0)
                 else:
                     rc = lib.svdss_ref_stream_batch(self._h, seq, last, 0, None, None, None, None, None,
                                                     comp.ctypes.data + g[0] if g[1] else None, g[1])
@@ -138,11 +134,11 @@ class ResidentRef:
         self.close()
 
 
-def load_reference(data, batch_bytes, bgzf=False, header_cap=None, device=0, jobs=None):
+def load_reference(data, batch_bytes, bgzf=False, header_cap=None, device=0, jobs=None, chunks_per_batch=1):
     """`data`: the bytes of a FASTA file, plain or (bgzf=True) as BGZF members.  Reads it on the GPU in batches of
     batch_bytes and returns (names, [upper-cased bytes per record], why it declined or None, counters).  A declined file
     delivers nothing: the caller reads it with the host reader."""
-    with RefStream(data, batch_bytes, bgzf, header_cap, device, jobs) as s:
+    with RefStream(data, batch_bytes, bgzf, header_cap, device, jobs, chunks_per_batch) as s:
         if s.declined:
             return [], [], s.declined, s.counters
         return s.names, [s.download(i) for i in range(len(s.names))], None, s.counters
