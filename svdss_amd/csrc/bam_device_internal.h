@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "bam_aux_walk.h"
 #include "bgzf_intake.h"
 
 // error bits a batch's kernels raise (hdr[H_ERR]; bam_smooth.hip adds one of its own)
@@ -37,26 +38,11 @@ namespace {   // (every unit its own copy: no device-side linking)
 // bam_aux_get + bam_aux2i for one two-letter tag, as BamReader::aux_int reads it (csrc/bam_reader.h): integer types
 // only, anything unexpected ends the scan with "absent"
 __device__ bool aux_int(const uint8_t* p, const uint8_t* e, char a, char b, int64_t& out) {
-  while (p + 3 <= e) {
+  while (p < e) {
+    const int64_t sz = svdss_aux_value_size(p, e);   // (bam_aux_walk.h: the value lies inside the block, or the walk gives up)
+    if (sz < 0) return false;
     const char t0 = (char)p[0], t1 = (char)p[1], ty = (char)p[2];
     p += 3;
-    int64_t sz = 0;
-    switch (ty) {
-      case 'A': case 'c': case 'C': sz = 1; break;
-      case 's': case 'S': sz = 2; break;
-      case 'i': case 'I': case 'f': sz = 4; break;
-      case 'Z': case 'H': { const uint8_t* z = p; while (z < e && *z) ++z; sz = (int64_t)(z - p) + 1; break; }
-      case 'B': {
-        if (p + 5 > e) return false;
-        const char st = (char)p[0];
-        const int32_t cnt = (int32_t)((uint32_t)p[1] | ((uint32_t)p[2] << 8) | ((uint32_t)p[3] << 16) | ((uint32_t)p[4] << 24));
-        const int64_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-        sz = 5 + es * (int64_t)(uint32_t)cnt;     // (size_t arithmetic on the host: a negative count is a huge one)
-        break;
-      }
-      default: return false;
-    }
-    if (sz > (int64_t)(e - p)) return false;
     if (t0 == a && t1 == b) {
       switch (ty) {
         case 'c': out = (int8_t)p[0]; return true;

@@ -7,6 +7,7 @@
 // With --region / --regions-file in force (bam_regions.h) next / next_raw / next_view pass over the records outside the
 // regions: the reader then reads the file that holds the others alone.
 #pragma once
+#include "bam_aux_walk.h"
 #include "bgzf_inflater.h"
 #include "bam_regions.h"
 
@@ -470,26 +471,11 @@ class BamReader {
   }
   static bool aux_int(const uint8_t* p, size_t n, const char tag[2], int64_t& out) {
     const uint8_t* e = p + n;
-    while (p + 3 <= e) {
+    while (p < e) {
+      const int64_t sz = svdss_aux_value_size(p, e);   // (bam_aux_walk.h: the value lies inside the block, or the walk gives up)
+      if (sz < 0) return false;
       const char t0 = (char)p[0], t1 = (char)p[1], ty = (char)p[2];
       p += 3;
-      size_t sz = 0;
-      switch (ty) {
-        case 'A': case 'c': case 'C': sz = 1; break;
-        case 's': case 'S': sz = 2; break;
-        case 'i': case 'I': case 'f': sz = 4; break;
-        case 'Z': case 'H': { const uint8_t* z = p; while (z < e && *z) ++z; sz = (size_t)(z - p) + 1; break; }
-        case 'B': {
-          if (p + 5 > e) return false;
-          const char st = (char)p[0];
-          int32_t cnt; memcpy(&cnt, p + 1, 4);
-          const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-          sz = 5 + es * (size_t)cnt;
-          break;
-        }
-        default: return false;
-      }
-      if (p + sz > e) return false;
       if (t0 == tag[0] && t1 == tag[1]) {
         switch (ty) {
           case 'c': out = (int8_t)p[0]; return true;

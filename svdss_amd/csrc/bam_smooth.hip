@@ -208,35 +208,14 @@ __global__ void __launch_bounds__(64) smooth_walk_kernel(SmWalkP A) {
     for (int d = 32; d >= 1; d >>= 1) { nm += __shfl_xor(nm, d, 64); nx += __shfl_xor(nx, d, 64); }
   }
   // set_xf (smooth_host.cpp; bam_aux_update_int): an integer XF is overwritten, else XF:C is appended; an aux block the
-  // walk cannot parse is left alone
+  // walk gives up on (bam_aux_walk.h) is left alone.  (ax <= rec_end here: smooth_meta_kernel keeps no record whose core,
+  // name, CIGAR, bases and qualities do not fit in its block_size -- it raises E_CORRUPT, the batch fails as the host
+  // reader's "corrupt record" does -- so an empty aux block is [ax, ax): absent, XF:C appended)
   int32_t xat = -1, xsz = 0;
   {
-    int64_t q = ax;
-    while (q + 3 <= rec_end) {
-      const char t0 = (char)A.buf[q], t1 = (char)A.buf[q + 1], ty = (char)A.buf[q + 2];
-      int64_t sz = 0;
-      bool bad = false;
-      switch (ty) {
-        case 'A': case 'c': case 'C': sz = 1; break;
-        case 's': case 'S': sz = 2; break;
-        case 'i': case 'I': case 'f': sz = 4; break;
-        case 'Z': case 'H': { int64_t z = q + 3; while (z < rec_end && A.buf[z]) ++z; sz = z - (q + 3) + 1; break; }
-        case 'B': {
-          if (q + 8 > rec_end) { bad = true; break; }
-          const char st = (char)A.buf[q + 3];
-          const int32_t cnt = (int32_t)ld32(A.buf, q + 4);
-          sz = 5 + (int64_t)cnt * ((st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4);
-          break;
-        }
-        default: bad = true;
-      }
-      if (bad) { xat = -2; break; }
-      if (t0 == 'X' && t1 == 'F' && (ty == 'c' || ty == 'C' || ty == 's' || ty == 'S' || ty == 'i' || ty == 'I')) {
-        xat = (int32_t)(q + 3 - p); xsz = (int32_t)sz;
-        break;
-      }
-      q += 3 + sz;
-    }
+    const int64_t at = svdss_aux_find_int(A.buf + ax, A.buf + rec_end, 'X', 'F', xsz);
+    if (at == SVDSS_AUX_BAD) xat = -2;
+    else if (at >= 0) xat = (int32_t)(ax + at - p);
   }
   if (lane == 0) {
     A.kpos[k] = (uint32_t)p;

@@ -27,6 +27,7 @@
 #include "host_common.h"
 #include "host_knobs.h"
 #include "bam_reader.h"
+#include "bam_aux_walk.h"
 #include "bam_device_select.h"
 #include "bam_input_index.h"
 #include "gpu_deflate_hook.h"
@@ -84,32 +85,16 @@ void mismatch_counts(const BamRecord& r, const std::string& seq, const std::stri
   }
 }
 
-// bam_aux_update_int(aln, "XF", v): overwrite an existing integer XF, else append XF:C
+// bam_aux_update_int(aln, "XF", v): overwrite an existing integer XF, else append XF:C; an aux block the walk gives up on
+// (bam_aux_walk.h) is left as it is
 void set_xf(std::vector<uint8_t>& aux, int v) {
-  size_t p = 0;
-  while (p + 3 <= aux.size()) {
-    const char t0 = (char)aux[p], t1 = (char)aux[p + 1], ty = (char)aux[p + 2];
-    size_t sz = 0;
-    switch (ty) {
-      case 'A': case 'c': case 'C': sz = 1; break;
-      case 's': case 'S': sz = 2; break;
-      case 'i': case 'I': case 'f': sz = 4; break;
-      case 'Z': case 'H': { size_t z = p + 3; while (z < aux.size() && aux[z]) ++z; sz = z - (p + 3) + 1; break; }
-      case 'B': {
-        if (p + 8 > aux.size()) return;
-        const char st = (char)aux[p + 3];
-        int32_t cnt; memcpy(&cnt, &aux[p + 4], 4);
-        sz = 5 + (size_t)cnt * ((st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4);
-        break;
-      }
-      default: return;
-    }
-    if (t0 == 'X' && t1 == 'F' && strchr("cCsSiI", ty)) {
-      memset(&aux[p + 3], 0, sz);
-      aux[p + 3] = (uint8_t)v;
-      return;
-    }
-    p += 3 + sz;
+  int32_t n = 0;
+  const int64_t at = svdss_aux_find_int(aux.data(), aux.data() + aux.size(), 'X', 'F', n);
+  if (at == SVDSS_AUX_BAD) return;
+  if (at >= 0) {
+    memset(&aux[(size_t)at], 0, (size_t)n);
+    aux[(size_t)at] = (uint8_t)v;
+    return;
   }
   aux.push_back('X'); aux.push_back('F'); aux.push_back('C'); aux.push_back((uint8_t)v);
 }

@@ -8,7 +8,8 @@ of every integer type already present, unmapped / secondary / low-MAPQ records -
 svdss_bam_smooth_set_search, batch by batch, and every batch is finished by svdss_bam_smooth_search.  The checker is a
 host twin: it inflates the BGZF members the same runs produced (S), walks the rebuilt records as `search` would (flags,
 l_seq >= 100, qname, HP, XF), unpacks their 4-bit bases to nt6 and searches them with the oracle.  Names, HP, which reads
-are searched and every SFS must agree."""
+are searched and every SFS must agree.  Then S itself is checked (check_smoothed_stream): the mirror of smoother.cpp applied to
+the input's records must give the records of S -- so the 19 / 20 / 21 bp indels count for the smoothing, too."""
 import ctypes as C
 import struct
 import zlib
@@ -244,7 +245,28 @@ def fuzz_smooth_sfs(rng, out_dir, it):
             if sfs != [(int(q[j]), int(l[j])) for j in range(int(first[k]), int(first[k + 1]))]:
                 raise Mismatch(f"SFS of exported read {k} ({n}) differ from the oracle's on the smoothed record's bases: " + where())
             k += 1
-    return len(want), f"{len(want)} reads dealt, {len(reads)} searched, {len(S)} bytes of S"
+    n_smoothed = check_smoothed_stream(S, data, contigs, 20, acc, where)
+    return len(want), f"{len(want)} reads dealt, {len(reads)} searched, {len(S)} bytes of S, {n_smoothed} records as the mirror smooths them"
+
+
+def check_smoothed_stream(S, data, contigs, min_mapq, acc, where):
+    """Was S smoothed correctly?  The mirror of smoother.cpp (tests/mirror/smoother.py) applied to the input's records: the
+    same records in the same order, XF, bases, qualities, CIGAR and aux block."""
+    import gzip
+    from tests.mirror import bamio, smoother
+    names, _, alns = bamio.parse_bam(gzip.decompress(bytes(data)))
+    _, _, got = bamio.parse_bam(b"".join(zlib.decompress(S[c:c + n], -15) for c, n, _, _ in bgzf.bgzf_blocks(S)))
+    chrom = {n: synth.to_ascii(c) for n, c in zip(names, contigs)}
+    kept = [a for a in alns if smoother.eligible(a, names, chrom, min_mapq)]
+    if [g.qname for g in got] != [a.qname for a in kept]:
+        raise Mismatch("the smoothed stream does not hold the records the filters keep, in their order: " + where())
+    for g, a in zip(got, kept):
+        xf, ns, nq, nc = smoother.smooth_read(a, a.qual, chrom[names[a.tid]], acc)
+        if xf != 0:
+            ns, nq, nc = a.seq, a.qual, a.cigar
+        if (g.flag, g.tid, g.pos, g.mapq, g.seq, g.qual, g.cigar, g.aux) != (a.flag, a.tid, a.pos, a.mapq, ns, nq, list(nc), smoother.update_xf(a.aux, xf)):
+            raise Mismatch(f"record {a.qname} (XF {xf} by the mirror) is not smoothed as the mirror smooths it: " + where())
+    return len(got)
 
 
 fuzz_gpu.FUZZERS["smooth_sfs"] = fuzz_smooth_sfs

@@ -6,6 +6,7 @@ import struct
 from typing import List, Tuple
 
 from .clusterer import Alignment
+from .smoother import aux_value_size
 
 SEQ16 = "=ACMGRSVTWYHKDBN"
 
@@ -15,6 +16,11 @@ def read_bam(path: str) -> Tuple[List[str], List[int], List[Alignment]]:
         data = fh.read()
     if data[:4] != b"BAM\1":
         raise ValueError(f"{path}: not a BAM file")
+    return parse_bam(data)
+
+
+def parse_bam(data: bytes) -> Tuple[List[str], List[int], List[Alignment]]:
+    """(reference names, reference lengths, records) of an inflated BAM stream"""
     o = 4
     (l_text,) = struct.unpack_from("<i", data, o)
     o += 4 + l_text
@@ -49,30 +55,33 @@ def read_bam(path: str) -> Tuple[List[str], List[int], List[Alignment]]:
         p += (l_seq + 1) // 2
         qual = bytes(rec[p:p + l_seq])
         p += l_seq
-        tags = {}
-        while p + 3 <= len(rec):
-            tag, ty = rec[p:p + 2].decode(), chr(rec[p + 2])
-            p += 3
-            if ty in "cCsSiI":
-                fmt = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I"}[ty]
-                (val,) = struct.unpack_from("<" + fmt, rec, p)
-                p += struct.calcsize(fmt)
-                tags[tag] = val
-            elif ty == "A":
-                p += 1
-            elif ty == "f":
-                p += 4
-            elif ty in "ZH":
-                e = rec.index(b"\0", p)
-                p = e + 1
-            elif ty == "B":
-                st = chr(rec[p])
-                (cnt,) = struct.unpack_from("<i", rec, p + 1)
-                p += 5 + cnt * (1 if st in "cC" else 2 if st in "sS" else 4)
-            else:
-                break
-        alns.append(Alignment(qname, flag, tid, pos, mapq, cigar, seq, tags, qual))
+        aux = bytes(rec[p:])
+        alns.append(Alignment(qname, flag, tid, pos, mapq, cigar, seq, parse_tags(aux), qual, aux))
     return names, lens, alns
+
+
+_INT_FMT = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I"}
+
+
+def parse_tags(aux: bytes) -> dict:
+    """The integer tags (value) and B arrays (list of values) of an aux block, by tag name (a later tag of the same name
+    replaces an earlier one); the walk stops where csrc/bam_aux_walk.h gives up."""
+    tags = {}
+    p = 0
+    while p < len(aux):
+        sz = aux_value_size(aux, p)
+        if sz is None:
+            break
+        tag, ty = aux[p:p + 2].decode("latin-1"), chr(aux[p + 2])
+        if ty in _INT_FMT:
+            (tags[tag],) = struct.unpack_from("<" + _INT_FMT[ty], aux, p + 3)
+        elif ty == "B":
+            st = chr(aux[p + 3])
+            fmt = _INT_FMT.get(st, "f" if st == "f" else None)
+            n = int.from_bytes(aux[p + 4:p + 8], "little")
+            tags[tag] = list(struct.unpack_from(f"<{n}{fmt}", aux, p + 8)) if fmt else bytes(aux[p + 8:p + 3 + sz])
+        p += 3 + sz
+    return tags
 
 
 from svdss_amd.bgzf import bgzf_blocks, gpu_inflate  # noqa: E402,F401  (kept importable from here)

@@ -25,6 +25,7 @@ class Alignment:
     seq: str
     tags: Dict[str, int] = field(default_factory=dict)
     qual: bytes = b""
+    aux: bytes = b""                  # the raw aux block (tests/mirror/bamio.py keeps it)
 
     def endpos(self) -> int:          # bam_endpos
         ref = sum(l for l, op in self.cigar if op in (BAM_CMATCH, BAM_CDEL, BAM_CREF_SKIP, BAM_CEQUAL, BAM_CDIFF))
