@@ -33,6 +33,7 @@ extern __device__ unsigned long long g_sfs_iters[64];
 #define SV_COUNT_PASS() do { if ((threadIdx.x & 63) == __builtin_ctzll(__ballot(1))) atomicAdd(&g_sfs_iters[1], 1ULL); } while (0)
 #endif
 #include "sfs_core2.h"
+#include "sfs_plan.h"
 #include "sym_window.h"
 // profiling build (make searchprof -> libsvdss_hip_searchprof.so): shader-clock cycles per section of the main loop, summed over
 // the wavefronts -- [0] tickets + item start, [1] sv_decide, [2] addresses + loads issued, [3..] the apply of each operation
@@ -734,6 +735,7 @@ struct svdss_sfs_batch {
   // calls on different batch objects -- e.g. two threads feeding the GPU from a BAM file -- overlap
   hipStream_t own_stream = nullptr;
   SfsBuf packed, byte_off, lens32;   // svdss_sfs_search_batch_bam: the 4-bit bases as they sit in the BAM records
+  void reset_results() { n_reads = 0; total = 0; total_ext = 0; kernel_ms = 0.0; search_ms = 0.0; }
 };
 
 extern "C" void svdss_sfs_batch_free(svdss_sfs_batch_t* b) {
@@ -763,15 +765,20 @@ static int launch_grid(int device, int* blocks_out) {
   return SVDSS_OK;
 }
 
-extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint8_t* d_reads,
-                                             const int64_t* d_offsets, int64_t n_reads,
-                                             int64_t total_syms, int32_t flags, void* stream_,
-                                             svdss_sfs_batch_t** out) {
-  if (!ix || !out || n_reads < 0 || total_syms < 0) return SVDSS_EINVAL;
-  if (n_reads > 0 && (!d_reads || !d_offsets)) return SVDSS_EINVAL;
-  if (((uintptr_t)d_reads & 15u) != 0) return SVDSS_EINVAL;
-  if (ix->device < 0 || !ix->d_blocks) return SVDSS_ENODEV;
-  hipStream_t stream = (hipStream_t)stream_;
+// The only place that names the eight instantiations of the search kernel: [wide suffix array][segmented][BS].
+static void launch_search(bool wide, bool seg, bool bs, unsigned blocks, size_t lds, hipStream_t stream, const SfsParams& p) {
+  using Kernel = void (*)(SfsParams);
+  static const Kernel kernels[2][2][2] = {
+      {{sfs_search2_kernel<uint32_t, false, false>, sfs_search2_kernel<uint32_t, false, true>},
+       {sfs_search2_kernel<uint32_t, true, false>, sfs_search2_kernel<uint32_t, true, true>}},
+      {{sfs_search2_kernel<uint64_t, false, false>, sfs_search2_kernel<uint64_t, false, true>},
+       {sfs_search2_kernel<uint64_t, true, false>, sfs_search2_kernel<uint64_t, true, true>}}};
+  hipLaunchKernelGGL(kernels[wide][seg][bs], dim3(blocks), dim3(256), lds, stream, p);
+}
+
+// The batch object of a call, on the index's device (made current): *out, or a new one left there.  own_stream: with the
+// stream of the host-buffer entry points.
+static int batch_get(const svdss_index_t* ix, svdss_sfs_batch_t** out, bool own_stream, svdss_sfs_batch** bp) {
   HIPCHK(hipSetDevice(ix->device));
   svdss_sfs_batch* b = *out;
   if (!b) {
@@ -780,250 +787,224 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
     b->device = ix->device;
     *out = b;
   }
-  if (b->device != ix->device) return SVDSS_EINVAL;
-  if (!b->ev0) HIPCHK(hipEventCreate(&b->ev0));
-  if (!b->ev1) HIPCHK(hipEventCreate(&b->ev1));
-  if (!b->ek0) HIPCHK(hipEventCreate(&b->ek0));
-  if (!b->ek1) HIPCHK(hipEventCreate(&b->ek1));
-  b->n_reads = n_reads;
-  b->total = 0;
-  b->total_ext = 0;
-  b->kernel_ms = 0.0;
-  b->search_ms = 0.0;
-  if (n_reads == 0) return SVDSS_OK;
+  if (own_stream && !b->own_stream) HIPCHK(svdss_make_stream(&b->own_stream, "SVDSS_SEARCH_CUS"));
+  *bp = b;
+  return SVDSS_OK;
+}
 
-  int rc;
-  const int64_t rec_total = (total_syms >> 3) + 8 * n_reads + 16;
-  if ((rc = b->rec.ensure((size_t)rec_total * sizeof(uint2)))) return rc;
-  if ((rc = b->counts.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = b->n_ext.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
-  if ((rc = b->out_off.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = b->misc.ensure(64))) return rc;
-  if ((rc = b->sum.ensure(64))) return rc;
-
+// One call of svdss_sfs_search_batch_device on a batch of at least one read.  run() names the stages in their order; the
+// decisions are sfs_plan.h's, the stages only allocate and enqueue.  misc: [0] next_read, [1] overflow count, [2] n_fallback.
+struct SfsRun {
+  svdss_sfs_batch* const b;
+  const svdss_index_t* const ix;
+  const uint8_t* const d_reads;
+  const int64_t* const d_offsets;
+  const int64_t n_reads, total_syms;
+  const int32_t flags;
+  const hipStream_t stream;
+  const SfsKnobs kn = SfsKnobs::from_env();
+  SfsPlan pl;
   SfsParams p;
-  p.ix = svdss_device_view(ix);
-  p.chunks = (const svdss_u4*)d_reads;
-  p.max_chunk = total_syms > 0 ? ((total_syms + 15) >> 4) - 1 : 0;
-  p.offsets = d_offsets;
-  p.n_reads = n_reads;
-  p.rec = (uint2*)b->rec.p;
-  p.rec_base = nullptr;
-  p.rec_cap = nullptr;
-  p.counts = (int64_t*)b->counts.p;
-  p.n_ext = (int64_t*)b->n_ext.p;
-  p.next_read = (unsigned long long*)b->misc.p;
-  p.assemble = (flags & SVDSS_SFS_ASSEMBLE) ? 1 : 0;
-  unsigned long long* d_overflow = (unsigned long long*)b->misc.p + 1;
-  p.n_seg = 1;
-  p.seg_shift = 0;
-  p.seg_rec = nullptr;
-  p.seg_info = nullptr;
-  p.read_ids = nullptr;
-  p.sub_ids = nullptr;
-  p.n_sub = 0;
-  p.use_set = 1;
-  if (const char* e = getenv("SVDSS_SET")) p.use_set = atoi(e) != 0;
-  // (BS needs the suffix array, a k-mer table, and few enough records for their '$' positions to sit in LDS)
-  p.use_bs = p.ix.sa != nullptr && p.ix.k > 0 && p.ix.n_dollar > 0 && p.ix.n_dollar <= SV_BS_MAX_DOLLAR;
-  // The BS instantiation is chosen by the reference (round 5; rounds 3-4: opt-in).  Measured at GRCh38 lengths with 45 % of
-  // the bases in 40 repeat families (profiles/r04h_search_bs.txt, ms per 1,048,576 reads, plain -> BS kernel): copies 1 %
-  // apart 408 -> 363, 5 % apart 197 -> 209, 15 % apart 103 -> 108, the headline reference 67.7 either way when the plain
-  // kernel is the one launched.  svdss_index::deep_frac (the share of K-mer occurrences in K-mers with SV_BS_MIN or more
-  // of them, sampled while the table is built) was 0.001 / 0.206 / 0.329 / 0.371 on the four: from 0.35 on the copies are
-  // young enough for the binary search to pay.  Most of a real genome's repeats are old: it keeps the plain kernel.
-  // SVDSS_BS=0|1 overrides, SVDSS_BS_DEEP moves the threshold.  Either kernel gives the same SFS and extension counts.
-  const double bs_deep = getenv("SVDSS_BS_DEEP") ? atof(getenv("SVDSS_BS_DEEP")) : 0.35;
-  bool use_bs_kernel = p.use_bs && ix->deep_frac >= bs_deep;
-  if (const char* e = getenv("SVDSS_BS")) if (*e == '0' || *e == '1') use_bs_kernel = p.use_bs && *e == '1';
-  p.use_bs = use_bs_kernel;
-  b->used_bs = use_bs_kernel ? 1 : 0;
-  p.ticket_chunk = 8;
-  if (const char* e = getenv("SVDSS_TICKETS")) p.ticket_chunk = atoi(e) > 0 ? atoi(e) : 8;
-  p.n_items = n_reads;
-  p.n_fallback = (unsigned long long*)b->misc.p + 2;
-  p.fallback_ids = nullptr;
-  p.epoch = ++b->epoch ? b->epoch : ++b->epoch;
+  unsigned long long* d_overflow = nullptr;
 
-  // (the kernel fetches a read's symbols 64 bytes at a time: a batch smaller than that is searched in a padded copy)
-  if (total_syms < 64) {
-    if ((rc = b->tiny.ensure(96))) return rc;
-    HIPCHK(hipMemsetAsync(b->tiny.p, 0, 96, stream));
-    if (total_syms > 0) HIPCHK(hipMemcpyAsync(b->tiny.p, d_reads, (size_t)total_syms, hipMemcpyDeviceToDevice, stream));
-    p.chunks = (const svdss_u4*)b->tiny.p;
-    p.max_chunk = 3;
-  }
-  int max_blocks = 0;
-  if ((rc = launch_grid(ix->device, &max_blocks))) return rc;
-  // Small batches cannot fill the GPU with one lane per read (256 CUs x 16 waves x 64 lanes):
-  // cut every read into n_seg segments searched by separate lanes and stitch the chains.
-  int n_seg = 1;
-  {
-    const int64_t lanes = (int64_t)max_blocks * 256 / 2;   // 4 waves per SIMD resident
-    const int64_t want = 4 * lanes / (n_reads > 0 ? n_reads : 1);   // ~4 items per resident lane: short items bound the tail
-    n_seg = (int)(want < 4 ? 1 : (want > 8 ? 8 : want));   // large batches fill the GPU with one lane per read; beyond 8
-                                                              // the odd unstitchable read costs more than it saves
-    // On the rank blocks alone (no text, no suffix array: svdss_index_attach_blocks) a read is thousands of dependent rank steps
-    // whatever its segments do, and the reads such a search gets -- smoothed ones -- have too few SFS for their segments to be
-    // stitched at (27 % searched again at 30x): from half a lane-load of reads on, one lane per read (`search` at 30x: the two
-    // launches 0.44 -> 0.29 s, profiles/r06av_*)
-    if ((!ix->d_text || !ix->d_sa) && 2 * n_reads >= lanes) n_seg = 1;
-    if (const char* e = getenv("SVDSS_SEGMENTS")) n_seg = atoi(e);
-    if (n_seg < 1) n_seg = 1;
-    if (n_seg > 16) n_seg = 16;
-    while (n_seg & (n_seg - 1)) n_seg &= n_seg - 1;   // power of two: item -> (read, segment) by shift
-    if (total_syms / (n_reads > 0 ? n_reads : 1) < 1024) n_seg = 1;
-    if (n_reads * (int64_t)n_seg >= ((int64_t)1 << 31)) n_seg = 1;   // item tickets are 32-bit in the kernel
-  }
-  if (n_seg > 1) {
-    const int64_t seg_total = (total_syms >> 3) + (8 + 24 * (int64_t)n_seg) * n_reads + 64;
-    if ((rc = b->seg_rec.ensure((size_t)seg_total * sizeof(uint4)))) return rc;
-    if ((rc = b->seg_info.ensure((size_t)(n_reads * n_seg) * sizeof(SvSegInfo)))) return rc;
-    if ((rc = b->fallback.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
-    if ((rc = b->seg_take.ensure((size_t)(2 * n_reads * n_seg) * sizeof(int32_t)))) return rc;
-    p.seg_rec = (uint4*)b->seg_rec.p;
-    p.seg_info = (SvSegInfo*)b->seg_info.p;
-    p.fallback_ids = (int64_t*)b->fallback.p;
-    p.seg_take = (int32_t*)b->seg_take.p;
-  }
-  b->n_seg = n_seg;
-  b->n_fallback = 0;
-  int cap_blocks = max_blocks;
-  if (const char* e = getenv("SVDSS_BLOCKS")) cap_blocks = atoi(e) > 0 ? atoi(e) : max_blocks;
-  auto blocks_for = [&](int64_t items) {
-    const int64_t w = (items + 255) / 256;
-    return (int)(w < 1 ? 1 : (w < cap_blocks ? w : cap_blocks));
-  };
-  const int64_t gw = (n_reads + 3) / 4;  // 4 waves per block, one read per wave iteration
-  const int gblocks = (int)(gw < 4 * (int64_t)max_blocks ? (gw > 0 ? gw : 1) : 4 * (int64_t)max_blocks);
-
-  size_t tmp_bytes = 0, tmp2 = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, p.counts, (int64_t*)b->out_off.p,
-                                          (int)(n_reads + 1), stream));
-  HIPCHK(hipcub::DeviceReduce::Sum(nullptr, tmp2, p.n_ext, (int64_t*)b->sum.p, (int)n_reads, stream));
-  if (tmp2 > tmp_bytes) tmp_bytes = tmp2;
-  if ((rc = b->tmp.ensure(tmp_bytes))) return rc;
-
-  // heavy reads first (see sfs_order_kernel); SVDSS_ORDER=0 keeps the input order
-  const char* ord_env = getenv("SVDSS_ORDER");
-  const bool use_order = n_reads >= 1024 && p.ix.k >= 8 && !(ord_env && atoi(ord_env) == 0);
-  if (use_order) {
-    if ((rc = b->order.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
-    if ((rc = b->order_cnt.ensure((size_t)(2 * n_reads + 2) * sizeof(int64_t)))) return rc;   // flags, their scan
-    size_t t3 = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (int64_t*)b->order_cnt.p, (int64_t*)b->order_cnt.p + n_reads + 1,
-                                            (int)(n_reads + 1), stream));
-    if (t3 > b->tmp.cap && (rc = b->tmp.ensure(t3))) return rc;
-  }
-  for (int pass = 0; pass < 2; ++pass) {
-    HIPCHK(hipMemsetAsync(b->misc.p, 0, 64, stream));
-    HIPCHK(hipMemsetAsync((int64_t*)b->counts.p + n_reads, 0, sizeof(int64_t), stream));
-    const bool wide = ix->sa_wide;
-    const bool seg = n_seg > 1 && pass == 0;   // the exact-capacity rerun is always unsegmented
-    HIPCHK(hipEventRecord(b->ev0, stream));
-    if (use_order && pass == 0) {
-      int64_t* heavy = (int64_t*)b->order_cnt.p;
-      int64_t* hscan = heavy + n_reads + 1;
-      HIPCHK(hipMemsetAsync(heavy + n_reads, 0, sizeof(int64_t), stream));
-      hipLaunchKernelGGL(sfs_order_kernel, dim3((unsigned)((n_reads + 15) / 16)), dim3(256), 0, stream, p, heavy);
+  int run() {
+    int rc;
+    if ((rc = plan())) return rc;
+    if ((rc = buffers())) return rc;
+    for (int pass = 0; pass < 2; ++pass) {
+      HIPCHK(hipMemsetAsync(b->misc.p, 0, 64, stream));
+      HIPCHK(hipMemsetAsync((int64_t*)b->counts.p + n_reads, 0, sizeof(int64_t), stream));
+      HIPCHK(hipEventRecord(b->ev0, stream));
+      if (pl.use_order && pass == 0 && (rc = order())) return rc;
+      // (the exact-capacity rerun is always unsegmented)
+      if ((rc = pl.n_seg > 1 && pass == 0 ? search_segmented() : search_plain(pass))) return rc;
       HIPCHK(hipGetLastError());
-      size_t t3 = b->tmp.cap;
-      HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t3, heavy, hscan, (int)(n_reads + 1), stream));
-      hipLaunchKernelGGL(sfs_order_scatter_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, stream, n_reads, heavy,
-                         hscan, (int64_t*)b->order.p);
-      HIPCHK(hipGetLastError());
-      p.read_ids = (const int64_t*)b->order.p;
+      HIPCHK(hipEventRecord(b->ev1, stream));
+      unsigned long long n_over = 0;
+      if ((rc = collect(pass, &n_over))) return rc;
+      if (n_over == 0) break;
+      if (pass == 1) return SVDSS_ERANGE;  // cannot happen: capacities were exact
+      if ((rc = exact_capacity())) return rc;
     }
-    if (seg) {
-      p.n_seg = n_seg;
-      p.seg_shift = __builtin_ctz((unsigned)n_seg);
-      p.n_items = n_reads * n_seg;
-      HIPCHK(hipEventRecord(b->ek0, stream));
-      // SVDSS_EXTRA_LDS (developer knob): unused dynamic LDS per block, to study the kernel at lower occupancy
-      const char* xl = getenv("SVDSS_EXTRA_LDS");
-      const size_t extra_lds = xl ? (size_t)atol(xl) : 0;
-      if (wide && use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, true, true>), dim3(blocks_for(p.n_items)), dim3(256), extra_lds, stream, p);
-      else if (wide) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, true, false>), dim3(blocks_for(p.n_items)), dim3(256), extra_lds, stream, p);
-      else if (use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, true, true>), dim3(blocks_for(p.n_items)), dim3(256), extra_lds, stream, p);
-      else hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, true, false>), dim3(blocks_for(p.n_items)), dim3(256), extra_lds, stream, p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(b->ek1, stream));
-      hipLaunchKernelGGL(sfs_stitch_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, stream, p);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(sfs_assemble_kernel, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, stream, p);
-      HIPCHK(hipGetLastError());
-      unsigned long long n_fb = 0;
+    return SVDSS_OK;
+  }
+
+  int plan() {
+    int max_blocks = 0, rc;
+    if ((rc = launch_grid(ix->device, &max_blocks))) return rc;
+    p.ix = svdss_device_view(ix);
+    const bool bs_possible = sfs_bs_possible(p.ix.sa != nullptr, p.ix.k, p.ix.n_dollar, SV_BS_MAX_DOLLAR);
+    pl = sfs_plan(kn, SfsShape{n_reads, total_syms, max_blocks, bs_possible, ix->deep_frac, ix->d_text && ix->d_sa, p.ix.k});
+    b->used_bs = pl.use_bs ? 1 : 0;
+    b->n_seg = pl.n_seg;
+    b->n_fallback = 0;
+    return SVDSS_OK;
+  }
+
+  int buffers() {
+    int rc;
+    if ((rc = b->rec.ensure((size_t)pl.rec_total * sizeof(uint2)))) return rc;
+    if ((rc = b->counts.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+    if ((rc = b->n_ext.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
+    if ((rc = b->out_off.ensure((size_t)(n_reads + 1) * sizeof(int64_t)))) return rc;
+    if ((rc = b->misc.ensure(64))) return rc;
+    if ((rc = b->sum.ensure(64))) return rc;
+
+    p.chunks = (const svdss_u4*)d_reads;
+    p.max_chunk = total_syms > 0 ? ((total_syms + 15) >> 4) - 1 : 0;
+    p.offsets = d_offsets;
+    p.n_reads = n_reads;
+    p.rec = (uint2*)b->rec.p;
+    p.rec_base = nullptr;
+    p.rec_cap = nullptr;
+    p.counts = (int64_t*)b->counts.p;
+    p.n_ext = (int64_t*)b->n_ext.p;
+    p.next_read = (unsigned long long*)b->misc.p;
+    p.assemble = (flags & SVDSS_SFS_ASSEMBLE) ? 1 : 0;
+    d_overflow = (unsigned long long*)b->misc.p + 1;
+    p.n_seg = 1;
+    p.seg_shift = 0;
+    p.seg_rec = nullptr;
+    p.seg_info = nullptr;
+    p.read_ids = nullptr;
+    p.sub_ids = nullptr;
+    p.n_sub = 0;
+    p.use_set = kn.use_set;
+    p.use_bs = pl.use_bs;
+    p.ticket_chunk = kn.ticket_chunk;
+    p.n_items = n_reads;
+    p.n_fallback = (unsigned long long*)b->misc.p + 2;
+    p.fallback_ids = nullptr;
+    p.epoch = ++b->epoch ? b->epoch : ++b->epoch;
+
+    if (pl.tiny) {
+      if ((rc = b->tiny.ensure(96))) return rc;
+      HIPCHK(hipMemsetAsync(b->tiny.p, 0, 96, stream));
+      if (total_syms > 0) HIPCHK(hipMemcpyAsync(b->tiny.p, d_reads, (size_t)total_syms, hipMemcpyDeviceToDevice, stream));
+      p.chunks = (const svdss_u4*)b->tiny.p;
+      p.max_chunk = 3;
+    }
+    if (pl.n_seg > 1) {
+      if ((rc = b->seg_rec.ensure((size_t)pl.seg_total * sizeof(uint4)))) return rc;
+      if ((rc = b->seg_info.ensure((size_t)pl.seg_info_n * sizeof(SvSegInfo)))) return rc;
+      if ((rc = b->fallback.ensure((size_t)pl.fallback_n * sizeof(int64_t)))) return rc;
+      if ((rc = b->seg_take.ensure((size_t)pl.seg_take_n * sizeof(int32_t)))) return rc;
+      p.seg_rec = (uint4*)b->seg_rec.p;
+      p.seg_info = (SvSegInfo*)b->seg_info.p;
+      p.fallback_ids = (int64_t*)b->fallback.p;
+      p.seg_take = (int32_t*)b->seg_take.p;
+    }
+
+    size_t tmp_bytes = 0, tmp2 = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, p.counts, (int64_t*)b->out_off.p,
+                                            (int)(n_reads + 1), stream));
+    HIPCHK(hipcub::DeviceReduce::Sum(nullptr, tmp2, p.n_ext, (int64_t*)b->sum.p, (int)n_reads, stream));
+    if (tmp2 > tmp_bytes) tmp_bytes = tmp2;
+    if ((rc = b->tmp.ensure(tmp_bytes))) return rc;
+    if (pl.use_order) {
+      if ((rc = b->order.ensure((size_t)n_reads * sizeof(int64_t)))) return rc;
+      if ((rc = b->order_cnt.ensure((size_t)(2 * n_reads + 2) * sizeof(int64_t)))) return rc;   // flags, their scan
+      size_t t3 = 0;
+      HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (int64_t*)b->order_cnt.p, (int64_t*)b->order_cnt.p + n_reads + 1,
+                                              (int)(n_reads + 1), stream));
+      if (t3 > b->tmp.cap && (rc = b->tmp.ensure(t3))) return rc;
+    }
+    return SVDSS_OK;
+  }
+
+  // heavy reads first (see sfs_order_kernel)
+  int order() {
+    int64_t* heavy = (int64_t*)b->order_cnt.p;
+    int64_t* hscan = heavy + n_reads + 1;
+    HIPCHK(hipMemsetAsync(heavy + n_reads, 0, sizeof(int64_t), stream));
+    hipLaunchKernelGGL(sfs_order_kernel, dim3((unsigned)((n_reads + 15) / 16)), dim3(256), 0, stream, p, heavy);
+    HIPCHK(hipGetLastError());
+    size_t t3 = b->tmp.cap;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, t3, heavy, hscan, (int)(n_reads + 1), stream));
+    hipLaunchKernelGGL(sfs_order_scatter_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, stream, n_reads, heavy,
+                       hscan, (int64_t*)b->order.p);
+    HIPCHK(hipGetLastError());
+    p.read_ids = (const int64_t*)b->order.p;
+    return SVDSS_OK;
+  }
+
+  // a segmented launch of q's items, then stitch and assemble over n of its reads
+  int segmented_launch(const SfsParams& q, int64_t n, size_t lds, bool timed) {
+    if (timed) HIPCHK(hipEventRecord(b->ek0, stream));
+    launch_search(ix->sa_wide, true, pl.use_bs, pl.blocks_for(q.n_items), lds, stream, q);
+    HIPCHK(hipGetLastError());
+    if (timed) HIPCHK(hipEventRecord(b->ek1, stream));
+    hipLaunchKernelGGL(sfs_stitch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, q);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(sfs_assemble_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, q);
+    HIPCHK(hipGetLastError());
+    return SVDSS_OK;
+  }
+
+  int search_segmented() {
+    int rc;
+    p.n_seg = pl.n_seg;
+    p.seg_shift = __builtin_ctz((unsigned)pl.n_seg);
+    p.n_items = n_reads * pl.n_seg;
+    if ((rc = segmented_launch(p, n_reads, kn.extra_lds, true))) return rc;
+    unsigned long long n_fb = 0;
+    HIPCHK(hipMemcpyAsync(&n_fb, p.n_fallback, sizeof n_fb, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    b->n_fallback = (int64_t)n_fb;
+    if (kn.debug) {
+      hipEvent_t e2;
+      (void)hipEventCreate(&e2);
+      (void)hipEventRecord(e2, stream);
+      (void)hipEventSynchronize(e2);
+      float t = 0.f;
+      (void)hipEventElapsedTime(&t, b->ev0, e2);
+      fprintf(stderr, "[svdss] segmented search + stitch: %.3f ms, %llu of %lld reads to redo\n", t, n_fb,
+              (long long)n_reads);
+      sfs_report_op_counts();
+      (void)hipEventDestroy(e2);
+    }
+    // the fallback ladder (sfs_next_level) over the reads whose chains could not be stitched
+    int lvl_seg = pl.n_seg;
+    while (n_fb > 0) {
+      lvl_seg = sfs_next_level(lvl_seg, n_fb, kn.fallback_direct);
+      if ((rc = b->fallback2.ensure((size_t)n_fb * sizeof(int64_t)))) return rc;
+      HIPCHK(hipMemcpyAsync(b->fallback2.p, p.fallback_ids, (size_t)n_fb * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+      SfsParams q = p;
+      q.read_ids = (const int64_t*)b->fallback2.p;
+      HIPCHK(hipMemsetAsync(b->misc.p, 0, 8, stream));                    // next_read
+      if (lvl_seg == 1) {
+        q.n_seg = 1;
+        q.n_items = (int64_t)n_fb;
+        launch_search(ix->sa_wide, false, pl.use_bs, pl.blocks_for(q.n_items), 0, stream, q);
+        HIPCHK(hipGetLastError());
+        break;
+      }
+      HIPCHK(hipMemsetAsync(p.n_fallback, 0, 8, stream));
+      q.n_seg = lvl_seg;
+      q.seg_shift = __builtin_ctz((unsigned)lvl_seg);
+      q.n_items = (int64_t)n_fb * lvl_seg;
+      q.sub_ids = q.read_ids;
+      q.n_sub = (int64_t)n_fb;
+      q.epoch = ++b->epoch;
+      if ((rc = segmented_launch(q, (int64_t)n_fb, 0, false))) return rc;
       HIPCHK(hipMemcpyAsync(&n_fb, p.n_fallback, sizeof n_fb, hipMemcpyDeviceToHost, stream));
       HIPCHK(hipStreamSynchronize(stream));
-      b->n_fallback = (int64_t)n_fb;
-      if (getenv("SVDSS_DEBUG")) {
-        hipEvent_t e2;
-        (void)hipEventCreate(&e2);
-        (void)hipEventRecord(e2, stream);
-        (void)hipEventSynchronize(e2);
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, b->ev0, e2);
-        fprintf(stderr, "[svdss] segmented search + stitch: %.3f ms, %llu of %lld reads to redo\n", t, n_fb,
-                (long long)n_reads);
-        sfs_report_op_counts();
-        (void)hipEventDestroy(e2);
-      }
-      // reads whose chains could not be stitched are searched again with a quarter of the segments (their
-      // boundaries fall elsewhere), at the end one lane per read
-      int lvl_seg = n_seg;
-      // (a handful of reads: one lane each at once -- a launch of so few lanes lasts as long as its longest read either
-      // way, and an intermediate level that fails again costs that time twice; SVDSS_FALLBACK_DIRECT moves the limit)
-      const unsigned long long direct = getenv("SVDSS_FALLBACK_DIRECT") ? (unsigned long long)atoll(getenv("SVDSS_FALLBACK_DIRECT")) : 64ull;
-      while (n_fb > 0) {
-        lvl_seg = lvl_seg / 4 < 1 || n_fb <= direct ? 1 : lvl_seg / 4;
-        if ((rc = b->fallback2.ensure((size_t)n_fb * sizeof(int64_t)))) return rc;
-        HIPCHK(hipMemcpyAsync(b->fallback2.p, p.fallback_ids, (size_t)n_fb * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-        SfsParams q = p;
-        q.read_ids = (const int64_t*)b->fallback2.p;
-        HIPCHK(hipMemsetAsync(b->misc.p, 0, 8, stream));                    // next_read
-        if (lvl_seg == 1) {
-          q.n_seg = 1;
-          q.n_items = (int64_t)n_fb;
-          if (wide && use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, false, true>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-          else if (wide) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, false, false>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-          else if (use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, false, true>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-          else hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, false, false>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-          HIPCHK(hipGetLastError());
-          break;
-        }
-        HIPCHK(hipMemsetAsync(p.n_fallback, 0, 8, stream));
-        q.n_seg = lvl_seg;
-        q.seg_shift = __builtin_ctz((unsigned)lvl_seg);
-        q.n_items = (int64_t)n_fb * lvl_seg;
-        q.sub_ids = q.read_ids;
-        q.n_sub = (int64_t)n_fb;
-        q.epoch = ++b->epoch;
-        if (wide && use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, true, true>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-        else if (wide) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, true, false>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-        else if (use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, true, true>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-        else hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, true, false>), dim3(blocks_for(q.n_items)), dim3(256), 0, stream, q);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(sfs_stitch_kernel, dim3((unsigned)((n_fb + 255) / 256)), dim3(256), 0, stream, q);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(sfs_assemble_kernel, dim3((unsigned)((n_fb + 3) / 4)), dim3(256), 0, stream, q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&n_fb, p.n_fallback, sizeof n_fb, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-      }
-    } else {
-      p.n_seg = 1;
-      p.n_items = n_reads;
-      if (pass == 0) HIPCHK(hipEventRecord(b->ek0, stream));
-      const char* xl1 = getenv("SVDSS_EXTRA_LDS");   // (developer knob, as above)
-      const size_t xlds = xl1 ? (size_t)atol(xl1) : 0;
-      if (wide && use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, false, true>), dim3(blocks_for(n_reads)), dim3(256), xlds, stream, p);
-      else if (wide) hipLaunchKernelGGL((sfs_search2_kernel<uint64_t, false, false>), dim3(blocks_for(n_reads)), dim3(256), xlds, stream, p);
-      else if (use_bs_kernel) hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, false, true>), dim3(blocks_for(n_reads)), dim3(256), xlds, stream, p);
-      else hipLaunchKernelGGL((sfs_search2_kernel<uint32_t, false, false>), dim3(blocks_for(n_reads)), dim3(256), xlds, stream, p);
-      if (pass == 0) HIPCHK(hipEventRecord(b->ek1, stream));
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(b->ev1, stream));
+    return SVDSS_OK;
+  }
+
+  int search_plain(int pass) {
+    p.n_seg = 1;
+    p.n_items = n_reads;
+    if (pass == 0) HIPCHK(hipEventRecord(b->ek0, stream));
+    launch_search(ix->sa_wide, false, pl.use_bs, pl.blocks_for(n_reads), kn.extra_lds, stream, p);
+    if (pass == 0) HIPCHK(hipEventRecord(b->ek1, stream));
+    return SVDSS_OK;
+  }
+
+  // scan of the counts, the total, gather, sum of the extensions, overflow count; the times of the pass
+  int collect(int pass, unsigned long long* n_over) {
+    int rc;
     size_t tb = b->tmp.cap;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, tb, p.counts, (int64_t*)b->out_off.p,
                                             (int)(n_reads + 1), stream));
@@ -1031,18 +1012,17 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
     HIPCHK(hipMemcpyAsync(&total, (int64_t*)b->out_off.p + n_reads, sizeof(int64_t),
                           hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    if (p.n_seg == 1 && getenv("SVDSS_DEBUG")) sfs_report_op_counts();
+    if (p.n_seg == 1 && kn.debug) sfs_report_op_counts();
     if ((rc = b->out_qs.ensure((size_t)(total + 1) * sizeof(int32_t)))) return rc;
     if ((rc = b->out_len.ensure((size_t)(total + 1) * sizeof(int32_t)))) return rc;
-    hipLaunchKernelGGL(sfs_gather_kernel, dim3(gblocks), dim3(256), 0, stream, p,
+    hipLaunchKernelGGL(sfs_gather_kernel, dim3(pl.gather_blocks), dim3(256), 0, stream, p,
                        (const int64_t*)b->out_off.p, (int32_t*)b->out_qs.p, (int32_t*)b->out_len.p,
                        d_overflow);
     HIPCHK(hipGetLastError());
     tb = b->tmp.cap;
     HIPCHK(hipcub::DeviceReduce::Sum(b->tmp.p, tb, p.n_ext, (int64_t*)b->sum.p, (int)n_reads, stream));
-    unsigned long long n_over = 0;
     int64_t total_ext = 0;
-    HIPCHK(hipMemcpyAsync(&n_over, d_overflow, sizeof n_over, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(n_over, d_overflow, sizeof *n_over, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(&total_ext, b->sum.p, sizeof total_ext, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0.f;
@@ -1055,12 +1035,15 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
     }
     b->total = total;
     b->total_ext = total_ext;
-    if (n_over == 0) break;
-    if (pass == 1) return SVDSS_ERANGE;  // cannot happen: capacities were exact
-    // Some read produced more SFS than its default region holds (e.g. a read
-    // of N against an N-free reference gives one SFS per base).  The counts
-    // are exact, so rerun with regions sized from them.
-    if ((rc = b->rec.ensure((size_t)(total + 1) * sizeof(uint2)))) return rc;
+    return SVDSS_OK;
+  }
+
+  // Some read produced more SFS than its default region holds (e.g. a read
+  // of N against an N-free reference gives one SFS per base).  The counts
+  // are exact, so rerun with regions sized from them.
+  int exact_capacity() {
+    int rc;
+    if ((rc = b->rec.ensure((size_t)(b->total + 1) * sizeof(uint2)))) return rc;
     if ((rc = b->base2.ensure((size_t)(2 * (n_reads + 1)) * sizeof(int64_t)))) return rc;
     int64_t* base2 = (int64_t*)b->base2.p;
     int64_t* cap2 = base2 + (n_reads + 1);
@@ -1071,22 +1054,31 @@ extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint
     p.rec = (uint2*)b->rec.p;
     p.rec_base = base2;
     p.rec_cap = cap2;
+    return SVDSS_OK;
   }
-  return SVDSS_OK;
-}
+};
 
-static int batch_for_host_entry(const svdss_index_t* ix, svdss_sfs_batch_t** out, svdss_sfs_batch** bp) {
-  HIPCHK(hipSetDevice(ix->device));
-  svdss_sfs_batch* b = *out;
-  if (!b) {
-    b = new (std::nothrow) svdss_sfs_batch();
-    if (!b) return SVDSS_ENOMEM;
-    b->device = ix->device;
-    *out = b;
-  }
-  if (!b->own_stream) HIPCHK(svdss_make_stream(&b->own_stream, "SVDSS_SEARCH_CUS"));
-  *bp = b;
-  return SVDSS_OK;
+extern "C" int svdss_sfs_search_batch_device(const svdss_index_t* ix, const uint8_t* d_reads,
+                                             const int64_t* d_offsets, int64_t n_reads,
+                                             int64_t total_syms, int32_t flags, void* stream_,
+                                             svdss_sfs_batch_t** out) {
+  if (!ix || !out || n_reads < 0 || total_syms < 0) return SVDSS_EINVAL;
+  if (n_reads > 0 && (!d_reads || !d_offsets)) return SVDSS_EINVAL;
+  if (((uintptr_t)d_reads & 15u) != 0) return SVDSS_EINVAL;
+  if (ix->device < 0 || !ix->d_blocks) return SVDSS_ENODEV;
+  svdss_sfs_batch* b = nullptr;
+  int rc;
+  if ((rc = batch_get(ix, out, false, &b))) return rc;
+  if (b->device != ix->device) return SVDSS_EINVAL;
+  if (!b->ev0) HIPCHK(hipEventCreate(&b->ev0));
+  if (!b->ev1) HIPCHK(hipEventCreate(&b->ev1));
+  if (!b->ek0) HIPCHK(hipEventCreate(&b->ek0));
+  if (!b->ek1) HIPCHK(hipEventCreate(&b->ek1));
+  b->reset_results();
+  b->n_reads = n_reads;
+  if (n_reads == 0) return SVDSS_OK;
+  SfsRun run{b, ix, d_reads, d_offsets, n_reads, total_syms, flags, (hipStream_t)stream_};
+  return run.run();
 }
 
 extern "C" int svdss_sfs_search_batch(const svdss_index_t* ix, const uint8_t* reads,
@@ -1097,9 +1089,9 @@ extern "C" int svdss_sfs_search_batch(const svdss_index_t* ix, const uint8_t* re
   if (ix->device < 0 || !ix->d_blocks) return SVDSS_ENODEV;
   svdss_sfs_batch* b = nullptr;
   int rc;
-  if ((rc = batch_for_host_entry(ix, out, &b))) return rc;
+  if ((rc = batch_get(ix, out, true, &b))) return rc;
   if (n_reads == 0) {
-    b->n_reads = 0; b->total = 0; b->total_ext = 0; b->kernel_ms = 0.0; b->search_ms = 0.0;
+    b->reset_results();
     return SVDSS_OK;
   }
   if (offsets[0] != 0) return SVDSS_EINVAL;
@@ -1150,9 +1142,9 @@ extern "C" int svdss_sfs_search_batch_bam(const svdss_index_t* ix, const uint8_t
   if (ix->device < 0 || !ix->d_blocks) return SVDSS_ENODEV;
   svdss_sfs_batch* b = nullptr;
   int rc;
-  if ((rc = batch_for_host_entry(ix, out, &b))) return rc;
+  if ((rc = batch_get(ix, out, true, &b))) return rc;
   if (n_reads == 0) {
-    b->n_reads = 0; b->total = 0; b->total_ext = 0; b->kernel_ms = 0.0; b->search_ms = 0.0;
+    b->reset_results();
     return SVDSS_OK;
   }
   std::vector<int64_t> sym_off((size_t)n_reads + 1, 0);

@@ -312,6 +312,28 @@ def test_segmented_search_is_exact(monkeypatch, segments):
         pp.close()
 
 
+def test_knobs_are_read_by_every_call(monkeypatch):
+    """The knobs of the search batch belong to a call, not to the batch object or the process: one index, one PingPong,
+    SVDSS_SEGMENTS unset (4 x 131,072 resident lanes / 512 reads: the most, 8 segments), set to 2, unset again."""
+    monkeypatch.delenv("SVDSS_SEGMENTS", raising=False)
+    ref = synth.make_reference([200000], seed=1)
+    hap, _ = synth.implant_svs(ref, 4, seed=2, min_len=50, max_len=300)
+    flat, offs, _ = synth.simulate_reads(hap, 512, 2048, 0.005, seed=3)
+    ix = svdss_amd.FMDIndex.build(ref).to_device(0)
+    c, q, l, e = O.OracleFMD.build(ref).search_batch(flat, offs, True)
+    pp = svdss_amd.PingPong(ix, assemble=True)
+    for segments in (None, "2", None):
+        if segments is None:
+            monkeypatch.delenv("SVDSS_SEGMENTS", raising=False)
+        else:
+            monkeypatch.setenv("SVDSS_SEGMENTS", segments)
+        got = pp.ping_pong_search(flat, offs)
+        assert pp.last_segments == (8 if segments is None else int(segments))
+        assert (got.counts == c).all() and (got.n_ext == e).all()
+        assert (got.qs == q).all() and (got.len == l).all()
+    pp.close()
+
+
 @pytest.mark.parametrize("n_reads,direct", [(24, None), (150, None), (150, "0"), (24, "1000000")])
 def test_reads_with_long_novel_insertions_in_segmented_launches(monkeypatch, n_reads, direct):
     """What `SVDSS search` sees after `SVDSS smooth`: reads that equal the reference except for one long insertion of
