@@ -219,6 +219,7 @@ extern "C" int svdss_index_load_blocks(const char* path, svdss_index_t** out) {
 extern "C" int svdss_index_save_fmd(const svdss_index_t* ix, const char* path) {
   if (!ix || !path) return SVDSS_EINVAL;
   { const int rc = materialize(ix); if (rc != SVDSS_OK) return rc; }
+  if (ix->blocks.empty()) return SVDSS_ENODEV;   // (a replica of the rank blocks alone keeps no host copy: svdss_index_replicate)
   std::vector<uint8_t> bwt;
   try { bwt.resize((size_t)ix->n); } catch (...) { return SVDSS_ENOMEM; }
   svdss_index_decode_bwt(ix, bwt.data());
@@ -484,6 +485,7 @@ extern "C" int svdss_index_acc(const svdss_index_t* ix, int64_t acc[7]) {
 extern "C" int svdss_index_bwt(const svdss_index_t* ix, uint8_t* bwt_out) {
   if (!ix || !bwt_out) return SVDSS_EINVAL;
   { const int rc = materialize(ix); if (rc != SVDSS_OK) return rc; }
+  if (ix->blocks.empty()) return SVDSS_ENODEV;   // (a replica of the rank blocks alone keeps no host copy: svdss_index_replicate)
   svdss_index_decode_bwt(ix, bwt_out);
   return SVDSS_OK;
 }
@@ -797,7 +799,7 @@ static SvdssDevIndex host_view(const svdss_index* ix) {
 
 extern "C" int64_t svdss_index_count(const svdss_index_t* ix, const uint8_t* pat, int64_t len) {
   if (!ix || !pat || len <= 0) return -1;
-  if (materialize(ix) != SVDSS_OK) return -1;
+  if (materialize(ix) != SVDSS_OK || ix->blocks.empty()) return -1;
   const SvdssDevIndex v = host_view(ix);
   int c = pat[len - 1];
   if (c > 5) return -1;

@@ -386,7 +386,7 @@ int svdss_index_load_blocks_host(const char* path, svdss_index* ix) {
   ix->n = h.n;
   memcpy(ix->acc, h.acc, sizeof h.acc);
   ix->n_contigs = h.n_contigs;
-  ix->sa_wide = h.n >= (int64_t)0x7fffffff;
+  ix->sa_wide = h.n >= (int64_t)0x7fffffff || getenv("SVDSS_FORCE_SA64") != nullptr;  // (the test hook of the builders)
   return SVDSS_OK;
 }
 

@@ -125,6 +125,24 @@ class FMDIndex:
         """ropebwt3's rld0 dump (`ropebwt3 build -d` / upstream `SVDSS index`)."""
         check(lib.svdss_index_save_fmd(self._h, path.encode()), "svdss_index_save_fmd")
 
+    def append_blocks(self, path: str) -> None:
+        """The rank blocks and '$' rows behind the records of the file save_records wrote (what `SVDSS index` leaves in
+        its sidecar): load_blocks / attach_blocks of it give the index as a rank structure alone."""
+        check(lib.svdss_index_append_blocks(self._h, path.encode()), "svdss_index_append_blocks")
+
+    @classmethod
+    def load_blocks(cls, path: str) -> "FMDIndex":
+        """The index as its rank blocks alone (no records, no text, no suffix array): what `SVDSS search` makes resident
+        when it has few reads to search.  SvdssError (SVDSS_EINVAL) where the file has no such section."""
+        h = C.c_void_p()
+        check(lib.svdss_index_load_blocks(path.encode(), C.byref(h)), "svdss_index_load_blocks")
+        return cls(h.value)
+
+    def attach_blocks(self, path: str) -> "FMDIndex":
+        """The same on a handle that is not resident yet: its records are dropped for the file's rank blocks."""
+        check(lib.svdss_index_attach_blocks(self._h, path.encode()), "svdss_index_attach_blocks")
+        return self
+
     def close(self) -> None:
         if self._h:
             lib.svdss_index_free(self._h)

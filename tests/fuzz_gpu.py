@@ -142,9 +142,15 @@ def fuzz_search(rng, out_dir, it):
         env["SVDSS_FORCE_SA64"] = "1"
     if rng.random() < 0.3:
         env["SVDSS_SEGMENTS"] = "1"
+    # a third of the iterations: the index as its rank blocks alone (what `search` makes resident for few reads), with a
+    # random order of its small table
+    rank_only = rng.random() < 1 / 3
+    if rank_only:
+        env["SVDSS_LF_KMER"] = str(int(rng.integers(0, 11)))
+    route = "rank_only" if rank_only else "full"
     reads = _weird_reads(rng, contigs, int(rng.integers(1, 500)))
     flat, offs = svdss_amd.pack_reads(reads)
-    old = {k_: os.environ.get(k_) for k_ in ("SVDSS_KMER", "SVDSS_SA_PIECE", "SVDSS_FORCE_SA64", "SVDSS_SEGMENTS")}
+    old = {k_: os.environ.get(k_) for k_ in ("SVDSS_KMER", "SVDSS_SA_PIECE", "SVDSS_FORCE_SA64", "SVDSS_SEGMENTS", "SVDSS_LF_KMER")}
     for k_ in old:
         os.environ.pop(k_, None)
     os.environ.update(env)
@@ -156,6 +162,13 @@ def fuzz_search(rng, out_dir, it):
         v = ix.verify(1)
         if v["bad_order"] or v["bad_bwt"] or v["bad_range"] or v["bad_block"] or v["bad_dollar"]:
             raise Mismatch(f"index verify {v}: " + _dump(out_dir, f"search_{it}", contigs=contigs, env=str(env)))
+        if rank_only:
+            from tests import rank_only_cases
+            ix, want_k = rank_only_cases.rank_only(contigs, full=ix)
+            ix.to_device(0)
+            if ix.kmer_k != want_k or rank_only_cases.records_code(ix) != rank_only_cases.ENODEV:
+                raise Mismatch(f"not the rank blocks alone (order {ix.kmer_k}, expected {want_k}): " +
+                               _dump(out_dir, f"search_{route}_{it}", contigs=contigs, env=str(env)))
         for assemble in (False, True):
             pp = svdss_amd.PingPong(ix, assemble=assemble)
             got = pp.ping_pong_search(flat, offs)
@@ -163,8 +176,8 @@ def fuzz_search(rng, out_dir, it):
             c, q, l, e = fm.search_batch(flat, offs, assemble)
             if not ((got.counts == c).all() and (got.n_ext == e).all() and len(got.qs) == len(q) and (got.qs == q).all() and (got.len == l).all()):
                 bad = np.nonzero((got.counts != c) | (got.n_ext != e))[0]
-                raise Mismatch(f"search differs (assemble={assemble}, env={env}, first bad read {bad[:1]}): " +
-                               _dump(out_dir, f"search_{it}", contigs=contigs, reads=reads, env=str(env)))
+                raise Mismatch(f"search differs (route={route}, assemble={assemble}, env={env}, first bad read {bad[:1]}): " +
+                               _dump(out_dir, f"search_{route}_{it}", contigs=contigs, reads=reads, env=str(env)))
         ix.close()
     finally:
         for k_ in env:

@@ -2,7 +2,7 @@
 // fastx_reader.h, rld0.cpp) run over one input file, for tests/test_host_io_robustness.py: built with
 // -fsanitize=address,undefined, fed valid files and damaged ones.  A reader may accept a file or refuse it with its
 // error message; it may not read outside its buffers, overflow, throw out of main or hang.  Test infrastructure.
-//   host_io_harness bam <file> | bai <file.bam> | fastx <file> | fmd <file> | sidecar <file> | sfs <file> | scan <file.bam> | regions <file.bam>
+//   host_io_harness bam <file> | bai <file.bam> | fastx <file> | fmd <file> | sidecar <file> | blocks <file> | sfs <file> | scan <file.bam> | regions <file.bam>
 // exit 0: read to a clean end; 1: the reader reported an error (printed); anything else: a finding.
 #include <cstdint>
 #include <cstdio>
@@ -248,6 +248,20 @@ static int run_sidecar(const std::string& path) {
   return 0;
 }
 
+static int run_blocks(const std::string& path) {
+  // the rank blocks and '$' rows behind the records of a sidecar ("SVDSSBK1"): what `search` makes resident for few reads
+  svdss_index ix;
+  const int rc = svdss_index_load_blocks_host(path.c_str(), &ix);
+  if (rc != 0) { printf("error: blocks %d\n", rc); return 1; }
+  touch(ix.blocks.data(), ix.blocks.size() * sizeof(svdss_u4));
+  touch(ix.dollar.data(), ix.dollar.size() * sizeof(int64_t));
+  std::vector<uint8_t> bwt((size_t)ix.n);
+  svdss_index_decode_bwt(&ix, bwt.data());
+  touch(bwt.data(), bwt.size());
+  printf("blocks: %lld symbols, %zu '$' rows\n", (long long)ix.n, ix.dollar.size());
+  return 0;
+}
+
 static int run_sfs(const std::string& path) {
   // the piecewise reader against the line-by-line one, with several piece counts
   SfsMap want;
@@ -280,6 +294,7 @@ int main(int argc, char** argv) {
     else if (mode == "fastx") rc = run_fastx(path);
     else if (mode == "fmd") rc = run_fmd(path);
     else if (mode == "sidecar") rc = run_sidecar(path);
+    else if (mode == "blocks") rc = run_blocks(path);
     else if (mode == "sfs") rc = run_sfs(path);
     else if (mode == "scan") rc = run_scan(path);
     else if (mode == "regions") rc = run_regions(path);

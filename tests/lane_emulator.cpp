@@ -36,7 +36,8 @@ int64_t emu2_run(const svdss_index* ix, const uint8_t* reads_padded, const int64
   v.pad_ = 0;
   memcpy(v.acc, ix->acc, sizeof v.acc);
   std::vector<uint8_t> text((size_t)ix->n + 128 + 16, 0);
-  memcpy(text.data() + 64, ix->text.data(), (size_t)ix->n);
+  // (a handle that holds the rank blocks alone has no text: what is there is copied, the rest stays '$')
+  if (!ix->text.empty()) memcpy(text.data() + 64, ix->text.data(), std::min(ix->text.size(), (size_t)ix->n));
   v.text = text.data() + 64;
   v.sa = (use_text & 1) ? (ix->sa64.empty() ? (const void*)ix->sa32.data() : (const void*)ix->sa64.data()) : nullptr;
   const bool use_set = (use_text & 2) != 0;   // bit 1: SET mode (2-4 occurrences followed in the text)
@@ -228,7 +229,8 @@ extern "C" int64_t emu_search2(const svdss_index* ix, const uint8_t* reads_padde
                                int assemble, int K, int use_text, int64_t* counts, int32_t* qs,
                                int32_t* len, int64_t cap_total, int64_t* n_ext, int64_t* op_counts,
                                int n_seg, int64_t* seg_stats) {
-  if (ix->sa64.empty())
+  // (the interval width of the handle: 64-bit with a 64-bit suffix array, and on the rank blocks alone when sa_wide says so)
+  if (ix->sa64.empty() && !(ix->sa_wide && ix->sa32.empty()))
     return emu2_run<uint32_t>(ix, reads_padded, offsets, n_reads, total_syms, assemble, K, use_text,
                               counts, qs, len, cap_total, n_ext, op_counts, n_seg, seg_stats);
   return emu2_run<uint64_t>(ix, reads_padded, offsets, n_reads, total_syms, assemble, K, use_text,

@@ -49,7 +49,7 @@ def test_batches_smaller_than_one_fetch():
 
 # ---- v2 state machine (sfs_core2.h): k-mer table + LF + unique-match TEXT mode ----
 
-V2_CONFIGS = [(0, False), (0, True), (5, False), (7, True), (10, True)]
+V2_CONFIGS = [(0, False), (0, True), (5, False), (8, False), (7, True), (10, True)]
 
 
 def test_v2_golden_through_lane_code():
