@@ -778,6 +778,10 @@ double svdss_aln_batch_kernel_ms(const svdss_aln_batch_t* b);
  * with more than one wavefront, out[2] the kernel's wavefronts per workgroup, the largest over the chunks (1, 4 or 8),
  * out[3] chunks run again with one wavefront per pair after a wait that did not end.  All 0 after an empty batch. */
 int svdss_aln_batch_launch_info(const svdss_aln_batch_t* b, int64_t out[4]);
+/* what the last call computed of its matrices (csrc/aln_band.h; SVDSS_ALIGN_BAND): out[0] wavefront steps executed, out[1]
+ * the steps of the full matrices, out[2] pairs run as one band of diagonals, out[3] pairs run as two bands with the gap
+ * carried across.  All 0 after an empty batch. */
+int svdss_aln_batch_band_info(const svdss_aln_batch_t* b, int64_t out[4]);
 /* scores int32[n_pairs], n_cigar int64[n_pairs], cigar uint32[total_cigar] (pairs concatenated) */
 int svdss_aln_batch_fetch(const svdss_aln_batch_t* b, int32_t* scores, int64_t* n_cigar, uint32_t* cigar);
 void svdss_aln_batch_free(svdss_aln_batch_t* b);

@@ -190,6 +190,7 @@ SIGNATURES = {
     "svdss_aln_batch_cells": (_i64, [_p]),
     "svdss_aln_batch_kernel_ms": (C.c_double, [_p]),
     "svdss_aln_batch_launch_info": (C.c_int, [_p, _p]),
+    "svdss_aln_batch_band_info": (C.c_int, [_p, _p]),
     "svdss_aln_batch_fetch": (C.c_int, [_p, _p, _p, _p]),
     "svdss_aln_batch_free": (None, [_p]),
     "svdss_poa_consensus_batch": (C.c_int, [_p, _p, _p, _i64, _i32, C.POINTER(_p)]),

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/svdss_hip.h"
+#include "aln_band.h"
 #include "call_streams.h"
 #include "dev_arena.h"
 #include "hip_check.h"
@@ -46,6 +47,7 @@ struct AlnPair {
   int32_t ql, tl;
   int32_t slot;           // index of the pair in the caller's order (results are written there)
   int32_t waves;          // wavefronts that share the pair's stripes (1, or the kernel's W for the longest pairs)
+  AlnBand band;           // the diagonals an optimal alignment can cross (aln_band.h); ALN_FULL: the whole matrix
 };
 
 __device__ __forceinline__ int dp_shr1(int x) {   // value of the lane below (lane 0: unchanged, it is overwritten)
@@ -53,8 +55,8 @@ __device__ __forceinline__ int dp_shr1(int x) {   // value of the lane below (la
 }
 
 // One wavefront per pair -- or, for the longest pairs of a batch, W wavefronts (round 5): a pair is a chain of
-// (tl / 64) x (ql + 63) dependent steps, so a launch lasts as long as its longest pair (26 ms of a bench step's
-// realignment, all of it the 2.6 kb x 2.6 kb pairs, while the whole batch is 8 ms of work).  The stripes of a pair only
+// (tl / 64) x (ql + 63) dependent steps, so a launch lasts as long as its longest pair (with full matrices: 26 ms of a bench
+// step's realignment, all of it the 2.6 kb x 2.6 kb pairs, while the whole batch was 8 ms of work).  The stripes of a pair only
 // depend on each other through the boundary row, column by column: stripe s + 1 can run three blocks of 64 columns behind
 // stripe s.  Wavefront v of the pair's workgroup takes stripes v, v + W, ...; the boundary rows go through W + 1 buffers
 // in HBM (workgroup-scope release / loads: producer and consumer sit on the same CU and share its L1), progress through one LDS word per buffer, (stripe + 1) << 20 | columns done -- the stripe number in
@@ -64,19 +66,26 @@ __device__ __forceinline__ int dp_shr1(int x) {   // value of the lane below (la
 // Cell (i, j): i indexes the target, j the query.
 // Recurrences and tie rules are those of ksw2's extd2 (left-aligned), see the oracle
 // (oracle/svdss_oracle_call.c, orc_ksw_extd2_global) which this kernel must match bit for bit.
-template <int W>
-__global__ void __launch_bounds__(64 * W) align_wave_kernel(
-    const AlnPair* pairs, const uint8_t* qsyms, const uint8_t* tsyms, int m, const int8_t* mat_g,
-    GapModel gm, int32_t* ws, uint8_t* dirs, uint32_t* cigars, int32_t* scores, int32_t* n_cigar, int32_t* abort_flag) {
-  const AlnPair P = pairs[blockIdx.x];
+//
+// BAND (aln_band.h has the bound and why the result stays bit-exact): only the cells on the pair's live diagonals are
+// computed.  A stripe runs the steps in which some lane's cell is live (aln_band_stripe_steps: one range, or two with a
+// jump between them); in an executed step a lane whose cell is not live hands on "no path" (DP_NEG) instead.  After a jump
+// every value a lane takes from the skipped steps is "no path", set in one place (`repair` below).  The boundary row of the
+// stripe above holds only the columns that stripe's lane 63 found live: the READER substitutes "no path" for every other
+// column (fetch, and lane 0's diagonal value after a jump), so nothing a buffer holds from an earlier stripe or an earlier
+// call is ever used.  A dead interior is crossed by one gap run (ALN_CARRY): horizontally the lane keeps F / F2 in its own
+// registers, - e and - e2 per cell; vertically the cell on diagonal c2 leaves what the cell below it would receive in two
+// per-column arrays behind the boundary buffers, and the cell of that column on diagonal c1 -- at least two stripes
+// further down, so after every stripe above it has passed the column -- takes it, less e and e2 per skipped row.
+// The backtrack never reads a direction byte of a cell that was not computed.
+template <int W, bool BAND>
+__device__ __forceinline__ void align_pair(
+    const AlnPair& P, const uint8_t* qsyms, const uint8_t* tsyms, int m, const int8_t* mat_g,
+    const GapModel& gm, int32_t* ws, uint8_t* dirs, uint32_t* cigars, int32_t* scores, int32_t* n_cigar, int32_t* abort_flag) {
   const int ql = P.ql, tl = P.tl;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int Wp = W > 1 ? P.waves : 1, NB = Wp + 1;
-  if (wave >= Wp) return;
-  if (ql <= 0 || tl <= 0) {   // ksw2 returns before touching ez: score 0, no CIGAR
-    if (lane == 0) { scores[P.slot] = 0; n_cigar[P.slot] = 0; }
-    return;
-  }
+  // (the kernel holds both instantiations of this function, so these W + 2 words are allocated twice: 2 x 24 bytes at W = 4)
   __shared__ volatile int32_t prog[W + 1];
   __shared__ int32_t s_score;
   const uint8_t* q = qsyms + P.q_off;
@@ -84,6 +93,14 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
   uint8_t* dir = dirs + P.dir_off;
   const int bstride = ql + 64;
   int32_t* bnd = ws + P.bnd_off;
+  const AlnBand B = P.band;
+  const bool horiz = BAND && B.mode == ALN_CARRY && ql > tl, vert = BAND && B.mode == ALN_CARRY && ql < tl;
+  const int dead_w = B.c2 - B.c1 - 1;
+  int32_t* xarr = bnd + (int64_t)NB * 3 * bstride;   // vert: E, E2 arriving below the upper band's last cell, per column
+  auto decayed = [](int32_t v, int per, int n) {     // v - per * n, not below "no path"
+    const int64_t x = (int64_t)v - (int64_t)per * n;
+    return x < DP_NEG ? (int32_t)DP_NEG : (int32_t)x;
+  };
   // boundary above row 0 ("stripe -1", buffer NB - 1): H(-1, j) = -gap(j + 1), no gap state
   {
     int32_t* b0 = bnd + (int64_t)(NB - 1) * 3 * bstride;
@@ -110,49 +127,92 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
       const int ti = row_ok ? t[i] : 0;
       for (int k = 0; k < m; ++k) rowbits |= (uint64_t)(uint8_t)mat_g[ti * m + k] << (8 * k);
     }
-    int32_t Hl = -dp_gap(i + 1, gm), Fl = DP_NEG, F2l = DP_NEG;          // (i, j-1): the column left of j = 0
+    // (i, j-1): the column left of j = 0, exact where column 0 is live for the row
+    int32_t Hl = !BAND || aln_band_live(-i, B) ? -dp_gap(i + 1, gm) : DP_NEG, Fl = DP_NEG, F2l = DP_NEG;
     int32_t Hout = 0, Eout = DP_NEG, E2out = DP_NEG;                    // what the lane above reads next step
     int32_t Hd = 0;                                                     // (i-1, j-1)
     int qcur = 0;
     const int n_steps = ql + rows - 1;
+    AlnStripeSteps R;
+    if (BAND) R = aln_band_stripe_steps(ql, tl, s, B);
+    else { R.a[0] = 0; R.e[0] = n_steps; R.a[1] = R.e[1] = n_steps; }
+    const int dl = (s << 6) + 2 * lane;                                 // the lane's cell at step tau is on diagonal tau - dl
+    // vert: the carried gap arrives at the row's cell on diagonal c1, column xcol, step xcol + lane
+    const int xcol = B.c1 + i;
+    int32_t Xv = DP_NEG, X2v = DP_NEG;
     // the next 64 columns of the query and of the boundary row, one per lane, fetched a block ahead
     int32_t nH = 0, nE = 0, nE2 = 0;
     int nq = 0;
+    const int32_t none = BAND ? DP_NEG : 0;
+    // several wavefronts: wait until the stripe above has announced `need` columns
+    auto wait_above = [&](int need) {
+      int polls = 0;
+      for (;;) {
+        const int32_t v = prog[in_slot];
+        if ((v >> 20) == s && (v & 0xFFFFF) >= need) return;
+        if (++polls > (1 << 22)) { aborted = true; return; }
+        __builtin_amdgcn_s_sleep(2);
+      }
+    };
     auto fetch = [&](int tau0) {
       const int jj = tau0 + lane;
-      const bool in = jj < ql;
-      nq = in ? q[jj] : 0;
+      // BAND: a column the stripe above did not find live reads as "no path", whatever the buffer holds
+      const bool in = jj < ql && (!BAND || aln_band_live(jj - (s << 6) + 1, B));
+      const bool xin = vert && row_ok && xcol >= 0 && xcol < ql && xcol + lane >= tau0 && xcol + lane < tau0 + 64;
+      nq = jj < ql ? q[jj] : 0;
       if (W > 1 && Wp > 1) {
         // columns tau0 .. tau0 + 63 of the stripe above: wait until its wavefront has them in memory
-        const int need = tau0 + 64 < ql ? tau0 + 64 : ql;
-        int polls = 0;
-        for (;;) {
-          const int32_t v = prog[in_slot];
-          if ((v >> 20) == s && (v & 0xFFFFF) >= need) break;
-          if (++polls > (1 << 22)) { aborted = true; break; }
-          __builtin_amdgcn_s_sleep(2);
-        }
+        wait_above(tau0 + 64 < ql ? tau0 + 64 : ql);
         if (aborted) { nH = 0; nE = 0; nE2 = 0; return; }
         // acquire side of the producer's workgroup-scope release: the boundary row is read after the progress word
         // whatever the CU mode (relaxed loads alone are only ordered while both waves share one L1)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        nH = in ? __hip_atomic_load(&bin[jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
-        nE = in ? __hip_atomic_load(&bin[bstride + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
-        nE2 = in ? __hip_atomic_load(&bin[2 * bstride + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+        nH = in ? __hip_atomic_load(&bin[jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : none;
+        nE = in ? __hip_atomic_load(&bin[bstride + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : none;
+        nE2 = in ? __hip_atomic_load(&bin[2 * bstride + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : none;
+        if (BAND && xin) {   // (the stripes above have all passed column xcol <= tau0 + 63: the wait above)
+          Xv = decayed(__hip_atomic_load(&xarr[xcol], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), gm.e, dead_w);
+          X2v = decayed(__hip_atomic_load(&xarr[bstride + xcol], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), gm.e2, dead_w);
+        }
       } else {
-        nH = in ? bin[jj] : 0; nE = in ? bin[bstride + jj] : 0; nE2 = in ? bin[2 * bstride + jj] : 0;
+        nH = in ? bin[jj] : none; nE = in ? bin[bstride + jj] : none; nE2 = in ? bin[2 * bstride + jj] : none;
+        if (BAND && xin) { Xv = decayed(xarr[xcol], gm.e, dead_w); X2v = decayed(xarr[bstride + xcol], gm.e2, dead_w); }
       }
     };
-    fetch(0);
-    uint8_t* dcell = dir + (int64_t)(s << 6) * tl + i;   // cell (i, j) at (i + j) * tl + i: + tl per step
-    for (int tau0 = 0; tau0 < n_steps && !aborted; tau0 += 64) {
+    for (int r = 0; r < (BAND ? 2 : 1) && !aborted; ++r) {
+    const int ra = r ? R.a[1] : R.a[0], re = r ? R.e[1] : R.e[0];
+    if (ra >= re) continue;
+    fetch(ra);
+    if (BAND && ra > 0 && !aborted) {
+      // repair: the steps before `ra` were not run, and every cell of them was dead (or, on a lane that has not started
+      // its row, is still to come): what a lane takes from them is "no path", the query symbol is read again
+      const int jq = ra - 1 - lane;
+      qcur = jq >= 0 && jq < ql ? q[jq] : 0;
+      Hout = DP_NEG; Eout = DP_NEG; E2out = DP_NEG;
+      Hd = DP_NEG;
+      if (lane == 0 && ra - 1 < ql && aln_band_live(ra - (s << 6), B))   // (i-1, ra-1), if the stripe above found it live
+        Hd = W > 1 && Wp > 1 ? __hip_atomic_load(&bin[ra - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : bin[ra - 1];
+      if (ra - lane > 0) {
+        // horizontal carry: the gap run went on through the skipped cells of the row
+        // (it may open at the lane's last live cell: Hl is that cell's H there, "no path" on a lane already past it)
+        if (horiz && r == 1) {
+          Fl = decayed(Hl - gm.q > Fl ? Hl - gm.q : Fl, gm.e, ra - R.e[0]);
+          F2l = decayed(Hl - gm.q2 > F2l ? Hl - gm.q2 : F2l, gm.e2, ra - R.e[0]);
+        }
+        else { Fl = DP_NEG; F2l = DP_NEG; }
+        Hl = DP_NEG;
+      }
+    }
+    uint8_t* dcell = dir + (int64_t)((s << 6) + ra) * tl + i;   // cell (i, j) at (i + j) * tl + i: + tl per step
+    for (int tau0 = ra; tau0 < re && !aborted; tau0 += 64) {
       // wait for the block here, once, so that the 64 steps below never wait on memory (their direction-byte stores
       // stay in flight: vmcnt counts stores too)
       asm volatile("" : "+v"(nq), "+v"(nH), "+v"(nE), "+v"(nE2));
+      if (BAND) asm volatile("" : "+v"(Xv), "+v"(X2v));
       const int qblk = nq;
       const int32_t bH = nH, bE = nE, bE2 = nE2;
-      if (tau0 + 64 < n_steps) fetch(tau0 + 64);
-      const int kmax = n_steps - tau0 < 64 ? n_steps - tau0 : 64;
+      if (tau0 + 64 < re) fetch(tau0 + 64);
+      const int kmax = re - tau0 < 64 ? re - tau0 : 64;
       for (int k = 0; k < kmax; ++k) {
         const int tau = tau0 + k;
         const int qs = __builtin_amdgcn_readlane(qblk, k);
@@ -162,10 +222,21 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
         int32_t Hu = dp_shr1(Hout), Eu = dp_shr1(Eout), E2u = dp_shr1(E2out);
         if (lane == 0) { qcur = qs; Hu = hb; Eu = eb; E2u = e2b; }
         const int j = tau - lane;
-        if (row_ok && j >= 0 && j < ql) {
+        const bool inr = row_ok && j >= 0 && j < ql;
+        const int dg = tau - dl;
+        if (BAND && inr && !aln_band_live(dg, B)) {
+          // not computed: no path through the cell -- but for the gap run that crosses the dead interior along the row
+          if (horiz && dg > B.c1 && dg < B.c2) {
+            Fl = (Hl - gm.q > Fl ? Hl - gm.q : Fl) - gm.e;
+            F2l = (Hl - gm.q2 > F2l ? Hl - gm.q2 : F2l) - gm.e2;
+          } else { Fl = DP_NEG; F2l = DP_NEG; }
+          Hl = DP_NEG;
+          Hout = DP_NEG; Eout = DP_NEG; E2out = DP_NEG;
+        } else if (inr) {
           const int32_t hdiag = j == 0 ? (i == 0 ? 0 : -dp_gap(i, gm)) : Hd;
-          const int32_t Ein = (Hu - gm.q > Eu ? Hu - gm.q : Eu) - gm.e;
-          const int32_t E2in = (Hu - gm.q2 > E2u ? Hu - gm.q2 : E2u) - gm.e2;
+          int32_t Ein = (Hu - gm.q > Eu ? Hu - gm.q : Eu) - gm.e;
+          int32_t E2in = (Hu - gm.q2 > E2u ? Hu - gm.q2 : E2u) - gm.e2;
+          if (BAND && vert && dg == B.c1) { Ein = Xv; E2in = X2v; }   // the cells above are the dead interior
           const int32_t Fin = (Hl - gm.q > Fl ? Hl - gm.q : Fl) - gm.e;
           const int32_t F2in = (Hl - gm.q2 > F2l ? Hl - gm.q2 : F2l) - gm.e2;
           int32_t z = hdiag + (int32_t)(int8_t)(rowbits >> (8 * qcur));
@@ -182,6 +253,10 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
           Hout = z; Eout = Ein; E2out = E2in;
           Hl = z; Fl = Fin; F2l = F2in;
           if (writes_bnd) { bout[j] = z; bout[bstride + j] = Ein; bout[2 * bstride + j] = E2in; }
+          if (BAND && vert && dg == B.c2) {   // what the dead cell below would receive
+            xarr[j] = (z - gm.q > Ein ? z - gm.q : Ein) - gm.e;
+            xarr[bstride + j] = (z - gm.q2 > E2in ? z - gm.q2 : E2in) - gm.e2;
+          }
           if (i == tl - 1 && j == ql - 1) final_score = z;
         }
         Hd = Hu;
@@ -197,8 +272,18 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
         if (lane == 63) prog[out_slot] = ((s + 1) << 20) | (done < 0 ? 0 : done > ql ? ql : done);
       }
     }
+    // (no announcement for the columns a jump skips: a stripe only ever announces a column after a block that waited
+    // for the stripe above to announce it, so "stripe s - 1 has passed column c" still means every stripe above has --
+    // which is what lets a lane read the carried gap of column c from the exit arrays)
+    }
     if (W == 1 || Wp == 1) __syncthreads();   // (one wavefront: the boundary row is in memory before the next stripe reads it)
-    else if (s + 1 < n_stripes) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); if (lane == 63) prog[out_slot] = ((s + 1) << 20) | ql; }
+    else if (s + 1 < n_stripes) {
+      // vert: a stripe whose bands end short of the last column has not waited for it; it ends after the stripe above, so
+      // that its "all columns done" says the same of every stripe above (whose exit arrays the stripes below read)
+      if (BAND && vert && !aborted) { wait_above(ql); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      if (lane == 63) prog[out_slot] = ((s + 1) << 20) | ql;
+    }
     if (s == n_stripes - 1) {   // the lane that owned (tl-1, ql-1) has the score
       const int owner = (tl - 1) & 63;
       final_score = __builtin_amdgcn_readlane(final_score, owner);
@@ -225,6 +310,19 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
     int i0 = -(1 << 28), j0 = 0;
     uint32_t win = 0;
     while (i >= 0 && j >= 0) {
+      if (BAND && !aln_band_live(j - i, B)) {
+        // a cell that was not computed has no direction byte.  In the dead interior the walk is inside the one gap run that
+        // crosses it (aln_band.h: the stored bits would say "extended" all the way): the run goes on to the live band.
+        // Any other state there, or a cell outside the hull, cannot occur; the walk then moves on as if "extended" were
+        // stored as well, without reading anything.
+        const int dg = j - i;
+        if (horiz && dg > B.c1 && dg < B.c2 && (state == 2 || state == 4)) { push(1, (uint32_t)(dg - B.c1)); j -= dg - B.c1; }
+        else if (vert && dg > B.c1 && dg < B.c2 && (state == 1 || state == 3)) { push(2, (uint32_t)(B.c2 - dg)); i -= B.c2 - dg; }
+        else if (state == 0) { push(0, 1); --i; --j; }
+        else if (state == 1 || state == 3) { push(2, 1); --i; }
+        else { push(1, 1); --j; }
+        continue;
+      }
       int k = i0 - i, d = j - (j0 - k);
       if (k < 0 || k > 63 || d < 0 || d > 3) {
         i0 = i; j0 = j - 1; k = 0; d = 1;       // columns j0-k .. j0-k+3 of row i0-k (room for two D and one I moves)
@@ -253,6 +351,65 @@ __global__ void __launch_bounds__(64 * W) align_wave_kernel(
     if (cur_op != 0xffffffffu) { if (lane == 0) cg[n] = (cur_len << 4) | cur_op; ++n; }
     if (lane == 0) n_cigar[P.slot] = n;
   }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) align_wave_kernel(
+    const AlnPair* pairs, const uint8_t* qsyms, const uint8_t* tsyms, int m, const int8_t* mat_g,
+    GapModel gm, int32_t* ws, uint8_t* dirs, uint32_t* cigars, int32_t* scores, int32_t* n_cigar, int32_t* abort_flag) {
+  const AlnPair P = pairs[blockIdx.x];
+  if ((int)(threadIdx.x >> 6) >= (W > 1 ? P.waves : 1)) return;
+  if (P.ql <= 0 || P.tl <= 0) {   // ksw2 returns before touching ez: score 0, no CIGAR
+    if ((threadIdx.x & 63) == 0) { scores[P.slot] = 0; n_cigar[P.slot] = 0; }
+    return;
+  }
+  // a pair planned "full matrix" runs the code without the masks (the branch is uniform over the workgroup)
+  if (P.band.mode != ALN_FULL) align_pair<W, true>(P, qsyms, tsyms, m, mat_g, gm, ws, dirs, cigars, scores, n_cigar, abort_flag);
+  else align_pair<W, false>(P, qsyms, tsyms, m, mat_g, gm, ws, dirs, cigars, scores, n_cigar, abort_flag);
+}
+
+// The two diagonal sums of a pair's S_lb (aln_band.h), one wavefront per pair: sum_out = max over x of (prefix [0, x) on
+// diagonal 0 + suffix [x, n) on diagonal D), n = min(ql, tl) -- the sum of the suffix diagonal plus the largest prefix sum
+// of (diagonal 0 - diagonal D), the empty prefix included; the plain diagonal for D = 0.  The host subtracts the gap and
+// plans.  Lane l takes positions [l per, (l + 1) per).  A symbol outside the matrix raises *bad (the batch then runs its
+// full matrices, as the host's look-ups have no entry for it either).
+__global__ void __launch_bounds__(64) aln_slb_kernel(const uint8_t* qsyms, const int64_t* q_off, const uint8_t* tsyms, const int64_t* t_off,
+                                                     int m, const int8_t* mat_g, int64_t* sum_out, int32_t* bad) {
+  const int64_t p = blockIdx.x;
+  const int64_t ql = q_off[p + 1] - q_off[p], tl = t_off[p + 1] - t_off[p];
+  const int64_t n = ql < tl ? ql : tl, D = ql - tl;
+  const int lane = threadIdx.x;
+  if (n <= 0) { if (lane == 0) sum_out[p] = 0; return; }
+  const uint8_t* q = qsyms + (q_off[p] - q_off[0]);
+  const uint8_t* t = tsyms + (t_off[p] - t_off[0]);
+  const int64_t qs = D > 0 ? D : 0, ts = D < 0 ? -D : 0;
+  const int64_t per = (n + 63) >> 6, k0 = lane * per, k1 = k0 + per < n ? k0 + per : n;
+  bool off = false;
+  auto score = [&](int tsym, int qsym) {
+    if (tsym >= m || qsym >= m) { off = true; return 0; }
+    return (int)mat_g[tsym * m + qsym];
+  };
+  int64_t sb = 0, sc = 0, mp = 0;   // the chunk's sum on diagonal D, of the difference, and its largest prefix of the difference
+  for (int64_t k = k0; k < k1; ++k) {
+    const int a = score(t[k], q[k]), bq = D != 0 ? score(t[k + ts], q[k + qs]) : a;
+    sb += bq;
+    sc += a - bq;
+    mp = sc > mp ? sc : mp;
+  }
+  if (__any(off) && lane == 0) atomicExch(bad, 1);
+  // in lane order: sum of the chunks before + the chunk's own largest prefix
+  int64_t before = sc;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t v = __shfl_up(before, o, 64);
+    if (lane >= o) before += v;
+  }
+  int64_t best = before - sc + mp, tot = sb;
+  for (int o = 32; o > 0; o >>= 1) {
+    const int64_t v = __shfl_xor(best, o, 64), w = __shfl_xor(tot, o, 64);
+    best = v > best ? v : best;
+    tot += w;
+  }
+  if (lane == 0) sum_out[p] = tot + (best > 0 ? best : 0);
 }
 
 // barrier that orders LDS traffic only
@@ -391,12 +548,14 @@ struct svdss_aln_batch {
   int64_t cells = 0;
   double kernel_ms = 0.0;
   int64_t info[4] = {0, 0, 0, 0};   // the last call: chunks, pairs with several wavefronts, largest W, chunks run again
+  int64_t band[4] = {0, 0, 0, 0};   // the last call: wavefront steps executed, those of the full matrices, pairs with one band, pairs with a carried gap
   std::vector<int32_t> scores;
   std::vector<int64_t> n_cigar;
   std::vector<uint32_t> cigar;   // per pair, forward order, concatenated
   // device state kept between calls
   int device = -1;
-  DevArena arena;
+  DevArena arena;      // a chunk's workspace
+  DevArena in_arena;   // the call's symbols, matrix and offsets, uploaded once, and the planning kernel's sums
 };
 
 namespace {
@@ -426,6 +585,7 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
   b->cells = 0;
   b->kernel_ms = 0.0;
   b->info[0] = b->info[1] = b->info[2] = b->info[3] = 0;
+  b->band[0] = b->band[1] = b->band[2] = b->band[3] = 0;
   b->scores.assign((size_t)n_pairs, 0);
   b->n_cigar.assign((size_t)n_pairs, 0);
   b->cigar.clear();
@@ -438,6 +598,7 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
   const int64_t qtot = q_off[n_pairs] - q_off[0], ttot = t_off[n_pairs] - t_off[0];
   if (b->device != device) {
     b->arena.drop();
+    b->in_arena.drop();
     b->device = device;
   }
   // the call's one stream, from the call side's pool (call_streams.h): calls of different threads overlap
@@ -464,7 +625,9 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
   int64_t start = 0;
   // the longest pairs of the batch get ALN_W wavefronts each (align_wave_kernel): within a factor of four of the largest
   // matrix (SVDSS_ALIGN_FRAC, default eight), or every pair of a batch too small to fill the GPU with one wavefront per pair.
-  // SVDSS_ALIGN_WAVES=1: never; =8: eight.  Measured on a bench step (5,093 pairs): 26.5 -> 16.5 ms.
+  // SVDSS_ALIGN_WAVES=1: never; =8: eight.  Measured on a bench step (5,093 pairs) with full matrices: 26.5 -> 16.5 ms.
+  // The choice still goes by ql x tl, not by the steps a pair is planned to run (aln_band.h); whether several wavefronts
+  // pay for a pair that runs two blocks of 64 steps per stripe has not been measured.
   const int ALN_W = getenv("SVDSS_ALIGN_WAVES") && atoi(getenv("SVDSS_ALIGN_WAVES")) == 8 ? 8 : 4;
   const int64_t aln_frac = getenv("SVDSS_ALIGN_FRAC") && atoll(getenv("SVDSS_ALIGN_FRAC")) > 0 ? atoll(getenv("SVDSS_ALIGN_FRAC")) : 8;
   int64_t max_cells = 0;
@@ -474,6 +637,52 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
     if (!multi || tl < 8 * 64 || ql >= (1 << 20)) return 1;
     return (ql * tl * aln_frac >= max_cells || n_pairs < 2048) ? ALN_W : 1;
   };
+  // the symbols and the matrix go up once per call
+  HIPCHK(b->in_arena.reserve(DevArena::padded((size_t)qtot) + DevArena::padded((size_t)ttot) + DevArena::padded(64) +
+                             3 * DevArena::padded(sizeof(int64_t) * (size_t)(n_pairs + 1)) + DevArena::padded(64)));
+  void* d_q = b->in_arena.take((size_t)qtot);
+  void* d_t = b->in_arena.take((size_t)ttot);
+  void* d_mat = b->in_arena.take(64);
+  if (qtot) HIPCHK(hipMemcpyAsync(d_q, queries + q_off[0], (size_t)qtot, hipMemcpyHostToDevice, st));
+  if (ttot) HIPCHK(hipMemcpyAsync(d_t, targets + t_off[0], (size_t)ttot, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_mat, mat, (size_t)(m * m), hipMemcpyHostToDevice, st));
+  // SVDSS_ALIGN_BAND: 0 the full matrix of every pair, 1 one band of diagonals per pair, 2 (default) two bands with the
+  // gap carried across where the plan finds a dead interior (aln_band.h).  Planned here, before the pairs are laid out:
+  // the two diagonal sums of every pair on the device, the intervals from them on the host.  (Planned on the host
+  // alone, a table look-up per symbol, a bench step's 5,093 pairs took 3.3 ms and the call 4 ms longer; the kernel takes
+  // 0.07 ms and costs the two offset arrays up, the sums down and one stream synchronise: profiles/realign_band.txt 3a.)
+  int band_level = getenv("SVDSS_ALIGN_BAND") ? std::max(0, std::min(2, atoi(getenv("SVDSS_ALIGN_BAND")))) : 2;
+  std::vector<AlnBand> bands((size_t)n_pairs);
+  std::vector<int64_t> band_steps((size_t)n_pairs), full_steps((size_t)n_pairs);
+  {
+    const AlnScoring sc{(int)m, mat, gapo, gape, gapo2, gape2};
+    int M = 0;
+    std::vector<int64_t> sums((size_t)n_pairs, 0);
+    if (band_level > 0 && aln_band_provable(sc, &M)) {
+      void* d_qo = b->in_arena.take(sizeof(int64_t) * (size_t)(n_pairs + 1));
+      void* d_to = b->in_arena.take(sizeof(int64_t) * (size_t)(n_pairs + 1));
+      void* d_sum = b->in_arena.take(sizeof(int64_t) * (size_t)n_pairs);
+      void* d_bad = b->in_arena.take(64);
+      int32_t bad = 0;
+      HIPCHK(hipMemcpyAsync(d_qo, q_off, sizeof(int64_t) * (size_t)(n_pairs + 1), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(d_to, t_off, sizeof(int64_t) * (size_t)(n_pairs + 1), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemsetAsync(d_bad, 0, 64, st));
+      hipLaunchKernelGGL(aln_slb_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, (const uint8_t*)d_q, (const int64_t*)d_qo,
+                         (const uint8_t*)d_t, (const int64_t*)d_to, (int)m, (const int8_t*)d_mat, (int64_t*)d_sum, (int32_t*)d_bad);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(sums.data(), d_sum, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (bad) band_level = 0;   // a symbol outside the matrix
+    } else {
+      band_level = 0;
+    }
+    for (int64_t i = 0; i < n_pairs; ++i) {
+      const int64_t ql = q_off[i + 1] - q_off[i], tl = t_off[i + 1] - t_off[i], k = ql < tl ? tl - ql : ql - tl;
+      bands[(size_t)i] = aln_band_plan_slb(ql, tl, sc, band_level, sums[(size_t)i] - aln_gap(k, sc));
+      band_steps[(size_t)i] = aln_band_steps(ql, tl, bands[(size_t)i], &full_steps[(size_t)i]);
+    }
+  }
   while (start < n_pairs) {
     std::vector<AlnPair> hp;
     int64_t ws = 0, dirb = 0, cig = 0, end = start;
@@ -493,29 +702,26 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
       a.tl = (int32_t)tl;
       a.slot = (int32_t)(end - start);
       a.waves = waves_of(ql, tl);
+      a.band = bands[(size_t)end];
       any_multi = any_multi || a.waves > 1;
       hp.push_back(a);
       cig_at[(size_t)end] = {cig, (int64_t)chunk_cigs.size()};
-      ws += 3 * (a.waves + 1) * (ql + 64);
+      ws += (3 * (a.waves + 1) + 2) * (ql + 64);   // the boundary buffers, and the two arrays of a vertically carried gap
       dirb += need;
       cig += ql + tl + 2;
       b->cells += ql * tl;
       ++end;
     }
     const int64_t np = end - start;
-    // longest pairs first: a pair is one chain of (tl / 64) x (ql + 63) dependent steps, the longest ones decide when
-    // the launch ends
-    std::stable_sort(hp.begin(), hp.end(), [](const AlnPair& x, const AlnPair& y) {
-      return (int64_t)x.ql * x.tl > (int64_t)y.ql * y.tl;
+    // longest pairs first: a pair is one chain of dependent steps (aln_band_steps: (tl / 64) x (ql + 63) for a full matrix),
+    // the longest ones decide when the launch ends
+    std::stable_sort(hp.begin(), hp.end(), [&](const AlnPair& x, const AlnPair& y) {
+      return band_steps[(size_t)(start + x.slot)] > band_steps[(size_t)(start + y.slot)];
     });
-    const size_t need_bytes = DevArena::padded((size_t)qtot) + DevArena::padded((size_t)ttot) + DevArena::padded(64) +
-                              DevArena::padded(sizeof(AlnPair) * (size_t)np) + DevArena::padded(sizeof(int32_t) * (size_t)ws) +
+    const size_t need_bytes = DevArena::padded(sizeof(AlnPair) * (size_t)np) + DevArena::padded(sizeof(int32_t) * (size_t)ws) +
                               DevArena::padded((size_t)dirb) + DevArena::padded(sizeof(uint32_t) * (size_t)cig) +
                               2 * DevArena::padded(sizeof(int32_t) * (size_t)np) + DevArena::padded(64);
     HIPCHK(b->arena.reserve(need_bytes));
-    void* d_q = b->arena.take((size_t)qtot);
-    void* d_t = b->arena.take((size_t)ttot);
-    void* d_mat = b->arena.take(64);
     void* d_pairs = b->arena.take(sizeof(AlnPair) * (size_t)np);
     void* d_ws = b->arena.take(sizeof(int32_t) * (size_t)ws);
     void* d_dir = b->arena.take((size_t)dirb);
@@ -523,9 +729,6 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
     void* d_sc = b->arena.take(sizeof(int32_t) * (size_t)np);
     void* d_nc = b->arena.take(sizeof(int32_t) * (size_t)np);
     void* d_abort = b->arena.take(64);
-    if (qtot) HIPCHK(hipMemcpyAsync(d_q, queries + q_off[0], (size_t)qtot, hipMemcpyHostToDevice, st));
-    if (ttot) HIPCHK(hipMemcpyAsync(d_t, targets + t_off[0], (size_t)ttot, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_mat, mat, (size_t)(m * m), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_pairs, hp.data(), sizeof(AlnPair) * (size_t)np, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_abort, 0, 64, st));
     HIPCHK(hipEventRecord(ev0, st));
@@ -557,7 +760,13 @@ extern "C" int svdss_align_global_batch(const uint8_t* queries, const int64_t* q
       }
     }
     ++b->info[0];
-    for (const AlnPair& a : hp) b->info[1] += a.waves > 1;
+    for (const AlnPair& a : hp) {
+      b->info[1] += a.waves > 1;
+      b->band[0] += band_steps[(size_t)(start + a.slot)];
+      b->band[1] += full_steps[(size_t)(start + a.slot)];
+      b->band[2] += a.band.mode == ALN_ONE_BAND;
+      b->band[3] += a.band.mode == ALN_CARRY;
+    }
     b->info[2] = std::max<int64_t>(b->info[2], any_multi ? ALN_W : 1);
     chunk_cigs.emplace_back((size_t)cig);
     HIPCHK(hipMemcpyAsync(&b->scores[(size_t)start], d_sc, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
@@ -595,6 +804,12 @@ extern "C" double svdss_aln_batch_kernel_ms(const svdss_aln_batch_t* b) { return
 extern "C" int svdss_aln_batch_launch_info(const svdss_aln_batch_t* b, int64_t out[4]) {
   if (!b || !out) return SVDSS_EINVAL;
   memcpy(out, b->info, sizeof b->info);
+  return SVDSS_OK;
+}
+
+extern "C" int svdss_aln_batch_band_info(const svdss_aln_batch_t* b, int64_t out[4]) {
+  if (!b || !out) return SVDSS_EINVAL;
+  memcpy(out, b->band, sizeof b->band);
   return SVDSS_OK;
 }
 
