@@ -71,6 +71,29 @@ int svdss_index_save_fmd(const svdss_index_t* ix, const char* path);
 /* The BWT an rld0 `.fmd` holds, as nt6 bytes: *n_out symbols (bwt_out may be NULL to ask for the size only;
  * SVDSS_ERANGE if cap is too small). */
 int svdss_fmd_read_bwt(const char* path, uint8_t* bwt_out, int64_t cap, int64_t* n_out);
+/* The rld0 `.fmd` of a BWT (nt6 bytes, '$' = 0) -> path.  device >= 0: rank blocks of the BWT built on the host, uploaded,
+ * and the file encoded on that GPU (csrc/rld0_dev.hip: run starts from the bit planes, the chain of block starts by tile
+ * tables, a lane per 64-byte block) -- the bytes the host encoder writes; device == -1: the host encoder (csrc/rld0.cpp).
+ * The device declines whole calls, never part of a file -- the host encoder then writes it: an empty BWT, a block of
+ * SVDSS_FMD_DECLINE_SYMS (default and at most 2^30) symbols or more, a plan that does not fit in free HBM, no GPU or
+ * SVDSS_INDEX_CPU set. */
+int svdss_fmd_encode(const uint8_t* bwt, int64_t n, const char* path, int device);
+/* How the calling thread's last .fmd encode (svdss_fmd_encode, svdss_index_save_fmd, svdss_index_save_fmd_on) ran:
+ * *route one of SVDSS_FMD_*; on the device also its runs, data blocks and pieces of 2^23 words, and ms[0..4] = the
+ * milliseconds of the stages planes, plan, chain, emit, download + write; ms[5] = the whole call.  SVDSS_ENODEV before the
+ * first encode. */
+#define SVDSS_FMD_HOST 0              /* the host encoder, as asked (device -1, SVDSS_FMD_ENCODE_DEVICE=0) */
+#define SVDSS_FMD_DEVICE 1            /* the device encoder */
+#define SVDSS_FMD_DECLINED_EMPTY 2    /* declined: n == 0 */
+#define SVDSS_FMD_DECLINED_BLOCK 3    /* declined: a block of SVDSS_FMD_DECLINE_SYMS symbols or more */
+#define SVDSS_FMD_DECLINED_MEMORY 4   /* declined: the plan does not fit in free HBM */
+#define SVDSS_FMD_DECLINED_NO_GPU 5   /* declined: no GPU, or SVDSS_INDEX_CPU set */
+int svdss_fmd_encode_last(int32_t* route, int64_t* runs, int64_t* blocks, int64_t* pieces, double ms[6]);
+/* svdss_index_save_fmd with the encoder named: device >= 0 the device encoder on that GPU (from the resident rank blocks
+ * where the handle is resident there, else its host blocks are uploaded), -1 the host encoder, -2 what
+ * svdss_index_save_fmd does: SVDSS_FMD_ENCODE_DEVICE=1 or unset the device (where the handle is resident, else GPU 0;
+ * the default since profiles/fmd_encode.txt), 0 the host. */
+int svdss_index_save_fmd_on(const svdss_index_t* ix, const char* path, int32_t device);
 /* The strings of the collection a BWT stands for (nt6, '$' = 0 in `bwt`): string r is the one spelled from row r;
  * they are written back to back into out (n - m bytes), their lengths into lens.  device >= 0: rank blocks built
  * and walked there (csrc/bwt_invert.hip: marked LF walks, a walker per lane; the same walk on the host where HBM has

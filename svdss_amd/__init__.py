@@ -7,5 +7,5 @@ raises ImportError -- there is no CPU fallback.
 """
 from ._lib import LIB_PATH, SVDSS_SFS_ASSEMBLE, SvdssError, lib  # noqa: F401
 from .pingpong import (FMDIndex, NT6_TABLE, PingPong, SFSBatch, bwt_strings, bwt_strings_last,  # noqa: F401
-                       nt6_encode, output_batch, pack_reads, parse_sfsfile)
+                       fmd_encode, fmd_encode_last, nt6_encode, output_batch, pack_reads, parse_sfsfile)
 from . import calldp  # noqa: F401,E402

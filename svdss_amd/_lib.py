@@ -53,6 +53,9 @@ SIGNATURES = {
     "svdss_index_save_records": (C.c_int, [_p, C.c_char_p]),
     "svdss_index_save_fmd": (C.c_int, [_p, C.c_char_p]),
     "svdss_fmd_read_bwt": (C.c_int, [C.c_char_p, _p, _i64, _p]),
+    "svdss_fmd_encode": (C.c_int, [_p, _i64, C.c_char_p, C.c_int]),
+    "svdss_fmd_encode_last": (C.c_int, [_p, _p, _p, _p, _p]),
+    "svdss_index_save_fmd_on": (C.c_int, [_p, C.c_char_p, _i32]),
     "svdss_bwt_strings": (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p]),
     "svdss_bwt_strings_last": (C.c_int, [_p, _p, _p, _p]),
     "svdss_index_load": (C.c_int, [C.c_char_p, C.POINTER(_p)]),

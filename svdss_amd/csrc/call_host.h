@@ -31,6 +31,9 @@ struct CallOptions {
   bool clipped = false;        // --clipped: imprecise SVs from soft-clipped alignments (clipper.cpp; EXPERIMENTAL)
   std::string smoothed;        // run only: --smoothed <FILE>, the smoothed BAM (with write_index / compress above)
   std::string write_bam_index; // call, run: --write-bam-index <FILE>, the index of --bam (bam_input_index.h); bamindex: its -o
+  // run --build-index: called once after run's own refusals (options, knobs, the samples list, BAMs that do not exist) and
+  // before the GPU is looked for and anything is opened for writing -- builds a missing --index (svdss_main.cpp)
+  void (*before_stages)(const CallOptions&) = nullptr;
 };
 
 // `SVDSS run` (run_host.cpp) drives the two units below; what passes between them:

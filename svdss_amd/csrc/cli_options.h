@@ -31,6 +31,7 @@ struct Options {
   std::string write_bam_index;                     // call / run --write-bam-index FILE: the index of --bam, a by-product of its pass
   std::string out;                                 // bamindex -o FILE (default: <BAM>.bai)
   bool gpus_all = false;                           // --gpus all (the caller asks the library how many there are)
+  bool build_index = false;                        // run --build-index: a missing --index is built (and stored) first
   bool putative = true, assemble = true, verbose = false, version = false, help = false, clipped = false, binary = false;
 };
 
@@ -110,7 +111,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
       {"noputative", FLAG}, {"binary", FLAG}, {"version", FLAG}, {"help", FLAG}, {"h", FLAG}, {"l", FLT}, {"verbose", FLAG},
       {"gpus", STR}, {"io-threads", INT}, {"write-index", STR},
       {"compress", STR}, {"nobam", FLAG}, {"smoothed", STR}, {"region", STR}, {"regions-file", STR},
-      {"samples", STR}, {"write-bam-index", STR}, {"o", STR}};   // (the last eleven: this program's own)
+      {"samples", STR}, {"write-bam-index", STR}, {"o", STR}, {"build-index", FLAG}};   // (the last twelve: this program's own)
   auto find = [&](const std::string& name) -> const Spec* {
     for (const Spec& sp : specs)
       if (name == sp.name) return &sp;
@@ -140,6 +141,7 @@ inline bool parse_options(int argc, char** argv, int first, Options& o, std::str
     else if (n == "region") o.regions.push_back(v); else if (n == "regions-file") o.regions_file = v;
     else if (n == "samples") o.samples = v;
     else if (n == "write-bam-index") o.write_bam_index = v; else if (n == "o") o.out = v;
+    else if (n == "build-index") o.build_index = b;
     else if (n == "compress") { o.compress_given = true; if (v == "runs") o.compress = 0; else if (v == "lz") o.compress = 1; else return failed(v); }
     else if (n == "gpus") { if (v == "all") o.gpus_all = true; else if (!to_int(v, o.gpus)) return failed(v); }
     return true;

@@ -216,15 +216,46 @@ extern "C" int svdss_index_load_blocks(const char* path, svdss_index_t** out) {
   return SVDSS_OK;
 }
 
-extern "C" int svdss_index_save_fmd(const svdss_index_t* ix, const char* path) {
-  if (!ix || !path) return SVDSS_EINVAL;
+// The encoder of the .fmd: the device one (rld0_dev.hip) reads the rank blocks where they are resident -- no host copy of
+// the index, no byte-per-symbol BWT -- and declines whole calls; the host one (rld0.cpp) then writes the file, as it does
+// where it is asked for.  svdss_fmd_encode_last tells which ran.
+extern "C" int svdss_index_save_fmd_on(const svdss_index_t* ix, const char* path, int32_t device) {
+  if (!ix || !path || device < -2) return SVDSS_EINVAL;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (device == -2) {
+    // (unset: the device encoder -- its slowest run beat the parent's fastest at 3.1 Gb and at 400 Mb, profiles/fmd_encode.txt;
+    // without a GPU it declines and the host writes the file)
+    const char* e = getenv("SVDSS_FMD_ENCODE_DEVICE");
+    device = e && atoi(e) == 0 ? -1 : (ix->device >= 0 ? ix->device : 0);
+  }
+  int32_t route = SVDSS_FMD_HOST;
+  if (device >= 0) {
+    int rc;
+    if (getenv("SVDSS_INDEX_CPU")) {
+      rc = -SVDSS_FMD_DECLINED_NO_GPU;
+    } else if (ix->device == device && ix->d_blocks) {
+      HIPCHK(hipSetDevice(device));
+      rc = rld0_dev_encode(ix->d_blocks, ix->n, ix->acc, path);
+    } else {
+      rc = materialize(ix);
+      if (rc != SVDSS_OK) return rc;
+      if (ix->blocks.empty()) return SVDSS_ENODEV;
+      rc = rld0_dev_encode_host_blocks(ix, device, path);
+    }
+    if (rc >= 0) return rc;   // written on the device, or an error
+    route = -rc;
+  }
   { const int rc = materialize(ix); if (rc != SVDSS_OK) return rc; }
   if (ix->blocks.empty()) return SVDSS_ENODEV;   // (a replica of the rank blocks alone keeps no host copy: svdss_index_replicate)
   std::vector<uint8_t> bwt;
   try { bwt.resize((size_t)ix->n); } catch (...) { return SVDSS_ENOMEM; }
   svdss_index_decode_bwt(ix, bwt.data());
-  return rld0_write(path, bwt.data(), ix->n);
+  const int rc = rld0_write(path, bwt.data(), ix->n);
+  rld0_encode_note(route, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return rc;
 }
+
+extern "C" int svdss_index_save_fmd(const svdss_index_t* ix, const char* path) { return svdss_index_save_fmd_on(ix, path, -2); }
 
 extern "C" int svdss_fmd_read_bwt(const char* path, uint8_t* bwt_out, int64_t cap, int64_t* n_out) {
   if (!path || !n_out) return SVDSS_EINVAL;

@@ -149,6 +149,61 @@ bool write_all(FILE* f, const void* p, size_t bytes) { return bytes == 0 || fwri
 
 }  // namespace
 
+// The rank frames (rld_rank_index) from the block headers of the data words, fed in slices: rld0_write feeds all of them
+// at once, the device encoder (rld0_dev.hip) every slice as it comes down.
+void Rld0Frames::begin(uint64_t total, int64_t k) {
+  const uint64_t n_blks = (uint64_t)k / SSIZE + 1;
+  last = (k >> SBITS) << SBITS;
+  ibits = ilog2_64(std::max<uint64_t>(1, total / n_blks)) + RLD_IBITS_PLUS;
+  n_frames = ((total + ((uint64_t)1 << ibits) - 1) >> ibits) + 1;
+  frame.assign((size_t)(n_frames * ASIZE1), 0);
+  for (int j = 0; j < ASIZE; ++j) cnt[j] = 0;
+  fk = 1;
+}
+
+// words z[0, n_words) are the data words first_word, first_word + 1, ...; first_word a multiple of the block size, and a
+// slice that is not the last a whole number of blocks
+void Rld0Frames::feed(const uint64_t* z, int64_t first_word, int64_t n_words) {
+  for (int64_t i = std::max<int64_t>(SSIZE, first_word); i <= last && i < first_word + n_words; i += SSIZE) {
+    const uint64_t* h0 = z + (i - first_word);
+    const uint64_t w0 = h0[0];
+    if ((w0 >> 62) == 2) {
+      for (int j = 1; j <= ASIZE; ++j) cnt[j - 1] += h0[j];
+    } else if (w0 >> 62) {
+      uint32_t h[ASIZE1];
+      memcpy(h, h0, sizeof h);
+      for (int j = 1; j <= ASIZE; ++j) cnt[j - 1] += h[j] & 0x3fffffffu;
+    } else {
+      uint16_t h[ASIZE1];
+      memcpy(h, h0, sizeof h);
+      for (int j = 1; j <= ASIZE; ++j) cnt[j - 1] += h[j];
+    }
+    uint64_t sum = 0;
+    for (int j = 0; j < ASIZE; ++j) sum += cnt[j];
+    while (sum >= (fk << ibits)) ++fk;
+    if (fk < n_frames) {
+      const uint64_t x = fk * ASIZE1;
+      frame[(size_t)x] = (uint64_t)i;
+      for (int j = 0; j < ASIZE; ++j) frame[(size_t)(x + j + 1)] = cnt[j];
+    }
+  }
+}
+
+void Rld0Frames::finish() {
+  for (uint64_t f = 1; f < n_frames; ++f) {   // frames no block starts in: the previous one
+    const uint64_t x = f * ASIZE1;
+    if (frame[(size_t)x] == 0)
+      for (int j = 0; j <= ASIZE; ++j) frame[(size_t)(x + j)] = frame[(size_t)(x - ASIZE1 + j)];
+  }
+}
+
+bool rld0_write_header(FILE* f, int64_t k, uint64_t n_frames, const uint64_t mcnt[6]) {
+  const uint32_t a = (uint32_t)ASIZE << 16 | (uint32_t)SBITS;
+  const uint64_t k64 = (uint64_t)k;
+  return write_all(f, "RLD\3", 4) && write_all(f, &a, 4) && write_all(f, &k64, 8) && write_all(f, &n_frames, 8) &&
+         write_all(f, mcnt, 8 * ASIZE);
+}
+
 bool rld0_is_fmd(const char* path) {
   FILE* f = fopen(path, "rb");
   if (!f) return false;
@@ -234,49 +289,15 @@ int rld0_write(const char* path, const uint8_t* bwt, int64_t n) {
   encode_runs(e, bwt, n);
   const int64_t k = e.finish();
   // rld_rank_index: one frame per 2^ibits positions
-  const uint64_t total = e.cnt[0];
-  const uint64_t n_blks = (uint64_t)k / SSIZE + 1;
-  const int64_t last = (k >> SBITS) << SBITS;
-  const int ibits = ilog2_64(std::max<uint64_t>(1, total / n_blks)) + RLD_IBITS_PLUS;
-  const uint64_t n_frames = ((total + ((uint64_t)1 << ibits) - 1) >> ibits) + 1;
-  std::vector<uint64_t> frame((size_t)(n_frames * ASIZE1), 0);
-  {
-    uint64_t cnt[ASIZE] = {0};
-    uint64_t fk = 1;
-    for (int64_t i = SSIZE; i <= last; i += SSIZE) {
-      const uint64_t w0 = e.z[(size_t)i];
-      if ((w0 >> 62) == 2) {
-        for (int j = 1; j <= ASIZE; ++j) cnt[j - 1] += e.z[(size_t)i + (size_t)j];
-      } else if (w0 >> 62) {
-        uint32_t h[ASIZE1];
-        memcpy(h, &e.z[(size_t)i], sizeof h);
-        for (int j = 1; j <= ASIZE; ++j) cnt[j - 1] += h[j] & 0x3fffffffu;
-      } else {
-        uint16_t h[ASIZE1];
-        memcpy(h, &e.z[(size_t)i], sizeof h);
-        for (int j = 1; j <= ASIZE; ++j) cnt[j - 1] += h[j];
-      }
-      uint64_t sum = 0;
-      for (int j = 0; j < ASIZE; ++j) sum += cnt[j];
-      while (sum >= (fk << ibits)) ++fk;
-      if (fk < n_frames) {
-        const uint64_t x = fk * ASIZE1;
-        frame[(size_t)x] = (uint64_t)i;
-        for (int j = 0; j < ASIZE; ++j) frame[(size_t)(x + j + 1)] = cnt[j];
-      }
-    }
-    for (uint64_t f = 1; f < n_frames; ++f) {   // frames no block starts in: the previous one
-      const uint64_t x = f * ASIZE1;
-      if (frame[(size_t)x] == 0)
-        for (int j = 0; j <= ASIZE; ++j) frame[(size_t)(x + j)] = frame[(size_t)(x - ASIZE1 + j)];
-    }
-  }
+  Rld0Frames fr;
+  fr.begin(e.cnt[0], k);
+  fr.feed(e.z.data(), 0, k);
+  fr.finish();
+  const uint64_t n_frames = fr.n_frames;
+  const std::vector<uint64_t>& frame = fr.frame;
   FILE* f = fopen(path, "wb");
   if (!f) return SVDSS_EIO;
-  const uint32_t a = (uint32_t)ASIZE << 16 | (uint32_t)SBITS;
-  const uint64_t k64 = (uint64_t)k;
-  bool ok = write_all(f, "RLD\3", 4) && write_all(f, &a, 4) && write_all(f, &k64, 8) && write_all(f, &n_frames, 8) &&
-            write_all(f, e.cnt + 1, 8 * ASIZE) && write_all(f, e.z.data(), 8 * (size_t)k) &&
+  bool ok = rld0_write_header(f, k, n_frames, e.cnt + 1) && write_all(f, e.z.data(), 8 * (size_t)k) &&
             write_all(f, frame.data(), 8 * frame.size());
   ok = (fclose(f) == 0) && ok;
   return ok ? SVDSS_OK : SVDSS_EIO;

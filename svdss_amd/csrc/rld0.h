@@ -1,6 +1,7 @@
 // rld0.h -- ropebwt3's `.fmd` (rld0, magic "RLD\3") export / import; see rld0.cpp.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 
 #include <vector>
 
@@ -9,6 +10,23 @@ struct svdss_index;
 bool rld0_is_fmd(const char* path);
 // BWT symbols 0..5 -> file; SVDSS_OK / SVDSS_EINVAL / SVDSS_EIO
 int rld0_write(const char* path, const uint8_t* bwt, int64_t n);
+// the rank frames from the block headers of the data words, fed in slices (rld0.cpp); the file's header
+struct Rld0Frames {
+  std::vector<uint64_t> frame;
+  uint64_t n_frames = 0, fk = 1, cnt[6] = {0, 0, 0, 0, 0, 0};
+  int64_t last = 0;
+  int ibits = 0;
+  void begin(uint64_t total, int64_t k);
+  void feed(const uint64_t* z, int64_t first_word, int64_t n_words);
+  void finish();
+};
+bool rld0_write_header(FILE* f, int64_t k, uint64_t n_frames, const uint64_t mcnt[6]);
+// rld0_dev.hip, the encoder on the device: the .fmd of the BWT behind rank blocks resident on the current device / on the
+// host (uploaded to `device`).  SVDSS_OK: written there; -(SVDSS_FMD_DECLINED_*): declined, nothing written; else an error
+int rld0_dev_encode(const void* d_blocks, int64_t n, const int64_t acc[7], const char* path);
+int rld0_dev_encode_host_blocks(const svdss_index* ix, int device, const char* path);
+// what svdss_fmd_encode_last reports after the HOST encoder wrote a file: why it did (SVDSS_FMD_HOST, SVDSS_FMD_DECLINED_*)
+void rld0_encode_note(int32_t route, double total_ms);
 // the header's occurrence count of every symbol (cheap: 72 bytes read)
 int rld0_header_counts(const char* path, uint64_t mcnt_out[6]);
 // file -> BWT symbols

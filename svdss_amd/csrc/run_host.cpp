@@ -186,6 +186,12 @@ int main_run(const CallOptions& o) {
   const SmoothKnobs smooth_knobs;
   // ---- what it cannot run on is said before anything is opened or written
   refuse_what_cannot_run(o, smooth_knobs);
+  if (o.before_stages) {   // (--build-index: every refusal that needs no GPU comes before the index is built)
+    struct stat stb;
+    if (o.bsize <= 0) die("batch size smaller than the number of threads");
+    if (stat(o.bam.c_str(), &stb) != 0) die("cannot read " + o.bam);
+    o.before_stages(o);
+  }
   if (svdss_device_count() <= 0) die("no GPU found: SVDSS run smooths, searches and calls on the GPU");
   if (o.bsize <= 0) die("batch size smaller than the number of threads");
   SmoothHooks hooks;
@@ -216,6 +222,7 @@ int main_run_samples(const CallOptions& o, const std::string& list, const std::v
       for (const RunSample& t : samples) if (same_file(*out, t.bam)) die(where + "the output " + *out + " is an input of the run");
     }
   }
+  if (o.before_stages) o.before_stages(o);   // (--build-index: once, before the first sample, after every refusal above)
   if (svdss_device_count() <= 0) die("no GPU found: SVDSS run smooths, searches and calls on the GPU");
   // (fewer MB of HBM free than this after a sample's smoothing stage: the index leaves for the call stage)
   const int64_t min_free = env_from("SVDSS_RUN_INDEX_MIN_FREE_MB", 0, 8192) << 20;

@@ -114,6 +114,9 @@ static const char* RUN_USAGE =
     "      --bsize <int> --noputative --noassemble                              as in search\n"
     "      --min-cluster-weight <int> --min-sv-length <int> -l <float> --noht   as in call\n"
     "      --poa <FILE> --clusters <FILE> --clipped                             as in call\n"
+    "      --build-index         where <FMD> does not exist: build it first, as `SVDSS index -d <FASTA> -o <FMD> -t <threads>`\n"
+    "                            does (<FMD> and <FMD>.svdss are written, once for all of --samples), then go on; where it\n"
+    "                            exists nothing changes.  A build that fails leaves no file and ends the process\n"
     "      --verbose             stage timings and the record store's size on stderr\n"
     "      --samples <LIST>      instead of --bam: many BAMs in this one process, in the order of LIST; the reference, the index\n"
     "                            and the pools stay between them.  LIST: one sample per line, BAM<TAB>VCF[<TAB>SFS]; empty lines\n"
@@ -218,6 +221,8 @@ static const char* INDEX_USAGE =
     "      -t <int>              threads of the host side (default: 4)\n"
     "      --verbose             where OLD's records came from, and how many\n";
 
+static int build_index_files(const std::vector<std::string>& inputs, const std::string& old, const std::string& out, int threads, bool verbose);
+
 static int main_index(int argc, char** argv) {
   // ropebwt3 `build` flags as run_svdss:142 passes them: -t T -d <fasta> -o <out>; -i <old> as ropebwt3 spells the index to
   // append to [UPSTREAM-UNVERIFIED], --append as the reference's config.hpp:22
@@ -236,11 +241,35 @@ static int main_index(int argc, char** argv) {
     else if (argv[i][0] == '-' && argv[i][1] == 'd' && argv[i][2]) continue;
     else if (argv[i][0] != '-') inputs.push_back(argv[i]);
   }
-  const bool to_stdout = out.empty();
-  if (inputs.empty() || (to_stdout && isatty(STDOUT_FILENO))) {
+  if (inputs.empty() || (out.empty() && isatty(STDOUT_FILENO))) {
     fputs(INDEX_USAGE, stderr);
     return EXIT_FAILURE;
   }
+  return build_index_files(inputs, old, out, threads, verbose);
+}
+
+// one line of `--verbose`: which encoder wrote the .fmd (svdss_fmd_encode_last)
+static void report_fmd_encoder() {
+  int32_t route = -1;
+  int64_t runs = 0, blocks = 0, pieces = 0;
+  double ms[6] = {0, 0, 0, 0, 0, 0};
+  if (svdss_fmd_encode_last(&route, &runs, &blocks, &pieces, ms) != SVDSS_OK) return;
+  if (route == SVDSS_FMD_DEVICE)
+    fprintf(stderr, "fmd: encoded on the device: %lld runs, %lld blocks, %lld pieces; planes/plan/chain/emit/download %.1f/%.1f/%.1f/%.1f/%.1f ms\n",
+            (long long)runs, (long long)blocks, (long long)pieces, ms[0], ms[1], ms[2], ms[3], ms[4]);
+  else
+    fprintf(stderr, "fmd: encoded on the host (%s)\n",
+            route == SVDSS_FMD_DECLINED_EMPTY ? "the device declined: an empty BWT" :
+            route == SVDSS_FMD_DECLINED_BLOCK ? "the device declined: a block of SVDSS_FMD_DECLINE_SYMS symbols or more" :
+            route == SVDSS_FMD_DECLINED_MEMORY ? "the device declined: the plan does not fit in free HBM" :
+            route == SVDSS_FMD_DECLINED_NO_GPU ? "the device declined: no GPU, or SVDSS_INDEX_CPU set" :
+            "SVDSS_FMD_ENCODE_DEVICE=0");
+}
+
+// What `SVDSS index [-i old] -d inputs... [-o out] -t threads` does, for `index` and for `run --build-index` (out empty:
+// the .fmd to stdout, no sidecar)
+static int build_index_files(const std::vector<std::string>& inputs, const std::string& old, const std::string& out, int threads, bool verbose) {
+  const bool to_stdout = out.empty();
   // The index is built in HBM.  Without a GPU the command fails instead of quietly taking the host builder (which
   // stays in the library for the texts the GPU builder refuses, and for SVDSS_INDEX_CPU=1: developer runs on a
   // machine without a GPU).
@@ -343,6 +372,7 @@ static int main_index(int argc, char** argv) {
     // no -o: the .fmd to stdout (rld0_write never seeks), no sidecar -- there is no name to put it under
     check(svdss_index_save_fmd(ix, "/dev/stdout"), "svdss_index_save_fmd");
     mark("rld0 .fmd written");
+    if (verbose) report_fmd_encoder();
     svdss_index_free(ix);
     return 0;
   }
@@ -356,6 +386,7 @@ static int main_index(int argc, char** argv) {
     if (rc_side == SVDSS_OK && !getenv("SVDSS_INDEX_NO_BLOCKS")) rc_side = svdss_index_append_blocks(ix, (out + ".svdss.tmp").c_str());
   });
   const int rc_fmd = svdss_index_save_fmd(ix, out.c_str());
+  if (verbose && rc_fmd == SVDSS_OK) report_fmd_encoder();   // (this thread's encode: before anything else encodes here)
   if (side.joinable()) side.join();
   if (rc_fmd != SVDSS_OK || rc_side != SVDSS_OK) (void)unlink((out + ".svdss.tmp").c_str());
   check(rc_fmd, "svdss_index_save_fmd");
@@ -371,6 +402,30 @@ static int main_index(int argc, char** argv) {
   mark("sidecar written");
   svdss_index_free(ix);
   return 0;
+}
+
+// `run --build-index`: the block run_svdss:136-147 of the reference's driver -- a missing index is built from the reference
+// and stored, exactly as `SVDSS index -d FA -o FMD -t threads` would, before the smoothing stage starts.  An index that
+// exists is not touched.  Refusals come before anything is opened for writing; a build that fails takes FMD, FMD.svdss and
+// FMD.svdss.tmp with it (die_context) -- none of run's outputs exists at that point.  Called by main_run / main_run_samples
+// (CallOptions::before_stages) after run's own refusals -- --gpus, the knobs it does not run with, a samples list that does
+// not validate, a BAM that does not exist -- so that a command that is going to be refused does not build an index first.
+static void build_missing_index(const CallOptions& o) {
+  struct stat st;
+  if (stat(o.index.c_str(), &st) == 0) return;
+  if (access(o.reference.c_str(), R_OK) != 0) die("run --build-index: cannot read " + o.reference + " (the reference the index is built from)");
+  const size_t slash = o.index.find_last_of('/');
+  const std::string dir = slash == std::string::npos ? "." : slash == 0 ? "/" : o.index.substr(0, slash);
+  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || access(dir.c_str(), W_OK | X_OK) != 0)
+    die("run --build-index: cannot write " + o.index + ": " + dir + " is not a directory that can be written to");
+  if (svdss_device_count() <= 0 && !getenv("SVDSS_INDEX_CPU"))
+    die("no GPU found: SVDSS index builds the index in HBM (SVDSS_INDEX_CPU=1 runs the host builder instead)");
+  fprintf(stderr, "[run] [info] Building FMD index: %s\n", o.index.c_str());
+  std::vector<std::string>& gone = die_context().unlink;
+  const size_t had = gone.size();
+  for (const char* suffix : {"", ".svdss", ".svdss.tmp"}) gone.push_back(o.index + suffix);
+  if (build_index_files({o.reference}, "", o.index, o.threads, o.verbose) != 0) die("run --build-index: the index was not built");
+  gone.resize(had);
 }
 
 int main(int argc, char** argv) {
@@ -391,6 +446,9 @@ int main(int argc, char** argv) {
     for (int i = 2; i < argc; ++i)
       if (!strncmp(argv[i], "--write-bam-index", 17) && (argv[i][17] == 0 || argv[i][17] == '='))
         die("--write-bam-index is an option of `SVDSS call` and `SVDSS run` only, not of `SVDSS index`");
+    for (int i = 2; i < argc; ++i)
+      if (!strncmp(argv[i], "--build-index", 13) && (argv[i][13] == 0 || argv[i][13] == '='))
+        die("--build-index is an option of `SVDSS run` only, not of `SVDSS index`");
     logmsg("info", "FM-index construction (stands for 'ropebwt3 build')");
     const int rc = main_index(argc, argv);
     if (rc) return rc;
@@ -411,6 +469,8 @@ int main(int argc, char** argv) {
       die(std::string("--smoothed is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
     if (!o.samples.empty() && strcmp(argv[1], "run") != 0)
       die(std::string("--samples is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
+    if (o.build_index && strcmp(argv[1], "run") != 0)
+      die(std::string("--build-index is an option of `SVDSS run` only, not of `SVDSS ") + argv[1] + "`");
     // --write-bam-index FILE / bamindex -o FILE: what they do not go with, before anything is opened for writing
     const bool is_bamindex = !strcmp(argv[1], "bamindex");
     if (!o.out.empty() && !is_bamindex) die(std::string("-o is an option of `SVDSS bamindex` only, not of `SVDSS ") + argv[1] + "`");
@@ -477,6 +537,7 @@ int main(int argc, char** argv) {
       c.min_cluster_weight = o.min_cluster_weight; c.min_sv_length = o.min_sv_length; c.useht = o.useht; c.min_ratio = o.min_ratio;
       c.poa = o.poa; c.clusters = o.clusters; c.clipped = o.clipped; c.verbose = o.verbose; c.write_bam_index = o.write_bam_index;
       if (!main_run || !main_run_samples) die("this build of the binary has no `run` (run_host.cpp was left out)");
+      if (o.build_index) c.before_stages = build_missing_index;
       if (o.samples.empty()) main_run(c);
       else main_run_samples(c, o.samples, o.regions, o.regions_file);
     } else if (is_bamindex) {

@@ -82,6 +82,29 @@ def bwt_strings_last() -> dict:
             "blocks_ms": ms[0], "pass1_ms": ms[1], "pass2_ms": ms[2]}
 
 
+FMD_ROUTES = ("host", "device", "declined, empty", "declined, block total", "declined, memory", "declined, no GPU")
+
+
+def fmd_encode(bwt, path: str, device: int = -1) -> None:
+    """The rld0 `.fmd` of a BWT (nt6 symbols, '$' = 0) -> path: svdss_fmd_encode.  device >= 0: encoded on that GPU
+    (csrc/rld0_dev.hip), the bytes of the host encoder; -1: the host encoder.  The device declines whole calls (an empty
+    BWT, a block of SVDSS_FMD_DECLINE_SYMS symbols or more, no room in HBM, no GPU) and the host encoder writes the file:
+    fmd_encode_last() tells."""
+    b = np.ascontiguousarray(bwt, dtype=np.uint8)
+    check(lib.svdss_fmd_encode(b.ctypes.data, int(b.size), str(path).encode(), device), "svdss_fmd_encode")
+
+
+def fmd_encode_last() -> dict:
+    """How this thread's last .fmd encode (fmd_encode, FMDIndex.save_fmd) ran: route (one of FMD_ROUTES); on the device its
+    runs, data blocks and pieces and the milliseconds of its stages."""
+    route = C.c_int32(-1)
+    runs, blocks, pieces = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    ms = (C.c_double * 6)()
+    check(lib.svdss_fmd_encode_last(C.byref(route), C.byref(runs), C.byref(blocks), C.byref(pieces), ms), "svdss_fmd_encode_last")
+    return {"route": FMD_ROUTES[route.value], "runs": runs.value, "blocks": blocks.value, "pieces": pieces.value,
+            "planes_ms": ms[0], "plan_ms": ms[1], "chain_ms": ms[2], "emit_ms": ms[3], "download_ms": ms[4], "total_ms": ms[5]}
+
+
 class FMDIndex:
     """FM-index over every record and its reverse complement (rb3_fmi_t role)."""
 
@@ -121,9 +144,11 @@ class FMDIndex:
         resident instead of reading text + suffix array from disk."""
         check(lib.svdss_index_save_records(self._h, path.encode()), "svdss_index_save_records")
 
-    def save_fmd(self, path: str) -> None:
-        """ropebwt3's rld0 dump (`ropebwt3 build -d` / upstream `SVDSS index`)."""
-        check(lib.svdss_index_save_fmd(self._h, path.encode()), "svdss_index_save_fmd")
+    def save_fmd(self, path: str, device: Optional[int] = None) -> None:
+        """ropebwt3's rld0 dump (`ropebwt3 build -d` / upstream `SVDSS index`).  device=None: SVDSS_FMD_ENCODE_DEVICE
+        decides (1 / unset: encoded on the GPU, from the resident rank blocks where the index is resident; 0: on the
+        host); device=d: on GPU d; device=-1: on the host.  The same bytes either way; fmd_encode_last() tells."""
+        check(lib.svdss_index_save_fmd_on(self._h, str(path).encode(), -2 if device is None else device), "svdss_index_save_fmd_on")
 
     def append_blocks(self, path: str) -> None:
         """The rank blocks and '$' rows behind the records of the file save_records wrote (what `SVDSS index` leaves in
